@@ -12,13 +12,20 @@ torch.distributed.run (RANK / WORLD_SIZE in the environment), or -- `python benc
 on its own -- this process starts them itself as FRESH child processes before it has made any GPU
 call, relays rank 0's JSON line and exits non-zero if any rank fails (an RCCL error included).
 
-Prints ONE JSON line (rank 0).  Besides the driver's contract it carries
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the
+headline (value, ms_per_step, device_ms_per_step, final_loss, step_tflops).  --full adds the
+secondary legs, each measured after the timed region:
   roofline      dominant kernel family (implicit-GEMM conv), hipEvent-timed on the launch stream
   cpu_baseline  the CPU oracle (torch fp32, the reference's own arithmetic) on this host's cores,
                 run on the SAME batch and the SAME initial weights as the GPU: its outputs and
                 first-step loss are the parity check of this very run (parity_max_abs_err)
   allreduce     per-bucket timing of the gradient all-reduce (N > 1, or --force-dp)
   infer_ms      single-frame inference latency (predict_controls path), median
+                (+ batched inference, the input pipeline, the ResNet-50 variant and bf16 legs)
+
+--dump-outputs DIR writes what the last timed step left to its caller, as float32 .npy files:
+loss (the six loss terms of train_step's loss buffer), params / exp_avg / exp_avg_sq / grads (a
+fixed seeded sample of each flat arena), bn_running (the BatchNorm running-statistics arena).
 """
 import argparse
 import json
@@ -147,6 +154,28 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_SAMPLE = 1 << 21          # elements sampled from each 22.4 M-float arena: 8 MB per file
+
+
+def dump_outputs(out_dir, trainer):
+    """--dump-outputs: what the last timed step hands its caller -- train_step's loss buffer and
+    the model / optimizer state it updated -- as float32 .npy files (34 MB in all).  The arenas
+    are sampled at the same seeded positions in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    eng = trainer.eng
+    g = torch.Generator().manual_seed(0)
+    idx = torch.randint(0, eng.n_arena, (min(DUMP_SAMPLE, eng.n_arena),), generator=g)
+    idx = idx.sort().values.to(eng.params.device)
+    arrays = {"loss": trainer.loss_buf[:6], "bn_running": eng.bn}
+    for name, arena in (("params", eng.params), ("exp_avg", trainer.exp_avg),
+                        ("exp_avg_sq", trainer.exp_avg_sq), ("grads", eng.grads)):
+        arrays[name] = arena[idx]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.detach().float().cpu().numpy())
+    log(f"outputs of the last timed step written to {out_dir}: {', '.join(sorted(arrays))}")
+
+
 def rehearse(args, rank, world, real_stdout):
     """--rehearse: the multi-rank plumbing of this file on CPU ranks (gloo) -- the launcher, the
     rendezvous, the bucketed gradient all-reduce over a stand-in gradient arena, the barrier /
@@ -196,7 +225,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=128, help="frames per GPU")
     ap.add_argument("--config", default="A", choices=["A", "B"])
-    ap.add_argument("--profile-steps", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs: per-kernel profile / roofline, CPU baseline + "
+                         "parity, all-reduce buckets, inference, loader, ResNet-50 and bf16 legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32)")
+    ap.add_argument("--profile-steps", type=int, default=3, help="(--full) per-kernel profile steps")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-infer", action="store_true")
     ap.add_argument("--no-loader", action="store_true",
@@ -263,18 +297,24 @@ def main():
 
     # ---- parity of THIS run (rank 0, one GPU, dropout-free config): what the GPU computes from
     # its initial weights on the batch it is about to time -- a train-mode forward and the first
-    # train step -- is recomputed by the CPU oracle in cpu_baseline() below and must agree
-    want_parity = (world == 1 and rank == 0 and not args.no_cpu_baseline and cfg.dropout == 0
-                   and args.config == "A")
+    # train step -- is recomputed by the CPU oracle in cpu_baseline() below and must agree.  The
+    # two GPU calls run with or without --full, so that final_loss and --dump-outputs of a run do
+    # not depend on whether its secondary legs were asked for.
+    first_step = (world == 1 and rank == 0 and not args.no_cpu_baseline and cfg.dropout == 0
+                  and args.config == "A")
+    want_parity = first_step and args.full
     state0 = gpu_out = gpu_loss1 = None
-    if want_parity:
-        state0 = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+    if first_step:
+        if want_parity:
+            state0 = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
         model.train()
         with torch.no_grad():
             c0, s0 = model(batch[0], batch[1], batch[2])
-        gpu_out = (c0.cpu(), s0.cpu())
+        if want_parity:
+            gpu_out = (c0.cpu(), s0.cpu())
         trainer.train_step(*batch)
-        gpu_loss1 = trainer.losses()
+        if want_parity:
+            gpu_loss1 = trainer.losses()
 
     def sync():
         torch.cuda.synchronize(dev)
@@ -300,11 +340,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall = float(t.item())
     loss_total = trainer.losses()["total"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer)
 
     # ---- per-bucket timing of the gradient all-reduce, each bucket alone on an idle GPU (every
     # rank takes part; in the step the buckets overlap the remaining backward)
     ar = None
-    if pg is not None:
+    if args.full and pg is not None:
         ar = []
         for (_, b, e) in trainer.reducer.buckets:
             view = trainer.eng.grads[b:e]
@@ -357,7 +399,7 @@ def main():
                                     "overlap the remaining backward"}
 
     log(f"{value:.1f} frames/s, {wall / args.steps * 1e3:.3f} ms/step")
-    if world == 1 and args.profile_steps > 0:
+    if args.full and world == 1 and args.profile_steps > 0:
         # ---- per-kernel hipEvent timing on the launch stream (extra steps, same step fn) ----
         pl = trainer.eng.plan(args.batch, 88, 200)
         pl.profile_reset()
@@ -475,7 +517,7 @@ def main():
             for l, r in sorted(table.items()) if l.startswith("conv_")}
 
         log("per-kernel profile done; inference latency")
-    if world == 1 and not args.no_infer:
+    if args.full and world == 1 and not args.no_infer:
         # ---- single-frame inference latency (predict_controls path) ----
         from cilrs_mi355.predict import Predictor
         pr = Predictor(model)

@@ -434,6 +434,46 @@ def test_bench_launcher_propagates_rank_failure():
     assert not [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
 
 
+_DUMP = r"""
+import sys, types
+import torch
+sys.path.insert(0, sys.argv[1])
+import bench
+from cilrs_mi355 import _lib
+lib = _lib.lib()
+n = lib.cilrs_param_arena_floats()
+g = torch.Generator().manual_seed(7)
+eng = types.SimpleNamespace(n_arena=n, params=torch.randn(n, generator=g),
+                            grads=torch.randn(n, generator=g),
+                            bn=torch.randn(lib.cilrs_bn_arena_floats(), generator=g))
+tr = types.SimpleNamespace(eng=eng, exp_avg=eng.params * 0.5, exp_avg_sq=eng.grads ** 2,
+                           loss_buf=torch.arange(8, dtype=torch.float32))
+bench.dump_outputs(sys.argv[2], tr)
+"""
+
+
+def test_bench_dump_outputs_are_float32_bounded_and_sampled_at_fixed_positions(tmp_path):
+    """`bench.py --dump-outputs DIR` (here on a stand-in trainer with the real arena sizes, in a
+    fresh process each time): float32 .npy files, at most 64 MB in all, and the same state gives
+    the same files in two processes -- the arena sample positions do not vary from run to run."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dirs = [str(tmp_path / d) for d in ("a", "b")]
+    for d in dirs:
+        r = subprocess.run([sys.executable, "-c", _DUMP, root, d], capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) == sorted(
+        f"{k}.npy" for k in ("loss", "bn_running", "params", "exp_avg", "exp_avg_sq", "grads"))
+    assert sum(os.path.getsize(os.path.join(dirs[0], f)) for f in names) <= 64 * 2 ** 20
+    for f in names:
+        a, b = np.load(os.path.join(dirs[0], f)), np.load(os.path.join(dirs[1], f))
+        assert a.dtype == np.float32 and np.array_equal(a, b), f
+    assert np.array_equal(np.load(os.path.join(dirs[0], "loss.npy")), np.arange(6))
+
+
 def test_batch_loader_rank_shards_are_disjoint_and_cover_the_single_process_draw():
     """SURVEY.md 8e rank-strided sampling: with one shared sampler stream (equal seeds) the two
     ranks' epoch orders are disjoint POSITIONS of the single-process WeightedRandomSampler draw

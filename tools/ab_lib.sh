@@ -4,7 +4,7 @@
 for rep in 1 2 3; do
   for lib in product exp; do
     if [ $lib = exp ]; then export CILRS_LIB=tools/bin/libcilrs_hip_exp.so; else unset CILRS_LIB; fi
-    python bench.py --no-cpu-baseline --no-infer --no-loader 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-infer --no-loader 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lib', d['ms_per_step'], 'frac', d['roofline']['frac'], 'fwd', d['kernels']['conv_fwd']['ms_per_step'], 'dgrad', d['kernels']['conv_dgrad']['ms_per_step'])"
   done

@@ -5,8 +5,8 @@ T=${1:-ab}; K=${2:-"wino or b128 or train_steps_golden or fused_backward"}
 O=gpurun_out/$T; mkdir -p $O
 timeout -k 10 500 python -m pytest tests/test_ops_gpu.py tests/test_model_gpu.py -x -q -m gpu -k "$K" > $O/tests.log 2>&1
 tail -4 $O/tests.log
-python bench.py --no-cpu-baseline --no-infer --no-loader > $O/bench.log 2> $O/bench.err || exit 1
-CILRS_OVERLAP=0 python bench.py --no-cpu-baseline --no-infer --no-loader --steps 20 > $O/bench_serial.log 2> $O/bench_serial.err || exit 1
+python bench.py --full --no-cpu-baseline --no-infer --no-loader > $O/bench.log 2> $O/bench.err || exit 1
+CILRS_OVERLAP=0 python bench.py --full --no-cpu-baseline --no-infer --no-loader --steps 20 > $O/bench_serial.log 2> $O/bench_serial.err || exit 1
 python - <<P
 import json
 for f in ["$O/bench.log", "$O/bench_serial.log"]:
