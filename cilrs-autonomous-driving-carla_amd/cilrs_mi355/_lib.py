@@ -70,6 +70,8 @@ SIGNATURES = {
     "cilrs_dropout": (i32, [vp, i32, i32, i32, f32, u64, i32, vp]),
     "cilrs_net_forward": (i32, [vp, C.POINTER(Buffers), vp, C.c_long, C.c_long, C.c_long,
                                 C.c_long, vp, vp, i32, f32, u64, vp, vp, vp]),
+    "cilrs_net_forward_frozen": (i32, [vp, C.POINTER(Buffers), vp, C.c_long, C.c_long, C.c_long,
+                                       C.c_long, vp, vp, vp, vp, vp]),
     "cilrs_net_forward_u8": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp, vp, vp]),
     "cilrs_net_forward_camera": (i32, [vp, C.POINTER(Buffers), vp, i32, i32, i32, C.c_long,
                                        C.c_long, vp, vp, vp, vp, vp]),
@@ -89,9 +91,13 @@ SIGNATURES = {
     "cilrs_net_forward_u8_bf16_graph": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp, vp, vp]),
     "cilrs_loss_fwd_bwd": (i32, [vp, vp, vp, vp, i32, i32, c_float_p, f32, vp, vp, vp, vp]),
     "cilrs_net_backward": (i32, [vp, C.POINTER(Buffers), vp, vp, i32, i32, vp]),
+    "cilrs_net_input_grads": (i32, [vp, C.POINTER(Buffers), vp, C.c_long, C.c_long, C.c_long,
+                                    C.c_long, vp, vp]),
     "cilrs_stem_conv_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "cilrs_stem_conv_wgrad_scratch_floats": (sz, [i32, i32, i32]),
     "cilrs_stem_conv_wgrad": (i32, [vp, vp, vp, vp, sz, i32, i32, i32, vp]),
+    "cilrs_stem_conv_dgrad": (i32, [vp, vp, vp, C.c_long, C.c_long, C.c_long, C.c_long, i32, i32,
+                                    i32, vp]),
     "cilrs_net_backward_step": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp]),
     "cilrs_segment_range": (i32, [i32, C.POINTER(sz), C.POINTER(sz)]),
     "cilrs_variant_segment_range": (i32, [i32, i32, C.POINTER(sz), C.POINTER(sz)]),

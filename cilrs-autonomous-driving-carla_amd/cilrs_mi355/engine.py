@@ -322,6 +322,26 @@ class Engine:
         self.last_plan = pl
         return controls, pred_speed, pl
 
+    def run_forward_frozen(self, image, speed, command):
+        """model.eval() forward that keeps its graph (BatchNorm on the running statistics, no
+        dropout, running buffers untouched): the forward of an eval-mode autograd graph.
+        Returns (controls, pred_speed, plan)."""
+        b = self._check_inputs(image, speed, command)
+        pl = self.plan(b, image.size(2), image.size(3))
+        speed = speed.contiguous()
+        command = command.contiguous()
+        controls = torch.empty(b, 3, dtype=torch.float32, device=self.device)
+        pred_speed = torch.empty(b, dtype=torch.float32, device=self.device)
+        sn, sc, sh, sw = image.stride()
+        self.poll_versions()
+        self._announce_weights(pl)
+        L.check(L.lib().cilrs_net_forward_frozen(
+            pl.handle, C.byref(pl.bufs), L.ptr(image), sn, sc, sh, sw,
+            L.ptr(speed), L.ptr(command), L.ptr(controls), L.ptr(pred_speed), self._stream()))
+        pl.generation += 1                    # the saved activations of earlier graphs are gone
+        self.last_plan = pl
+        return controls, pred_speed, pl
+
     def check_status(self):
         """Raise if the last forward saw an out-of-range command (one device->host read)."""
         if self.last_plan is not None:
@@ -398,6 +418,24 @@ class Engine:
             pl.handle, C.byref(bufs), L.ptr(dcontrols), L.ptr(dpred_speed), seg_begin, seg_end,
             self._stream()))
 
+    def run_input_grads(self, pl, dimage=None, dspeed=None):
+        """After run_backward of the plan's last graph-keeping forward: d image (any strides)
+        and / or d speed into the given tensors (None: not computed)."""
+        if dimage is not None:
+            if (dimage.dtype != torch.float32 or dimage.device != self.device or
+                    tuple(dimage.shape) != (pl.batch, 3, pl.h, pl.w)):
+                raise RuntimeError(f"dimage must be float32 [{pl.batch},3,{pl.h},{pl.w}] on "
+                                   f"{self.device}")
+            strides = dimage.stride()
+        else:
+            strides = (0, 0, 0, 0)
+        if dspeed is not None and (dspeed.dtype != torch.float32 or tuple(dspeed.shape) != (pl.batch,)
+                                   or not dspeed.is_contiguous() or dspeed.device != self.device):
+            raise RuntimeError(f"dspeed must be a contiguous float32 [{pl.batch}] on {self.device}")
+        L.check(L.lib().cilrs_net_input_grads(
+            pl.handle, C.byref(pl.bufs), L.ptr(dimage) if dimage is not None else None, *strides,
+            L.ptr(dspeed) if dspeed is not None else None, self._stream()))
+
     def run_backward_step(self, pl, dcontrols, dpred_speed, exp_avg, exp_avg_sq, lr, betas, eps,
                           weight_decay, step, grad_scale=1.0):
         """loss.backward() + Adam.step() in one library call (cilrs_net_backward_step): each
@@ -423,25 +461,39 @@ class Engine:
 
     # ------------------------------------------------------------------------------------------
     def forward(self, image, speed, command, training, dropout_p, seed):
-        needs_graph = training and torch.is_grad_enabled() and any(
-            p.requires_grad for p in self.module.parameters())
+        # a graph is built for train-mode steps with trainable parameters, and -- in either mode --
+        # whenever an input asks for its gradient (eval mode: BatchNorm frozen on the running
+        # statistics, as torch's own eval-mode autograd); otherwise the detached fast path
+        grad_on = torch.is_grad_enabled()
+        needs_graph = grad_on and (image.requires_grad or speed.requires_grad)
+        if not needs_graph:
+            needs_graph = training and grad_on and any(
+                p.requires_grad for p in self.module.parameters())
         if not needs_graph:
             c, s, _ = self.run_forward(image, speed, command, training, dropout_p, seed)
             return c, s
         return _CILRSFunction.apply(self, image, speed, command, float(dropout_p), int(seed),
-                                    *self.module.parameters())
+                                    bool(training), *self.module.parameters())
+
+
+_N_LEADING = 7        # _CILRSFunction.forward arguments in front of the parameters
 
 
 class _CILRSFunction(torch.autograd.Function):
     """Composable path: lets ``loss.backward()`` + any torch.optim drive the HIP engine
-    (notebook/notebook.ipynb:549-555).  Gradients w.r.t. the image are not produced (the
-    reference never asks for them)."""
+    (notebook/notebook.ipynb:549-555), and gives image.grad / speed.grad (saliency, sensitivity
+    to the speed input) in train mode and -- through the frozen forward -- in eval mode."""
 
     @staticmethod
-    def forward(ctx, eng, image, speed, command, dropout_p, seed, *params):
-        controls, pred_speed, pl = eng.run_forward(image, speed, command, True, dropout_p, seed)
+    def forward(ctx, eng, image, speed, command, dropout_p, seed, training, *params):
+        if training:
+            controls, pred_speed, pl = eng.run_forward(image, speed, command, True, dropout_p, seed)
+        else:
+            controls, pred_speed, pl = eng.run_forward_frozen(image, speed, command)
         ctx.eng, ctx.pl, ctx.generation = eng, pl, pl.generation
         ctx.n_params = len(params)
+        ctx.channels_last = (not image.is_contiguous()
+                             and image.is_contiguous(memory_format=torch.channels_last))
         return controls, pred_speed
 
     @staticmethod
@@ -450,7 +502,10 @@ class _CILRSFunction(torch.autograd.Function):
         if pl.generation != ctx.generation:
             raise RuntimeError(
                 "CILRS backward: the saved activations of this forward were overwritten by a "
-                "later train-mode forward with the same input shape (one graph per shape)")
+                "later train-mode forward (or eval-mode forward with an input requiring grad) "
+                "with the same input shape (one graph per shape)")
+        need_image, need_speed = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        need_params = any(ctx.needs_input_grad[_N_LEADING:])
         b = pl.batch
         if dcontrols is None:
             dcontrols = torch.zeros(b, 3, device=eng.device)
@@ -464,14 +519,27 @@ class _CILRSFunction(torch.autograd.Function):
         # views of the arena for loops that consume the gradients before the next backward
         # (optimizer.step() + zero_grad(set_to_none=True)); when some p.grad still lives in the
         # arena that backward is written to a second arena instead, so accumulation stays correct.
+        # (a backward for input gradients alone must not disturb parameter gradients that live
+        # in the arena either)
         dst = eng.grads
-        if eng.zero_copy_grads and eng.grads_aliased():
+        if (eng.zero_copy_grads or not need_params) and eng.grads_aliased():
             if eng._scratch_grads is None:
                 eng._scratch_grads = torch.zeros_like(eng.grads)
             dst = eng._scratch_grads
         eng.run_backward(pl, dcontrols.contiguous().float(), dpred_speed.contiguous().float(),
                          into=None if dst is eng.grads else dst)
+        dimage = dspeed = None
+        if need_image or need_speed:
+            if need_image:
+                fmt = torch.channels_last if ctx.channels_last else torch.contiguous_format
+                dimage = torch.empty((b, 3, pl.h, pl.w), dtype=torch.float32, device=eng.device,
+                                     memory_format=fmt)
+            if need_speed:
+                dspeed = torch.empty(b, dtype=torch.float32, device=eng.device)
+            eng.run_input_grads(pl, dimage, dspeed)
+        if not need_params:
+            return (None, dimage, dspeed, None, None, None, None) + (None,) * ctx.n_params
         src = dst if eng.zero_copy_grads else dst.clone()
         grads = [_arena_view(src, off, numel, shape)
                  for (_, off, numel, shape) in eng.params_layout]
-        return (None, None, None, None, None, None, *grads)
+        return (None, dimage, dspeed, None, None, None, None, *grads)

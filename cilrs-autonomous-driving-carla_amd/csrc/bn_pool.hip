@@ -405,11 +405,12 @@ __global__ __launch_bounds__(kApplyThreads) void bn_finalize_apply_kernel(
 }
 
 // coef layout: [0,C) c1 = gamma*rstd | [C,2C) c2 = sum(g)/M | [2C,3C) c3 = sum(g*xhat)/M
+// (frozen: statistics that do not depend on the batch -- eval mode -- c2 = c3 = 0)
 template <bool SC1>
 __device__ __forceinline__ void bwd_finalize_channel(
     const float* __restrict__ partial, const int nblk, const int M, const int C, const int c,
     const float* __restrict__ gamma, const float* __restrict__ stats, float* dgamma,
-    float* dbeta, float* __restrict__ coef, const int accumulate) {
+    float* dbeta, float* __restrict__ coef, const int accumulate, const int frozen) {
     double s1, s2;
     if (SC1 ? !partial_sums4(partial, nblk, C, c, c < C, s1, s2)
             : !partial_sums(partial, nblk, C, c, s1, s2)) return;
@@ -418,20 +419,20 @@ __device__ __forceinline__ void bwd_finalize_channel(
     dgamma[c] = accumulate ? dgamma[c] + dg : dg;
     if (SC1) {
         st_sc1(coef + c, gamma[c] * stats[C + c]);
-        st_sc1(coef + C + c, (float)(s1 / M));
-        st_sc1(coef + 2 * C + c, (float)(s2 / M));
+        st_sc1(coef + C + c, frozen ? 0.f : (float)(s1 / M));
+        st_sc1(coef + 2 * C + c, frozen ? 0.f : (float)(s2 / M));
     } else {
         coef[c] = gamma[c] * stats[C + c];
-        coef[C + c] = (float)(s1 / M);
-        coef[2 * C + c] = (float)(s2 / M);
+        coef[C + c] = frozen ? 0.f : (float)(s1 / M);
+        coef[2 * C + c] = frozen ? 0.f : (float)(s2 / M);
     }
 }
 __global__ __launch_bounds__(kFinThreads) void bn_bwd_finalize_kernel(
     const float* __restrict__ partial, const int nblk, const int M, const int C,
     const float* __restrict__ gamma, const float* __restrict__ stats, float* dgamma,
-    float* dbeta, float* __restrict__ coef, const int accumulate) {
+    float* dbeta, float* __restrict__ coef, const int accumulate, const int frozen) {
     bwd_finalize_channel<false>(partial, nblk, M, C, blockIdx.x, gamma, stats, dgamma, dbeta, coef,
-                                accumulate);
+                                accumulate, frozen);
 }
 
 // g = dz * (z>0 if relu);  dy = (g - c2 - xhat*c3) * c1;  optionally g_out = g (residual path)
@@ -466,7 +467,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
 struct BnBwdFinArgs {
     const float* partial; int nblk; int M;
     const float* gamma; float* dgamma; float* dbeta; int accumulate;
-    int* sync; int target;
+    int* sync; int target; int frozen;
 };
 __global__ __launch_bounds__(kApplyThreads) void bn_bwd_finalize_apply_kernel(
     const BnBwdFinArgs f, const float* __restrict__ dz, const float* __restrict__ z,
@@ -476,7 +477,7 @@ __global__ __launch_bounds__(kApplyThreads) void bn_bwd_finalize_apply_kernel(
     for (int base = blockIdx.x * 4; base < C; base += gridDim.x * 4) {
         const int c = base + (threadIdx.x >> 8);
         bwd_finalize_channel<true>(f.partial, f.nblk, f.M, C, c, f.gamma, stats, f.dgamma, f.dbeta,
-                                   coef, f.accumulate);
+                                   coef, f.accumulate, f.frozen);
         if ((threadIdx.x & 255) == 0 && c < C) publish_channel(f.sync, c);
     }
     const int cq = C >> 2;
@@ -1192,7 +1193,7 @@ int launch_bn_eval_fwd(const float* y, int M, int C, const float* gamma, const f
 int launch_bn_bwd(const float* dz, const float* z, const float* y, int M, int C,
                   const float* gamma, const float* stats, int relu, float* dgamma, float* dbeta,
                   int accumulate, float* coef, float* partial, float* dy, float* g_out,
-                  int pre_nblk, hipStream_t s, void* dy16, BnSync* sync) {
+                  int pre_nblk, hipStream_t s, void* dy16, BnSync* sync, int frozen) {
     if (check_c(C)) return 1;
     int nblk = pre_nblk;
     if (nblk <= 0) {
@@ -1205,14 +1206,15 @@ int launch_bn_bwd(const float* dz, const float* z, const float* y, int M, int C,
     const size_t total4 = (size_t)M * C / 4;
     if (sync && sync->dev && C <= 1024 && C % 8 == 0) {
         sync->total = (int)((unsigned)sync->total + (unsigned)(C / 8));
-        const BnBwdFinArgs f{partial, nblk, M, gamma, dgamma, dbeta, accumulate, sync->dev, sync->total};
+        const BnBwdFinArgs f{partial, nblk, M, gamma, dgamma, dbeta, accumulate, sync->dev, sync->total,
+                             frozen};
         bn_bwd_finalize_apply_kernel<<<grid_for(total4, kApplyThreads, apply_grid_cap()), kApplyThreads, 0, s>>>(
             f, dz, z, y, stats, coef, dy, g_out, total4, C, relu, reinterpret_cast<__bf16*>(dy16));
         CILRS_LAUNCH_CHECK();
         return 0;
     }
     bn_bwd_finalize_kernel<<<C, kFinThreads, 0, s>>>(partial, nblk, M, C, gamma, stats,
-                                                        dgamma, dbeta, coef, accumulate);
+                                                        dgamma, dbeta, coef, accumulate, frozen);
     CILRS_LAUNCH_CHECK();
     bn_bwd_apply_kernel<<<grid_for(total4), 256, 0, s>>>(dz, z, y, stats, coef, dy, g_out, total4,
                                                          C, relu, reinterpret_cast<__bf16*>(dy16));
@@ -1235,7 +1237,8 @@ int launch_bn_relu_maxpool_fwd(const float* y, const float* stats, float* out,
 // BatchNorm backward of  maxpool(relu(bn(y)))  given d(maxpool output): dgamma, dbeta, dy
 int launch_bn_bwd_pool(const float* dpool, const unsigned char* argmax, const float* y, int N,
                        int H, int W, int C, const float* gamma, const float* stats, float* dgamma,
-                       float* dbeta, float* coef, float* partial, float* dy, hipStream_t s) {
+                       float* dbeta, float* coef, float* partial, float* dy, hipStream_t s,
+                       int frozen) {
     if (check_c(C)) return 1;
     CILRS_CHECK(C <= 1024, "bn_bwd_pool: at most 1024 channels (got %d)", C);
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
@@ -1252,7 +1255,7 @@ int launch_bn_bwd_pool(const float* dpool, const unsigned char* argmax, const fl
                                                   Ho, Wo, ppb);
     CILRS_LAUNCH_CHECK();
     bn_bwd_finalize_kernel<<<C, kFinThreads, 0, s>>>(partial, nblk, M, C, gamma, stats, dgamma,
-                                                     dbeta, coef, 0);
+                                                     dbeta, coef, 0, frozen);
     CILRS_LAUNCH_CHECK();
     const size_t total = (size_t)NP * (C / 4);
     bn_bwd_apply_pool_kernel<<<grid_for(total), 256, 0, s>>>(y, dpool, argmax, stats, coef, dy, N,
@@ -1356,7 +1359,7 @@ int launch_bn16_bwd(const void* dz16, const void* z16, const void* y16, int M, i
         nblk = p.nblk;
     }
     bn_bwd_finalize_kernel<<<C, kFinThreads, 0, s>>>(partial, nblk, M, C, gamma, stats, dgamma,
-                                                     dbeta, coef, 0);
+                                                     dbeta, coef, 0, 0);
     CILRS_LAUNCH_CHECK();
     const size_t total8 = (size_t)M * C / 8;
     bn16_bwd_apply_kernel<<<grid_for(total8, 256 * 3), 256, 0, s>>>(

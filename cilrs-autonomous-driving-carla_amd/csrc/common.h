@@ -234,7 +234,11 @@ int launch_bn_eval_fwd(const float* y, int M, int C, const float* gamma, const f
 int launch_bn_bwd(const float* dz, const float* z, const float* y, int M, int C,
                   const float* gamma, const float* stats, int relu, float* dgamma, float* dbeta,
                   int accumulate, float* coef, float* partial, float* dy, float* g_out,
-                  int pre_nblk, hipStream_t s, void* dy16 = nullptr, BnSync* sync = nullptr);
+                  int pre_nblk, hipStream_t s, void* dy16 = nullptr, BnSync* sync = nullptr,
+                  int frozen = 0);
+// frozen != 0 (launch_bn_bwd, launch_bn_bwd_pool): BatchNorm with FIXED statistics (eval mode,
+// `stats` from the running buffers): dy = gamma * rstd * g -- the batch-statistics terms vanish --
+// while dgamma = sum g * xhat and dbeta = sum g come from the same column reductions
 // The same passes on bf16 NHWC tensors (bf16 training mode: 16-bit activations and gradients end to
 // end, fp32 statistics and coefficients; C % 8 == 0).  y16 / z16 / residual16 / dz16 / dy16 /
 // g_out16 are bf16; BatchNorm is the fp32 BatchNorm of the stored y16.
@@ -254,7 +258,8 @@ int launch_bn_relu_maxpool_fwd(const float* y, const float* stats, float* out,
                                void* out16 = nullptr);
 int launch_bn_bwd_pool(const float* dpool, const unsigned char* argmax, const float* y, int N,
                        int H, int W, int C, const float* gamma, const float* stats, float* dgamma,
-                       float* dbeta, float* coef, float* partial, float* dy, hipStream_t s);
+                       float* dbeta, float* coef, float* partial, float* dy, hipStream_t s,
+                       int frozen = 0);
 int launch_maxpool_fwd(const float* x, float* out, unsigned char* argmax, int N, int H, int W,
                        int C, hipStream_t s);
 int launch_maxpool_bwd(const float* dout, const unsigned char* argmax, float* dx, int N, int H,
@@ -283,6 +288,10 @@ int launch_colsum(const float* dy, float* db, int B, int out, int dy_ld, int acc
                   hipStream_t s);
 int launch_relu_mask(float* d, const float* act, int B, int cols, int d_ld, int act_ld,
                      float scale, hipStream_t s);
+// out[b] = sum_c d[b][c] * w[c] in column order (the speed gradient: d of the speed encoder's
+// first pre-activation times its [cols][1] weight)
+int launch_rowdot(const float* d, const float* w, float* out, int B, int cols, int d_ld,
+                  hipStream_t s);
 // The reference builds one control branch per command (autonomous_drive.py:362, 380-381); every
 // caller passes 4.  Plans are generic up to kMaxCmd branches (a plan parameter, encoded in the
 // variant code: trunk | num_commands << 8, 0 meaning 4).
@@ -549,6 +558,10 @@ int launch_stem_f32(const float* x4, const float* w, float* y, float* bn_partial
 size_t stem_wgrad_f32_scratch_floats(int N, int H, int W);
 int launch_stem_wgrad_f32(const float* x4, const float* dy, float* dw, float* scratch, int N, int H,
                           int W, hipStream_t s);
+// its data gradient: dx (logical NCHW [N][3][H][W], element strides sn..sw, overwritten) from
+// dy = [N][Ho][Wo][64] and w = OHWI [64][7][7][3]; any geometry, no scratch, deterministic
+int launch_stem_dgrad_f32(const float* dy, const float* w, float* dx, long sn, long sc, long sh,
+                          long sw, int N, int H, int W, hipStream_t s);
 // 16-bit stem of the serving path (stem_f16.hip): conv 7x7/s2 + folded BN + ReLU on the channel-
 // padded fp32 image -> 16-bit [N][Ho][Wo][64]; max-pool 3x3/s2/p1 on 16-bit NHWC
 int launch_fold_stem_f16(const float* w, const float* stats, void* w16, float* bias, int bf16,

@@ -249,6 +249,19 @@ __global__ __launch_bounds__(256) void relu_mask_kernel(float* __restrict__ d,
     d[o] = act[(size_t)b * act_ld + c] > 0.f ? d[o] * scale : 0.f;
 }
 
+// out[b] = sum_c d[b][c] * w[c], c in order -- the input gradient of a Linear(1, cols) layer
+__global__ __launch_bounds__(256) void rowdot_kernel(const float* __restrict__ d,
+                                                     const float* __restrict__ w,
+                                                     float* __restrict__ out, const int B,
+                                                     const int cols, const int d_ld) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const float* row = d + (size_t)b * d_ld;
+    float v = 0.f;
+    for (int c = 0; c < cols; ++c) v = fmaf(row[c], w[c], v);
+    out[b] = v;
+}
+
 // out[b][c] = ((p0+p1)+p2)+... (+ tail for c < cols_tail) -- fixed order, deterministic
 __global__ __launch_bounds__(256) void sum_parts_kernel(const SumParts parts, float* __restrict__ out,
                                                         const int B, const int cols,
@@ -681,6 +694,13 @@ int launch_colsum(const float* dy, float* db, int B, int out, int dy_ld, int acc
 int launch_relu_mask(float* d, const float* act, int B, int cols, int d_ld, int act_ld,
                      float scale, hipStream_t s) {
     relu_mask_kernel<<<cdiv(B * cols, 256), 256, 0, s>>>(d, act, B, cols, d_ld, act_ld, scale);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_rowdot(const float* d, const float* w, float* out, int B, int cols, int d_ld,
+                 hipStream_t s) {
+    rowdot_kernel<<<cdiv(B, 256), 256, 0, s>>>(d, w, out, B, cols, d_ld);
     CILRS_LAUNCH_CHECK();
     return 0;
 }

@@ -344,6 +344,12 @@ struct cilrs_net {
     const void* prep_bufs[3] = {nullptr, nullptr, nullptr};     // params, bn_running, workspace
     bool trained_fwd = false;
     float last_dropout = 0.f;
+    // the last graph-keeping forward was cilrs_net_forward_frozen (BatchNorm on the running
+    // statistics: its backward drops the batch-statistics terms)
+    bool frozen_fwd = false;
+    // segments of the last backward whose outputs cilrs_net_input_grads reads are still in the
+    // workspace: bit 0 = d(speed encoder) of segment 0, bit 5 = d(stem conv output) in G[1]
+    unsigned bwd_done = 0;
     // bf16 training mode (CILRS_PLAN_BF16_TRAIN): the trunk convolutions after the stem multiply
     // bf16 operands on v_mfma_f32_32x32x16_bf16 (fp32 accumulation, fp32 results); everything
     // else -- BatchNorm, residual adds, the stem, the heads, loss, Adam, master weights -- stays
@@ -1159,16 +1165,23 @@ int cilrs_dropout(float* a, int rows, int cols, int ld, float p, uint64_t seed, 
 // ------------------------------------------------------------------------------------------------
 static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const float* speed,
                            const int64_t* command, int train, float dropout_p, uint64_t seed,
-                           float* controls, float* pred_speed, hipStream_t s, int half = 0) {
+                           float* controls, float* pred_speed, hipStream_t s, int half = 0,
+                           bool frozen = false) {
     const Arch& A = *net->A;
     float* ws = reinterpret_cast<float*>(bufs->workspace);
     net->ws_base = ws;
+    CILRS_CHECK(!(frozen && (train || half || net->bf16_train)),
+                "frozen forward: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan rejects it)");
     if (zero_counters_once(net, bufs->workspace, s)) return 1;
     const float* P = bufs->params;
     float* R = bufs->bn_running;
     const int B = net->B;
     const float eps = 1e-5f, mom = 0.1f;
     const bool bf16t = train && net->bf16_train;      // trunk convolutions on the bf16 matrix pipe
+    // train: batch statistics; frozen: the running statistics -- both keep every activation the
+    // backward pass reads (y, z, the max-pool argmax, the head inputs)
+    const bool graph = train || frozen;
+    net->bwd_done = 0;
 
     // (residual: fp32 tensor, or the bf16 identity in the bf16 training mode)
     auto bn = [&](int ci, const void* residual_v, int relu, int pre_nblk, hipStream_t st = nullptr,
@@ -1212,7 +1225,7 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
             launch_pad_cin3_to_4(P + A.convs[0].w, ws + net->w4, 64 * 49, s));
     if (train) { net->prep_key = 0; net->fold_key = 0; }     // weights / BN buffers are about to change
     const float* cur;
-    if (train) {
+    if (graph) {
         // this step's weight images -- the Winograd-transformed filters (forward + data-gradient
         // forms), in the bf16 mode the 16-bit arena and the transposed, tap-flipped copies the data
         // gradients read -- depend on the parameters only: they are built on the side stream while
@@ -1253,7 +1266,18 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
         }
         // stem BatchNorm: statistics only -- its apply + ReLU is fused into the max-pool, the
         // post-BN tensor (144 MB at B=128) is never written
-        {
+        if (frozen) {
+            // every layer's scale / shift from the running statistics (the prep cache of the eval
+            // path holds the same values); the other BatchNorms re-derive theirs in the bn() apply
+            if (!prep_cached) {
+                RUN(net, "bn_fwd.eval", 0.0, 0.0, s,
+                    launch_bn_eval_stats_all(net->bn_table, P, R, ws, eps, s));
+                net->prep_key = net->weights_key;
+                net->prep_bufs[0] = bufs->params; net->prep_bufs[1] = bufs->bn_running;
+                net->prep_bufs[2] = bufs->workspace;
+                net->fold_key = 0;
+            }
+        } else {
             const ConvT& c0 = A.convs[0];
             const ConvG& g0 = net->cg[0];
             const BnT& b0 = A.bns[c0.bn];
@@ -1490,7 +1514,7 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
 
     int* status = reinterpret_cast<int*>(reinterpret_cast<char*>(bufs->workspace) + net->status_b);
     const int feat = A.feat, comb = A.feat + 128;
-    if (!train && B <= kHeadsSmallMaxB && A.variant == 0) {
+    if (!graph && B <= kHeadsSmallMaxB && A.variant == 0) {
         // ---- inference at control-loop batch sizes: 4 launches, commanded branch only ----
         RUN(net, "heads_fwd", 0.0, 0.0, s,
             launch_heads_small_pre(cur, net->featHW, speed, P + A.se0.w, P + A.se0.b, P + A.se3.w,
@@ -1535,7 +1559,7 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
         RUN(net, "heads_fwd", 0.0, 0.0, s,
             launch_avgpool_fwd(cur, ws + net->combined, B, net->featHW, feat, comb, s));
 
-    if (train) {   // backward needs the inputs of the heads
+    if (graph) {   // backward needs the inputs of the heads
         if (launch_keep_head_inputs(speed, reinterpret_cast<const long long*>(command), ws + net->speed_in,
                                     reinterpret_cast<long long*>(reinterpret_cast<char*>(bufs->workspace) +
                                                                  net->cmd_b), B, s)) return 1;
@@ -1584,7 +1608,8 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
     RUN(net, "heads_fwd", 0.0, 0.0, s,
         launch_branch_gather(ws + net->all_out, reinterpret_cast<const long long*>(command),
                              controls, B, NC, status, s));
-    net->trained_fwd = train != 0;
+    net->trained_fwd = graph;
+    net->frozen_fwd = frozen;
     net->last_dropout = pdrop;
     return 0;
 }
@@ -1611,6 +1636,20 @@ int cilrs_net_forward(cilrs_net* net, const cilrs_buffers* bufs, const float* im
         launch_nchw3_to_nhwc4(image, ws + net->x4, net->B, net->H, net->W, sn, sc, sh, sw, s));
     return forward_from_x4(net, bufs, speed, command, train, dropout_p, seed, controls,
                            pred_speed, s);
+}
+
+int cilrs_net_forward_frozen(cilrs_net* net, const cilrs_buffers* bufs, const float* image, long sn,
+                             long sc, long sh, long sw, const float* speed, const int64_t* command,
+                             float* controls, float* pred_speed, void* stream) {
+    if (check_bufs(net, bufs, false)) return 1;
+    CILRS_CHECK(image && speed && command && controls && pred_speed, "forward_frozen: NULL tensor");
+    CILRS_CHECK(!net->bf16_train, "forward_frozen: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan "
+                "rejects the frozen mode)");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
+    RUN(net, "transform", 0.0, 0.0, s,
+        launch_nchw3_to_nhwc4(image, ws + net->x4, net->B, net->H, net->W, sn, sc, sh, sw, s));
+    return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s, 0, true);
 }
 
 int cilrs_net_forward_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
@@ -2152,6 +2191,10 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
         return 0;
     };
 
+    // (segment 0 rewrites d(speed encoder); segments 1..5 cycle the buffer G[1] that segment 5
+    //  leaves d(stem conv output) in)
+    if (seg_begin == 0) net->bwd_done = 0;
+    if (seg_begin <= 5 && seg_end > 1) net->bwd_done &= ~(1u << 5);
     for (int seg = seg_begin; seg < seg_end; ++seg) {
         if (seg == 0) {
             CILRS_CHECK(dcontrols && dpred_speed, "backward: output gradients missing");
@@ -2167,6 +2210,7 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
                     launch_avgpool_bwd(ws + net->dcombined, ws + net->G[3], B, net->featHW, A.feat,
                                        A.feat + 128, s));
             if (segment_done(seg)) return 1;
+            net->bwd_done |= 1u;
             continue;
         }
         if (seg >= 1 && seg <= 4) {
@@ -2240,7 +2284,7 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
                                           P + b.gamma, ws + g.stats, relu, Gp + b.gamma,
                                           Gp + b.beta, 0, ws + net->bn_coef, ws + net->bn_partial,
                                           Gf(gdy), gg >= 0 ? Gf(gg) : nullptr, pre_nblk, s, nullptr,
-                                          bn_sync(net, ws, 1)));
+                                          bn_sync(net, ws, 1), net->frozen_fwd ? 1 : 0));
                     }
                     return 0;
                 };
@@ -2309,7 +2353,8 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
             RUN(net, "bn_bwd.stem", 0.0, 4.0 * g0.M * 64 * 3.0, s,
                 launch_bn_bwd_pool(ws + net->G[3], argmax, ws + g0.y, B, net->H0, net->W0, 64,
                                    P + b0.gamma, ws + g0.stats, Gp + b0.gamma, Gp + b0.beta,
-                                   ws + net->bn_coef, ws + net->bn_partial, ws + net->G[1], s));
+                                   ws + net->bn_coef, ws + net->bn_partial, ws + net->G[1], s,
+                                   net->frozen_fwd ? 1 : 0));
             // the stem's weight gradient runs on the main stream and uses the same slab scratch as
             // the weight gradients of the side stream: those must have finished (between the
             // segments of one call nothing else joins the two streams any more)
@@ -2326,6 +2371,7 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
                 return 1;
             }
             if (segment_done(seg)) return 1;
+            net->bwd_done |= 1u << 5;
         }
     }
     // everything the side stream still runs (weight gradients, fused Adam launches) joins here
@@ -2356,6 +2402,34 @@ int cilrs_net_backward_step(cilrs_net* net, const cilrs_buffers* bufs, const flo
     const int rc = cilrs_net_backward(net, bufs, dcontrols, dpred_speed, 0, 6, stream);
     net->fused_adam = nullptr;
     return rc;
+}
+
+int cilrs_net_input_grads(cilrs_net* net, const cilrs_buffers* bufs, float* dimage, long sn, long sc,
+                          long sh, long sw, float* dspeed, void* stream) {
+    if (check_bufs(net, bufs, false)) return 1;
+    CILRS_CHECK(net->trained_fwd, "input_grads needs a preceding graph-keeping forward on this plan");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const Arch& A = *net->A;
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
+    const int B = net->B;
+    if (dspeed) {
+        CILRS_CHECK(net->bwd_done & 1u, "input_grads: dspeed needs segment 0 (heads) of "
+                    "cilrs_net_backward after the forward");
+        // speed -> Linear(1, 128): d speed = d(pre-activation) . W_se0 (ds1 is masked by ReLU and
+        // dropout and dropout-scaled in backward_heads)
+        RUN(net, "heads_bwd.dspeed", 2.0 * B * 128, 4.0 * B * 129, s,
+            launch_rowdot(ws + net->ds1, bufs->params + A.se0.w, dspeed, B, 128, 128, s));
+    }
+    if (dimage) {
+        CILRS_CHECK(net->bwd_done & (1u << 5), "input_grads: dimage needs segment 5 (stem) of "
+                    "cilrs_net_backward after the forward");
+        const ConvG& g0 = net->cg[0];
+        RUN(net, "conv_dgrad.stem", 2.0 * g0.M * 64 * 147,
+            4.0 * g0.M * 64 + 12.0 * B * net->H * net->W, s,
+            launch_stem_dgrad_f32(ws + net->G[1], bufs->params + A.convs[0].w, dimage, sn, sc, sh, sw,
+                                  B, net->H, net->W, s));
+    }
+    return 0;
 }
 
 static int backward_heads(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
@@ -2501,6 +2575,13 @@ int cilrs_stem_conv_fwd(const float* x4, const float* w, float* y, float* bn_par
     CILRS_CHECK(rows > 0, "stem_conv_fwd: geometry %dx%dx%d not served", N, H, W);
     if (partial_rows) *partial_rows = rows;
     return launch_stem_f32(x4, w, y, bn_partial, N, H, W, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cilrs_stem_conv_dgrad(const float* dy, const float* w, float* dx, long sn, long sc, long sh,
+                          long sw, int N, int H, int W, void* stream) {
+    CILRS_CHECK(dy && w && dx, "stem_conv_dgrad: NULL argument");
+    return launch_stem_dgrad_f32(dy, w, dx, sn, sc, sh, sw, N, H, W,
+                                 reinterpret_cast<hipStream_t>(stream));
 }
 
 size_t cilrs_stem_conv_wgrad_scratch_floats(int N, int H, int W) {

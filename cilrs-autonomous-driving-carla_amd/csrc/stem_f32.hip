@@ -496,7 +496,141 @@ int launch_stem_wgrad_t(const StemWgradArgs& a, const StemWgradPlan& p, float* d
     return 0;
 }
 
+// ---- data gradient of the stem -----------------------------------------------------------------------
+// d image[n][c][ih][iw] = sum over (oh, ow, co) with ih = 2 oh - 3 + kh, iw = 2 ow - 3 + kw of
+// w[co][kh][kw][c] * dy[n][oh][ow][co]  (input gradients through visual_encoder.0: saliency maps,
+// attribution, robustness checks).  Space-to-depth: the 12 values (a, b, c) of the input patch
+// (2 p + a, 2 q + b) are a 4 x 4 stride-1 correlation of dy over 64 channels,
+//   dx[2p+a][2q+b][c] = sum_{t,u < 4} sum_co dy[p-1+t][q-1+u][co] * w[co][5+a-2t][5+b-2u][c]
+// (taps outside the 7 x 7 filter are zero weights).  One GEMM: M = patches, N = 12 (a, b, c) padded
+// to 16, K = 16 taps x 64 channels, on v_mfma_f32_16x16x4_f32 (exact fp32):
+//   * a tile is DG_R x DG_Q patches (four 16-patch M-blocks, one patch row each); the dy pixels it
+//     reads, (DG_R + 3) x (DG_Q + 3) of them with zeros outside the image, are copied into LDS;
+//   * wave t owns filter row t of the 4 x 4 correlation (K split four ways); its 256 weights
+//     (4 taps x 64 channels, this lane's column) live in REGISTERS for the life of the workgroup;
+//   * a lane's A operand is a ds_read_b128 of 4 channels of one dy pixel, feeding 4 MFMAs (the
+//     channel order inside K is permuted accordingly, the same for A and B);
+//   * the four waves' partial products meet in LDS and are summed in wave order (no atomics: the
+//     result is bit-identical from run to run), then written in the caller's NCHW strides.
+constexpr int DG_R = 4, DG_Q = 16;
+constexpr int DG_TR = DG_R + 3, DG_TC = DG_Q + 3;        // dy rows / columns a tile reads
+constexpr int DG_PITCH = 68;     // floats per dy pixel in LDS: 16 consecutive pixels cover 64 banks
+constexpr int DG_RED = 17;       // floats per patch of the reduction scratch
+constexpr int DG_LDS_FLOATS = DG_TR * DG_TC * DG_PITCH;
+static_assert(4 * DG_R * DG_Q * DG_RED <= DG_LDS_FLOATS, "reduction scratch fits in the dy tile");
+
+struct StemDgradArgs {
+    const float* dy;        // [N][Ho][Wo][64]
+    const float* w;         // OHWI [64][7][7][3]
+    float* dx;              // logical NCHW [N][3][H][W], element strides sn, sc, sh, sw
+    long sn, sc, sh, sw;
+    int N, H, W, Ho, Wo;
+    int tiles_w, tiles_per_img, ntiles;
+};
+
+__global__ __launch_bounds__(256) void stem_dgrad_f32_kernel(const StemDgradArgs a) {
+    __shared__ __attribute__((aligned(16))) float sm[DG_LDS_FLOATS];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int t = __builtin_amdgcn_readfirstlane(tid >> 6);      // filter row of the correlation
+    const int l15 = lane & 15, lg = lane >> 4;
+
+    // B[k][j] of MFMA (u, cb, s): k = lg <-> channel 16 cb + 4 lg + s, j = l15 = (a, b, c)
+    float bw[4][4][4];
+    {
+        const int ja = l15 / 6, jb = (l15 / 3) & 1, jc = l15 % 3;
+        const int kh = 5 + ja - 2 * t;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int kw = 5 + jb - 2 * u;
+            const bool ok = l15 < 12 && kh >= 0 && kh < 7 && kw >= 0 && kw < 7;
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int co = 16 * cb + 4 * lg + s;
+                    bw[u][cb][s] = ok ? a.w[co * 147 + (kh * 7 + kw) * 3 + jc] : 0.f;
+                }
+        }
+    }
+
+    for (int tile = (int)blockIdx.x; tile < a.ntiles; tile += (int)gridDim.x) {
+        const int n = tile / a.tiles_per_img, r = tile - n * a.tiles_per_img;
+        const int p0 = (r / a.tiles_w) * DG_R, q0 = (r % a.tiles_w) * DG_Q;
+        __syncthreads();                               // the previous tile's reduction is read
+        // dy pixels (p0 - 1 .. p0 + DG_R + 1) x (q0 - 1 .. q0 + DG_Q + 1), zero outside the image
+        for (int e = tid; e < DG_TR * DG_TC * 16; e += 256) {
+            const int px = e >> 4, c4 = e & 15;
+            const int rr = px / DG_TC, cc = px - rr * DG_TC;
+            const int oh = p0 - 1 + rr, ow = q0 - 1 + cc;
+            f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (oh >= 0 && oh < a.Ho && ow >= 0 && ow < a.Wo)
+                v = *reinterpret_cast<const f32x4*>(a.dy + (((size_t)n * a.Ho + oh) * a.Wo + ow) * 64 + c4 * 4);
+            *reinterpret_cast<f32x4*>(sm + px * DG_PITCH + c4 * 4) = v;
+        }
+        __syncthreads();
+
+        f32x4 acc[DG_R];
+#pragma unroll
+        for (int i = 0; i < DG_R; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // A[m][k] of M-block i: patch (p0 + i, q0 + l15), dy pixel (i + t, l15 + u) of the tile
+        const float* ab = sm + (t * DG_TC + l15) * DG_PITCH + 4 * lg;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) {
+                f32x4 av[DG_R];
+#pragma unroll
+                for (int i = 0; i < DG_R; ++i)
+                    av[i] = *reinterpret_cast<const f32x4*>(ab + (i * DG_TC + u) * DG_PITCH + 16 * cb);
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+#pragma unroll
+                    for (int i = 0; i < DG_R; ++i)
+                        acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][s], bw[u][cb][s], acc[i], 0, 0, 0);
+            }
+        __syncthreads();                               // every wave is done with the dy tile
+        // D[m][j]: lane (lg, l15), register rr = patch column 4 lg + rr of M-block i, column l15
+#pragma unroll
+        for (int i = 0; i < DG_R; ++i)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr)
+                sm[(t * DG_R * DG_Q + i * DG_Q + 4 * lg + rr) * DG_RED + l15] = acc[i][rr];
+        __syncthreads();
+        // 12 x 64 results, iw fastest: e = (((c * 2 + a) * DG_R + i) * DG_Q + q) * 2 + b
+        for (int e = tid; e < 12 * DG_R * DG_Q; e += 256) {
+            const int b = e & 1, q = (e >> 1) % DG_Q, i = (e / (2 * DG_Q)) % DG_R;
+            const int ca = e / (2 * DG_Q * DG_R), c = ca >> 1, ja = ca & 1;
+            const int m = i * DG_Q + q, j = ja * 6 + b * 3 + c;
+            float v = sm[m * DG_RED + j];
+#pragma unroll
+            for (int w = 1; w < 4; ++w) v += sm[(w * DG_R * DG_Q + m) * DG_RED + j];
+            const int ih = 2 * (p0 + i) + ja, iw = 2 * (q0 + q) + b;
+            if (ih < a.H && iw < a.W) a.dx[n * a.sn + c * a.sc + ih * a.sh + iw * a.sw] = v;
+        }
+    }
+}
+
 }  // namespace
+
+int launch_stem_dgrad_f32(const float* dy, const float* w, float* dx, long sn, long sc, long sh,
+                          long sw, int N, int H, int W, hipStream_t s) {
+    CILRS_CHECK(dy && w && dx, "stem_dgrad_f32: NULL tensor");
+    CILRS_CHECK(N > 0 && H > 0 && W > 0, "stem_dgrad_f32: empty geometry %dx%dx%d", N, H, W);
+    StemDgradArgs a;
+    a.dy = dy; a.w = w; a.dx = dx;
+    a.sn = sn; a.sc = sc; a.sh = sh; a.sw = sw;
+    a.N = N; a.H = H; a.W = W;
+    a.Ho = (H + 6 - 7) / 2 + 1; a.Wo = (W + 6 - 7) / 2 + 1;
+    a.tiles_w = cdiv(a.Wo, DG_Q);
+    a.tiles_per_img = cdiv(a.Ho, DG_R) * a.tiles_w;
+    CILRS_CHECK((long long)N * a.tiles_per_img < (1ll << 31), "stem_dgrad_f32: too many tiles");
+    a.ntiles = N * a.tiles_per_img;
+    // four workgroups per CU (36 KB of LDS each): while one copies its dy tile the others multiply
+    const int resident = 4 * device_cus();
+    stem_dgrad_f32_kernel<<<a.ntiles < resident ? a.ntiles : resident, 256, 0, s>>>(a);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
 
 // rows of the [2][64][rows] column partials the launch writes; 0 = this geometry is not served here
 // (the caller keeps the implicit GEMM)

@@ -110,6 +110,17 @@ int cilrs_net_forward(cilrs_net* net, const cilrs_buffers* bufs, const float* im
                       int train, float dropout_p, uint64_t seed, float* controls,
                       float* pred_speed, void* stream);
 
+/* model.eval() forward that keeps its graph -- torch.autograd through the reference's module in
+ * eval mode (frozen BatchNorm): the same outputs as cilrs_net_forward(train = 0), computed by the
+ * train-mode launch sequence so that every activation cilrs_net_backward and
+ * cilrs_net_input_grads read is kept.  Every BatchNorm uses the running statistics; the running
+ * buffers and num_batches_tracked are not touched; no dropout.  cilrs_net_backward after it is
+ * the backward of that graph (BatchNorm with fixed statistics: d input = gamma * rstd * g).
+ * fp32 plans of every variant; a CILRS_PLAN_BF16_TRAIN plan rejects it. */
+int cilrs_net_forward_frozen(cilrs_net* net, const cilrs_buffers* bufs, const float* image, long sn,
+                             long sc, long sh, long sw, const float* speed, const int64_t* command,
+                             float* controls, float* pred_speed, void* stream);
+
 /* Byte offset, inside the workspace, of the plan's int32[4] status words.  The library zeroes them
  * ONCE per workspace (the first entry point that sees a workspace pointer); after that the kernels
  * only ever SET them, so a word means "since the caller last cleared it" (sticky): read them after
@@ -266,12 +277,21 @@ int cilrs_loss_fwd_bwd(const float* controls, const float* target_controls,
                        float* dpred_speed, float* loss_out, void* stream);
 
 /* loss.backward() (notebook/notebook.ipynb:552) for the graph recorded by the last train-mode
- * cilrs_net_forward: writes (overwrites) every parameter gradient of the segments
+ * cilrs_net_forward (or cilrs_net_forward_frozen: BatchNorm with fixed statistics): writes (overwrites) every parameter gradient of the segments
  * [seg_begin, seg_end) into bufs->grads.  Segments, in execution order:
  * 0 heads, 1 layer4, 2 layer3, 3 layer2, 4 layer1, 5 stem  (so data-parallel callers can
  * all-reduce a finished segment's gradient range while the next one runs). */
 int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
                        const float* dpred_speed, int seg_begin, int seg_end, void* stream);
+/* Gradients with respect to the INPUTS (image.grad / speed.grad after loss.backward(), or
+ * torch.autograd.grad(out, image) -- saliency maps, d controls / d speed) of the graph of the last
+ * cilrs_net_forward(train != 0) or cilrs_net_forward_frozen on this plan, after
+ * cilrs_net_backward of that forward: dimage (may be NULL) = logical NCHW f32 [B,3,H,W] with
+ * element strides (sn,sc,sh,sw), overwritten -- needs segment 5 of that backward; dspeed (may be
+ * NULL) = f32 [B], overwritten -- needs segment 0.  Both are plain sums in a fixed order
+ * (bit-identical from run to run). */
+int cilrs_net_input_grads(cilrs_net* net, const cilrs_buffers* bufs, float* dimage, long sn, long sc,
+                          long sh, long sw, float* dspeed, void* stream);
 /* float range [begin,end) of the gradient arena that segment `seg` produces */
 int cilrs_segment_range(int seg, size_t* begin, size_t* end);
 /* the same for architecture variant `variant` (0 = the reference's ResNet-34, 1 = ResNet-50) */
@@ -310,6 +330,12 @@ int cilrs_stem_conv_fwd(const float* x4, const float* w, float* y, float* bn_par
 size_t cilrs_stem_conv_wgrad_scratch_floats(int N, int H, int W);
 int cilrs_stem_conv_wgrad(const float* x4, const float* dy, float* dw, float* scratch,
                           size_t scratch_floats, int N, int H, int W, void* stream);
+
+/* ... and its data gradient (d image through that layer: torch.nn.grad.conv2d_input):
+ * dx = logical NCHW f32 [N,3,H,W] with element strides (sn,sc,sh,sw), overwritten, from
+ * dy = [N,Ho,Wo,64] and w = OHWI [64,7,7,3].  Any geometry; no scratch; no atomics. */
+int cilrs_stem_conv_dgrad(const float* dy, const float* w, float* dx, long sn, long sc, long sh,
+                          long sw, int N, int H, int W, void* stream);
 
 /* loss.backward() + optimizer.step() (notebook/notebook.ipynb:552, 555) in ONE call for steps
  * without gradient clipping: cilrs_net_backward over all six segments, and the Adam update of a
