@@ -160,10 +160,10 @@ int launch_augment_u8(const unsigned char* frames, const cilrs_aug_params* param
                       int W, float* out_f32, unsigned char* out_u8, hipStream_t s) {
     CILRS_CHECK(B >= 1 && H >= 2 && W >= 2 && (size_t)B * H * W < (1u << 31),
                 "augment: bad batch geometry");
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
     augment_u8_kernel<<<cdiv(B * H * W, 256), 256, 0, s>>>(frames, params, B, H, W, out_f32, out_u8,
-                                                           mean[0], mean[1], mean[2], stdv[0],
-                                                           stdv[1], stdv[2]);
+                                                           kImageMean[0], kImageMean[1],
+                                                           kImageMean[2], kImageStd[0],
+                                                           kImageStd[1], kImageStd[2]);
     CILRS_LAUNCH_CHECK();
     return 0;
 }

@@ -1098,16 +1098,7 @@ int grid_for(size_t total, int per_block = 256, int cap = 4096) {
 }
 
 // one 1,024-thread workgroup per CU: every workgroup of the finalize-inside-apply kernels is resident
-int apply_grid_cap() {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 64;
-        cus = p.multiProcessorCount > 0 ? p.multiProcessorCount : 64;
-    }
-    return cus;
-}
+int apply_grid_cap() { return device_cus(); }
 
 struct ColPlan { int nblk; int rows_per_block; };
 int col_groups(int C) { return C > 1024 ? C / 1024 : 1; }

@@ -48,10 +48,14 @@ const char* last_error();
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // Per-DEVICE launch state (one process may drive several devices): the CU count of the current
-// device, and "is this the first time `key` (a kernel) is prepared on the current device" for
-// function attributes such as the dynamic-LDS limit.
+// device, and a kernel's dynamic-LDS limit, set once per (kernel, device) -- safe to call on every
+// launch and from several threads; non-zero (with set_error) when the runtime refuses it.
 int device_cus();
-bool once_per_device(const void* key);
+int set_max_dynamic_lds(const void* kernel, int bytes);
+
+// ImageNet mean / std that normalise the uint8 camera frames
+constexpr float kImageMean[3] = {0.485f, 0.456f, 0.406f};
+constexpr float kImageStd[3] = {0.229f, 0.224f, 0.225f};
 
 // Tuning / diagnostic switches whose measured result is a recorded negative
 // are COMPILED OUT of the product library: experiment_env() is the constant default unless the

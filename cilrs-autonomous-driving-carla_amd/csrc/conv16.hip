@@ -444,10 +444,8 @@ Conv16Plan conv16_plan(const ConvF16Args& a) {
 template <typename T, int BN, int EPI, int NST = 3>
 int launch_conv16p_epi(const ConvF16Args& a, const Conv16Plan& p, hipStream_t s) {
     constexpr size_t lds = conv16p_lds<BN, NST>();
-    if (once_per_device(reinterpret_cast<const void*>(&conv16p_kernel<T, BN, NST, EPI>))) {
-        CILRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv16p_kernel<T, BN, NST, EPI>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
+    if (set_max_dynamic_lds(reinterpret_cast<const void*>(&conv16p_kernel<T, BN, NST, EPI>), (int)lds))
+        return 1;
     conv16p_kernel<T, BN, NST, EPI><<<p.grid, 256, lds, s>>>(a);
     CILRS_LAUNCH_CHECK();
     return 0;

@@ -922,13 +922,9 @@ int launch_cfg(const ConvArgs& a, int M, int Krow, int KT, hipStream_t s) {
     constexpr int B_FLOATS = (MODE == 0) ? BN * APIT : BK * (SWZ ? BN : BN + 4);
     constexpr int NSTAGE = DMA ? 3 : 2;
     constexpr size_t lds = (size_t)(NSTAGE * BM * APIT + NSTAGE * B_FLOATS) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        CILRS_HIP(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&conv_igemm_kernel<BM, BN, WM, WN, TU, MODE, DMA>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
+    if (set_max_dynamic_lds(
+            reinterpret_cast<const void*>(&conv_igemm_kernel<BM, BN, WM, WN, TU, MODE, DMA>), (int)lds))
+        return 1;
     dim3 grid(cdiv(M, BM) * (a.Cout / BN), 1, a.splitk > 1 ? a.splitk : 1);
     conv_igemm_kernel<BM, BN, WM, WN, TU, MODE, DMA><<<grid, 256, lds, s>>>(a, M, Krow, KT);
     CILRS_LAUNCH_CHECK();
@@ -1250,14 +1246,10 @@ int launch_conv_dgrad(const DgradArgs& d, hipStream_t s) {
                         c.w_cin % 4 == 0,
                     "conv_dgrad: operands must be 16-byte aligned");
         constexpr size_t lds = (size_t)(2 * 64 * BK + 2 * BK * 64) * sizeof(float);
-        static bool attr_set = false;
-        if (!attr_set) {
-            CILRS_HIP(hipFuncSetAttribute(
-                reinterpret_cast<const void*>(
-                    &conv_igemm_kernel<64, 64, 2, 2, true, 1, false, true>),
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_set = true;
-        }
+        if (set_max_dynamic_lds(
+                reinterpret_cast<const void*>(&conv_igemm_kernel<64, 64, 2, 2, true, 1, false, true>),
+                (int)lds))
+            return 1;
         conv_igemm_kernel<64, 64, 2, 2, true, 1, false, true>
             <<<dim3(total, 1, 1), 256, lds, s>>>(c, 0, c.KH * c.KW * c.Cin, 0);
         CILRS_LAUNCH_CHECK();

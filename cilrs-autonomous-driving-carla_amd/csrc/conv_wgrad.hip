@@ -436,16 +436,9 @@ int launch_conv_wgrad(const WgradArgs& a_in, hipStream_t s) {
     // CILRS_WGRAD_PIN=0: let the compiler place the LDS reads (A/B switch for tools/conv_bench.py)
     static const bool pin = experiment_env("CILRS_WGRAD_PIN", 1) != 0;
     if (p.bt == 128) {
-        static bool attr = false;
-        if (!attr) {
-            CILRS_HIP(hipFuncSetAttribute(
-                reinterpret_cast<const void*>(&conv_wgrad_kernel<128, true, true>),
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            CILRS_HIP(hipFuncSetAttribute(
-                reinterpret_cast<const void*>(&conv_wgrad_kernel<128, true, false>),
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr = true;
-        }
+        if (set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wgrad_kernel<128, true, true>), (int)lds) ||
+            set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wgrad_kernel<128, true, false>), (int)lds))
+            return 1;
         if (pin)
             conv_wgrad_kernel<128, true, true><<<grid, 256, lds, s>>>(a, Mpix, p.splits,
                                                                       p.tiles_ci, p.ncols, p.ntiles, ntiles_co, xcd);

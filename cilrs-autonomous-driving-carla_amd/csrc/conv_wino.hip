@@ -1091,13 +1091,8 @@ constexpr size_t kWinoLds = (size_t)2 * (16 * WT * WP + 16 * WK * WP) * sizeof(f
 // (a plan calls this when it is built: the attribute must not be set for the first time inside a
 //  stream capture)
 int wino_prepare() {
-    if (once_per_device(reinterpret_cast<const void*>(&conv_wino_kernel<false>))) {
-        CILRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_kernel<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWinoLds));
-        CILRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_kernel<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWinoLds));
-    }
-    return 0;
+    return set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wino_kernel<false>), (int)kWinoLds) ||
+           set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wino_kernel<true>), (int)kWinoLds);
 }
 
 // How a launch is cut: `full` 64-tile groups on the main kernel, the remaining tiles as 16-tile
@@ -1212,10 +1207,7 @@ int launch_conv_wino_wgrad(const WinoWgradArgs& a_in, hipStream_t s) {
     CILRS_CHECK((size_t)a.N * a.H * a.W * a.C * 4 < (1ull << 31) &&
                     (size_t)a.N * a.H * a.W * a.K * 4 < (1ull << 31),
                 "conv_wino_wgrad: tensor too large for 32-bit offsets");
-    if (once_per_device(reinterpret_cast<const void*>(&wino_wgrad_kernel))) {
-        CILRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_wgrad_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWinoGLds));
-    }
+    if (set_max_dynamic_lds(reinterpret_cast<const void*>(&wino_wgrad_kernel), (int)kWinoGLds)) return 1;
     wino_wgrad_split(a.N, a.H, a.W, a.C, a.K, &a.splits, &a.tiles_per_split);
     wino_wgrad_kernel<<<a.splits * (a.C / 64) * (a.K / 64), WTHREADS, kWinoGLds, s>>>(a);
     CILRS_LAUNCH_CHECK();

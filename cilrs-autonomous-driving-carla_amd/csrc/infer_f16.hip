@@ -509,12 +509,7 @@ __global__ __launch_bounds__(256) void avgpool_f16_kernel(const T* __restrict__ 
 template <typename T, int BM, int BN>
 static int launch_conv_f16_cfg(const ConvF16Args& a, int M, hipStream_t s) {
     constexpr size_t lds = (size_t)2 * (BM + BN) * HPITCH * 2;
-    static bool attr_set = false;
-    if (!attr_set) {
-        CILRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16_kernel<T, BM, BN>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
+    if (set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_f16_kernel<T, BM, BN>), (int)lds)) return 1;
     conv_f16_kernel<T, BM, BN><<<cdiv(M, BM) * (a.Cout / BN), 256, lds, s>>>(a);
     CILRS_LAUNCH_CHECK();
     return 0;
@@ -571,27 +566,10 @@ void conv_f16_up2_classes(ConvF16Args& c) {
 template <typename T>
 static int launch_conv_f16_train_blocks(const ConvF16Args& a, int blocks, hipStream_t s) {
     constexpr size_t lds = (size_t)2 * (64 + 64) * HPITCH * 2;
-    if (once_per_device(reinterpret_cast<const void*>(&conv_f16_kernel<T, 64, 64, true>)))
-        CILRS_HIP(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&conv_f16_kernel<T, 64, 64, true>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_f16_kernel<T, 64, 64, true>), (int)lds))
+        return 1;
     if (blocks <= 0) return 0;
     conv_f16_kernel<T, 64, 64, true><<<blocks, 256, lds, s>>>(a);
-    CILRS_LAUNCH_CHECK();
-    return 0;
-}
-
-template <typename T>
-static int launch_conv_f16_train_t(const ConvF16Args& a, int M, hipStream_t s) {
-    constexpr size_t lds = (size_t)2 * (64 + 64) * HPITCH * 2;
-    static bool attr_set = false;
-    if (!attr_set) {
-        CILRS_HIP(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&conv_f16_kernel<T, 64, 64, true>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
-    conv_f16_kernel<T, 64, 64, true><<<cdiv(M, 64) * (a.Cout / 64), 256, lds, s>>>(a);
     CILRS_LAUNCH_CHECK();
     return 0;
 }
@@ -625,8 +603,9 @@ int launch_conv_f16_train(const ConvF16Args& a, hipStream_t s) {
     // large layers: persistent 128-row tiles (conv16.hip); -1 = this launch stays on 64x64
     const int rc = launch_conv16_large(a, s);
     if (rc >= 0) return rc;
-    return a.bf16 ? launch_conv_f16_train_t<__bf16>(a, M, s)
-                  : launch_conv_f16_train_t<_Float16>(a, M, s);
+    const int blocks = cdiv(M, 64) * (a.Cout / 64);
+    return a.bf16 ? launch_conv_f16_train_blocks<__bf16>(a, blocks, s)
+                  : launch_conv_f16_train_blocks<_Float16>(a, blocks, s);
 }
 
 template <typename T>

@@ -18,6 +18,8 @@
 
 #include <algorithm>
 #include <map>
+#include <mutex>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -47,9 +49,15 @@ int device_cus() {
     }
     return cus[dev];
 }
-bool once_per_device(const void* key) {
-    static std::map<std::pair<const void*, int>, bool> seen;
-    return seen.emplace(std::make_pair(key, current_device()), true).second;
+int set_max_dynamic_lds(const void* kernel, int bytes) {
+    static std::mutex mu;
+    static std::set<std::pair<const void*, int>> done;     // (kernel, device)
+    const std::pair<const void*, int> key(kernel, current_device());
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.count(key)) return 0;
+    CILRS_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done.insert(key);
+    return 0;
 }
 
 #ifdef CILRS_EXPERIMENTS
@@ -1163,25 +1171,67 @@ int cilrs_dropout(float* a, int rows, int cols, int ld, float p, uint64_t seed, 
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
-static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const float* speed,
-                           const int64_t* command, int train, float dropout_p, uint64_t seed,
-                           float* controls, float* pred_speed, hipStream_t s, int half = 0,
-                           bool frozen = false) {
+// Weight-derived eval state, cached across calls: the channel-padded stem weights and every
+// layer's BatchNorm scale/shift (prep_key, eval_prep), and for half = 1 / 2 the 16-bit folded
+// weights / biases (fold_key, fold_half, fold_prep).  Current while the caller's weights key is set
+// and unchanged and the buffers are the ones the state was computed from.
+static bool eval_state_current(const cilrs_net* net, const cilrs_buffers* bufs, int half) {
+    const bool prep = net->weights_key != 0 && net->prep_key == net->weights_key &&
+                      net->prep_bufs[0] == (const void*)bufs->params &&
+                      net->prep_bufs[1] == (const void*)bufs->bn_running &&
+                      net->prep_bufs[2] == (const void*)bufs->workspace;
+    return prep && (!half || (net->fold_key == net->weights_key && net->fold_half == half));
+}
+
+// eval: running statistics -> per-channel scale/shift (one launch for all 36 layers), folded with
+// ReLU / residual add into each conv's epilogue; no pre-BN tensor is stored
+static int eval_prep(cilrs_net* net, const cilrs_buffers* bufs, hipStream_t s) {
+    if (eval_state_current(net, bufs, 0)) return 0;
     const Arch& A = *net->A;
     float* ws = reinterpret_cast<float*>(bufs->workspace);
-    net->ws_base = ws;
-    CILRS_CHECK(!(frozen && (train || half || net->bf16_train)),
-                "frozen forward: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan rejects it)");
-    if (zero_counters_once(net, bufs->workspace, s)) return 1;
+    RUN(net, "transform", 0.0, 0.0, s,
+        launch_pad_cin3_to_4(bufs->params + A.convs[0].w, ws + net->w4, 64 * 49, s));
+    RUN(net, "bn_fwd.eval", 0.0, 0.0, s,
+        launch_bn_eval_stats_all(net->bn_table, bufs->params, bufs->bn_running, ws, 1e-5f, s));
+    net->prep_key = net->weights_key;
+    net->prep_bufs[0] = bufs->params; net->prep_bufs[1] = bufs->bn_running;
+    net->prep_bufs[2] = bufs->workspace;
+    net->fold_key = 0;
+    return 0;
+}
+
+// 16-bit eval: BatchNorm folded into the fp16 / bf16 trunk and stem weights (reads the scale/shift
+// of eval_prep, which runs first)
+static int fold_prep(cilrs_net* net, const cilrs_buffers* bufs, int half, hipStream_t s) {
+    if (eval_state_current(net, bufs, half)) return 0;
+    const Arch& A = *net->A;
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
+    const int bf16 = half == 2;
+    RUN(net, "transform", 0.0, 0.0, s,
+        launch_fold_bn_f16(net->f16_table, bufs->params, ws,
+                           reinterpret_cast<cilrs_half*>(ws + net->f16_w), ws + net->f16_bias, bf16,
+                           s));
+    RUN(net, "transform", 0.0, 0.0, s,
+        launch_fold_stem_f16(bufs->params + A.convs[0].w, ws + net->cg[0].stats,
+                             h16(ws, net->stem16_w), ws + net->stem16_b, bf16, s));
+    net->fold_key = net->weights_key;
+    net->fold_half = half;
+    return 0;
+}
+
+// Trunk of the graph-keeping forwards -- the fp32 train step, the bf16 training mode and the frozen
+// eval-with-grad forward: BatchNorm on the batch statistics (train) or the running ones (frozen,
+// scale/shift from eval_prep); keeps every activation the backward pass reads (y, z, the max-pool
+// argmax).  *feat: the last feature map, or nullptr when it is already pooled into `combined`.
+static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train, bool frozen,
+                           hipStream_t s, const float** feat) {
+    const Arch& A = *net->A;
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
     const float* P = bufs->params;
     float* R = bufs->bn_running;
     const int B = net->B;
     const float eps = 1e-5f, mom = 0.1f;
     const bool bf16t = train && net->bf16_train;      // trunk convolutions on the bf16 matrix pipe
-    // train: batch statistics; frozen: the running statistics -- both keep every activation the
-    // backward pass reads (y, z, the max-pool argmax, the head inputs)
-    const bool graph = train || frozen;
-    net->bwd_done = 0;
 
     // (residual: fp32 tensor, or the bf16 identity in the bf16 training mode)
     auto bn = [&](int ci, const void* residual_v, int relu, int pre_nblk, hipStream_t st = nullptr,
@@ -1215,309 +1265,293 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
     };
 
     // ---- stem: conv7x7/s2 + BN + ReLU + maxpool3x3/s2 ----
-    const bool same_bufs = net->prep_bufs[0] == (const void*)bufs->params &&
-                           net->prep_bufs[1] == (const void*)bufs->bn_running &&
-                           net->prep_bufs[2] == (const void*)bufs->workspace;
-    const bool prep_cached = !train && net->weights_key != 0 && same_bufs &&
-                             net->prep_key == net->weights_key;
-    if (!prep_cached)
-        RUN(net, "transform", 0.0, 0.0, s,
-            launch_pad_cin3_to_4(P + A.convs[0].w, ws + net->w4, 64 * 49, s));
-    if (train) { net->prep_key = 0; net->fold_key = 0; }     // weights / BN buffers are about to change
-    const float* cur;
-    if (graph) {
-        // this step's weight images -- the Winograd-transformed filters (forward + data-gradient
-        // forms), in the bf16 mode the 16-bit arena and the transposed, tap-flipped copies the data
-        // gradients read -- depend on the parameters only: they are built on the side stream while
-        // the stem and the max-pool run (memory-bound launches beside a matrix-pipe-bound one); the
-        // first residual block waits for them
-        {
-            hipStream_t ts = s;
-            const bool fork = use_overlap(net) && (net->wino_table.n || bf16t);
-            if (fork) {
-                if (gbuf_side_begin(net, s)) return 1;
-                ts = net->side[0];
-            }
-            if (net->wino_table.n)
-                RUN(net, "transform", 0.0, 4.0 * 4.6 * (double)net->wino_table.blk_begin[net->wino_table.n] * 256, ts,
-                    launch_wino_weights_all(net->wino_table, P, ws + net->wino_base, ts));
-            if (bf16t) {
-                RUN(net, "transform", 0.0, 6.0 * A.arena_floats, ts,
-                    launch_f32_to_f16(P, h16(ws, net->w16_all), A.arena_floats, 1, ts));
-                RUN(net, "transform", 0.0, 0.0, ts,
-                    launch_transpose_flip_f16_all(net->tr_table, P, h16(ws, net->wT16), 1, ts));
-            }
-            if (fork) {
-                CILRS_HIP(hipEventRecord(net->wprep_ev, ts));
-                net->wprep_pending = true;
-            }
+    // this step's weight images -- the Winograd-transformed filters (forward + data-gradient
+    // forms), in the bf16 mode the 16-bit arena and the transposed, tap-flipped copies the data
+    // gradients read -- depend on the parameters only: they are built on the side stream while
+    // the stem and the max-pool run (memory-bound launches beside a matrix-pipe-bound one); the
+    // first residual block waits for them
+    {
+        hipStream_t ts = s;
+        const bool fork = use_overlap(net) && (net->wino_table.n || bf16t);
+        if (fork) {
+            if (gbuf_side_begin(net, s)) return 1;
+            ts = net->side[0];
         }
-        int nb = 0;                             // batch statistics fused into the conv epilogue
-        if (const int srows = stem_f32_rows(B, net->H, net->W)) {
-            // (weights in registers, k = 7 x 22 instead of 13 x 16: stem_f32.hip)
-            RUN(net, "conv_fwd.stem", 2.0 * net->cg[0].M * 64 * 147,
-                16.0 * B * net->H * net->W + 4.0 * net->cg[0].M * 64, s,
-                launch_stem_f32(ws + net->x4, P + A.convs[0].w, ws + net->cg[0].y,
-                                ws + net->bn_partial, B, net->H, net->W, s));
-            nb = srows;
-        } else if (conv_fwd(net, A.convs[0], net->cg[0], ws + net->x4, 4, ws + net->w4,
-                            ws + net->cg[0].y, ws, s, &nb)) {
-            return 1;
+        if (net->wino_table.n)
+            RUN(net, "transform", 0.0, 4.0 * 4.6 * (double)net->wino_table.blk_begin[net->wino_table.n] * 256, ts,
+                launch_wino_weights_all(net->wino_table, P, ws + net->wino_base, ts));
+        if (bf16t) {
+            RUN(net, "transform", 0.0, 6.0 * A.arena_floats, ts,
+                launch_f32_to_f16(P, h16(ws, net->w16_all), A.arena_floats, 1, ts));
+            RUN(net, "transform", 0.0, 0.0, ts,
+                launch_transpose_flip_f16_all(net->tr_table, P, h16(ws, net->wT16), 1, ts));
         }
-        // stem BatchNorm: statistics only -- its apply + ReLU is fused into the max-pool, the
-        // post-BN tensor (144 MB at B=128) is never written
-        if (frozen) {
-            // every layer's scale / shift from the running statistics (the prep cache of the eval
-            // path holds the same values); the other BatchNorms re-derive theirs in the bn() apply
-            if (!prep_cached) {
-                RUN(net, "bn_fwd.eval", 0.0, 0.0, s,
-                    launch_bn_eval_stats_all(net->bn_table, P, R, ws, eps, s));
-                net->prep_key = net->weights_key;
-                net->prep_bufs[0] = bufs->params; net->prep_bufs[1] = bufs->bn_running;
-                net->prep_bufs[2] = bufs->workspace;
-                net->fold_key = 0;
-            }
-        } else {
-            const ConvT& c0 = A.convs[0];
-            const ConvG& g0 = net->cg[0];
-            const BnT& b0 = A.bns[c0.bn];
-            RUN(net, "bn_fwd.stem", 0.0, 0.0, s,
-                launch_bn_train_fwd(ws + g0.y, g0.M, c0.cout, P + b0.gamma, P + b0.beta,
-                                    R + b0.rm, R + b0.rv,
-                                    reinterpret_cast<long long*>(bufs->bn_nbt) + c0.bn, mom, eps,
-                                    nullptr, 1, ws + g0.stats, ws + net->bn_partial, nullptr, nb,
-                                    s));
-        }
-        unsigned char* argmax = reinterpret_cast<unsigned char*>(bufs->workspace) + net->argmax_b;
-        RUN(net, "maxpool", 0.0, 4.0 * net->cg[0].M * 64 * 1.25, s,
-            launch_bn_relu_maxpool_fwd(ws + net->cg[0].y, ws + net->cg[0].stats, ws + net->pool,
-                                       argmax, B, net->H0, net->W0, 64, s,
-                                       bf16t ? (void*)h16(ws, net->pool16) : nullptr));
-        // (this step's weight images were requested before the stem, on the side stream)
-        if (net->wprep_pending) {
-            CILRS_HIP(hipStreamWaitEvent(s, net->wprep_ev, 0));
-            net->wprep_pending = false;
-        }
-        // ---- residual blocks: BasicBlock conv-BN-ReLU-conv-BN-(+id)-ReLU, Bottleneck with a third
-        //      conv-BN pair; the identity (or downsample branch) joins at the last BatchNorm ----
-        cur = ws + net->pool;
-        const cilrs_half* cur16 = h16(ws, net->pool16);
-        for (const BlockT& blk : A.blocks) {
-            const int chain[3] = {blk.conv1, blk.conv2, blk.conv3};
-            const int nchain = blk.conv3 >= 0 ? 3 : 2;
-            const void* identity = bf16t ? (const void*)cur16 : (const void*)cur;
-            const float* x = cur;
-            const cilrs_half* x16 = cur16;
-            // The down-sample branch (1x1 / stride-2 convolution + BatchNorm: three short launches
-            // that leave most of the chip idle) depends on the block's input only: it is built on
-            // the side stream beside conv1 / bn1 / conv2, with column-partial scratch of its own
-            // and no split-K scratch; the block's last BatchNorm -- which adds it -- waits for it.
-            bool branch_pending = false;
-            const bool branch_aside = blk.down >= 0 && use_overlap(net) && bn_sync(net, ws, 0) == nullptr;
-            auto down_branch = [&](hipStream_t st, bool aside) -> int {
-                const ConvT& cd = A.convs[blk.down];
-                const ConvG& gd = net->cg[blk.down];
-                int nbd = 0;
-                // (1: beside the main stream, own partial scratch; 2: on the main stream -- in BOTH
-                //  cases without split-K, so that the plan, hence the summation order, of this
-                //  convolution does not depend on whether the streams overlap)
-                net->side_branch = aside ? 1 : 2;
-                int rc = bf16t ? conv_fwd16(net, cd, gd, blk.down, cur16, ws, st, &nbd)
-                               : conv_fwd(net, cd, gd, cur, cd.cin, P + cd.w, ws + gd.y, ws, st, &nbd);
-                net->side_branch = 0;
-                if (rc) return 1;
-                if (bn(blk.down, nullptr, 0, nbd, st, aside)) return 1;
-                identity = bf16t ? (const void*)h16(ws, net->z16[blk.down]) : (const void*)(ws + gd.z);
-                return 0;
-            };
-            if (branch_aside) {
-                if (gbuf_side_begin(net, s)) return 1;            // the side stream sees the block's input
-                if (down_branch(net->side[0], true)) return 1;
-                CILRS_HIP(hipEventRecord(net->branch_ev, net->side[0]));
-                branch_pending = true;
-            }
-            for (int i = 0; i < nchain; ++i) {
-                const ConvT& c = A.convs[chain[i]];
-                const ConvG& g = net->cg[chain[i]];
-                nb = 0;
-                if (bf16t) {
-                    if (conv_fwd16(net, c, g, chain[i], x16, ws, s, &nb)) return 1;
-                } else {
-                    if (conv_fwd(net, c, g, x, c.cin, P + c.w, ws + g.y, ws, s, &nb)) return 1;
-                }
-                if (i == 0 && blk.down >= 0 && !branch_aside) {
-                    // (issued after conv1 so that both convolutions reading `cur` are adjacent)
-                    if (bn(chain[0], nullptr, 1, nb)) return 1;
-                    if (down_branch(s, false)) return 1;
-                } else if (i + 1 < nchain) {
-                    if (bn(chain[i], nullptr, 1, nb)) return 1;
-                } else {
-                    if (branch_pending) {
-                        CILRS_HIP(hipStreamWaitEvent(s, net->branch_ev, 0));
-                        branch_pending = false;
-                    }
-                    if (bn(chain[i], identity, 1, nb)) return 1;
-                }
-                x = ws + g.z;
-                x16 = h16(ws, net->z16[chain[i]]);
-            }
-            cur = x;
-            cur16 = x16;
-        }
-        if (bf16t) {         // features from the bf16 feature map
-            RUN(net, "heads_fwd", 0.0, 0.0, s,
-                launch_avgpool_f16(cur16, ws + net->combined, B, net->featHW, A.feat,
-                                   A.feat + 128, 1, s));
-            cur = nullptr;
-        }
-    } else {
-        // eval: running statistics -> per-channel scale/shift (one launch for all 36 layers),
-        // folded with ReLU / residual add into each conv's epilogue; no pre-BN tensor is stored
-        if (!prep_cached) {
-            RUN(net, "bn_fwd.eval", 0.0, 0.0, s,
-                launch_bn_eval_stats_all(net->bn_table, P, R, ws, eps, s));
-            net->prep_key = net->weights_key;
-            net->prep_bufs[0] = bufs->params; net->prep_bufs[1] = bufs->bn_running;
-            net->prep_bufs[2] = bufs->workspace;
-            net->fold_key = 0;
-        }
-        if (!half) {
-            if (conv_fwd(net, A.convs[0], net->cg[0], ws + net->x4, 4, ws + net->w4,
-                         ws + net->cg[0].z, ws, s, nullptr, ws + net->cg[0].stats, 1)) return 1;
-            RUN(net, "maxpool", 0.0, 4.0 * net->cg[0].M * 64 * 1.25, s,
-                launch_maxpool_fwd(ws + net->cg[0].z, ws + net->pool, nullptr, B, net->H0,
-                                   net->W0, 64, s));
-        }
-        cur = ws + net->pool;
-        if (half) {
-            // ---- fp16 trunk (BASELINE config 5): BatchNorm folded into fp16 weights, fp16 NHWC
-            //      activations, v_mfma_f32_32x32x16_f16 with fp32 accumulation (infer_f16.hip) ----
-            cilrs_half* w16 = reinterpret_cast<cilrs_half*>(ws + net->f16_w);
-            float* b16 = ws + net->f16_bias;
-            const int bf16 = half == 2;
-            cilrs_half* act[5];
-            for (int k = 0; k < 5; ++k) act[k] = reinterpret_cast<cilrs_half*>(ws + net->f16_act[k]);
-            const bool fold_cached = net->weights_key != 0 && net->fold_key == net->weights_key &&
-                                     net->fold_half == half && prep_cached;
-            if (!fold_cached) {
-                RUN(net, "transform", 0.0, 0.0, s,
-                    launch_fold_bn_f16(net->f16_table, P, ws, w16, b16, bf16, s));
-                RUN(net, "transform", 0.0, 0.0, s,
-                    launch_fold_stem_f16(P + A.convs[0].w, ws + net->cg[0].stats,
-                                         h16(ws, net->stem16_w), ws + net->stem16_b, bf16, s));
-                net->fold_key = net->weights_key;
-                net->fold_half = half;
-            }
-            // stem on the 16-bit pipe too (stem_f16.hip): conv 7x7/s2 + folded BN + ReLU from the
-            // channel-padded fp32 image, 16-bit output parked in the (otherwise unused) fp32 stem
-            // buffer, then the 16-bit max-pool straight into the first activation buffer
-            {
-                const ConvG& g0 = net->cg[0];
-                RUN(net, "conv_fwd.stem", 2.0 * g0.M * 64 * 147, 16.0 * B * net->H * net->W +
-                    2.0 * g0.M * 64, s,
-                    launch_stem_f16(ws + net->x4, h16(ws, net->stem16_w), ws + net->stem16_b,
-                                    h16(ws, g0.z), B, net->H, net->W, bf16, s));
-                RUN(net, "maxpool", 0.0, 2.0 * g0.M * 64 * 1.25, s,
-                    launch_maxpool_f16(h16(ws, g0.z), act[0], B, net->H0, net->W0, 64, bf16, s));
-            }
-            int ic = 0;                                  // index of the buffer holding `cur`
-            auto conv16 = [&](int ci, const cilrs_half* x, const cilrs_half* residual,
-                              cilrs_half* y, int relu) -> int {
-                const ConvT& c = A.convs[ci];
-                const ConvG& g = net->cg[ci];
-                ConvF16Args a;
-                memset(&a, 0, sizeof(a));
-                a.x = x; a.w = w16 + net->f16_table.w16[ci - 1];
-                a.bias = b16 + net->f16_table.bias[ci - 1];
-                a.residual = residual; a.y = y; a.bf16 = bf16;
-                a.N = B; a.H = g.H; a.W = g.W; a.Cin = c.cin; a.Ho = g.Ho; a.Wo = g.Wo;
-                a.Cout = c.cout; a.K = c.k; a.stride = c.stride; a.pad = c.pad; a.relu = relu;
-                const double bytes = 2.0 * ((double)B * g.H * g.W * c.cin + (double)g.M * c.cout *
-                                            (residual ? 2.0 : 1.0) + (double)c.cout * c.k * c.k * c.cin);
-                RUN(net, std::string("conv_fwd.") + kGroupName[c.group],
-                    2.0 * g.M * c.cout * c.k * c.k * c.cin, bytes, s, launch_conv_f16(a, s));
-                return 0;
-            };
-            for (const BlockT& blk : A.blocks) {
-                // five rotating buffers: block input, two intermediates, projected identity, output
-                const int it1 = (ic + 1) % 5, it2 = (ic + 2) % 5, iid = (ic + 3) % 5,
-                          io = (ic + 4) % 5;
-                if (conv16(blk.conv1, act[ic], nullptr, act[it1], 1)) return 1;
-                const cilrs_half* identity = act[ic];
-                if (blk.down >= 0) {
-                    if (conv16(blk.down, act[ic], nullptr, act[iid], 0)) return 1;
-                    identity = act[iid];
-                }
-                if (blk.conv3 >= 0) {
-                    if (conv16(blk.conv2, act[it1], nullptr, act[it2], 1)) return 1;
-                    if (conv16(blk.conv3, act[it2], identity, act[io], 1)) return 1;
-                } else {
-                    if (conv16(blk.conv2, act[it1], identity, act[io], 1)) return 1;
-                }
-                ic = io;
-            }
-            RUN(net, "heads_fwd", 0.0, 0.0, s,
-                launch_avgpool_f16(act[ic], ws + net->combined, B, net->featHW, A.feat,
-                                   A.feat + 128, bf16, s));
-            cur = nullptr;                               // features already pooled into `combined`
-        } else {
-        // a layer with few output pixels (single-frame inference) takes the one-launch
-        // latency kernel (conv_small.hip) instead of split-K implicit GEMM + reduce
-        auto conv_eval = [&](const ConvT& c, const ConvG& g, const float* x, float* y, int relu,
-                             const float* addend, int relu_post) -> int {
-            // one 16-wave block per 16x16 tile: worth it while every block gets its own CU
-            // CILRS_SMALL_BLOCKS / CILRS_SMALL_K: routing thresholds for tools/infer_ab.py
-            static const int max_blocks =
-                experiment_env("CILRS_SMALL_BLOCKS", kSmallConvBlocks);
-            static const int max_k = experiment_env("CILRS_SMALL_K", kSmallConvK);
-            if (cdiv(g.M, 16) * (c.cout / 16) > max_blocks || c.cin % 16 != 0 ||
-                c.k * c.k * c.cin > max_k)
-                return conv_fwd(net, c, g, x, c.cin, P + c.w, y, ws, s, nullptr, ws + g.stats,
-                                relu, addend, relu_post);
-            ConvSmallArgs a;
-            memset(&a, 0, sizeof(a));
-            a.x = x; a.w = P + c.w; a.y = y;
-            a.scale = ws + g.stats + 2 * c.cout; a.shift = ws + g.stats + 3 * c.cout;
-            a.addend = addend; a.relu = relu; a.relu_post = relu_post;
-            a.N = B; a.H = g.H; a.W = g.W; a.Cin = c.cin; a.Ho = g.Ho; a.Wo = g.Wo;
-            a.Cout = c.cout; a.K = c.k; a.stride = c.stride; a.pad = c.pad;
-            RUN(net, std::string("conv_fwd.") + kGroupName[c.group],
-                2.0 * g.M * c.cout * c.k * c.k * c.cin, 0.0, s, launch_conv_small(a, s));
-            return 0;
-        };
-        for (const BlockT& blk : A.blocks) {
-            const ConvT& c1 = A.convs[blk.conv1];
-            const ConvT& c2 = A.convs[blk.conv2];
-            const ConvG& g1 = net->cg[blk.conv1];
-            const ConvG& g2 = net->cg[blk.conv2];
-            if (conv_eval(c1, g1, cur, ws + g1.z, 1, nullptr, 0)) return 1;
-            const float* identity = cur;
-            if (blk.down >= 0) {
-                const ConvT& cd = A.convs[blk.down];
-                const ConvG& gd = net->cg[blk.down];
-                if (conv_eval(cd, gd, cur, ws + gd.z, 0, nullptr, 0)) return 1;
-                identity = ws + gd.z;
-            }
-            if (blk.conv3 >= 0) {      // Bottleneck: 1x1 -> 3x3 -> 1x1 (+ identity)
-                const ConvT& c3 = A.convs[blk.conv3];
-                const ConvG& g3 = net->cg[blk.conv3];
-                if (conv_eval(c2, g2, ws + g1.z, ws + g2.z, 1, nullptr, 0)) return 1;
-                if (conv_eval(c3, g3, ws + g2.z, ws + g3.z, 0, identity, 1)) return 1;
-                cur = ws + g3.z;
-            } else {
-                if (conv_eval(c2, g2, ws + g1.z, ws + g2.z, 0, identity, 1)) return 1;
-                cur = ws + g2.z;
-            }
-        }
+        if (fork) {
+            CILRS_HIP(hipEventRecord(net->wprep_ev, ts));
+            net->wprep_pending = true;
         }
     }
+    int nb = 0;                             // batch statistics fused into the conv epilogue
+    if (const int srows = stem_f32_rows(B, net->H, net->W)) {
+        // (weights in registers, k = 7 x 22 instead of 13 x 16: stem_f32.hip)
+        RUN(net, "conv_fwd.stem", 2.0 * net->cg[0].M * 64 * 147,
+            16.0 * B * net->H * net->W + 4.0 * net->cg[0].M * 64, s,
+            launch_stem_f32(ws + net->x4, P + A.convs[0].w, ws + net->cg[0].y,
+                            ws + net->bn_partial, B, net->H, net->W, s));
+        nb = srows;
+    } else if (conv_fwd(net, A.convs[0], net->cg[0], ws + net->x4, 4, ws + net->w4,
+                        ws + net->cg[0].y, ws, s, &nb)) {
+        return 1;
+    }
+    // stem BatchNorm: statistics only -- its apply + ReLU is fused into the max-pool, the post-BN
+    // tensor (144 MB at B=128) is never written.  (frozen: eval_prep derived every layer's scale /
+    // shift from the running statistics; the other BatchNorms re-derive theirs in the bn() apply)
+    if (!frozen) {
+        const ConvT& c0 = A.convs[0];
+        const ConvG& g0 = net->cg[0];
+        const BnT& b0 = A.bns[c0.bn];
+        RUN(net, "bn_fwd.stem", 0.0, 0.0, s,
+            launch_bn_train_fwd(ws + g0.y, g0.M, c0.cout, P + b0.gamma, P + b0.beta,
+                                R + b0.rm, R + b0.rv,
+                                reinterpret_cast<long long*>(bufs->bn_nbt) + c0.bn, mom, eps,
+                                nullptr, 1, ws + g0.stats, ws + net->bn_partial, nullptr, nb,
+                                s));
+    }
+    unsigned char* argmax = reinterpret_cast<unsigned char*>(bufs->workspace) + net->argmax_b;
+    RUN(net, "maxpool", 0.0, 4.0 * net->cg[0].M * 64 * 1.25, s,
+        launch_bn_relu_maxpool_fwd(ws + net->cg[0].y, ws + net->cg[0].stats, ws + net->pool,
+                                   argmax, B, net->H0, net->W0, 64, s,
+                                   bf16t ? (void*)h16(ws, net->pool16) : nullptr));
+    // (this step's weight images were requested before the stem, on the side stream)
+    if (net->wprep_pending) {
+        CILRS_HIP(hipStreamWaitEvent(s, net->wprep_ev, 0));
+        net->wprep_pending = false;
+    }
+    // ---- residual blocks: BasicBlock conv-BN-ReLU-conv-BN-(+id)-ReLU, Bottleneck with a third
+    //      conv-BN pair; the identity (or downsample branch) joins at the last BatchNorm ----
+    const float* cur = ws + net->pool;
+    const cilrs_half* cur16 = h16(ws, net->pool16);
+    for (const BlockT& blk : A.blocks) {
+        const int chain[3] = {blk.conv1, blk.conv2, blk.conv3};
+        const int nchain = blk.conv3 >= 0 ? 3 : 2;
+        const void* identity = bf16t ? (const void*)cur16 : (const void*)cur;
+        const float* x = cur;
+        const cilrs_half* x16 = cur16;
+        // The down-sample branch (1x1 / stride-2 convolution + BatchNorm: three short launches
+        // that leave most of the chip idle) depends on the block's input only: it is built on
+        // the side stream beside conv1 / bn1 / conv2, with column-partial scratch of its own
+        // and no split-K scratch; the block's last BatchNorm -- which adds it -- waits for it.
+        bool branch_pending = false;
+        const bool branch_aside = blk.down >= 0 && use_overlap(net) && bn_sync(net, ws, 0) == nullptr;
+        auto down_branch = [&](hipStream_t st, bool aside) -> int {
+            const ConvT& cd = A.convs[blk.down];
+            const ConvG& gd = net->cg[blk.down];
+            int nbd = 0;
+            // (1: beside the main stream, own partial scratch; 2: on the main stream -- in BOTH
+            //  cases without split-K, so that the plan, hence the summation order, of this
+            //  convolution does not depend on whether the streams overlap)
+            net->side_branch = aside ? 1 : 2;
+            int rc = bf16t ? conv_fwd16(net, cd, gd, blk.down, cur16, ws, st, &nbd)
+                           : conv_fwd(net, cd, gd, cur, cd.cin, P + cd.w, ws + gd.y, ws, st, &nbd);
+            net->side_branch = 0;
+            if (rc) return 1;
+            if (bn(blk.down, nullptr, 0, nbd, st, aside)) return 1;
+            identity = bf16t ? (const void*)h16(ws, net->z16[blk.down]) : (const void*)(ws + gd.z);
+            return 0;
+        };
+        if (branch_aside) {
+            if (gbuf_side_begin(net, s)) return 1;            // the side stream sees the block's input
+            if (down_branch(net->side[0], true)) return 1;
+            CILRS_HIP(hipEventRecord(net->branch_ev, net->side[0]));
+            branch_pending = true;
+        }
+        for (int i = 0; i < nchain; ++i) {
+            const ConvT& c = A.convs[chain[i]];
+            const ConvG& g = net->cg[chain[i]];
+            nb = 0;
+            if (bf16t) {
+                if (conv_fwd16(net, c, g, chain[i], x16, ws, s, &nb)) return 1;
+            } else {
+                if (conv_fwd(net, c, g, x, c.cin, P + c.w, ws + g.y, ws, s, &nb)) return 1;
+            }
+            if (i == 0 && blk.down >= 0 && !branch_aside) {
+                // (issued after conv1 so that both convolutions reading `cur` are adjacent)
+                if (bn(chain[0], nullptr, 1, nb)) return 1;
+                if (down_branch(s, false)) return 1;
+            } else if (i + 1 < nchain) {
+                if (bn(chain[i], nullptr, 1, nb)) return 1;
+            } else {
+                if (branch_pending) {
+                    CILRS_HIP(hipStreamWaitEvent(s, net->branch_ev, 0));
+                    branch_pending = false;
+                }
+                if (bn(chain[i], identity, 1, nb)) return 1;
+            }
+            x = ws + g.z;
+            x16 = h16(ws, net->z16[chain[i]]);
+        }
+        cur = x;
+        cur16 = x16;
+    }
+    if (bf16t) {         // features from the bf16 feature map
+        RUN(net, "heads_fwd", 0.0, 0.0, s,
+            launch_avgpool_f16(cur16, ws + net->combined, B, net->featHW, A.feat,
+                               A.feat + 128, 1, s));
+        cur = nullptr;
+    }
+    *feat = cur;
+    return 0;
+}
 
+// fp32 eval trunk: BatchNorm (scale/shift from eval_prep) folded into the conv epilogues
+static int trunk_fwd_eval32(cilrs_net* net, const cilrs_buffers* bufs, hipStream_t s,
+                            const float** feat) {
+    const Arch& A = *net->A;
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
+    const float* P = bufs->params;
+    const int B = net->B;
+    if (conv_fwd(net, A.convs[0], net->cg[0], ws + net->x4, 4, ws + net->w4,
+                 ws + net->cg[0].z, ws, s, nullptr, ws + net->cg[0].stats, 1)) return 1;
+    RUN(net, "maxpool", 0.0, 4.0 * net->cg[0].M * 64 * 1.25, s,
+        launch_maxpool_fwd(ws + net->cg[0].z, ws + net->pool, nullptr, B, net->H0,
+                           net->W0, 64, s));
+    // a layer with few output pixels (single-frame inference) takes the one-launch
+    // latency kernel (conv_small.hip) instead of split-K implicit GEMM + reduce
+    auto conv_eval = [&](const ConvT& c, const ConvG& g, const float* x, float* y, int relu,
+                         const float* addend, int relu_post) -> int {
+        // one 16-wave block per 16x16 tile: worth it while every block gets its own CU
+        // CILRS_SMALL_BLOCKS / CILRS_SMALL_K: routing thresholds for tools/infer_ab.py
+        static const int max_blocks =
+            experiment_env("CILRS_SMALL_BLOCKS", kSmallConvBlocks);
+        static const int max_k = experiment_env("CILRS_SMALL_K", kSmallConvK);
+        if (cdiv(g.M, 16) * (c.cout / 16) > max_blocks || c.cin % 16 != 0 ||
+            c.k * c.k * c.cin > max_k)
+            return conv_fwd(net, c, g, x, c.cin, P + c.w, y, ws, s, nullptr, ws + g.stats,
+                            relu, addend, relu_post);
+        ConvSmallArgs a;
+        memset(&a, 0, sizeof(a));
+        a.x = x; a.w = P + c.w; a.y = y;
+        a.scale = ws + g.stats + 2 * c.cout; a.shift = ws + g.stats + 3 * c.cout;
+        a.addend = addend; a.relu = relu; a.relu_post = relu_post;
+        a.N = B; a.H = g.H; a.W = g.W; a.Cin = c.cin; a.Ho = g.Ho; a.Wo = g.Wo;
+        a.Cout = c.cout; a.K = c.k; a.stride = c.stride; a.pad = c.pad;
+        RUN(net, std::string("conv_fwd.") + kGroupName[c.group],
+            2.0 * g.M * c.cout * c.k * c.k * c.cin, 0.0, s, launch_conv_small(a, s));
+        return 0;
+    };
+    const float* cur = ws + net->pool;
+    for (const BlockT& blk : A.blocks) {
+        const ConvT& c1 = A.convs[blk.conv1];
+        const ConvT& c2 = A.convs[blk.conv2];
+        const ConvG& g1 = net->cg[blk.conv1];
+        const ConvG& g2 = net->cg[blk.conv2];
+        if (conv_eval(c1, g1, cur, ws + g1.z, 1, nullptr, 0)) return 1;
+        const float* identity = cur;
+        if (blk.down >= 0) {
+            const ConvT& cd = A.convs[blk.down];
+            const ConvG& gd = net->cg[blk.down];
+            if (conv_eval(cd, gd, cur, ws + gd.z, 0, nullptr, 0)) return 1;
+            identity = ws + gd.z;
+        }
+        if (blk.conv3 >= 0) {      // Bottleneck: 1x1 -> 3x3 -> 1x1 (+ identity)
+            const ConvT& c3 = A.convs[blk.conv3];
+            const ConvG& g3 = net->cg[blk.conv3];
+            if (conv_eval(c2, g2, ws + g1.z, ws + g2.z, 1, nullptr, 0)) return 1;
+            if (conv_eval(c3, g3, ws + g2.z, ws + g3.z, 0, identity, 1)) return 1;
+            cur = ws + g3.z;
+        } else {
+            if (conv_eval(c2, g2, ws + g1.z, ws + g2.z, 0, identity, 1)) return 1;
+            cur = ws + g2.z;
+        }
+    }
+    *feat = cur;
+    return 0;
+}
+
+// ---- fp16 / bf16 trunk (BASELINE config 5; half = 1 / 2): BatchNorm folded into 16-bit weights
+//      (fold_prep), 16-bit NHWC activations, v_mfma_f32_32x32x16_f16 with fp32 accumulation
+//      (infer_f16.hip).  The features end up pooled into `combined` (*feat = nullptr). ----
+static int trunk_fwd_eval16(cilrs_net* net, const cilrs_buffers* bufs, int half, hipStream_t s,
+                            const float** feat) {
+    const Arch& A = *net->A;
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
+    const int B = net->B;
+    const cilrs_half* w16 = reinterpret_cast<const cilrs_half*>(ws + net->f16_w);
+    const float* b16 = ws + net->f16_bias;
+    const int bf16 = half == 2;
+    cilrs_half* act[5];
+    for (int k = 0; k < 5; ++k) act[k] = reinterpret_cast<cilrs_half*>(ws + net->f16_act[k]);
+    // stem on the 16-bit pipe too (stem_f16.hip): conv 7x7/s2 + folded BN + ReLU from the
+    // channel-padded fp32 image, 16-bit output parked in the (otherwise unused) fp32 stem
+    // buffer, then the 16-bit max-pool straight into the first activation buffer
+    {
+        const ConvG& g0 = net->cg[0];
+        RUN(net, "conv_fwd.stem", 2.0 * g0.M * 64 * 147, 16.0 * B * net->H * net->W +
+            2.0 * g0.M * 64, s,
+            launch_stem_f16(ws + net->x4, h16(ws, net->stem16_w), ws + net->stem16_b,
+                            h16(ws, g0.z), B, net->H, net->W, bf16, s));
+        RUN(net, "maxpool", 0.0, 2.0 * g0.M * 64 * 1.25, s,
+            launch_maxpool_f16(h16(ws, g0.z), act[0], B, net->H0, net->W0, 64, bf16, s));
+    }
+    int ic = 0;                                  // index of the buffer holding `cur`
+    auto conv16 = [&](int ci, const cilrs_half* x, const cilrs_half* residual,
+                      cilrs_half* y, int relu) -> int {
+        const ConvT& c = A.convs[ci];
+        const ConvG& g = net->cg[ci];
+        ConvF16Args a;
+        memset(&a, 0, sizeof(a));
+        a.x = x; a.w = w16 + net->f16_table.w16[ci - 1];
+        a.bias = b16 + net->f16_table.bias[ci - 1];
+        a.residual = residual; a.y = y; a.bf16 = bf16;
+        a.N = B; a.H = g.H; a.W = g.W; a.Cin = c.cin; a.Ho = g.Ho; a.Wo = g.Wo;
+        a.Cout = c.cout; a.K = c.k; a.stride = c.stride; a.pad = c.pad; a.relu = relu;
+        const double bytes = 2.0 * ((double)B * g.H * g.W * c.cin + (double)g.M * c.cout *
+                                    (residual ? 2.0 : 1.0) + (double)c.cout * c.k * c.k * c.cin);
+        RUN(net, std::string("conv_fwd.") + kGroupName[c.group],
+            2.0 * g.M * c.cout * c.k * c.k * c.cin, bytes, s, launch_conv_f16(a, s));
+        return 0;
+    };
+    for (const BlockT& blk : A.blocks) {
+        // five rotating buffers: block input, two intermediates, projected identity, output
+        const int it1 = (ic + 1) % 5, it2 = (ic + 2) % 5, iid = (ic + 3) % 5,
+                  io = (ic + 4) % 5;
+        if (conv16(blk.conv1, act[ic], nullptr, act[it1], 1)) return 1;
+        const cilrs_half* identity = act[ic];
+        if (blk.down >= 0) {
+            if (conv16(blk.down, act[ic], nullptr, act[iid], 0)) return 1;
+            identity = act[iid];
+        }
+        if (blk.conv3 >= 0) {
+            if (conv16(blk.conv2, act[it1], nullptr, act[it2], 1)) return 1;
+            if (conv16(blk.conv3, act[it2], identity, act[io], 1)) return 1;
+        } else {
+            if (conv16(blk.conv2, act[it1], identity, act[io], 1)) return 1;
+        }
+        ic = io;
+    }
+    RUN(net, "heads_fwd", 0.0, 0.0, s,
+        launch_avgpool_f16(act[ic], ws + net->combined, B, net->featHW, A.feat,
+                           A.feat + 128, bf16, s));
+    *feat = nullptr;
+    return 0;
+}
+
+// Heads: speed encoder, the command branches and the speed predictor.  `feat`: the trunk's last
+// feature map, or nullptr when its features are already pooled into `combined`.  graph: a
+// graph-keeping forward (the backward pass needs the heads' inputs); pdrop: training dropout.
+static int heads_fwd(cilrs_net* net, const cilrs_buffers* bufs, const float* feat,
+                     const float* speed, const int64_t* command, bool graph, float pdrop,
+                     uint64_t seed, float* controls, float* pred_speed, hipStream_t s) {
+    const Arch& A = *net->A;
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
+    const float* P = bufs->params;
+    const int B = net->B;
     int* status = reinterpret_cast<int*>(reinterpret_cast<char*>(bufs->workspace) + net->status_b);
-    const int feat = A.feat, comb = A.feat + 128;
+    const int featw = A.feat, comb = A.feat + 128;
     if (!graph && B <= kHeadsSmallMaxB && A.variant == 0) {
         // ---- inference at control-loop batch sizes: 4 launches, commanded branch only ----
         RUN(net, "heads_fwd", 0.0, 0.0, s,
-            launch_heads_small_pre(cur, net->featHW, speed, P + A.se0.w, P + A.se0.b, P + A.se3.w,
+            launch_heads_small_pre(feat, net->featHW, speed, P + A.se0.w, P + A.se0.b, P + A.se3.w,
                                    P + A.se3.b, ws + net->combined, B, s));
         HeadsSmallArgs h;
         memset(&h, 0, sizeof(h));
@@ -1549,22 +1583,19 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
                 4.0 * (h.in[0] * h.out[0] + h.in[1] * h.out[1]), s,
                 launch_heads_small_layer(h, s));
         }
-        net->trained_fwd = false;
-        net->last_dropout = 0.f;
         return 0;
     }
 
     // ---- avgpool + flatten -> combined[:, 0:512] ----
-    if (cur != nullptr)
+    if (feat != nullptr)
         RUN(net, "heads_fwd", 0.0, 0.0, s,
-            launch_avgpool_fwd(cur, ws + net->combined, B, net->featHW, feat, comb, s));
+            launch_avgpool_fwd(feat, ws + net->combined, B, net->featHW, featw, comb, s));
 
     if (graph) {   // backward needs the inputs of the heads
         if (launch_keep_head_inputs(speed, reinterpret_cast<const long long*>(command), ws + net->speed_in,
                                     reinterpret_cast<long long*>(reinterpret_cast<char*>(bufs->workspace) +
                                                                  net->cmd_b), B, s)) return 1;
     }
-    const float pdrop = train ? dropout_p : 0.f;
     // Every layer of every chain that can run at the same time is ONE grouped launch
     // (heads_gemm.hip): 7 launches for the whole head instead of ~25 on five side streams.
     auto fwd_group = [&](HGemmGroup& g, const float* x, int x_ld, const LinT& l, float* y, int y_ld,
@@ -1585,7 +1616,7 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
     memset(&h, 0, sizeof(h));
     fwd_group(h.g[0], speed, 1, A.se0, ws + net->s1, 128, 0);
     if (run_fwd(h, 1, 1)) return 1;
-    fwd_group(h.g[0], ws + net->s1, 128, A.se3, ws + net->combined + feat, comb, kNoDrop);
+    fwd_group(h.g[0], ws + net->s1, 128, A.se3, ws + net->combined + featw, comb, kNoDrop);
     if (run_fwd(h, 1, 1)) return 1;
     // ---- the branches (all evaluated, :394-396) + speed predictor (:383-387, 393), layer by layer;
     //      dropout streams: 1 + 2k / 2 + 2k for branch k, 2 NC + 1 for the speed predictor (= 9 for
@@ -1608,6 +1639,41 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
     RUN(net, "heads_fwd", 0.0, 0.0, s,
         launch_branch_gather(ws + net->all_out, reinterpret_cast<const long long*>(command),
                              controls, B, NC, status, s));
+    return 0;
+}
+
+// Every forward entry ends here, with the input image in x4.  Modes: train (batch-statistics
+// BatchNorm, dropout), frozen (running statistics, activations kept for the backward pass), else
+// eval in fp32 (half = 0), fp16 (1) or bf16 (2).
+static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const float* speed,
+                           const int64_t* command, int train, float dropout_p, uint64_t seed,
+                           float* controls, float* pred_speed, hipStream_t s, int half = 0,
+                           bool frozen = false) {
+    net->ws_base = reinterpret_cast<float*>(bufs->workspace);
+    CILRS_CHECK(!(frozen && (train || half || net->bf16_train)),
+                "frozen forward: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan rejects it)");
+    if (zero_counters_once(net, bufs->workspace, s)) return 1;
+    net->bwd_done = 0;
+    if (train) {
+        // the stem weights are padded every step; the cached eval state goes stale as the
+        // weights / BN buffers are about to change
+        RUN(net, "transform", 0.0, 0.0, s,
+            launch_pad_cin3_to_4(bufs->params + net->A->convs[0].w, net->ws_base + net->w4, 64 * 49, s));
+        net->prep_key = 0; net->fold_key = 0;
+    } else {
+        if (eval_prep(net, bufs, s)) return 1;
+        if (half && fold_prep(net, bufs, half, s)) return 1;
+    }
+    // train: batch statistics; frozen: the running statistics -- both keep every activation the
+    // backward pass reads (y, z, the max-pool argmax, the head inputs)
+    const bool graph = train || frozen;
+    const float* feat = nullptr;
+    const int rc = graph  ? trunk_fwd_graph(net, bufs, train, frozen, s, &feat)
+                   : half ? trunk_fwd_eval16(net, bufs, half, s, &feat)
+                          : trunk_fwd_eval32(net, bufs, s, &feat);
+    const float pdrop = train ? dropout_p : 0.f;
+    if (rc || heads_fwd(net, bufs, feat, speed, command, graph, pdrop, seed, controls, pred_speed, s))
+        return 1;
     net->trained_fwd = graph;
     net->frozen_fwd = frozen;
     net->last_dropout = pdrop;
@@ -1652,18 +1718,25 @@ int cilrs_net_forward_frozen(cilrs_net* net, const cilrs_buffers* bufs, const fl
     return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s, 0, true);
 }
 
+// uint8 HWC frames -> eval forward in fp32 (half = 0), fp16 (1) or bf16 (2)
+static int forward_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
+                      const float* speed, const int64_t* command, float* controls,
+                      float* pred_speed, void* stream, int half) {
+    if (check_bufs(net, bufs, false)) return 1;
+    CILRS_CHECK(frames && speed && command && controls && pred_speed, "forward_u8%s: NULL tensor",
+                half == 2 ? "_bf16" : half ? "_f16" : "");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
+    RUN(net, "transform", 0.0, 0.0, s,
+        launch_u8hwc_to_nhwc4(frames, ws + net->x4, (size_t)net->B * net->H * net->W, kImageMean,
+                              kImageStd, s));
+    return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s, half);
+}
+
 int cilrs_net_forward_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
                          const float* speed, const int64_t* command, float* controls,
                          float* pred_speed, void* stream) {
-    if (check_bufs(net, bufs, false)) return 1;
-    CILRS_CHECK(frames && speed && command && controls && pred_speed, "forward_u8: NULL tensor");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* ws = reinterpret_cast<float*>(bufs->workspace);
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-    RUN(net, "transform", 0.0, 0.0, s,
-        launch_u8hwc_to_nhwc4(frames, ws + net->x4, (size_t)net->B * net->H * net->W, mean, stdv,
-                              s));
-    return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s);
+    return forward_u8(net, bufs, frames, speed, command, controls, pred_speed, stream, 0);
 }
 
 int cilrs_net_forward_camera(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
@@ -1675,64 +1748,27 @@ int cilrs_net_forward_camera(cilrs_net* net, const cilrs_buffers* bufs, const ui
                 "forward_camera: NULL tensor");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float* ws = reinterpret_cast<float*>(bufs->workspace);
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
     RUN(net, "transform", 0.0, 0.0, s,
         launch_camera_to_nhwc4(frames, ws + net->x4, net->B, src_h, src_w, pixel_stride,
-                               row_stride, frame_stride, net->H, net->W, mean, stdv, s));
+                               row_stride, frame_stride, net->H, net->W, kImageMean, kImageStd, s));
     return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s);
 }
 
 int cilrs_net_forward_u8_f16(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
                              const float* speed, const int64_t* command, float* controls,
                              float* pred_speed, void* stream) {
-    if (check_bufs(net, bufs, false)) return 1;
-    CILRS_CHECK(frames && speed && command && controls && pred_speed,
-                "forward_u8_f16: NULL tensor");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* ws = reinterpret_cast<float*>(bufs->workspace);
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-    RUN(net, "transform", 0.0, 0.0, s,
-        launch_u8hwc_to_nhwc4(frames, ws + net->x4, (size_t)net->B * net->H * net->W, mean, stdv,
-                              s));
-    return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s, 1);
+    return forward_u8(net, bufs, frames, speed, command, controls, pred_speed, stream, 1);
 }
 
 int cilrs_net_forward_u8_bf16(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
                               const float* speed, const int64_t* command, float* controls,
                               float* pred_speed, void* stream) {
-    if (check_bufs(net, bufs, false)) return 1;
-    CILRS_CHECK(frames && speed && command && controls && pred_speed,
-                "forward_u8_bf16: NULL tensor");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* ws = reinterpret_cast<float*>(bufs->workspace);
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-    RUN(net, "transform", 0.0, 0.0, s,
-        launch_u8hwc_to_nhwc4(frames, ws + net->x4, (size_t)net->B * net->H * net->W, mean, stdv,
-                              s));
-    return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s, 2);
+    return forward_u8(net, bufs, frames, speed, command, controls, pred_speed, stream, 2);
 }
 
 // ------------------------------------------------------------------------------------------------
 // single-frame inference as ONE persistent launch (infer_b1.hip)
 // ------------------------------------------------------------------------------------------------
-// eval-mode weight-derived state (the same two kernels and cache keys as the eager eval path)
-static int eval_prep(cilrs_net* net, const cilrs_buffers* bufs, hipStream_t s) {
-    const Arch& A = *net->A;
-    float* ws = reinterpret_cast<float*>(bufs->workspace);
-    const bool same_bufs = net->prep_bufs[0] == (const void*)bufs->params &&
-                           net->prep_bufs[1] == (const void*)bufs->bn_running &&
-                           net->prep_bufs[2] == (const void*)bufs->workspace;
-    if (net->weights_key != 0 && same_bufs && net->prep_key == net->weights_key) return 0;
-    RUN(net, "transform", 0.0, 0.0, s,
-        launch_pad_cin3_to_4(bufs->params + A.convs[0].w, ws + net->w4, 64 * 49, s));
-    RUN(net, "bn_fwd.eval", 0.0, 0.0, s,
-        launch_bn_eval_stats_all(net->bn_table, bufs->params, bufs->bn_running, ws, 1e-5f, s));
-    net->prep_key = net->weights_key;
-    net->prep_bufs[0] = bufs->params; net->prep_bufs[1] = bufs->bn_running;
-    net->prep_bufs[2] = bufs->workspace;
-    net->fold_key = 0;
-    return 0;
-}
 
 // Stage table of the persistent kernel for this plan on a grid of `nblk` workgroups.
 static int b1_build(cilrs_net* net, int nblk) {
@@ -1968,8 +2004,7 @@ static int b1_launch(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* f
     // CILRS_B1_STAMPS=1: block 0 records its clock at every stage (cilrs_net_b1_stage_us)
     static const int stamps_on = getenv("CILRS_B1_STAMPS") ? atoi(getenv("CILRS_B1_STAMPS")) : 0;
     a.stamps = stamps_on ? reinterpret_cast<long long*>(ws + net->b1_stamps) : nullptr;
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-    for (int i = 0; i < 3; ++i) { a.mean[i] = mean[i]; a.stdv[i] = stdv[i]; }
+    for (int i = 0; i < 3; ++i) { a.mean[i] = kImageMean[i]; a.stdv[i] = kImageStd[i]; }
     RUN(net, "infer_b1", 2.0 * 2.798e9 / 2.0, 0.0, s, launch_infer_b1(a, net->b1_blocks, s));
     net->trained_fwd = false;
     net->last_dropout = 0.f;
@@ -1990,10 +2025,9 @@ int cilrs_net_forward_camera_b1(cilrs_net* net, const cilrs_buffers* bufs, const
     CILRS_CHECK(frame != nullptr, "forward_camera_b1: NULL frame");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float* ws = reinterpret_cast<float*>(bufs->workspace);
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
     RUN(net, "transform", 0.0, 0.0, s,
         launch_camera_to_nhwc4(frame, ws + net->x4, 1, src_h, src_w, pixel_stride, row_stride,
-                               (long)src_h * row_stride, net->H, net->W, mean, stdv, s));
+                               (long)src_h * row_stride, net->H, net->W, kImageMean, kImageStd, s));
     if (b1_launch(net, bufs, nullptr, 1, speed, command, controls, pred_speed, stream)) return 1;
     if (sync) CILRS_HIP(hipStreamSynchronize(s));
     return 0;
@@ -2088,8 +2122,6 @@ int cilrs_net_b1_stages(cilrs_net* net) {
 static int forward_u8_graph(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
                             const float* speed, const int64_t* command, float* controls,
                             float* pred_speed, void* stream, int half) {
-    auto eager = half == 2 ? cilrs_net_forward_u8_bf16
-                 : half ? cilrs_net_forward_u8_f16 : cilrs_net_forward_u8;
     if (check_bufs(net, bufs, false)) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     CILRS_CHECK(s != nullptr, "forward_u8_graph: capture needs a non-default stream");
@@ -2099,15 +2131,14 @@ static int forward_u8_graph(cilrs_net* net, const cilrs_buffers* bufs, const uin
                 net->graph_wkey == net->weights_key;
     for (int i = 0; i < 8 && same; ++i) same = key[i] == net->graph_key[i];
     if (!same) {
-        // first call eager: function attributes, side streams, events; and whenever the weights
-        // key moved, so that the weight-derived state is rebuilt OUTSIDE the capture and the graph
-        // holds only the per-frame kernels
-        // ... and whenever the 16-bit fold state is stale (another mode ran in between): the fold
-        // kernels must not be captured into the per-frame graph
-        const bool fold_stale = half && (net->fold_key != net->weights_key || net->fold_half != half);
-        if (!net->warmed || net->prep_key != net->weights_key || net->weights_key == 0 || fold_stale) {
+        // first call eager: function attributes, side streams, events; and whenever the
+        // weight-derived eval state is stale (the weights key moved, or another mode ran in
+        // between), so that it is rebuilt OUTSIDE the capture and the graph holds only the
+        // per-frame kernels
+        if (!net->warmed || !eval_state_current(net, bufs, half)) {
             if (ensure_streams(net)) return 1;
-            if (eager(net, bufs, frames, speed, command, controls, pred_speed, stream)) return 1;
+            if (forward_u8(net, bufs, frames, speed, command, controls, pred_speed, stream, half))
+                return 1;
             CILRS_HIP(hipStreamSynchronize(s));
             net->warmed = true;
         }
@@ -2115,7 +2146,7 @@ static int forward_u8_graph(cilrs_net* net, const cilrs_buffers* bufs, const uin
         net->prof.on = false;
         hipGraph_t graph = nullptr;
         CILRS_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const int rc = eager(net, bufs, frames, speed, command, controls, pred_speed, stream);
+        const int rc = forward_u8(net, bufs, frames, speed, command, controls, pred_speed, stream, half);
         const hipError_t e = hipStreamEndCapture(s, &graph);
         net->prof.on = prof;
         CILRS_CHECK(rc == 0, "forward_u8_graph: capture failed: %s", last_error());

@@ -259,12 +259,10 @@ bool stem_f32_plan(int N, int H, int W, int Ho, int Wo, StemPlan* p) {
 
 template <int TM, int PITCH, bool DB>
 int launch_stem_f32_t(const StemF32Args& a, const StemPlan& p, hipStream_t s) {
-    if (once_per_device(reinterpret_cast<const void*>(&stem_f32_kernel<TM, PITCH, DB>))) {
-        // (the row count, hence the LDS size, of one instantiation varies with the image width: set
-        //  the limit to the CU's 160 KB once, not to the first caller's size)
-        CILRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_f32_kernel<TM, PITCH, DB>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
+    // (the row count, hence the LDS size, of one instantiation varies with the image width: set
+    //  the limit to the CU's 160 KB once, not to the first caller's size)
+    if (set_max_dynamic_lds(reinterpret_cast<const void*>(&stem_f32_kernel<TM, PITCH, DB>), 160 * 1024))
+        return 1;
     const int resident = device_cus() * (DB ? 1 : 2);
     stem_f32_kernel<TM, PITCH, DB><<<p.ntiles < resident ? p.ntiles : resident, 512, p.lds, s>>>(a);
     CILRS_LAUNCH_CHECK();
@@ -485,10 +483,8 @@ bool stem_wgrad_plan(int N, int H, int W, int Ho, int Wo, StemWgradPlan* p) {
 
 template <int PITCH, int R>
 int launch_stem_wgrad_t(const StemWgradArgs& a, const StemWgradPlan& p, float* dw, hipStream_t s) {
-    if (once_per_device(reinterpret_cast<const void*>(&stem_wgrad_f32_kernel<PITCH, R, 25>))) {
-        CILRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_wgrad_f32_kernel<PITCH, R, 25>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
-    }
+    if (set_max_dynamic_lds(reinterpret_cast<const void*>(&stem_wgrad_f32_kernel<PITCH, R, 25>), (int)p.lds))
+        return 1;
     stem_wgrad_f32_kernel<PITCH, R, 25><<<p.grid, 512, p.lds, s>>>(a);
     CILRS_LAUNCH_CHECK();
     stem_wgrad_reduce_kernel<<<cdiv(64 * 147, 32), 256, 0, s>>>(a.slabs, dw, p.grid);

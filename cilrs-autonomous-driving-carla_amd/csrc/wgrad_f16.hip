@@ -257,12 +257,7 @@ size_t wgrad_f16_scratch_floats(const WgradF16Args& a) {
 template <typename T, int BT>
 static int launch_wgrad_f16_t(const WgradF16Args& a, const W16Plan& p, int Mpix, hipStream_t s) {
     constexpr size_t lds = (size_t)4 * WPIX * wpitch<BT>() * 2;
-    static bool attr_set = false;
-    if (!attr_set) {
-        CILRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_f16_kernel<T, BT>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
+    if (set_max_dynamic_lds(reinterpret_cast<const void*>(&wgrad_f16_kernel<T, BT>), (int)lds)) return 1;
     const int tiles = a.K * a.K * (a.Cin / BT) * (a.Cout / BT);
     wgrad_f16_kernel<T, BT><<<tiles * p.splits, 256, lds, s>>>(a, Mpix, p.splits, p.steps_per);
     CILRS_LAUNCH_CHECK();
