@@ -86,6 +86,10 @@ SIGNATURES = {
     "cilrs_net_b1_stages": (i32, [vp]),
     "cilrs_net_b1_set_epoch": (i32, [vp, C.POINTER(Buffers), i32, vp]),
     "cilrs_net_wino_convs": (i32, [vp]),
+    "cilrs_net_forward_ft": (i32, [vp, C.POINTER(Buffers), vp, C.c_long, C.c_long, C.c_long,
+                                   C.c_long, vp, vp, i32, i32, u64, f32, u64, vp, vp, vp]),
+    "cilrs_net_ft_wino_convs": (i32, [vp]),
+    "cilrs_net_ft_cut": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
     "cilrs_net_b1_stage_us": (i32, [vp, C.POINTER(Buffers), c_float_p, c_float_p, i32]),
     "cilrs_net_forward_u8_bf16": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp, vp, vp]),
     "cilrs_net_forward_u8_bf16_graph": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp, vp, vp]),
@@ -104,6 +108,8 @@ SIGNATURES = {
     "cilrs_sqnorm_scratch_bytes": (sz, []),
     "cilrs_grad_sqnorm": (i32, [vp, sz, f32, vp, vp, vp]),
     "cilrs_adam_step": (i32, [vp, vp, vp, vp, sz, f64, f64, f64, f64, f64, i64, vp, f32, vp]),
+    "cilrs_adam_step_groups": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, vp, f64, f64, f64, f64, vp, f32,
+                                     vp]),
     "cilrs_scale": (i32, [vp, sz, vp, f32, vp]),
     "cilrs_augment_u8": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
     "cilrs_eval_acc_doubles": (i32, []),
@@ -130,6 +136,8 @@ SIGNATURES = {
     "cilrs_conv2d_wino_split": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp]),
     "cilrs_conv2d_wino_scratch_floats": (sz, [i32, i32]),
     "cilrs_conv2d_wino_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "cilrs_conv2d_wino_fold_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32,
+                                         vp, vp]),
     "cilrs_wino_filter_transform": (i32, [vp, vp, i32, i32, i32, vp]),
     "cilrs_conv2d_wino_stamps": (i32, [vp]),
     "cilrs_conv2d_wino_pre": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),

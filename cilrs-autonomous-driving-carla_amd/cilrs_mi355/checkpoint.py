@@ -5,7 +5,9 @@ model/autonomous_drive.py:496-500 needs ``model_state_dict``, ``epoch``, ``val_l
 with ``strict=True``.  Tensors are saved as contiguous fp32 CPU tensors in torch's logical layout
 (OIHW conv weights), int64 scalar ``num_batches_tracked``; scalars are plain Python floats (the
 reference stored numpy scalars, which is why its loader needs a numpy._core shim, :35-44).
-``optimizer_state_dict`` is in torch.optim.Adam's own format (142 entries, parameters() order).
+``optimizer_state_dict`` is in torch.optim.Adam's own format (142 entries, parameters() order);
+``step`` is per parameter, as there: a tensor that sat out fine-tuning steps while frozen has a
+smaller one (and zero moments if it never stepped).
 """
 from __future__ import annotations
 
@@ -20,9 +22,10 @@ def optimizer_state_dict(trainer):
     eng, cfg = trainer.eng, trainer.cfg
     from .engine import _arena_view
     state = {}
+    steps = trainer.group_steps
     for i, (_, off, numel, shape) in enumerate(eng.params_layout):
         state[i] = {
-            "step": torch.tensor(float(trainer.step_count)),
+            "step": torch.tensor(float(steps[_group_of(eng, off)])),
             "exp_avg": _arena_view(trainer.exp_avg, off, numel, shape).cpu().contiguous().clone(),
             "exp_avg_sq": _arena_view(trainer.exp_avg_sq, off, numel, shape).cpu().contiguous().clone(),
         }
@@ -33,19 +36,30 @@ def optimizer_state_dict(trainer):
     return {"state": state, "param_groups": [group]}
 
 
+def _group_of(eng, off):
+    """Parameter group (stem, layer1 .. layer4, heads) of the tensor at arena offset `off`."""
+    for gi, (b, e) in enumerate(eng.group_ranges):
+        if b <= off < e:
+            return gi
+    raise RuntimeError(f"arena offset {off} lies in no parameter group")
+
+
 def load_optimizer_state_dict(trainer, sd):
     eng = trainer.eng
     from .engine import _arena_view
-    steps = set()
+    steps = [set() for _ in range(6)]
     with torch.no_grad():
         for i, (_, off, numel, shape) in enumerate(eng.params_layout):
             st = sd["state"][i]
             _arena_view(trainer.exp_avg, off, numel, shape).copy_(st["exp_avg"])
             _arena_view(trainer.exp_avg_sq, off, numel, shape).copy_(st["exp_avg_sq"])
-            steps.add(int(float(st["step"])))
-    if len(steps) != 1:
-        raise RuntimeError("per-tensor Adam step counts differ; the flat Adam needs one step")
-    trainer.step_count = steps.pop()
+            steps[_group_of(eng, off)].add(int(float(st["step"])))
+    if any(len(s) != 1 for s in steps):
+        raise RuntimeError("Adam step counts differ inside a parameter group; the ranged Adam "
+                           "needs one step per group (stem, layer1 .. layer4, heads)")
+    steps = [s.pop() for s in steps]
+    trainer.step_count = max(steps)
+    trainer.group_lag = [trainer.step_count - s for s in steps]
     trainer.lr = float(sd["param_groups"][0]["lr"])
 
 

@@ -62,6 +62,13 @@ def segment_ranges(variant=0):
     return out
 
 
+def group_ranges(variant=0):
+    """[(begin, end)] float ranges of the arena per parameter group, in arena (= parameters())
+    order: stem, layer1, layer2, layer3, layer4, heads.  Contiguous; starts are 16-byte aligned."""
+    segs = segment_ranges(variant)
+    return [segs[5], segs[4], segs[3], segs[2], segs[1], segs[0]]
+
+
 def _arena_view(arena, off, numel, shape):
     flat = arena[off:off + numel]
     if len(shape) == 4:                       # OHWI storage, logical OIHW
@@ -139,6 +146,10 @@ class Plan:
 
     def profile_reset(self):
         L.check(L.lib().cilrs_net_profile_reset(self.handle))
+
+    def ft_wino_convs(self) -> int:
+        """Folded-epilogue Winograd launches of the plan's last fine-tuning forward."""
+        return int(L.lib().cilrs_net_ft_wino_convs(self.handle))
 
     def wino_convs(self) -> int:
         """Convolutions of this plan's train step that run on the Winograd kernel (0: none)."""
@@ -231,6 +242,11 @@ class Engine:
             b for m in module.modules() if isinstance(m, torch.nn.BatchNorm2d)
             for b in (m.running_mean, m.running_var))
         self._version_sum = sum(map(_VERSION_OF, self._versioned))
+        # fine-tuning: arena range per parameter group, and the key under which a plan caches the
+        # weight-derived state of a frozen prefix (a new value whenever the cut changes or
+        # anything but a fine-tuning step of the same cut moved the weights epoch)
+        self.group_ranges = group_ranges(variant)
+        self._ft_epoch, self._ft_cut, self._ft_expect = 0, 0, -1
 
     # ------------------------------------------------------------------------------------------
     def is_attached(self) -> bool:
@@ -319,6 +335,60 @@ class Engine:
             L.ptr(controls), L.ptr(pred_speed), self._stream()))
         if train:
             pl.generation += 1
+        self.last_plan = pl
+        return controls, pred_speed, pl
+
+    def trainable_begin(self, frozen_groups) -> int:
+        """First arena float of the trainable range behind `frozen_groups` frozen trunk groups."""
+        return self.group_ranges[frozen_groups][0]
+
+    def check_freeze(self, e, g, image=None):
+        """What no fine-tuning step can serve (raised before any launch)."""
+        if g and self.train_precision == "bf16":
+            raise RuntimeError("CILRS fine-tuning: the bf16 training plan cannot freeze trunk "
+                               "groups (fp32 training only)")
+        if g and image is not None and image.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError("CILRS fine-tuning: image.requires_grad is set but the trunk is "
+                               f"frozen up to {SEG_NAMES[6 - g]}; input gradients through a frozen "
+                               "prefix are not supported")
+
+    def wrote_trainable(self, e):
+        """A kernel updated parameters behind an eval-mode prefix of `e` groups only (the ranged
+        Adam of a fine-tuning step): everything cached for inference is stale, the prefix's own
+        state is not."""
+        keep = e > 0 and self._ft_cut == e and self._ft_expect == self.weights_epoch
+        self.weights_epoch += 1
+        if keep:
+            self._ft_expect = self.weights_epoch
+
+    def run_forward_ft(self, image, speed, command, e, g, dropout_p, seed):
+        """Train-mode forward with the first `g` trunk groups taking no gradient and the first
+        `e` (0 or g) of them in eval mode (cilrs_net_forward_ft); (0, 0) is run_forward."""
+        if e == 0 and g == 0:
+            return self.run_forward(image, speed, command, True, dropout_p, seed)
+        self.check_freeze(e, g)
+        b = self._check_inputs(image, speed, command)
+        pl = self.plan(b, image.size(2), image.size(3))
+        speed = speed.contiguous()
+        command = command.contiguous()
+        controls = torch.empty(b, 3, dtype=torch.float32, device=self.device)
+        pred_speed = torch.empty(b, dtype=torch.float32, device=self.device)
+        sn, sc, sh, sw = image.stride()
+        key = 0
+        if e > 0:
+            self.poll_versions()              # torch-visible edits of the frozen prefix
+            if self._ft_cut != e or self._ft_expect != self.weights_epoch:
+                self._ft_epoch += 1
+            self._ft_cut = e
+            key = (self._ft_epoch * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF or 1
+        self.weights_epoch += 1               # BN running statistics behind the prefix move
+        self._ft_expect = self.weights_epoch if e > 0 else -1      # (e == 0: the prefix's move too)
+        self._announce_weights(pl)
+        L.check(L.lib().cilrs_net_forward_ft(
+            pl.handle, C.byref(pl.bufs), L.ptr(image), sn, sc, sh, sw,
+            L.ptr(speed), L.ptr(command), int(e), int(g), key, float(dropout_p), int(seed),
+            L.ptr(controls), L.ptr(pred_speed), self._stream()))
+        pl.generation += 1
         self.last_plan = pl
         return controls, pred_speed, pl
 
@@ -465,18 +535,26 @@ class Engine:
         # whenever an input asks for its gradient (eval mode: BatchNorm frozen on the running
         # statistics, as torch's own eval-mode autograd); otherwise the detached fast path
         grad_on = torch.is_grad_enabled()
+        # train mode: the frozen prefix the module's flags describe (raises on what cannot be served)
+        e = g = 0
+        if training:
+            e, g = self.module.freeze_state()
+            self.check_freeze(e, g, image)
         needs_graph = grad_on and (image.requires_grad or speed.requires_grad)
         if not needs_graph:
             needs_graph = training and grad_on and any(
                 p.requires_grad for p in self.module.parameters())
         if not needs_graph:
-            c, s, _ = self.run_forward(image, speed, command, training, dropout_p, seed)
+            if training:
+                c, s, _ = self.run_forward_ft(image, speed, command, e, g, dropout_p, seed)
+            else:
+                c, s, _ = self.run_forward(image, speed, command, False, dropout_p, seed)
             return c, s
         return _CILRSFunction.apply(self, image, speed, command, float(dropout_p), int(seed),
-                                    bool(training), *self.module.parameters())
+                                    bool(training), e, g, *self.module.parameters())
 
 
-_N_LEADING = 7        # _CILRSFunction.forward arguments in front of the parameters
+_N_LEADING = 9        # _CILRSFunction.forward arguments in front of the parameters
 
 
 class _CILRSFunction(torch.autograd.Function):
@@ -485,13 +563,15 @@ class _CILRSFunction(torch.autograd.Function):
     to the speed input) in train mode and -- through the frozen forward -- in eval mode."""
 
     @staticmethod
-    def forward(ctx, eng, image, speed, command, dropout_p, seed, training, *params):
+    def forward(ctx, eng, image, speed, command, dropout_p, seed, training, e, g, *params):
         if training:
-            controls, pred_speed, pl = eng.run_forward(image, speed, command, True, dropout_p, seed)
+            controls, pred_speed, pl = eng.run_forward_ft(image, speed, command, e, g, dropout_p,
+                                                          seed)
         else:
             controls, pred_speed, pl = eng.run_forward_frozen(image, speed, command)
         ctx.eng, ctx.pl, ctx.generation = eng, pl, pl.generation
         ctx.n_params = len(params)
+        ctx.frozen_groups = g if training else 0
         ctx.channels_last = (not image.is_contiguous()
                              and image.is_contiguous(memory_format=torch.channels_last))
         return controls, pred_speed
@@ -537,9 +617,12 @@ class _CILRSFunction(torch.autograd.Function):
             if need_speed:
                 dspeed = torch.empty(b, dtype=torch.float32, device=eng.device)
             eng.run_input_grads(pl, dimage, dspeed)
+        lead = (None, dimage, dspeed) + (None,) * (_N_LEADING - 3)
         if not need_params:
-            return (None, dimage, dspeed, None, None, None, None) + (None,) * ctx.n_params
+            return lead + (None,) * ctx.n_params
         src = dst if eng.zero_copy_grads else dst.clone()
-        grads = [_arena_view(src, off, numel, shape)
+        # (the backward stopped at the frozen prefix: its arena range was not written)
+        cut = eng.trainable_begin(ctx.frozen_groups)
+        grads = [_arena_view(src, off, numel, shape) if off >= cut else None
                  for (_, off, numel, shape) in eng.params_layout]
-        return (None, dimage, dspeed, None, None, None, None, *grads)
+        return (*lead, *grads)

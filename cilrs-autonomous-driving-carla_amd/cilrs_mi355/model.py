@@ -78,6 +78,11 @@ def _make_layer(inplanes, planes, blocks, stride):
     return nn.Sequential(*layers)
 
 
+# trunk groups a fine-tuning run freezes, in order, and where they sit in `visual_encoder`
+TRUNK_GROUPS = ("stem", "layer1", "layer2", "layer3", "layer4")
+_GROUP_CHILDREN = ((0, 1), (4,), (5,), (6,), (7,))
+
+
 class CILRS(nn.Module):
     VARIANT = 0          # engine architecture variant (include/cilrs_hip.h)
     FEATURES = 512
@@ -141,10 +146,119 @@ class CILRS(nn.Module):
             self.weights_changed()
         return super().train(mode)
 
+    # -- fine-tuning: a frozen prefix of the trunk ---------------------------------------------
+    def _freeze_lists(self):
+        """Per trunk group: [(name, parameter)], [(name, BatchNorm2d)]; then the heads' parameters."""
+        lists = self.__dict__.get("_ft_lists")
+        if lists is None:
+            groups = []
+            for children in _GROUP_CHILDREN:
+                ps, bns = [], []
+                for ci in children:
+                    child, prefix = self.visual_encoder[ci], f"visual_encoder.{ci}"
+                    ps += [(f"{prefix}.{n}", p) for n, p in child.named_parameters()]
+                    bns += [(f"{prefix}.{n}" if n else prefix, m) for n, m in child.named_modules()
+                            if isinstance(m, nn.BatchNorm2d)]
+                groups.append((ps, bns))
+            heads = [(n, p) for n, p in self.named_parameters()
+                     if not n.startswith("visual_encoder.")]
+            lists = (groups, heads)
+            self.__dict__["_ft_lists"] = lists
+        return lists
+
+    def freeze_state(self):
+        """(e, g), read from the module's own flags on every step: g = leading trunk groups
+        (stem, layer1 .. layer4) whose parameters all have requires_grad == False; e = leading
+        groups whose BatchNorm2d modules are all in eval mode while the model is in train mode (0
+        in eval mode).  Supported: e == g (torch's idiom: ``prefix.eval()`` +
+        ``requires_grad_(False)``) and e == 0 (``requires_grad_(False)`` alone: batch statistics
+        and moving running buffers in the prefix, as in torch).  Anything else raises a
+        RuntimeError that names the first offending parameter or module -- a pattern the engine
+        cannot honour must never silently train in full."""
+        groups, heads = self._freeze_lists()
+        g = 0
+        for ps, _ in groups:
+            if any(p.requires_grad for _, p in ps):
+                break
+            g += 1
+        for gi in range(g, len(groups)):
+            ps = groups[gi][0]
+            frozen = [n for n, p in ps if not p.requires_grad]
+            if not frozen:
+                continue
+            if gi == g:
+                live = next(n for n, p in ps if p.requires_grad)
+                raise RuntimeError(
+                    f"CILRS fine-tuning: {frozen[0]} is frozen (requires_grad=False) but {live}, "
+                    f"in the same group ({TRUNK_GROUPS[gi]}), is trainable; a group is frozen as a "
+                    f"whole (CILRS.freeze)")
+            raise RuntimeError(
+                f"CILRS fine-tuning: {frozen[0]} is frozen (requires_grad=False) behind the "
+                f"trainable group {TRUNK_GROUPS[g]}; only a leading prefix of the trunk can be "
+                f"frozen (CILRS.freeze)")
+        for n, p in heads:
+            if not p.requires_grad:
+                raise RuntimeError(
+                    f"CILRS fine-tuning: {n} is frozen (requires_grad=False); freezing heads or "
+                    f"single branches is not supported, only a leading prefix of the trunk")
+        if not self.training:
+            return 0, g
+        e = 0
+        for _, bns in groups:
+            if any(m.training for _, m in bns):
+                break
+            e += 1
+        for gi in range(e, len(groups)):
+            stopped = [n for n, m in groups[gi][1] if not m.training]
+            if stopped:
+                live = next(n for n, m in groups[e][1] if m.training)
+                why = (f"{live}, in the same group ({TRUNK_GROUPS[e]}), is in train mode" if gi == e
+                       else f"{live}, in the group {TRUNK_GROUPS[e]} in front of it, is in train mode")
+                raise RuntimeError(
+                    f"CILRS fine-tuning: BatchNorm {stopped[0]} is in eval mode but {why}; only a "
+                    f"leading prefix of the trunk can run on its running statistics")
+        if e > g:
+            raise RuntimeError(
+                f"CILRS fine-tuning: BatchNorm {groups[g][1][0][0]} is in eval mode but the "
+                f"parameters of its group ({TRUNK_GROUPS[g]}) are trainable; frozen statistics "
+                f"under trainable weights are not supported (freeze the parameters too)")
+        if 0 < e < g:
+            raise RuntimeError(
+                f"CILRS fine-tuning: BatchNorm {groups[e][1][0][0]} is in train mode but "
+                f"{groups[e - 1][1][0][0]} is in eval mode, inside the frozen prefix of {g} "
+                f"group(s); put the whole frozen prefix in eval mode, or none of it")
+        return e, g
+
+    def freeze(self, upto):
+        """Freeze the trunk up to and including group `upto` ("stem", "layer1" .. "layer4"):
+        ``requires_grad_(False)`` on its parameters and ``.eval()`` on its modules -- exactly
+        torch's idiom, nothing else.  Groups behind it are made trainable / put in the model's
+        mode.  ``model.train()`` clears the eval flags again, as in torch: call ``freeze`` after it
+        (``Trainer.train_step`` calls ``model.train()`` only when the model is in eval mode)."""
+        if upto not in TRUNK_GROUPS:
+            raise ValueError(f"freeze(upto): one of {TRUNK_GROUPS}, got {upto!r}")
+        k = TRUNK_GROUPS.index(upto) + 1
+        for gi, children in enumerate(_GROUP_CHILDREN):
+            for ci in children:
+                child = self.visual_encoder[ci]
+                child.requires_grad_(gi >= k)
+                child.train(self.training and gi >= k)
+        return self
+
+    def unfreeze(self):
+        """Undo ``freeze``: every trunk parameter trainable, every trunk module in the model's mode."""
+        for children in _GROUP_CHILDREN:
+            for ci in children:
+                child = self.visual_encoder[ci]
+                child.requires_grad_(True)
+                child.train(self.training)
+        return self
+
     # -- engine plumbing ---------------------------------------------------------------------
     def _apply(self, fn, *a, **k):
         # .to()/.cuda()/.cpu() re-create parameter storage: the flat arena must be rebuilt
         self._engine = None
+        self.__dict__.pop("_ft_lists", None)
         return super()._apply(fn, *a, **k)
 
     def engine(self) -> Engine:

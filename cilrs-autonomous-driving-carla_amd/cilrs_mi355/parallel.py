@@ -15,6 +15,10 @@ contiguous buckets as soon as the backward segments that fill them finish:
 xGMI is point-to-point, so few large buckets beat many small ones; the first bucket carries 63 %
 of the bytes and is in flight while layers 3..1 (70 % of backward FLOPs) still compute.
 The 1/world_size averaging is folded into the Adam kernel's gradient scale.
+
+Fine-tuning (a frozen prefix of the trunk, CILRS.freeze): only trainable ranges are reduced -- a
+bucket that lies wholly inside the frozen prefix is skipped, the one the cut runs through starts at
+the cut, and the segment loop stops at the last trainable segment.
 """
 from __future__ import annotations
 
@@ -24,11 +28,20 @@ import torch.distributed as dist
 from .engine import segment_ranges
 
 
-def bucket_plan(seg_ranges):
-    """[(last_segment, begin, end)] -- contiguous arena ranges, reverse-layer order."""
+def bucket_plan(seg_ranges, frozen_groups=0):
+    """[(last_segment, begin, end)] -- contiguous arena ranges, reverse-layer order.  With the
+    first `frozen_groups` trunk groups (stem, layer1 .. layer4) frozen: the trainable part of
+    every bucket that has one (group j is backward segment 5 - j)."""
     heads, l4, l3, l2, l1, stem = seg_ranges
     assert l4[1] == heads[0] and stem[1] == l1[0] and l1[1] == l2[0]
-    return [(1, l4[0], heads[1]), (2, l3[0], l3[1]), (5, stem[0], l2[1])]
+    plan = [(1, l4[0], heads[1]), (2, l3[0], l3[1]), (5, stem[0], l2[1])]
+    if frozen_groups == 0:
+        return plan
+    if not 0 <= frozen_groups <= 5:
+        raise ValueError("frozen_groups must be in 0..5")
+    last = 5 - frozen_groups                        # last trainable segment
+    cut = seg_ranges[last][0]                       # first trainable float of the arena
+    return [(min(s, last), max(b, cut), e) for s, b, e in plan if e > cut]
 
 
 class BucketedAllReduce:
@@ -38,9 +51,22 @@ class BucketedAllReduce:
         self.world_size = dist.get_world_size(self.pg)
         self.buckets = buckets if buckets is not None else bucket_plan(segment_ranges(variant))
         self._pending = []
+        self._full = list(self.buckets)
+        self._seg_ranges = None if buckets is not None else segment_ranges(variant)
+        self.collectives = 0                        # all-reduces issued so far
+
+    def _plan_for(self, frozen_groups):
+        """The bucket plan of a step with `frozen_groups` frozen trunk groups."""
+        if frozen_groups == 0:
+            return self._full
+        if self._seg_ranges is None:
+            raise RuntimeError("BucketedAllReduce was built with explicit buckets: pass "
+                               "bucket_plan(seg_ranges, frozen_groups) for a frozen prefix")
+        return bucket_plan(self._seg_ranges, frozen_groups)
 
     def reduce_bucket(self, i):
         _, b, e = self.buckets[i]
+        self.collectives += 1
         # async: the collective is ordered after everything already enqueued on the current
         # stream and runs on the process group's own stream, overlapping later compute
         self._pending.append(dist.all_reduce(self.flat[b:e], op=dist.ReduceOp.SUM, group=self.pg,
@@ -51,12 +77,14 @@ class BucketedAllReduce:
             w.wait()
         self._pending.clear()
 
-    def backward_and_reduce(self, eng, plan, dcontrols, dpred_speed, after_bucket=None):
+    def backward_and_reduce(self, eng, plan, dcontrols, dpred_speed, after_bucket=None,
+                            frozen_groups=0):
         """Segment-wise backward, one asynchronous all-reduce per finished bucket.  after_bucket
         (i, begin, end), if given, is called for every bucket in issue order once the compute
         stream has been made to wait for that bucket's collective -- the Trainer updates the
         bucket's parameter range there, so the Adam launches of the early (large) buckets run
         while the last (small) bucket's all-reduce, which nothing else can hide, is in flight."""
+        self.buckets = self._plan_for(frozen_groups)
         seg = 0
         for i, (last_seg, _, _) in enumerate(self.buckets):
             eng.run_backward(plan, dcontrols, dpred_speed, seg, last_seg + 1)

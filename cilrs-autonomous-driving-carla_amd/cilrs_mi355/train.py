@@ -33,6 +33,13 @@ class TrainConfig:
     eps: float = 1e-8
     lr_step_size: int = 8
     lr_gamma: float = 0.5
+    # fine-tuning: learning-rate multiplier per parameter group ("stem", "layer1" .. "layer4",
+    # "heads"; missing = 1.0) -- the lower trunk rate that is usual on top of a pretrained trunk.
+    # None, or all 1.0: the step is the single-rate step, launch for launch.
+    lr_mult: dict = None
+
+
+GROUP_NAMES = ("stem", "layer1", "layer2", "layer3", "layer4", "heads")
 
 
 def dropout_seed(torch_seed: int, call: int, rank: int = 0) -> int:
@@ -68,6 +75,15 @@ class Trainer:
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
         self.step_count = 0
+        # Adam's bias correction counts a tensor's OWN updates (torch.optim.Adam keeps `step` per
+        # parameter and skips `grad is None`): steps each parameter group sat out while frozen.
+        # A group's step is step_count - group_lag[i]; with nothing ever frozen all six are equal.
+        self.group_lag = [0] * 6
+        mult = dict(cfg.lr_mult or {})
+        unknown = set(mult) - set(GROUP_NAMES)
+        if unknown:
+            raise ValueError(f"lr_mult: unknown group(s) {sorted(unknown)}; one of {GROUP_NAMES}")
+        self.lr_mult = [float(mult.get(n, 1.0)) for n in GROUP_NAMES]
         self.epoch = 0
         self.lr = cfg.lr
         self.loss_buf = torch.zeros(8, dtype=torch.float32, device=dev)
@@ -125,28 +141,47 @@ class Trainer:
             L.ptr(self.loss_buf), self._stream()))
         return self.loss_buf, dc, dp
 
+    @property
+    def group_steps(self):
+        """Adam step count of each parameter group (GROUP_NAMES order)."""
+        return [self.step_count - lag for lag in self.group_lag]
+
+    def _freeze_state(self):
+        """The module's (e, g) (CILRS.freeze_state), refused where this Trainer cannot serve it."""
+        e, g = self.model.freeze_state()
+        self.eng.check_freeze(e, g)
+        return e, g
+
+    def _advance_steps(self, frozen_groups):
+        """One optimizer step begins: the trainable groups count it, the frozen ones sit it out."""
+        self.step_count += 1
+        for i in range(frozen_groups):
+            self.group_lag[i] += 1
+
     def optimizer_step(self, grad_scale=1.0):
-        """clip_grad_norm_ (nb:553-554) + Adam.step (nb:555) over the flat arena."""
+        """clip_grad_norm_ (nb:553-554) + Adam.step (nb:555) over the flat arena -- over its
+        trainable range when a prefix of the trunk is frozen (frozen parameters and their moments
+        are not touched and take no weight decay, like torch.optim.Adam's `grad is None`)."""
         lib = L.lib()
         eng, cfg = self.eng, self.cfg
+        e, g = self._freeze_state()
+        begin = eng.trainable_begin(g)
+        n = eng.n_arena - begin
         clip_ptr = None
         # arena * arena_grad_scale = the (rank-averaged) gradient this step's clip + Adam consume
         self.arena_grad_scale = 1.0 if cfg.grad_clip > 0 else float(grad_scale)
         if cfg.grad_clip > 0:
             if grad_scale != 1.0:
-                L.check(lib.cilrs_scale(L.ptr(eng.grads), eng.n_arena, None, grad_scale,
+                L.check(lib.cilrs_scale(L.ptr(eng.grads[begin:]), n, None, grad_scale,
                                         self._stream()))
                 grad_scale = 1.0
-            L.check(lib.cilrs_grad_sqnorm(L.ptr(eng.grads), eng.n_arena, cfg.grad_clip,
+            L.check(lib.cilrs_grad_sqnorm(L.ptr(eng.grads[begin:]), n, cfg.grad_clip,
                                           L.ptr(self.norm_scratch), L.ptr(self.clip_out),
                                           self._stream()))
             clip_ptr = L.ptr(self.clip_out)
-        self.step_count += 1
-        eng.weights_epoch += 1                # the fused Adam writes the parameter arena in place
-        L.check(lib.cilrs_adam_step(L.ptr(eng.params), L.ptr(eng.grads), L.ptr(self.exp_avg),
-                                    L.ptr(self.exp_avg_sq), eng.n_arena, self.lr, cfg.betas[0],
-                                    cfg.betas[1], cfg.eps, cfg.weight_decay, self.step_count,
-                                    clip_ptr, grad_scale, self._stream()))
+        self._advance_steps(g)
+        eng.wrote_trainable(e)                # the fused Adam writes the parameter arena in place
+        self._adam_range(begin, eng.n_arena, grad_scale, clip_ptr, g)
 
     # -- one iteration of train_one_epoch's loop (nb:549-555) ------------------------------------
     def train_step(self, imgs, speeds, cmds, tgts):
@@ -154,19 +189,28 @@ class Trainer:
         eng = self._ensure_engine()
         if not self.model.training:
             self.model.train()
+        # the frozen prefix the module's flags describe, re-read on every step (raises on a
+        # pattern that cannot be served, before any launch)
+        e, g = self._freeze_state()
+        if g and self.reducer is None and self.cfg.grad_clip <= 0 and self.fuse_optimizer:
+            raise RuntimeError("Trainer.fuse_optimizer cannot serve a frozen trunk prefix (one "
+                               "fused update per backward segment, one step count)")
         seed = self.next_dropout_seed() if self.cfg.dropout > 0 else 0
-        controls, pred_speed, pl = eng.run_forward(imgs, speeds, cmds, True, self.cfg.dropout,
-                                                   seed)
+        controls, pred_speed, pl = eng.run_forward_ft(imgs, speeds, cmds, e, g, self.cfg.dropout,
+                                                      seed)
         # `speeds` is both an input and the speed head's regression target (nb:550)
         _, dc, dp = self.loss(controls, tgts, pred_speed, speeds)
         if self.reducer is None and self.cfg.grad_clip <= 0 and self.fuse_optimizer:
             # backward + Adam in one call: a segment's update runs as soon as its gradients are
             # complete (clipping needs the global norm first and keeps the two-call path below)
-            self.step_count += 1
+            if len(set(self.lr_mult)) != 1 or len(set(self.group_lag)) != 1:
+                raise RuntimeError("Trainer.fuse_optimizer takes one learning rate and one step "
+                                   "count for the whole arena (lr_mult / earlier frozen steps)")
+            self._advance_steps(0)
             self.arena_grad_scale = 1.0
-            eng.run_backward_step(pl, dc, dp, self.exp_avg, self.exp_avg_sq, self.lr,
-                                  self.cfg.betas, self.cfg.eps, self.cfg.weight_decay,
-                                  self.step_count)
+            eng.run_backward_step(pl, dc, dp, self.exp_avg, self.exp_avg_sq,
+                                  self.lr * self.lr_mult[0], self.cfg.betas, self.cfg.eps,
+                                  self.cfg.weight_decay, self.group_steps[0])
         elif self.reducer is None:
             eng.run_backward(pl, dc, dp)
             self.optimizer_step(1.0)
@@ -174,25 +218,57 @@ class Trainer:
             # data parallel without clipping: Adam per all-reduce bucket, as soon as the bucket's
             # averaged gradient is there (the last bucket's collective runs under the first two
             # buckets' updates); same numbers as one launch over the arena
-            self.step_count += 1
-            eng.weights_epoch += 1
+            self._advance_steps(g)
+            eng.wrote_trainable(e)
             scale = 1.0 / self.reducer.world_size
             self.arena_grad_scale = scale
             self.reducer.backward_and_reduce(
-                eng, pl, dc, dp, after_bucket=lambda _i, b, e: self._adam_range(b, e, scale))
+                eng, pl, dc, dp, frozen_groups=g,
+                after_bucket=lambda _i, b, e_: self._adam_range(b, e_, scale, None, g))
         else:
-            self.reducer.backward_and_reduce(eng, pl, dc, dp)
+            self.reducer.backward_and_reduce(eng, pl, dc, dp, frozen_groups=g)
             self.optimizer_step(1.0 / self.reducer.world_size)
         return self.loss_buf
 
-    def _adam_range(self, begin, end, grad_scale):
-        """cilrs_adam_step over the arena range [begin, end) (step_count already advanced)."""
+    def _adam_range(self, begin, end, grad_scale, clip_ptr=None, frozen_groups=0):
+        """cilrs_adam_step over the trainable part of the arena range [begin, end) (step counts
+        already advanced).  Adjacent parameter groups that share learning rate and step
+        count form one run; one run is the plain cilrs_adam_step launch, several (lr_mult, or
+        an earlier freeze that tells the groups' step counts apart) go to the table-driven
+        launch."""
         eng, cfg = self.eng, self.cfg
-        L.check(L.lib().cilrs_adam_step(
-            L.ptr(eng.params[begin:end]), L.ptr(eng.grads[begin:end]),
-            L.ptr(self.exp_avg[begin:end]), L.ptr(self.exp_avg_sq[begin:end]), end - begin, self.lr,
-            cfg.betas[0], cfg.betas[1], cfg.eps, cfg.weight_decay, self.step_count, None,
-            float(grad_scale), self._stream()))
+        steps = self.group_steps
+        runs = []                             # [begin, end, lr, step]
+        for i in range(frozen_groups, 6):
+            b, e = eng.group_ranges[i]
+            b, e = max(b, begin), min(e, end)
+            if b >= e:
+                continue
+            lr = self.lr * self.lr_mult[i]
+            if runs and runs[-1][1] == b and runs[-1][2] == lr and runs[-1][3] == steps[i]:
+                runs[-1][1] = e
+            else:
+                runs.append([b, e, lr, steps[i]])
+        if not runs:
+            return
+        b, e = runs[0][0], runs[-1][1]
+        if len(runs) == 1:
+            _, _, lr, step = runs[0]
+            L.check(L.lib().cilrs_adam_step(
+                L.ptr(eng.params[b:e]), L.ptr(eng.grads[b:e]), L.ptr(self.exp_avg[b:e]),
+                L.ptr(self.exp_avg_sq[b:e]), e - b, lr, cfg.betas[0], cfg.betas[1], cfg.eps,
+                cfg.weight_decay, step, clip_ptr, float(grad_scale), self._stream()))
+            return
+        # several rates / step counts: still one launch, the kernel looks them up per range
+        # (range launches cost 0.044 ms per step at B=128, DESIGN.md "Fine-tuning")
+        k = len(runs)
+        ends = (C.c_size_t * k)(*[r[1] - b for r in runs])
+        lrs = (C.c_double * k)(*[r[2] for r in runs])
+        steps = (C.c_int64 * k)(*[r[3] for r in runs])
+        L.check(L.lib().cilrs_adam_step_groups(
+            L.ptr(eng.params[b:e]), L.ptr(eng.grads[b:e]), L.ptr(self.exp_avg[b:e]),
+            L.ptr(self.exp_avg_sq[b:e]), e - b, k, ends, lrs, steps, cfg.betas[0], cfg.betas[1],
+            cfg.eps, cfg.weight_decay, clip_ptr, float(grad_scale), self._stream()))
 
     def next_dropout_seed(self):
         """Seed of the next train step's dropout masks: torch's seed, the step count and the

@@ -378,6 +378,10 @@ int wino_groups(int N, int H, int W);        // 64-tile groups of a launch
 // (C > 0 and slab_floats: the channel split may change the answer)
 int wino_rows(int N, int H, int W, int K, int no_tail = 0, int C = 0, size_t slab_floats = 0);
 int launch_conv_wino(const WinoArgs& a, hipStream_t s);
+// the same convolution with an eval-mode BatchNorm folded into the epilogue (the frozen prefix of a
+// fine-tuning step): y = relu_post?(relu?(conv * scale[k] + shift[k]) + addend)
+struct WinoFold { const float* scale; const float* shift; int relu, relu_post; };
+int launch_conv_wino_fold(const WinoArgs& a, const WinoFold& f, hipStream_t s);
 int wino_last_csplit();                      // parts per tile of the most recent launch
 // Weight gradient of the same convolutions in the Winograd domain:
 //   dU_xi[k][c] = sum over tiles of (A dY A^T)_xi[tile][k] * (B^T d B)_xi[tile][c],  dw = G^T dU G
@@ -624,6 +628,14 @@ int launch_grad_sqnorm(const float* g, size_t n, float max_norm, double* partial
 int launch_adam(float* p, const float* g, float* m, float* v, size_t n, double lr, double beta1,
                 double beta2, double eps, double wd, long long step, const float* clip_out,
                 float gscale, hipStream_t s);
+// one launch over adjacent ranges [0, ends[0]), [ends[0], ends[1]) ... with a learning rate and a
+// step count each (heads_optim.hip adam_table_kernel)
+constexpr int kAdamTableMax = 8;
+struct AdamTable { int n; size_t end4[kAdamTableMax]; float neg_step_size[kAdamTableMax], bc2_sqrt[kAdamTableMax]; };
+int launch_adam_groups(float* p, const float* g, float* m, float* v, size_t n, int ngroups,
+                       const size_t* ends, const double* lrs, const long long* steps, double beta1,
+                       double beta2, double eps, double wd, const float* clip_out, float gscale,
+                       hipStream_t s);
 int launch_scale(float* g, size_t n, const float* coef_ptr, float c, hipStream_t s);
 int launch_keep_head_inputs(const float* speed, const long long* cmd, float* speed_dst,
                             long long* cmd_dst, int B, hipStream_t s);

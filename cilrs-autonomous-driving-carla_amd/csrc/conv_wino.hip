@@ -193,8 +193,14 @@ __global__ __launch_bounds__(256) void wino_weights_kernel(const float* __restri
 // the register file holds 32 more, the other half is requested right after the loop), so the
 // burst of 2 x 64 KB per block that all CUs used to issue TOGETHER after their last MFMA runs
 // under the last one and a half chunks instead.
-template <bool PRE>
-__device__ __forceinline__ void wino_full_body(const WinoArgs& a, float* smem, const int bid) {
+// FOLD (compile time; the frozen prefix of a fine-tuning step, net.hip trunk_fwd_eval32): the
+// epilogue applies an eval-mode BatchNorm as per-channel scale / shift, then ReLU, the residual
+// addend and the ReLU behind it -- the implicit-GEMM eval epilogue's order -- and emits no column
+// partials.  The addend must not ride in the accumulators there (it would be scaled): FOLD
+// launches are never PRE.
+template <bool PRE, bool FOLD = false>
+__device__ __forceinline__ void wino_full_body(const WinoArgs& a, float* smem, const int bid,
+                                               const WinoFold* fold = nullptr) {
     constexpr int STAGE = 16 * WT * WP + 16 * WK * WP;      // floats per stage (64 KB)
     float* Vs = smem;                          // [2 stages]: [16][WT][WP] | [16][WK][WP]
     float* Us = smem + 16 * WT * WP;
@@ -519,9 +525,28 @@ __device__ __forceinline__ void wino_full_body(const WinoArgs& a, float* smem, c
         y[1] = s0[1] - s0[2] - s0[3];
         y[2] = s1[0] + s1[1] + s1[2];
         y[3] = s1[1] - s1[2] - s1[3];
+        if constexpr (FOLD) {
+            const f32x4 sc = *reinterpret_cast<const f32x4*>(fold->scale + co + mb * 16);
+            const f32x4 sh = *reinterpret_cast<const f32x4*>(fold->shift + co + mb * 16);
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float v = fmaf(y[q][e], sc[e], sh[e]);
+                    y[q][e] = fold->relu ? fmaxf(v, 0.f) : v;
+                }
+        }
         if (with_add) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) y[q] += ad[mb][q];
+        }
+        if constexpr (FOLD) {
+            if (fold->relu_post) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) y[q][e] = fmaxf(y[q][e], 0.f);
+            }
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -602,7 +627,9 @@ __device__ __forceinline__ void wino_full_body(const WinoArgs& a, float* smem, c
 constexpr int QT = 16;
 constexpr int QSTAGE = 16 * QT * WP + 16 * WK * WP;          // floats per stage (40 KB)
 constexpr size_t kWinoQLds = (size_t)2 * QSTAGE * sizeof(float);
-__device__ __forceinline__ void wino_q_body(const WinoArgs& a, float* smem, const int bid) {
+template <bool FOLD = false>
+__device__ __forceinline__ void wino_q_body(const WinoArgs& a, float* smem, const int bid,
+                                            const WinoFold* fold = nullptr) {
     float* Vs = smem;                          // [2 stages]: [16][QT][WP] | [16][WK][WP]
     float* Us = smem + 16 * QT * WP;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -781,9 +808,28 @@ __device__ __forceinline__ void wino_q_body(const WinoArgs& a, float* smem, cons
         y[1] = s0[1] - s0[2] - s0[3];
         y[2] = s1[0] + s1[1] + s1[2];
         y[3] = s1[1] - s1[2] - s1[3];
+        if constexpr (FOLD) {
+            const f32x4 sc = *reinterpret_cast<const f32x4*>(fold->scale + co);
+            const f32x4 sh = *reinterpret_cast<const f32x4*>(fold->shift + co);
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float v = fmaf(y[q][e], sc[e], sh[e]);
+                    y[q][e] = fold->relu ? fmaxf(v, 0.f) : v;
+                }
+        }
         if (a.addend) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) y[q] += ad[q];
+        }
+        if constexpr (FOLD) {
+            if (fold->relu_post) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) y[q][e] = fmaxf(y[q][e], 0.f);
+            }
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -844,6 +890,14 @@ __global__ __launch_bounds__(WTHREADS) void conv_wino_kernel(const WinoArgs a, c
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if ((int)blockIdx.x < nfull) wino_full_body<PRE>(a, smem, (int)blockIdx.x);
     else wino_q_body(tail, smem, (int)blockIdx.x - nfull);
+}
+// the folded-epilogue variant (WinoFold): its own kernel, so the training kernels above keep their
+// argument layout and their code
+__global__ __launch_bounds__(WTHREADS) void conv_wino_fold_kernel(const WinoArgs a, const WinoArgs tail,
+                                                                  const int nfull, const WinoFold fold) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    if ((int)blockIdx.x < nfull) wino_full_body<false, true>(a, smem, (int)blockIdx.x, &fold);
+    else wino_q_body<true>(tail, smem, (int)blockIdx.x - nfull, &fold);
 }
 
 // ---- weight gradient in the Winograd domain ---------------------------------------------------------
@@ -1092,7 +1146,8 @@ constexpr size_t kWinoLds = (size_t)2 * (16 * WT * WP + 16 * WK * WP) * sizeof(f
 //  stream capture)
 int wino_prepare() {
     return set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wino_kernel<false>), (int)kWinoLds) ||
-           set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wino_kernel<true>), (int)kWinoLds);
+           set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wino_kernel<true>), (int)kWinoLds) ||
+           set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wino_fold_kernel), (int)kWinoLds);
 }
 
 // How a launch is cut: `full` 64-tile groups on the main kernel, the remaining tiles as 16-tile
@@ -1177,6 +1232,32 @@ int launch_conv_wino(const WinoArgs& a_in, hipStream_t s) {
         conv_wino_kernel<true><<<nfull + ntail, WTHREADS, nfull > 0 ? kWinoLds : kWinoQLds, s>>>(a, t, nfull);
     else
         conv_wino_kernel<false><<<nfull + ntail, WTHREADS, nfull > 0 ? kWinoLds : kWinoQLds, s>>>(a, t, nfull);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
+// y = relu_post?(relu?(conv * scale + shift) + addend): one launch, full blocks + tail, no channel
+// split (the slab reduce knows the training epilogues only) and no column partials
+int launch_conv_wino_fold(const WinoArgs& a_in, const WinoFold& f, hipStream_t s) {
+    WinoArgs a = a_in;
+    CILRS_CHECK(a.x && a.U && a.y && f.scale && f.shift, "conv_wino_fold: NULL tensor");
+    CILRS_CHECK(a.C % WC == 0 && a.K % WK == 0, "conv_wino_fold: C %% 8, K %% 64");
+    CILRS_CHECK((size_t)a.N * a.H * a.W * a.C * 4 < (1ull << 32) &&
+                    (size_t)a.N * a.H * a.W * a.K * 4 < (1ull << 32) &&
+                    (size_t)16 * a.C * a.K * 4 < (1ull << 32),
+                "conv_wino_fold: tensor too large for 32-bit offsets");
+    CILRS_CHECK((((uintptr_t)f.scale | (uintptr_t)f.shift) & 15) == 0,
+                "conv_wino_fold: scale / shift must be 16-byte aligned");
+    if (wino_prepare()) return 1;
+    a.bn_partial = nullptr; a.bwd_partial = nullptr; a.bwd_z = a.bwd_y = a.bwd_stats = nullptr;
+    a.slabs = nullptr; a.csplit = 1; a.stamps = nullptr;
+    const WinoSplit sp = wino_split(a.N, a.H, a.W, a.K, a.no_tail);
+    a.rows = sp.full + sp.tail;
+    WinoArgs t = a;
+    a.tile_begin = 0; a.row0 = 0;
+    t.tile_begin = sp.full * WT; t.row0 = sp.full;
+    const int nfull = sp.full * (a.K / WK), ntail = sp.tail * (a.K / WK);
+    conv_wino_fold_kernel<<<nfull + ntail, WTHREADS, nfull > 0 ? kWinoLds : kWinoQLds, s>>>(a, t, nfull, f);
     CILRS_LAUNCH_CHECK();
     return 0;
 }

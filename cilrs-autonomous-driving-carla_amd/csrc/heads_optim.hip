@@ -607,6 +607,44 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p,
     }
 }
 
+// The same update with the step size and the bias correction looked up per arena range (parameter
+// groups with learning rates / step counts of their own: TrainConfig.lr_mult, groups that sat out
+// fine-tuning steps while frozen) -- one launch instead of one per range.  Element for element the
+// arithmetic of adam_kernel.
+__global__ __launch_bounds__(256) void adam_table_kernel(float* __restrict__ p,
+                                                         const float* __restrict__ g,
+                                                         float* __restrict__ m, float* __restrict__ v,
+                                                         const size_t n4, const float omb1,
+                                                         const float beta2, const float omb2,
+                                                         const float eps, const float wd,
+                                                         const AdamTable t,
+                                                         const float* __restrict__ gscale_ptr,
+                                                         const float gscale_const) {
+    const float gs = gscale_ptr ? gscale_ptr[1] * gscale_const : gscale_const;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+         i += (size_t)gridDim.x * blockDim.x) {
+        int r = 0;
+        while (r + 1 < t.n && i >= t.end4[r]) ++r;
+        const float neg_step_size = t.neg_step_size[r], bc2_sqrt = t.bc2_sqrt[r];
+        f32x4 pv = *reinterpret_cast<const f32x4*>(p + i * 4);
+        f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
+        f32x4 mv = *reinterpret_cast<const f32x4*>(m + i * 4);
+        f32x4 vv = *reinterpret_cast<const f32x4*>(v + i * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float gg = gv[e] * gs;
+            gg = gg + wd * pv[e];
+            mv[e] = mv[e] + omb1 * (gg - mv[e]);
+            vv[e] = vv[e] * beta2 + (omb2 * gg) * gg;
+            const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
+            pv[e] = pv[e] + (neg_step_size * mv[e]) / denom;
+        }
+        *reinterpret_cast<f32x4*>(p + i * 4) = pv;
+        *reinterpret_cast<f32x4*>(m + i * 4) = mv;
+        *reinterpret_cast<f32x4*>(v + i * 4) = vv;
+    }
+}
+
 __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ g, const size_t n4,
                                                     const float* __restrict__ coef_ptr,
                                                     const float c) {
@@ -822,6 +860,35 @@ int launch_adam(float* p, const float* g, float* m, float* v, size_t n, double l
                                                  (float)beta2, (float)(1.0 - beta2), (float)eps,
                                                  (float)wd, neg_step_size, bc2_sqrt, clip_out,
                                                  gscale);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_adam_groups(float* p, const float* g, float* m, float* v, size_t n, int ngroups,
+                       const size_t* ends, const double* lrs, const long long* steps, double beta1,
+                       double beta2, double eps, double wd, const float* clip_out, float gscale,
+                       hipStream_t s) {
+    CILRS_CHECK(n % 4 == 0, "adam: n must be a multiple of 4");
+    CILRS_CHECK(ngroups >= 1 && ngroups <= kAdamTableMax && ends && lrs && steps,
+                "adam: 1..%d ranges", kAdamTableMax);
+    AdamTable t = {};
+    t.n = ngroups;
+    size_t prev = 0;
+    for (int r = 0; r < ngroups; ++r) {
+        CILRS_CHECK(ends[r] > prev && ends[r] % 4 == 0 && ends[r] <= n && steps[r] >= 1,
+                    "adam: range ends must increase in multiples of 4 up to n, steps >= 1");
+        prev = ends[r];
+        const double bc1 = 1.0 - pow(beta1, (double)steps[r]);
+        const double bc2 = 1.0 - pow(beta2, (double)steps[r]);
+        t.end4[r] = ends[r] / 4;
+        t.neg_step_size[r] = (float)(-(lrs[r] / bc1));
+        t.bc2_sqrt[r] = (float)sqrt(bc2);
+    }
+    CILRS_CHECK(prev == n, "adam: the last range must end at n");
+    const size_t n4 = n / 4;
+    adam_table_kernel<<<grid1d(n4, 4096), 256, 0, s>>>(p, g, m, v, n4, (float)(1.0 - beta1),
+                                                       (float)beta2, (float)(1.0 - beta2),
+                                                       (float)eps, (float)wd, t, clip_out, gscale);
     CILRS_LAUNCH_CHECK();
     return 0;
 }

@@ -285,6 +285,12 @@ using namespace cilrs;
 // ------------------------------------------------------------------------------------------------
 struct ConvG { int H, W, Ho, Wo, M; size_t y, z, stats; };
 constexpr int kTileCounters = 16384;
+// The frozen prefix of a fine-tuning step sends the layers the train plan gives to the Winograd
+// kernel through its folded-epilogue variant (conv_wino.hip FOLD) instead of the implicit GEMM
+// (DESIGN.md "Fine-tuning" has the per-shape measurement; CILRS_FT_WINO=0 of an experiments
+// build puts the implicit GEMM back, read on every call so that tools/finetune_bench.py can
+// compare the two in one process).
+static bool ft_wino_fold() { return experiment_env("CILRS_FT_WINO", 1) != 0; }
 
 // dy ring: bn_bwd writes each conv's output gradient into the next ring slot; the weight-gradient
 // GEMM that consumes it runs on side stream 0 and may lag the data-gradient chain by up to
@@ -375,6 +381,17 @@ struct cilrs_net {
     bool wino_on[kMaxConvs] = {};
     size_t wino_base = 0;
     WinoWeightTable wino_table;
+    // Fine-tuning (cilrs_net_forward_ft): leading trunk groups (stem, layer1..layer4) of the last
+    // graph-keeping forward that ran in eval mode (ft_bn: BatchNorm folded into the convolution
+    // epilogues, nothing kept for a backward pass) / whose parameters take no gradient (ft_grad:
+    // where cilrs_net_backward stops).  The prefix's weight-derived state -- scale / shift of its
+    // BatchNorms, the padded stem weights, the Winograd filter images of its layers -- is cached
+    // under the caller's prefix key.  ft_wino: folded-epilogue Winograd launches of that forward.
+    int ft_bn = 0, ft_grad = 0, ft_wino = 0;
+    bool ft_route_wino = false;            // conv_fwd is building a frozen prefix
+    uint64_t ft_prep_key = 0;
+    int ft_prep_groups = 0;
+    const void* ft_prep_bufs[3] = {nullptr, nullptr, nullptr};
     // persistent single-frame kernel (infer_b1.hip): stage table + barrier counters in the
     // workspace (offsets in floats; 0 = this plan has none), uploaded once per workspace
     size_t b1_table = 0, b1_sync = 0, b1_stamps = 0, b1_slabs = 0, b1_slab_floats = 0, b1_cmd = 0;
@@ -543,6 +560,23 @@ int conv_fwd(cilrs_net* net, const ConvT& c, const ConvG& g, const float* x, int
                                     16.0 * c.cout * c.cin);
         RUN(net, std::string("conv_fwd.") + kGroupName[c.group], flops, bytes, s,
             launch_conv_wino(wa, s));
+        return 0;
+    }
+    if (fold_stats && net->ft_route_wino && net->wino_on[ci] && ft_wino_fold()) {
+        // frozen prefix of a fine-tuning step: the Winograd kernel with the folded epilogue
+        WinoArgs wa;
+        memset(&wa, 0, sizeof(wa));
+        int e = 0;
+        while (net->wino_table.w[e] != (unsigned)c.w) ++e;
+        wa.x = x; wa.U = ws + net->wino_base + net->wino_table.u[e]; wa.y = y; wa.addend = addend;
+        wa.N = net->B; wa.H = g.H; wa.W = g.W; wa.C = c.cin; wa.K = c.cout;
+        const WinoFold f{fold_stats + 2 * c.cout, fold_stats + 3 * c.cout, relu, relu_post};
+        const double flops = 2.0 * g.M * c.cout * c.k * c.k * c.cin;      // DIRECT-convolution flops
+        const double bytes = 4.0 * ((double)net->B * g.H * g.W * c.cin + (double)g.M * c.cout *
+                                    (addend ? 2.0 : 1.0) + 16.0 * c.cout * c.cin);
+        RUN(net, std::string("conv_fwd.") + kGroupName[c.group], flops, bytes, s,
+            launch_conv_wino_fold(wa, f, s));
+        ++net->ft_wino;
         return 0;
     }
     ConvArgs a;
@@ -1219,12 +1253,34 @@ static int fold_prep(cilrs_net* net, const cilrs_buffers* bufs, int half, hipStr
     return 0;
 }
 
+// Entries of the plan's Winograd table whose layers lie in trunk groups [g0, g1) (1 = layer1 ...;
+// the table is in layer order, so this is a contiguous run), as a table of its own
+static WinoWeightTable wino_subtable(const cilrs_net* net, int g0, int g1) {
+    const Arch& A = *net->A;
+    const WinoWeightTable& t = net->wino_table;
+    WinoWeightTable o;
+    memset(&o, 0, sizeof(o));
+    for (int e = 0; e < t.n; ++e) {
+        int grp = -1;
+        for (const ConvT& c : A.convs)
+            if ((unsigned)c.w == t.w[e]) grp = c.group;
+        if (grp < g0 || grp >= g1) continue;
+        const int k = o.n++;
+        o.K[k] = t.K[e]; o.C[k] = t.C[e]; o.w[k] = t.w[e]; o.u[k] = t.u[e]; o.ud[k] = t.ud[e];
+        o.blk_begin[k + 1] = o.blk_begin[k] + (t.blk_begin[e + 1] - t.blk_begin[e]);
+    }
+    return o;
+}
+
 // Trunk of the graph-keeping forwards -- the fp32 train step, the bf16 training mode and the frozen
 // eval-with-grad forward: BatchNorm on the batch statistics (train) or the running ones (frozen,
 // scale/shift from eval_prep); keeps every activation the backward pass reads (y, z, the max-pool
 // argmax).  *feat: the last feature map, or nullptr when it is already pooled into `combined`.
+// ft_groups > 0 (fine-tuning): the first ft_groups trunk groups were already computed in eval mode
+// (trunk_fwd_eval32 up to that group, last output in `start`); this function builds the rest.
 static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train, bool frozen,
-                           hipStream_t s, const float** feat) {
+                           hipStream_t s, const float** feat, int ft_groups = 0,
+                           const float* start = nullptr) {
     const Arch& A = *net->A;
     float* ws = reinterpret_cast<float*>(bufs->workspace);
     const float* P = bufs->params;
@@ -1277,9 +1333,15 @@ static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train,
             if (gbuf_side_begin(net, s)) return 1;
             ts = net->side[0];
         }
-        if (net->wino_table.n)
+        if (net->wino_table.n && ft_groups == 0) {
             RUN(net, "transform", 0.0, 4.0 * 4.6 * (double)net->wino_table.blk_begin[net->wino_table.n] * 256, ts,
                 launch_wino_weights_all(net->wino_table, P, ws + net->wino_base, ts));
+        } else if (net->wino_table.n) {        // (the frozen layers' images are cached: ft_prep)
+            const WinoWeightTable t = wino_subtable(net, ft_groups, 5);
+            if (t.n)
+                RUN(net, "transform", 0.0, 4.0 * 4.6 * (double)t.blk_begin[t.n] * 256, ts,
+                    launch_wino_weights_all(t, P, ws + net->wino_base, ts));
+        }
         if (bf16t) {
             RUN(net, "transform", 0.0, 6.0 * A.arena_floats, ts,
                 launch_f32_to_f16(P, h16(ws, net->w16_all), A.arena_floats, 1, ts));
@@ -1292,7 +1354,9 @@ static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train,
         }
     }
     int nb = 0;                             // batch statistics fused into the conv epilogue
-    if (const int srows = stem_f32_rows(B, net->H, net->W)) {
+    if (ft_groups > 0) {
+        // (frozen stem: nothing of it is kept, the max-pool of the prefix ran without an argmax)
+    } else if (const int srows = stem_f32_rows(B, net->H, net->W)) {
         // (weights in registers, k = 7 x 22 instead of 13 x 16: stem_f32.hip)
         RUN(net, "conv_fwd.stem", 2.0 * net->cg[0].M * 64 * 147,
             16.0 * B * net->H * net->W + 4.0 * net->cg[0].M * 64, s,
@@ -1306,7 +1370,7 @@ static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train,
     // stem BatchNorm: statistics only -- its apply + ReLU is fused into the max-pool, the post-BN
     // tensor (144 MB at B=128) is never written.  (frozen: eval_prep derived every layer's scale /
     // shift from the running statistics; the other BatchNorms re-derive theirs in the bn() apply)
-    if (!frozen) {
+    if (!frozen && ft_groups == 0) {
         const ConvT& c0 = A.convs[0];
         const ConvG& g0 = net->cg[0];
         const BnT& b0 = A.bns[c0.bn];
@@ -1318,10 +1382,11 @@ static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train,
                                 s));
     }
     unsigned char* argmax = reinterpret_cast<unsigned char*>(bufs->workspace) + net->argmax_b;
-    RUN(net, "maxpool", 0.0, 4.0 * net->cg[0].M * 64 * 1.25, s,
-        launch_bn_relu_maxpool_fwd(ws + net->cg[0].y, ws + net->cg[0].stats, ws + net->pool,
-                                   argmax, B, net->H0, net->W0, 64, s,
-                                   bf16t ? (void*)h16(ws, net->pool16) : nullptr));
+    if (ft_groups == 0)
+        RUN(net, "maxpool", 0.0, 4.0 * net->cg[0].M * 64 * 1.25, s,
+            launch_bn_relu_maxpool_fwd(ws + net->cg[0].y, ws + net->cg[0].stats, ws + net->pool,
+                                       argmax, B, net->H0, net->W0, 64, s,
+                                       bf16t ? (void*)h16(ws, net->pool16) : nullptr));
     // (this step's weight images were requested before the stem, on the side stream)
     if (net->wprep_pending) {
         CILRS_HIP(hipStreamWaitEvent(s, net->wprep_ev, 0));
@@ -1329,9 +1394,10 @@ static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train,
     }
     // ---- residual blocks: BasicBlock conv-BN-ReLU-conv-BN-(+id)-ReLU, Bottleneck with a third
     //      conv-BN pair; the identity (or downsample branch) joins at the last BatchNorm ----
-    const float* cur = ws + net->pool;
+    const float* cur = ft_groups > 0 ? start : ws + net->pool;
     const cilrs_half* cur16 = h16(ws, net->pool16);
     for (const BlockT& blk : A.blocks) {
+        if (A.convs[blk.conv1].group < ft_groups) continue;
         const int chain[3] = {blk.conv1, blk.conv2, blk.conv3};
         const int nchain = blk.conv3 >= 0 ? 3 : 2;
         const void* identity = bf16t ? (const void*)cur16 : (const void*)cur;
@@ -1404,8 +1470,10 @@ static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train,
 }
 
 // fp32 eval trunk: BatchNorm (scale/shift from eval_prep) folded into the conv epilogues
+// groups < 5 (fine-tuning): only the first `groups` trunk groups (1 = the stem + max-pool alone);
+// *feat is then the last tensor written.
 static int trunk_fwd_eval32(cilrs_net* net, const cilrs_buffers* bufs, hipStream_t s,
-                            const float** feat) {
+                            const float** feat, int groups = 5) {
     const Arch& A = *net->A;
     float* ws = reinterpret_cast<float*>(bufs->workspace);
     const float* P = bufs->params;
@@ -1441,6 +1509,7 @@ static int trunk_fwd_eval32(cilrs_net* net, const cilrs_buffers* bufs, hipStream
     };
     const float* cur = ws + net->pool;
     for (const BlockT& blk : A.blocks) {
+        if (A.convs[blk.conv1].group >= groups) break;
         const ConvT& c1 = A.convs[blk.conv1];
         const ConvT& c2 = A.convs[blk.conv2];
         const ConvG& g1 = net->cg[blk.conv1];
@@ -1654,6 +1723,7 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
                 "frozen forward: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan rejects it)");
     if (zero_counters_once(net, bufs->workspace, s)) return 1;
     net->bwd_done = 0;
+    if (train || frozen) net->ft_bn = net->ft_grad = 0;
     if (train) {
         // the stem weights are padded every step; the cached eval state goes stale as the
         // weights / BN buffers are about to change
@@ -1677,6 +1747,64 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
     net->trained_fwd = graph;
     net->frozen_fwd = frozen;
     net->last_dropout = pdrop;
+    return 0;
+}
+
+// Weight-derived state of a frozen prefix of `groups` trunk groups: the padded stem weights, the
+// BatchNorm scale / shift (one launch derives every layer's; only the prefix's are read) and the
+// Winograd filter images of the prefix's layers.  Frozen weights do not change from step to step:
+// rebuilt only when the caller's prefix key, the cut or the buffers change (key 0: every call).
+static int ft_prep(cilrs_net* net, const cilrs_buffers* bufs, int groups, uint64_t prefix_key,
+                   hipStream_t s) {
+    if (prefix_key != 0 && net->ft_prep_key == prefix_key && net->ft_prep_groups == groups &&
+        net->ft_prep_bufs[0] == (const void*)bufs->params &&
+        net->ft_prep_bufs[1] == (const void*)bufs->bn_running &&
+        net->ft_prep_bufs[2] == (const void*)bufs->workspace)
+        return 0;
+    const Arch& A = *net->A;
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
+    RUN(net, "transform", 0.0, 0.0, s,
+        launch_pad_cin3_to_4(bufs->params + A.convs[0].w, ws + net->w4, 64 * 49, s));
+    RUN(net, "bn_fwd.eval", 0.0, 0.0, s,
+        launch_bn_eval_stats_all(net->bn_table, bufs->params, bufs->bn_running, ws, 1e-5f, s));
+    if (ft_wino_fold() && net->wino_table.n) {
+        const WinoWeightTable t = wino_subtable(net, 1, groups);
+        if (t.n)
+            RUN(net, "transform", 0.0, 4.0 * 4.6 * (double)t.blk_begin[t.n] * 256, s,
+                launch_wino_weights_all(t, bufs->params, ws + net->wino_base, s));
+    }
+    net->ft_prep_key = prefix_key;
+    net->ft_prep_groups = groups;
+    net->ft_prep_bufs[0] = bufs->params; net->ft_prep_bufs[1] = bufs->bn_running;
+    net->ft_prep_bufs[2] = bufs->workspace;
+    return 0;
+}
+
+// Train-mode forward behind a frozen prefix of k trunk groups: the prefix like trunk_fwd_eval32
+// (z only; eligible 3x3 layers on the Winograd kernel's folded epilogue), the rest of the trunk and
+// the heads on the train path, reading the prefix's last tensor.
+static int forward_ft_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const float* speed,
+                              const int64_t* command, int k, uint64_t prefix_key, float dropout_p,
+                              uint64_t seed, float* controls, float* pred_speed, hipStream_t s) {
+    net->ws_base = reinterpret_cast<float*>(bufs->workspace);
+    if (zero_counters_once(net, bufs->workspace, s)) return 1;
+    net->bwd_done = 0;
+    // the trainable weights / BatchNorm buffers are about to change: the cached eval state goes stale
+    net->prep_key = 0; net->fold_key = 0;
+    if (ft_prep(net, bufs, k, prefix_key, s)) return 1;
+    const float* mid = nullptr;
+    net->ft_wino = 0;
+    net->ft_route_wino = true;
+    const int rc0 = trunk_fwd_eval32(net, bufs, s, &mid, k);
+    net->ft_route_wino = false;
+    if (rc0) return 1;
+    const float* feat = mid;
+    if (k < 5 && trunk_fwd_graph(net, bufs, 1, false, s, &feat, k, mid)) return 1;
+    if (heads_fwd(net, bufs, feat, speed, command, true, dropout_p, seed, controls, pred_speed, s))
+        return 1;
+    net->trained_fwd = true;
+    net->frozen_fwd = false;
+    net->last_dropout = dropout_p;
     return 0;
 }
 
@@ -1716,6 +1844,44 @@ int cilrs_net_forward_frozen(cilrs_net* net, const cilrs_buffers* bufs, const fl
     RUN(net, "transform", 0.0, 0.0, s,
         launch_nchw3_to_nhwc4(image, ws + net->x4, net->B, net->H, net->W, sn, sc, sh, sw, s));
     return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s, 0, true);
+}
+
+// Fine-tuning on top of a pretrained trunk -- the reference's own first remedy for its failure on
+// the campus map, "collect a small CUSAT-specific dataset and fine-tune the checkpoint" (reference
+// README.md, "Why Results Degraded on CUSAT Map"; configs/train_config.json carries `pretrained`):
+// the train-mode forward with the first grad_frozen_groups trunk groups (stem, layer1 .. layer4)
+// taking no gradient and the first bn_frozen_groups of them in eval mode.
+int cilrs_net_forward_ft(cilrs_net* net, const cilrs_buffers* bufs, const float* image, long sn,
+                         long sc, long sh, long sw, const float* speed, const int64_t* command,
+                         int bn_frozen_groups, int grad_frozen_groups, uint64_t prefix_key,
+                         float dropout_p, uint64_t seed, float* controls, float* pred_speed,
+                         void* stream) {
+    if (check_bufs(net, bufs, false)) return 1;
+    CILRS_CHECK(image && speed && command && controls && pred_speed, "forward_ft: NULL tensor");
+    const int e = bn_frozen_groups, g = grad_frozen_groups;
+    CILRS_CHECK(0 <= g && g <= 5 && (e == 0 || e == g),
+                "forward_ft: supported cuts are bn_frozen_groups == grad_frozen_groups in 0..5, or "
+                "bn_frozen_groups == 0 (got %d, %d)", e, g);
+    CILRS_CHECK(!(net->bf16_train && g > 0), "forward_ft: a CILRS_PLAN_BF16_TRAIN plan cannot freeze");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
+    RUN(net, "transform", 0.0, 0.0, s,
+        launch_nchw3_to_nhwc4(image, ws + net->x4, net->B, net->H, net->W, sn, sc, sh, sw, s));
+    const int rc = e == 0 ? forward_from_x4(net, bufs, speed, command, 1, dropout_p, seed, controls,
+                                            pred_speed, s)
+                          : forward_ft_from_x4(net, bufs, speed, command, e, prefix_key, dropout_p,
+                                               seed, controls, pred_speed, s);
+    if (rc) return 1;
+    net->ft_bn = e;
+    net->ft_grad = g;
+    return 0;
+}
+int cilrs_net_ft_wino_convs(cilrs_net* net) { return net ? net->ft_wino : 0; }
+int cilrs_net_ft_cut(const cilrs_net* net, int* bn_frozen_groups, int* grad_frozen_groups) {
+    CILRS_CHECK(net != nullptr, "ft_cut: net is NULL");
+    if (bn_frozen_groups) *bn_frozen_groups = net->ft_bn;
+    if (grad_frozen_groups) *grad_frozen_groups = net->ft_grad;
+    return 0;
 }
 
 // uint8 HWC frames -> eval forward in fp32 (half = 0), fp16 (1) or bf16 (2)
@@ -2195,6 +2361,11 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
     if (check_bufs(net, bufs, true)) return 1;
     CILRS_CHECK(net->trained_fwd, "backward needs a preceding train-mode forward on this plan");
     CILRS_CHECK(0 <= seg_begin && seg_begin <= seg_end && seg_end <= 6, "bad segment range");
+    // fine-tuning: the graph ends where the frozen prefix begins -- segments of frozen groups are
+    // not run, and the first block of the last trainable group hands nothing further down
+    const int cut = net->ft_grad;
+    if (seg_end > 6 - cut) seg_end = 6 - cut;
+    if (seg_begin > seg_end) seg_begin = seg_end;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const Arch& A = *net->A;
     float* ws = reinterpret_cast<float*>(bufs->workspace);
@@ -2232,7 +2403,9 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
             net->bwd_nblk_next = 0;
             if (backward_heads(net, bufs, dcontrols, dpred_speed, nullptr, s)) return 1;
             // d visual -> avgpool backward -> grad of the last block's output, in G[3]
-            if (net->bf16_train)
+            if (cut == 5) {
+                // (whole trunk frozen: nobody reads d(feature map))
+            } else if (net->bf16_train)
                 RUN(net, "heads_bwd", 0.0, 0.0, s,
                     launch_avgpool_bwd16(ws + net->dcombined, h16(ws, net->G16[3]), B, net->featHW,
                                          A.feat, A.feat + 128, s));
@@ -2348,7 +2521,20 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
                 }
                 // 3. dW1 (side)
                 if (wgrad_side(c1, g1, xin, xin16, ga, Gp + c1.w)) return 1;
-                if (blk.down < 0) {
+                if (layer == cut && bi == first) {
+                    // boundary block of a fine-tuning step: its input belongs to the frozen
+                    // prefix -- no data gradient leaves it; the down-sample branch still takes
+                    // its own BatchNorm backward and weight gradient
+                    net->bwd_nblk_next = 0;
+                    if (blk.down >= 0) {
+                        const ConvT& cd = A.convs[blk.down];
+                        const ConvG& gd = net->cg[blk.down];
+                        const int gdn = next_ring();
+                        if (gbuf_acquire(net, s, gdn)) return 1;
+                        if (bnb(blk.down, 1, 0, gdn, -1, 0, 6.0)) return 1;
+                        if (wgrad_side(cd, gd, xin, xin16, gdn, Gp + cd.w)) return 1;
+                    }
+                } else if (blk.down < 0) {
                     // 4. dx = dgrad(conv1) + identity grad [1] -> [3]
                     // ... and carries the reductions of the previous block's last BatchNorm
                     const ConvG* prev = bi > 0 ? &net->cg[last_conv(A.blocks[bi - 1])] : nullptr;
@@ -2429,6 +2615,9 @@ int cilrs_net_backward_step(cilrs_net* net, const cilrs_buffers* bufs, const flo
                             const float* dpred_speed, const cilrs_adam_args* opt, void* stream) {
     CILRS_CHECK(net && opt && opt->exp_avg && opt->exp_avg_sq, "backward_step: NULL argument");
     CILRS_CHECK(opt->step >= 1, "backward_step: step must be >= 1");
+    CILRS_CHECK(net->ft_grad == 0, "backward_step: the last forward froze %d trunk group(s); one step "
+                "count for the whole arena cannot serve it (use cilrs_net_backward + cilrs_adam_step "
+                "on the trainable range)", net->ft_grad);
     net->fused_adam = opt;
     const int rc = cilrs_net_backward(net, bufs, dcontrols, dpred_speed, 0, 6, stream);
     net->fused_adam = nullptr;
@@ -2452,6 +2641,8 @@ int cilrs_net_input_grads(cilrs_net* net, const cilrs_buffers* bufs, float* dima
             launch_rowdot(ws + net->ds1, bufs->params + A.se0.w, dspeed, B, 128, 128, s));
     }
     if (dimage) {
+        CILRS_CHECK(net->ft_grad == 0, "input_grads: the last forward froze %d trunk group(s); the "
+                    "backward pass stops there, there is no image gradient", net->ft_grad);
         CILRS_CHECK(net->bwd_done & (1u << 5), "input_grads: dimage needs segment 5 (stem) of "
                     "cilrs_net_backward after the forward");
         const ConvG& g0 = net->cg[0];
@@ -2597,6 +2788,19 @@ int cilrs_adam_step(float* params, const float* grads, float* exp_avg, float* ex
     return launch_adam(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay,
                        (long long)step, clip_out2, grad_scale,
                        reinterpret_cast<hipStream_t>(stream));
+}
+
+int cilrs_adam_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                           size_t n, int ngroups, const size_t* ends, const double* lrs,
+                           const int64_t* steps, double beta1, double beta2, double eps,
+                           double weight_decay, const float* clip_out2, float grad_scale,
+                           void* stream) {
+    CILRS_CHECK(params && grads && exp_avg && exp_avg_sq, "adam: NULL argument");
+    long long st[kAdamTableMax];
+    for (int r = 0; r < ngroups && r < kAdamTableMax; ++r) st[r] = (long long)steps[r];
+    return launch_adam_groups(params, grads, exp_avg, exp_avg_sq, n, ngroups, ends, lrs, st, beta1,
+                              beta2, eps, weight_decay, clip_out2, grad_scale,
+                              reinterpret_cast<hipStream_t>(stream));
 }
 
 int cilrs_stem_conv_fwd(const float* x4, const float* w, float* y, float* bn_partial, int N, int H,
@@ -2931,6 +3135,20 @@ int cilrs_conv2d_wino_fwd(const float* x, const float* w, float* y, int N, int H
     memset(&a, 0, sizeof(a));
     a.x = x; a.U = scratch; a.y = y; a.N = N; a.H = H; a.W = W; a.C = Cin; a.K = Cout;
     return launch_conv_wino(a, s);
+}
+
+int cilrs_conv2d_wino_fold_fwd(const float* x, const float* w, float* y, const float* scale,
+                               const float* shift, const float* addend, int relu, int relu_post,
+                               int N, int H, int W, int Cin, int Cout, float* scratch, void* stream) {
+    CILRS_CHECK(x && w && y && scale && shift && scratch, "conv2d_wino_fold_fwd: NULL argument");
+    CILRS_CHECK(wino_supported(Cin, Cout, 3, 1, 1), "conv2d_wino_fold_fwd: Cin %% 8, Cout %% 64");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (launch_wino_weights(w, scratch, Cout, Cin, 0, s)) return 1;
+    WinoArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.U = scratch; a.y = y; a.addend = addend; a.N = N; a.H = H; a.W = W; a.C = Cin; a.K = Cout;
+    const WinoFold f{scale, shift, relu, relu_post};
+    return launch_conv_wino_fold(a, f, s);
 }
 
 size_t cilrs_conv2d_wino_wgrad_scratch_floats(int N, int H, int W, int Cin, int Cout) {

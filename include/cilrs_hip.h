@@ -121,6 +121,41 @@ int cilrs_net_forward_frozen(cilrs_net* net, const cilrs_buffers* bufs, const fl
                              long sc, long sh, long sw, const float* speed, const int64_t* command,
                              float* controls, float* pred_speed, void* stream);
 
+/* Fine-tuning on top of a pretrained trunk -- the reference's own first remedy for its failure on
+ * the campus map: "collect a small CUSAT-specific dataset and fine-tune the checkpoint" (reference
+ * README.md, "Why Results Degraded on CUSAT Map"; configs/train_config.json has a `pretrained`
+ * key).  The train-mode forward (dropout, batch statistics) of cilrs_net_forward with a frozen
+ * prefix of the trunk, counted in groups: 1 = stem, 2 = + layer1, ... 5 = the whole trunk.
+ *   grad_frozen_groups (g): the parameters of these groups take no gradient.  cilrs_net_backward
+ *     after this forward stops there: segments of frozen groups are not run (a wider segment range
+ *     is clamped), the first block of the last trainable group launches only its weight gradients
+ *     and the BatchNorm backward of its own layers, and the gradient-arena ranges of the frozen
+ *     groups are not written.  cilrs_net_backward_step and the image gradient of
+ *     cilrs_net_input_grads refuse such a graph.
+ *   bn_frozen_groups (e): these groups run in eval mode -- BatchNorm on the running statistics,
+ *     folded with ReLU and the residual add into the convolution epilogues (3x3 / stride-1 layers
+ *     that the train plan gives to the Winograd kernel take its folded-epilogue variant); only the
+ *     post-activation tensors are written, the running statistics and num_batches_tracked of the
+ *     prefix are not touched.  e == g, or e == 0 (requires_grad_(False) alone: torch still uses
+ *     the batch statistics there and moves the running buffers, and so does the ordinary train
+ *     forward this runs).  Every other pair is an error; so is any freeze on a
+ *     CILRS_PLAN_BF16_TRAIN plan.
+ *   prefix_key: the frozen prefix's weight-derived state (BatchNorm scale / shift, padded stem
+ *     weights, Winograd filter images) is rebuilt only when this value, the cut or the buffers
+ *     change; 0 = rebuild on every call.  The caller changes it whenever a parameter or BatchNorm
+ *     buffer of the prefix may have changed, and after any other forward on this plan.
+ * e == g == 0 is cilrs_net_forward(train = 1), launch for launch. */
+int cilrs_net_forward_ft(cilrs_net* net, const cilrs_buffers* bufs, const float* image, long sn,
+                         long sc, long sh, long sw, const float* speed, const int64_t* command,
+                         int bn_frozen_groups, int grad_frozen_groups, uint64_t prefix_key,
+                         float dropout_p, uint64_t seed, float* controls, float* pred_speed,
+                         void* stream);
+/* folded-epilogue Winograd launches of the last cilrs_net_forward_ft on this plan (= the eligible
+ * convolutions of its eval-mode prefix; 0 for small batches, where the train plan has none) */
+int cilrs_net_ft_wino_convs(cilrs_net* net);
+/* the cut of the plan's last graph-keeping forward (0, 0 after cilrs_net_forward / _frozen) */
+int cilrs_net_ft_cut(const cilrs_net* net, int* bn_frozen_groups, int* grad_frozen_groups);
+
 /* Byte offset, inside the workspace, of the plan's int32[4] status words.  The library zeroes them
  * ONCE per workspace (the first entry point that sees a workspace pointer); after that the kernels
  * only ever SET them, so a word means "since the caller last cleared it" (sticky): read them after
@@ -312,6 +347,16 @@ int cilrs_adam_step(float* params, const float* grads, float* exp_avg, float* ex
                     size_t n, double lr, double beta1, double beta2, double eps,
                     double weight_decay, int64_t step, const float* clip_out2, float grad_scale,
                     void* stream);
+/* The same update over `ngroups` (1..8) adjacent ranges [0, ends[0]), [ends[0], ends[1]) ... of the
+ * arrays (ends in floats, multiples of 4, the last one = n), each with its own learning rate and
+ * 1-based step count -- parameter groups with a learning-rate multiplier, and groups that sat out
+ * steps while frozen (torch.optim.Adam keeps `step` per parameter).  One launch; element for
+ * element the arithmetic of cilrs_adam_step on each range.  ends / lrs / steps: host arrays. */
+int cilrs_adam_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                           size_t n, int ngroups, const size_t* ends, const double* lrs,
+                           const int64_t* steps, double beta1, double beta2, double eps,
+                           double weight_decay, const float* clip_out2, float grad_scale,
+                           void* stream);
 int cilrs_scale(float* x, size_t n, const float* clip_out2, float c, void* stream);
 
 /* op-level stem convolution of the TRAINING step (visual_encoder.0 = torchvision resnet34.conv1,
@@ -489,6 +534,12 @@ int cilrs_bn16_bwd(const void* dz16, const void* z16, const void* y16, int M, in
 size_t cilrs_conv2d_wino_scratch_floats(int Cin, int Cout);
 int cilrs_conv2d_wino_fwd(const float* x, const float* w, float* y, int N, int H, int W, int Cin,
                           int Cout, float* scratch, void* stream);
+/* The forward form with an eval-mode BatchNorm folded into the epilogue (the frozen prefix of
+ * cilrs_net_forward_ft): y = relu_post?(relu?(conv(x, w) * scale[k] + shift[k]) + addend); addend
+ * (y's layout) may be NULL; scale / shift: Cout floats, 16-byte aligned. */
+int cilrs_conv2d_wino_fold_fwd(const float* x, const float* w, float* y, const float* scale,
+                               const float* shift, const float* addend, int relu, int relu_post,
+                               int N, int H, int W, int Cin, int Cout, float* scratch, void* stream);
 /* the two halves on their own: U = transformed filters ([16][Cred/8][Cout][8]; dgrad = 1: the
  * data gradient's filter, reduction over the forward Cout), and the convolution on a ready U */
 int cilrs_wino_filter_transform(const float* w, float* U, int Cin, int Cout, int dgrad, void* stream);
