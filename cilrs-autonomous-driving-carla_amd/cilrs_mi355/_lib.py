@@ -68,6 +68,10 @@ SIGNATURES = {
     "cilrs_net_activation_info": (i32, [vp, i32, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),
                                         C.POINTER(i32)]),
     "cilrs_dropout": (i32, [vp, i32, i32, i32, f32, u64, i32, vp]),
+    "cilrs_net_infer16_conv_info": (i32, [vp, i32, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),
+                                          C.POINTER(i32), C.POINTER(i32)]),
+    "cilrs_net_infer16_io_info": (i32, [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),
+                                        C.POINTER(i32), C.POINTER(i32)]),
     "cilrs_net_forward": (i32, [vp, C.POINTER(Buffers), vp, C.c_long, C.c_long, C.c_long,
                                 C.c_long, vp, vp, i32, f32, u64, vp, vp, vp]),
     "cilrs_net_forward_frozen": (i32, [vp, C.POINTER(Buffers), vp, C.c_long, C.c_long, C.c_long,
@@ -130,6 +134,11 @@ SIGNATURES = {
     "cilrs_conv2d_wgrad_16_scratch_floats": (sz, [i32] * 8),
     "cilrs_conv2d_wgrad_16": (i32, [vp, vp, vp, vp] + [i32] * 9 + [vp, vp]),
     "cilrs_conv2d_train_16": (i32, [vp] * 9 + [i32, vp] + [i32] * 12 + [vp, vp]),
+    "cilrs_conv2d_infer_16": (i32, [vp] * 5 + [i32] * 11 + [vp]),
+    "cilrs_stem_fold_16": (i32, [vp, vp, vp, vp, i32, vp]),
+    "cilrs_stem_infer_16": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "cilrs_maxpool_infer_16": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "cilrs_avgpool_infer_16": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "cilrs_bn16_train_fwd": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, i32,
                                    vp, vp, vp, i32, vp]),
     "cilrs_bn16_bwd": (i32, [vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp]),

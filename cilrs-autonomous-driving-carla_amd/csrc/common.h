@@ -548,7 +548,8 @@ struct FoldF16Table {
     unsigned w16[kMaxConvs];      // halfs into the folded-weight arena
     unsigned bias[kMaxConvs];     // floats into the folded-bias arena
 };
-int launch_conv_f16(const ConvF16Args& a, hipStream_t s);
+// tile: 0 = the 64x64 tile every plan uses, 128 = the 128x128 instantiation (Cout % 128 == 0)
+int launch_conv_f16(const ConvF16Args& a, hipStream_t s, int tile = 0);
 int launch_fold_bn_f16(const FoldF16Table& t, const float* params, const float* ws, void* w16,
                        float* bias, int bf16, hipStream_t s);
 int launch_f32_to_f16(const float* x, void* y, size_t n, int bf16, hipStream_t s);

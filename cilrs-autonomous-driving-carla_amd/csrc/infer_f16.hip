@@ -43,7 +43,8 @@ __device__ __forceinline__ f32x16 mfma16(const b8 a, const b8 b, const f32x16 c)
 //           layer of both networks at B=64 (ResNet-50 variant 4.74 vs 3.68 ms per batch, ResNet-34
 //           fp16 1.48 vs 0.92 ms): these convolutions have 1-18 K-tiles per block and are bound
 //           by memory-level parallelism, which two fat blocks per CU halve.  Opt-in only
-//           (CILRS_F16_TILE=128).
+//           (CILRS_F16_TILE=128 in an experiments build; cilrs_conv2d_infer_16 with tile = 128,
+//           which is how tests/test_infer16_gpu.py keeps this instantiation checked).
 // TRAIN: fp32 raw result (+ fp32 addend, + BatchNorm column partials) instead of the folded
 // 16-bit epilogue, and the stride-2 data-gradient gather (ConvF16Args::up2).
 template <typename T, int BM, int BN, bool TRAIN = false>
@@ -515,14 +516,15 @@ static int launch_conv_f16_cfg(const ConvF16Args& a, int M, hipStream_t s) {
     return 0;
 }
 
-int launch_conv_f16(const ConvF16Args& a, hipStream_t s) {
+int launch_conv_f16(const ConvF16Args& a, hipStream_t s, int tile) {
     CILRS_CHECK(a.Cin % HBK == 0 && a.Cout % 64 == 0 && a.K * a.K <= 16,
                 "conv_f16: Cin %% 64, Cout %% 64, <= 16 taps");
     CILRS_CHECK((size_t)a.N * a.H * a.W * a.Cin * 2 < (1ull << 32), "conv_f16: input too large");
     const int M = a.N * a.Ho * a.Wo;
     // 64x64 tiles everywhere (see the kernel's header); CILRS_F16_TILE=128 forces the big tile
     static const int force = experiment_env("CILRS_F16_TILE", 0);
-    const bool big = a.Cout % 128 == 0 && force == 128;
+    CILRS_CHECK(tile == 0 || (tile == 128 && a.Cout % 128 == 0), "conv_f16: tile 0 or 128 (Cout %% 128)");
+    const bool big = a.Cout % 128 == 0 && (force == 128 || tile == 128);
     if (big)
         return a.bf16 ? launch_conv_f16_cfg<__bf16, 128, 128>(a, M, s)
                       : launch_conv_f16_cfg<_Float16, 128, 128>(a, M, s);

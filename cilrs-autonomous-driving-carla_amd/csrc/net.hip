@@ -1188,6 +1188,39 @@ int cilrs_net_activation_info(const cilrs_net* net, int conv, size_t* y_offset, 
     return 0;
 }
 
+int cilrs_net_infer16_conv_info(const cilrs_net* net, int conv, size_t* w16_offset,
+                                size_t* bias_offset, size_t* w16_numel, int* channels,
+                                int* folded_half) {
+    CILRS_CHECK(net != nullptr, "infer16_conv_info: net is NULL");
+    CILRS_CHECK(conv >= 0 && conv < (int)net->cg.size(), "infer16_conv_info: conv %d out of range", conv);
+    const ConvT& c = net->A->convs[conv];
+    if (conv == 0) {         // the stem's [64][7][8][4] layout (kw padded 7 -> 8, c 3 -> 4)
+        if (w16_offset) *w16_offset = net->stem16_w * sizeof(float);
+        if (bias_offset) *bias_offset = net->stem16_b * sizeof(float);
+        if (w16_numel) *w16_numel = 64 * 224;
+    } else {
+        const int e = conv - 1;
+        if (w16_offset) *w16_offset = net->f16_w * sizeof(float) + (size_t)net->f16_table.w16[e] * 2;
+        if (bias_offset) *bias_offset = (net->f16_bias + net->f16_table.bias[e]) * sizeof(float);
+        if (w16_numel) *w16_numel = (size_t)c.cout * c.k * c.k * c.cin;
+    }
+    if (channels) *channels = c.cout;
+    // (what the arenas hold now: a later fp32 eval_prep of changed weights invalidates them)
+    if (folded_half) *folded_half = net->fold_key != 0 ? net->fold_half : 0;
+    return 0;
+}
+
+int cilrs_net_infer16_io_info(const cilrs_net* net, size_t* x4_offset, size_t* x4_numel,
+                              size_t* combined_offset, int* combined_ld, int* features) {
+    CILRS_CHECK(net != nullptr, "infer16_io_info: net is NULL");
+    if (x4_offset) *x4_offset = net->x4 * sizeof(float);
+    if (x4_numel) *x4_numel = (size_t)net->B * net->H * net->W * 4;
+    if (combined_offset) *combined_offset = net->combined * sizeof(float);
+    if (combined_ld) *combined_ld = net->A->feat + 128;
+    if (features) *features = net->A->feat;
+    return 0;
+}
+
 int cilrs_net_set_weights_key(cilrs_net* net, uint64_t key) {
     CILRS_CHECK(net != nullptr, "set_weights_key: net is NULL");
     net->weights_key = key;
@@ -3100,6 +3133,64 @@ int cilrs_conv2d_train_16(const void* x16, const void* w16, void* y16, float* y3
                 "conv2d_train_16: BatchNorm-backward partials are not available for this launch");
     if (partial_rows) *partial_rows = conv_f16_train_mtiles(a);
     return launch_conv_f16_train(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- the 16-bit INFERENCE trunk's operators (folded BatchNorm, one rounding per stored tensor),
+//      op by op: what trunk_fwd_eval16 / fold_prep launch ----
+int cilrs_conv2d_infer_16(const void* x16, const void* w16, const float* bias,
+                          const void* residual16, void* y16, int N, int H, int W, int Cin, int Cout,
+                          int K, int stride, int pad, int relu, int bf16, int tile, void* stream) {
+    CILRS_CHECK(x16 && w16 && bias && y16, "conv2d_infer_16: NULL argument");
+    CILRS_CHECK(N >= 1 && H >= 1 && W >= 1 && K >= 1 && (stride == 1 || stride == 2) && pad >= 0 &&
+                    H + 2 * pad >= K && W + 2 * pad >= K,
+                "conv2d_infer_16: bad geometry");
+    CILRS_CHECK(tile == 0 || (tile == 128 && Cout % 128 == 0),
+                "conv2d_infer_16: tile is 0 (the plan's choice) or 128 (needs Cout %% 128 == 0)");
+    CILRS_CHECK(((uintptr_t)x16 & 15) == 0 && ((uintptr_t)w16 & 15) == 0 &&
+                    ((uintptr_t)residual16 & 15) == 0 && ((uintptr_t)y16 & 15) == 0,
+                "conv2d_infer_16: 16-bit tensors must be 16-byte aligned");
+    ConvF16Args a;
+    memset(&a, 0, sizeof(a));
+    a.x = reinterpret_cast<const cilrs_half*>(x16);
+    a.w = reinterpret_cast<const cilrs_half*>(w16);
+    a.bias = bias;
+    a.residual = reinterpret_cast<const cilrs_half*>(residual16);
+    a.y = reinterpret_cast<cilrs_half*>(y16);
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.K = K; a.stride = stride; a.pad = pad;
+    a.Ho = (H + 2 * pad - K) / stride + 1; a.Wo = (W + 2 * pad - K) / stride + 1;
+    a.relu = relu; a.bf16 = bf16;
+    return launch_conv_f16(a, reinterpret_cast<hipStream_t>(stream), tile);
+}
+
+int cilrs_stem_fold_16(const float* w, const float* stats, void* w16, float* bias, int bf16,
+                       void* stream) {
+    CILRS_CHECK(w && stats && w16 && bias, "stem_fold_16: NULL argument");
+    return launch_fold_stem_f16(w, stats, w16, bias, bf16, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cilrs_stem_infer_16(const float* x4, const void* w16, const float* bias, void* z16, int N, int H,
+                        int W, int bf16, void* stream) {
+    CILRS_CHECK(x4 && w16 && bias && z16, "stem_infer_16: NULL argument");
+    CILRS_CHECK(N >= 1 && H >= 1 && W >= 1, "stem_infer_16: bad geometry");
+    CILRS_CHECK(((uintptr_t)x4 & 15) == 0 && ((uintptr_t)w16 & 15) == 0 && ((uintptr_t)z16 & 15) == 0,
+                "stem_infer_16: tensors must be 16-byte aligned");
+    return launch_stem_f16(x4, w16, bias, z16, N, H, W, bf16, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cilrs_maxpool_infer_16(const void* x16, void* out16, int N, int H, int W, int C, int bf16,
+                           void* stream) {
+    CILRS_CHECK(x16 && out16, "maxpool_infer_16: NULL argument");
+    CILRS_CHECK(N >= 1 && H >= 1 && W >= 1 && C >= 8, "maxpool_infer_16: bad geometry");
+    CILRS_CHECK(((uintptr_t)x16 & 15) == 0 && ((uintptr_t)out16 & 15) == 0,
+                "maxpool_infer_16: tensors must be 16-byte aligned");
+    return launch_maxpool_f16(x16, out16, N, H, W, C, bf16, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cilrs_avgpool_infer_16(const void* x16, float* out, int N, int HW, int C, int out_ld, int bf16,
+                           void* stream) {
+    CILRS_CHECK(x16 && out, "avgpool_infer_16: NULL argument");
+    CILRS_CHECK(N >= 1 && HW >= 1 && C >= 1 && out_ld >= C, "avgpool_infer_16: bad geometry");
+    return launch_avgpool_f16(x16, out, N, HW, C, out_ld, bf16, reinterpret_cast<hipStream_t>(stream));
 }
 
 int cilrs_bn16_train_fwd(const void* y16, int M, int C, const float* gamma, const float* beta,

@@ -187,6 +187,22 @@ int cilrs_net_set_weights_key(cilrs_net* net, uint64_t key);
 int cilrs_net_activation_info(const cilrs_net* net, int conv, size_t* y_offset, size_t* z_offset,
                               size_t* numel, int* channels);
 
+/* Where a 16-bit eval forward (cilrs_net_forward_u8_f16 / _bf16) keeps what its kernels read and
+ * write, as BYTE offsets into the workspace -- test aid: the layer-by-layer tests of the 16-bit
+ * inference mode read exactly what the engine's kernels read and wrote.
+ * cilrs_net_infer16_conv_info: convolution `conv` (numbered as in cilrs_net_activation_info) --
+ * its folded 16-bit weights (OHWI [Cout][K][K][Cin]; the stem, conv 0: [64][7][8][4] with the
+ * filter row padded 7 -> 8 and the channels 3 -> 4 by zeros), w16_numel 16-bit elements, and its
+ * fp32 bias [channels].  *folded_half: 1 / 2 when the arenas hold the fp16 / bf16 fold of the
+ * current weights, 0 before the first 16-bit forward (or after the weights changed).
+ * cilrs_net_infer16_io_info: the channel-padded fp32 image x4 [B][H][W][4] the u8 entries wrote
+ * (x4_numel floats) and the pooled features `combined` [B][combined_ld], features first. */
+int cilrs_net_infer16_conv_info(const cilrs_net* net, int conv, size_t* w16_offset,
+                                size_t* bias_offset, size_t* w16_numel, int* channels,
+                                int* folded_half);
+int cilrs_net_infer16_io_info(const cilrs_net* net, size_t* x4_offset, size_t* x4_numel,
+                              size_t* combined_offset, int* combined_ld, int* features);
+
 /* nn.Dropout(p) in training mode exactly as the fused heads apply it (inverted dropout, keep
  * where hash(seed, site, row * cols + col) >= p, kept values divided by 1 - p), in place over
  * a [rows][cols] matrix with row pitch ld.  `site` names the Dropout module:
@@ -216,7 +232,9 @@ int cilrs_net_forward_camera(cilrs_net* net, const cilrs_buffers* bufs, const ui
 
 /* cilrs_net_forward_u8 with the BasicBlock trunk in fp16 (batched serving, BASELINE config 5):
  * BatchNorm folded into fp16 weights on every call, fp16 NHWC activations, fp16 MFMA with fp32
- * accumulation; the stem and the heads stay fp32.  Outputs agree with the fp32 path to ~1e-3. */
+ * accumulation; the stem runs on the 16-bit pipe too, the heads stay fp32.  The mode is DEFINED by
+ * oracle/infer16_emulation.py (one rounding per stored tensor); tests/test_infer16_gpu.py holds
+ * every kernel to it layer by layer. */
 int cilrs_net_forward_u8_f16(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
                              const float* speed, const int64_t* command, float* controls,
                              float* pred_speed, void* stream);
@@ -228,8 +246,8 @@ int cilrs_net_forward_u8_f16_graph(cilrs_net* net, const cilrs_buffers* bufs,
                                    void* stream);
 
 /* The same with the trunk in bf16 (v_mfma_f32_32x32x16_bf16, fp32 accumulation): the "bf16 MFMA
- * path" of BASELINE.json configs[3]; works for both variants.  bf16 keeps 8 significant bits:
- * outputs agree with the fp32 path to ~1e-2. */
+ * path" of BASELINE.json configs[3]; works for both variants.  Same definition
+ * (oracle/infer16_emulation.py) with bf16's 8 significant bits in place of fp16's 11. */
 int cilrs_net_forward_u8_bf16(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
                               const float* speed, const int64_t* command, float* controls,
                               float* pred_speed, void* stream);
@@ -511,6 +529,31 @@ int cilrs_conv2d_train_16(const void* x16, const void* w16, void* y16, float* y3
                           float* bwd_partial, int N, int H, int W, int Cin, int Ho, int Wo, int Cout,
                           int K, int stride, int pad, int up2, int bf16, int* partial_rows,
                           void* stream);
+/* The 16-bit INFERENCE trunk's operators, op by op (what cilrs_net_forward_u8_f16 / _bf16 launch;
+ * bf16 = 0: fp16 tensors, 1: bf16).  No reference counterpart; defined by
+ * oracle/infer16_emulation.py.  All 16-bit tensors NHWC, 16-byte aligned.
+ *
+ * cilrs_conv2d_infer_16: y16 = round(relu?((acc + bias[co]) + residual16)), acc = fp32 sum of the
+ * products of x16 [N][H][W][Cin] and the folded weights w16 [Cout][K][K][Cin]; residual16 (y16's
+ * layout) may be NULL.  Cin, Cout multiples of 64, K x K <= 16 taps.  tile: 0 = the 64x64 tile every
+ * plan uses, 128 = the 128x128 instantiation (Cout % 128 == 0).
+ * cilrs_stem_fold_16: w16 [64][7][8][4] = round(w[64][7][7][3] * stats[128 + co]) (zero padding),
+ * bias[co] = stats[192 + co]; stats = the eval-mode BatchNorm table [mean | rstd | scale | shift].
+ * cilrs_stem_infer_16: z16 [N][Ho][Wo][64] = round(relu(conv7x7/s2/p3(round(x4), w16) + bias)) from
+ * the channel-padded fp32 image x4 [N][H][W][4].
+ * cilrs_maxpool_infer_16: MaxPool2d(3, 2, 1) of a 16-bit tensor (C % 8 == 0).
+ * cilrs_avgpool_infer_16: out[n * out_ld + c] = fp32 mean over the HW pixels of x16 [N][HW][C]. */
+int cilrs_conv2d_infer_16(const void* x16, const void* w16, const float* bias,
+                          const void* residual16, void* y16, int N, int H, int W, int Cin, int Cout,
+                          int K, int stride, int pad, int relu, int bf16, int tile, void* stream);
+int cilrs_stem_fold_16(const float* w, const float* stats, void* w16, float* bias, int bf16,
+                       void* stream);
+int cilrs_stem_infer_16(const float* x4, const void* w16, const float* bias, void* z16, int N, int H,
+                        int W, int bf16, void* stream);
+int cilrs_maxpool_infer_16(const void* x16, void* out16, int N, int H, int W, int C, int bf16,
+                           void* stream);
+int cilrs_avgpool_infer_16(const void* x16, float* out, int N, int HW, int C, int out_ld, int bf16,
+                           void* stream);
 /* BatchNorm2d (training) on bf16 NHWC tensors: statistics of y16 (from `partial` when pre_rows > 0:
  * rows written by cilrs_conv2d_train_16), z16 = round(relu?(bn(y16) (+ residual16))); and its
  * backward: dy16 = round(BatchNorm backward of g = dz16 * (z16 > 0 if relu)), g_out16 = g.
