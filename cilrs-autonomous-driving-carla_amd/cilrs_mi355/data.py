@@ -7,6 +7,10 @@ throttle, brake, speed_normalized, command_name) and  <data_dir>/sessionN/images
 the host only parses the CSVs, draws the class-balanced sample indices and each sample's random
 augmentation parameters, and decodes JPEGs on a thread pool into a pinned uint8 batch -- the
 augmentation itself, /255 and Normalize run as one HIP kernel (`cilrs_augment_u8`).
+
+`BatchLoader` decodes every frame every epoch.  When the decoded frames fit in device memory,
+`DeviceDataset` decodes them once into HBM and `CachedBatchLoader` builds the same batches, bit
+for bit, with one `cilrs_batch_assemble` launch each.
 """
 from __future__ import annotations
 
@@ -372,3 +376,334 @@ class BatchLoader:
             copied.synchronize()            # the staging slot may be refilled now
             free.put(slot)
             yield batch
+
+
+# ---- device-resident dataset -----------------------------------------------------------------
+def _decode_chunk():
+    try:
+        from cilrs_jpeg_worker import decode_chunk
+    except ImportError:          # the worker module sits next to the package directory
+        import sys
+        sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        from cilrs_jpeg_worker import decode_chunk
+    return decode_chunk
+
+
+class DeviceDataset:
+    """Every decoded frame of a `Sessions` plus its labels on one device: the JPEGs are decoded
+    ONCE (`fill`) and each batch is then built there by one `cilrs_batch_assemble` launch
+    (`assemble`, `CachedBatchLoader`) -- no decode, staging buffer or host-to-device copy per step.
+
+    The whole dataset must fit: `cache_bytes(n, h, w)` against `budget_bytes` (default: half of
+    the device memory free at construction) is checked before anything is allocated or decoded.
+    There is no partial cache; a dataset over budget is `BatchLoader`'s job."""
+
+    LABEL_BYTES = 4 + 8 + 12          # speed f32, command i64, targets f32 [3] per frame
+
+    @staticmethod
+    def cache_bytes(n: int, h: int = IMG_HEIGHT, w: int = IMG_WIDTH) -> int:
+        """Device bytes the cache of n frames takes: the uint8 frames and the label arrays."""
+        return int(n) * (int(h) * int(w) * 3 + DeviceDataset.LABEL_BYTES)
+
+    def __init__(self, sessions: Sessions, device, height: int = IMG_HEIGHT,
+                 width: int = IMG_WIDTH, budget_bytes: int = None, workers: int = 8,
+                 processes: bool = False, chunk_frames: int = 1024, fill: bool = True,
+                 process_group=None, mem_get_info=None):
+        """workers / processes: the decode pool, as in `BatchLoader`.  chunk_frames: frames per
+        pinned staging buffer (and, filling data-parallel, per collective).  fill=False leaves
+        the cache unallocated until `fill()` is called.  mem_get_info: stands in for
+        `torch.cuda.mem_get_info` (device -> (free, total) bytes)."""
+        self.s = sessions
+        self.n, self.h, self.w = len(sessions), height, width
+        self.device = torch.device(device)
+        self.workers, self.processes = max(1, workers), processes
+        self.chunk_frames = max(1, chunk_frames)
+        self.command = sessions.command           # host copy: the sampler's class weights
+        self.cache = self.speed = self.command_dev = self.targets = None
+        need = self.cache_bytes(self.n, height, width)
+        if budget_bytes is None:
+            free = (mem_get_info or torch.cuda.mem_get_info)(self.device)[0]
+            budget_bytes = free // 2
+        self.budget_bytes = int(budget_bytes)
+        if need > self.budget_bytes:
+            raise RuntimeError(
+                f"DeviceDataset: {self.n} frames of {width}x{height} need {need} bytes on the "
+                f"device, the budget is {self.budget_bytes} bytes; use BatchLoader (decode per "
+                "epoch) for a dataset that does not fit")
+        if fill:
+            self.fill(process_group)
+
+    @classmethod
+    def from_tensors(cls, cache: torch.Tensor, speed: torch.Tensor, command: torch.Tensor,
+                     targets: torch.Tensor):
+        """A dataset over frames and labels that are on the device already (uint8 [N,H,W,3],
+        f32 [N], i64 [N], f32 [N,3]); the tensors are used as they are, not copied."""
+        n = cache.size(0) if cache.dim() == 4 else -1
+        ok = cache.dtype == torch.uint8 and cache.dim() == 4 and cache.size(3) == 3 and n >= 1 \
+            and cache.device.type == "cuda" and cache.is_contiguous()
+        for t, dt, shape in ((speed, torch.float32, (n,)), (command, torch.int64, (n,)),
+                             (targets, torch.float32, (n, 3))):
+            ok = ok and t.dtype == dt and tuple(t.shape) == shape and t.device == cache.device \
+                and t.is_contiguous()
+        if not ok:
+            raise RuntimeError("DeviceDataset.from_tensors: need contiguous uint8 [N,H,W,3] frames, "
+                               "f32 [N] speed, i64 [N] command and f32 [N,3] targets on one GPU")
+        self = cls.__new__(cls)
+        self.s = None
+        self.n, self.h, self.w = n, cache.size(1), cache.size(2)
+        self.device = cache.device
+        self.command = command.cpu().numpy()
+        self.cache, self.speed, self.command_dev, self.targets = cache, speed, command, targets
+        self.budget_bytes = None
+        return self
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def filled(self):
+        return self.cache is not None
+
+    def fill(self, process_group=None):
+        """Decode every frame once and copy it to the device through pinned staging buffers.
+
+        process_group (world W > 1): rank r decodes frames r, r+W, r+2W, ... only and the ranks
+        all-gather their shares chunk by chunk, so every rank ends with the full cache, byte for
+        byte what a single-process fill gives (the sampler draws from the whole dataset on every
+        rank).  A gloo group exchanges the pinned host buffers themselves; any other backend the
+        uploaded shares."""
+        if self.device.type != "cuda":
+            raise RuntimeError("DeviceDataset: the cache lives on a GPU (no CPU fallback)")
+        rank, world, on_host = 0, 1, True
+        if process_group is not None:
+            import torch.distributed as dist
+            rank, world = dist.get_rank(process_group), dist.get_world_size(process_group)
+            on_host = "gloo" in str(dist.get_backend(process_group))
+        decode_chunk = _decode_chunk()
+        n, h, w, dev, s = self.n, self.h, self.w, self.device, self.s
+        share = -(-n // world)                      # frames rank 0 decodes; no rank has more
+        K = min(self.chunk_frames, share)           # frames per staging buffer
+        rounds = -(-share // K)                     # the same on every rank
+        cache = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+        speed = torch.from_numpy(np.ascontiguousarray(s.speed, dtype=np.float32)).to(dev)
+        command = torch.from_numpy(np.ascontiguousarray(s.command, dtype=np.int64)).to(dev)
+        targets = torch.from_numpy(np.ascontiguousarray(s.targets, dtype=np.float32)).to(dev)
+        mine = np.arange(rank, n, world)
+        piece = max(4, min(64, -(-K // self.workers)))
+
+        def tasks():
+            for c in range(rounds):
+                ids = mine[c * K:(c + 1) * K]
+                for k in range(0, len(ids), piece):
+                    yield (list(s.paths[ids[k:k + piece]]), h, w)
+
+        if self.processes:
+            import multiprocessing as mp
+            pool = mp.get_context("spawn").Pool(self.workers)
+        else:
+            from multiprocessing.pool import ThreadPool
+            pool = ThreadPool(self.workers)
+        stream = torch.cuda.current_stream(dev)
+        # two staging slots: the pool decodes into one while the other's copies are in flight
+        nslot = 2 if rounds > 1 else 1
+        slots = []
+        for _ in range(nslot):
+            send = torch.zeros(K, h, w, 3, dtype=torch.uint8).pin_memory()
+            recv = None
+            if world > 1:
+                recv = [torch.zeros(K, h, w, 3, dtype=torch.uint8).pin_memory() if on_host
+                        else torch.empty(K, h, w, 3, dtype=torch.uint8, device=dev)
+                        for _ in range(world)]
+            slots.append([send, send.numpy(), recv, None])
+        try:
+            results = pool.imap(decode_chunk, tasks())       # ordered, workers run ahead
+            for c in range(rounds):
+                slot = slots[c % nslot]
+                send, view, recv, done = slot
+                if done is not None:
+                    done.synchronize()                       # the slot's last copies have left it
+                ids = mine[c * K:(c + 1) * K]
+                k = 0
+                while k < len(ids):
+                    part = next(results)                     # a decode error surfaces here
+                    view[k:k + len(part)] = part
+                    k += len(part)
+                if world == 1:
+                    cache[c * K:c * K + len(ids)].copy_(send[:len(ids)], non_blocking=True)
+                else:
+                    import torch.distributed as dist
+                    if on_host:
+                        dist.all_gather(recv, send, group=process_group)
+                    else:
+                        dist.all_gather(recv, send.to(dev, non_blocking=True), group=process_group)
+                    for q in range(world):                   # rank q's share: q + W * (cK ...)
+                        first = q + world * c * K
+                        cnt = len(range(first, min(n, first + world * K), world))
+                        if cnt > 0:
+                            cache[first:first + world * cnt:world].copy_(recv[q][:cnt],
+                                                                         non_blocking=True)
+                done = torch.cuda.Event()
+                done.record(stream)
+                slot[3] = done
+            stream.synchronize()
+        finally:
+            pool.terminate()
+            pool.join()
+        self.cache, self.speed, self.command_dev, self.targets = cache, speed, command, targets
+        return self
+
+    def check_index(self, index: np.ndarray):
+        """Host check of the kernel's contract: every value in [0, n)."""
+        if index.size and (int(index.min()) < 0 or int(index.max()) >= self.n):
+            bad = index[(index < 0) | (index >= self.n)][0]
+            raise RuntimeError(f"DeviceDataset: index {int(bad)} outside [0, {self.n})")
+
+    def _launch(self, index_ptr: int, params_ptr: int, b: int, want_u8: bool = False):
+        """One cilrs_batch_assemble launch on the current stream from device-resident index /
+        parameter records (already checked on the host)."""
+        dev = self.device
+        out = torch.empty(b, self.h, self.w, 3, dtype=torch.float32, device=dev)
+        out8 = torch.empty(b, self.h, self.w, 3, dtype=torch.uint8, device=dev) if want_u8 else None
+        spd = torch.empty(b, dtype=torch.float32, device=dev)
+        cmd = torch.empty(b, dtype=torch.int64, device=dev)
+        tgt = torch.empty(b, 3, dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(L.lib().cilrs_batch_assemble(
+            L.ptr(self.cache), self.n, L.ptr(self.speed), L.ptr(self.command_dev),
+            L.ptr(self.targets), C.c_void_p(index_ptr), C.c_void_p(params_ptr), b, self.h, self.w,
+            L.ptr(out), L.ptr(out8), L.ptr(spd), L.ptr(cmd), L.ptr(tgt), C.c_void_p(stream)))
+        img = out.permute(0, 3, 1, 2)              # the NCHW view `augment_u8` returns
+        return (img, spd, cmd, tgt, out8) if want_u8 else (img, spd, cmd, tgt)
+
+    def assemble(self, index, params: np.ndarray, want_u8: bool = False):
+        """index (host integers [B], any order, repeats allowed) + one parameter record per sample
+        -> (image, speed, command, targets[, augmented uint8 frames]) on the device: what
+        `augment_u8(cache[index], params)` and an index_select of the labels give.  The index is
+        checked on the host before anything is launched."""
+        if isinstance(index, torch.Tensor):
+            index = index.cpu().numpy()
+        index = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
+        self.check_index(index)
+        if index.size < 1:
+            raise RuntimeError("DeviceDataset.assemble: empty index")
+        if params.shape != index.shape:
+            raise RuntimeError("DeviceDataset.assemble: one parameter record per index")
+        check_params(params, self.h, self.w)
+        if not self.filled:
+            raise RuntimeError("DeviceDataset.assemble: the cache is not filled (call fill())")
+        b = index.size
+        idx_dev = torch.from_numpy(index).to(self.device)
+        par_dev = torch.from_numpy(params.view(np.uint8).reshape(b, AUG_DTYPE.itemsize)).to(
+            self.device)
+        res = self._launch(idx_dev.data_ptr(), par_dev.data_ptr(), b, want_u8)
+        for t in (idx_dev, par_dev):
+            t.record_stream(torch.cuda.current_stream(self.device))
+        return res
+
+
+class _Ahead:
+    """fn() on a background thread; result() joins it and re-raises what it raised."""
+
+    def __init__(self, fn):
+        self.out = self.err = None
+        self.thread = threading.Thread(target=self._run, args=(fn,), daemon=True)
+        self.thread.start()
+
+    def _run(self, fn):
+        try:
+            self.out = fn()
+        except Exception as e:           # re-raised by result(), in the consumer
+            self.err = e
+
+    def result(self):
+        self.thread.join()
+        if self.err is not None:
+            raise self.err
+        return self.out
+
+
+class CachedBatchLoader:
+    """`BatchLoader` over a `DeviceDataset`: the same arguments, the same batches bit for bit for
+    the same (seed, rank, world_size, batch_size, train) -- the epoch order comes from the same
+    `torch.Generator` stream, the augmentation parameters from the same
+    `np.random.default_rng([seed, rank])` stream drawn batch by batch, and both carry over from
+    epoch to epoch.  The whole epoch's order and parameters (120 bytes a sample) go to the device
+    once when the epoch starts; each batch is then one kernel launch on the current stream, with
+    no copy, pinned ring, event wait or host synchronisation per step.  Drawing a training
+    epoch's parameters is host work of a few hundred microseconds a batch, so while one epoch
+    runs the next one's plan is drawn on a background thread: the device does not idle at the
+    epoch boundary."""
+
+    def __init__(self, dataset, indices, batch_size: int, train: bool, seed: int = 0,
+                 rank: int = 0, world_size: int = 1):
+        if not (0 <= rank < world_size):
+            raise ValueError(f"rank {rank} outside world of {world_size}")
+        self.ds, self.idx = dataset, np.asarray(indices)
+        self.bs, self.train = batch_size, train
+        self.h = getattr(dataset, "h", IMG_HEIGHT)
+        self.w = getattr(dataset, "w", IMG_WIDTH)
+        self.rank, self.world = rank, world_size
+        self.rng = np.random.default_rng([seed, rank])
+        self.gen = torch.Generator().manual_seed(seed)
+        self.weights = class_balanced_weights(dataset.command[self.idx]) if train else None
+        self._ahead = None
+
+    def close(self):
+        pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        pass
+
+    _shard_len = BatchLoader._shard_len
+    __len__ = BatchLoader.__len__
+    _order = BatchLoader._order
+
+    def epoch_plan(self):
+        """(order, params) of the next epoch, on the host: this rank's sample order (int64 [n])
+        and the augmentation records of its batches back to back (AUG_DTYPE [n]).  Touches no GPU;
+        advances the sampler and parameter streams exactly as one `BatchLoader` epoch does.
+        Successive calls, by the caller or by iteration, give successive epochs: a plan already
+        drawn ahead (`_plan_ahead`) is handed out before a new one is drawn."""
+        ahead, self._ahead = self._ahead, None
+        return ahead.result() if ahead is not None else self._draw_plan()
+
+    def _plan_ahead(self):
+        """Start drawing the next epoch's plan on a background thread."""
+        if self._ahead is None:
+            self._ahead = _Ahead(self._draw_plan)
+
+    def _draw_plan(self):
+        order = np.ascontiguousarray(self._order(), dtype=np.int64)
+        nb = len(self)
+        order = order[:nb * self.bs]
+        parts = []
+        for b in range(nb):
+            n = len(order[b * self.bs:(b + 1) * self.bs])
+            parts.append(draw_aug_params(self.rng, n, self.h, self.w) if self.train
+                         else identity_params(n))
+        params = np.concatenate(parts) if parts else np.zeros(0, dtype=AUG_DTYPE)
+        return order, params
+
+    def __iter__(self):
+        ds = self.ds
+        order, params = self.epoch_plan()
+        ds.check_index(order)
+        check_params(params, self.h, self.w)
+        if not ds.filled:
+            raise RuntimeError("CachedBatchLoader: the dataset's cache is not filled")
+        n = len(order)
+        if n == 0:
+            return
+        # pinned, so the two uploads are asynchronous; the caching host allocator keeps the pinned
+        # blocks until the copies have run
+        order_dev = torch.from_numpy(order).pin_memory().to(ds.device, non_blocking=True)
+        params_dev = torch.from_numpy(params.view(np.uint8).reshape(n, AUG_DTYPE.itemsize)) \
+            .pin_memory().to(ds.device, non_blocking=True)
+        if self.train:
+            self._plan_ahead()
+        ip, pp = order_dev.data_ptr(), params_dev.data_ptr()
+        for b0 in range(0, n, self.bs):
+            yield ds._launch(ip + b0 * 8, pp + b0 * AUG_DTYPE.itemsize, min(self.bs, n - b0))

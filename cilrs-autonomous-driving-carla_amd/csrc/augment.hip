@@ -90,16 +90,20 @@ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
     return x ^ (x >> 31);
 }
 
-__global__ __launch_bounds__(256) void augment_u8_kernel(
-    const unsigned char* __restrict__ frames, const cilrs_aug_params* __restrict__ params,
-    const int B, const int H, const int W, float* __restrict__ out_f32,
-    unsigned char* __restrict__ out_u8, const float m0, const float m1, const float m2,
-    const float d0, const float d1, const float d2) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B * H * W) return;
-    const int x = i % W, y = (i / W) % H, b = i / (W * H);
-    const cilrs_aug_params a = params[b];
-    const unsigned char* img = frames + (size_t)b * H * W * 3;
+// Mean / std of the final Normalize, passed by value to the kernels.
+struct NormConsts {
+    float m0, m1, m2, d0, d1, d2;
+};
+
+// Every stage for output pixel (y, x) of one sample: `img` is that sample's uint8 [H][W][3] source
+// frame, `i` the pixel's index in the output batch.  Both kernels below are this function behind
+// two ways of finding `img`, so their results are the same element for element.
+__device__ __forceinline__ void augment_pixel(const unsigned char* __restrict__ img,
+                                              const cilrs_aug_params& a, const int y, const int x,
+                                              const int H, const int W, const size_t i,
+                                              float* __restrict__ out_f32,
+                                              unsigned char* __restrict__ out_u8,
+                                              const NormConsts& nc) {
     float c[3];
     if (a.blur_k > 1) {
         // separable Gaussian written as one fixed-order 2-D sum over the colour-adjusted taps
@@ -143,16 +147,66 @@ __global__ __launch_bounds__(256) void augment_u8_kernel(
         if (y >= a.hole_y0[hI] && y < a.hole_y1[hI] && x >= a.hole_x0[hI] && x < a.hole_x1[hI])
             c[0] = c[1] = c[2] = 0.f;            // CoarseDropout fill = 0
     if (out_u8) {
-        unsigned char* o = out_u8 + (size_t)i * 3;
+        unsigned char* o = out_u8 + i * 3;
         o[0] = (unsigned char)c[0]; o[1] = (unsigned char)c[1]; o[2] = (unsigned char)c[2];
     }
     if (out_f32) {
-        float* o = out_f32 + (size_t)i * 3;      // /255, Normalize (notebook.ipynb:412-414)
-        o[0] = (c[0] / 255.0f - m0) / d0;
-        o[1] = (c[1] / 255.0f - m1) / d1;
-        o[2] = (c[2] / 255.0f - m2) / d2;
+        float* o = out_f32 + i * 3;              // /255, Normalize (notebook.ipynb:412-414)
+        o[0] = (c[0] / 255.0f - nc.m0) / nc.d0;
+        o[1] = (c[1] / 255.0f - nc.m1) / nc.d1;
+        o[2] = (c[2] / 255.0f - nc.m2) / nc.d2;
     }
 }
+
+__global__ __launch_bounds__(256) void augment_u8_kernel(
+    const unsigned char* __restrict__ frames, const cilrs_aug_params* __restrict__ params,
+    const int B, const int H, const int W, float* __restrict__ out_f32,
+    unsigned char* __restrict__ out_u8, const NormConsts nc) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * H * W) return;
+    const int x = i % W, y = (i / W) % H, b = i / (W * H);
+    const cilrs_aug_params a = params[b];
+    augment_pixel(frames + (size_t)b * H * W * 3, a, y, x, H, W, (size_t)i, out_f32, out_u8, nc);
+}
+
+// A whole training batch from the device-resident dataset: sample b of the batch is frame
+// index[b] of the cache (64-bit offset: the cache passes 4 GiB at 81.4 K reference-size frames),
+// augmented exactly as augment_u8_kernel would, and its labels are gathered by the same index by
+// the thread of the sample's first pixel.  An index outside [0, n_frames) is the caller's error
+// (checked on the host, cilrs_mi355/data.py); such a sample is skipped, never read.
+struct AssembleLabels {
+    const float* speed;
+    const long long* command;
+    const float* targets;
+    float* out_speed;
+    long long* out_command;
+    float* out_targets;
+};
+
+__global__ __launch_bounds__(256) void batch_assemble_kernel(
+    const unsigned char* __restrict__ cache, const long long n_frames,
+    const long long* __restrict__ index, const cilrs_aug_params* __restrict__ params, const int B,
+    const int H, const int W, float* __restrict__ out_f32, unsigned char* __restrict__ out_u8,
+    const AssembleLabels lab, const NormConsts nc) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * H * W) return;
+    const int x = i % W, y = (i / W) % H, b = i / (W * H);
+    const long long src = index[b];
+    if (src < 0 || src >= n_frames) return;
+    if (x == 0 && y == 0) {
+        if (lab.out_speed) lab.out_speed[b] = lab.speed[src];
+        if (lab.out_command) lab.out_command[b] = lab.command[src];
+        if (lab.out_targets) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) lab.out_targets[b * 3 + k] = lab.targets[src * 3 + k];
+        }
+    }
+    const cilrs_aug_params a = params[b];
+    augment_pixel(cache + (size_t)src * H * W * 3, a, y, x, H, W, (size_t)i, out_f32, out_u8, nc);
+}
+
+constexpr NormConsts kNorm = {kImageMean[0], kImageMean[1], kImageMean[2],
+                              kImageStd[0],  kImageStd[1],  kImageStd[2]};
 
 }  // namespace
 
@@ -161,9 +215,24 @@ int launch_augment_u8(const unsigned char* frames, const cilrs_aug_params* param
     CILRS_CHECK(B >= 1 && H >= 2 && W >= 2 && (size_t)B * H * W < (1u << 31),
                 "augment: bad batch geometry");
     augment_u8_kernel<<<cdiv(B * H * W, 256), 256, 0, s>>>(frames, params, B, H, W, out_f32, out_u8,
-                                                           kImageMean[0], kImageMean[1],
-                                                           kImageMean[2], kImageStd[0],
-                                                           kImageStd[1], kImageStd[2]);
+                                                           kNorm);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_batch_assemble(const unsigned char* cache, long long n_frames, const float* speed,
+                          const long long* command, const float* targets, const long long* index,
+                          const cilrs_aug_params* params, int B, int H, int W, float* out_f32,
+                          unsigned char* out_u8, float* out_speed, long long* out_command,
+                          float* out_targets, hipStream_t s) {
+    // the guard is on the BATCH (thread and output indices are int); the cache is addressed in
+    // 64 bits and may be any size
+    CILRS_CHECK(B >= 1 && H >= 2 && W >= 2 && (size_t)B * H * W < (1u << 31),
+                "batch_assemble: bad batch geometry");
+    CILRS_CHECK(n_frames >= 1, "batch_assemble: empty frame cache");
+    const AssembleLabels lab = {speed, command, targets, out_speed, out_command, out_targets};
+    batch_assemble_kernel<<<cdiv(B * H * W, 256), 256, 0, s>>>(cache, n_frames, index, params, B, H,
+                                                               W, out_f32, out_u8, lab, kNorm);
     CILRS_LAUNCH_CHECK();
     return 0;
 }

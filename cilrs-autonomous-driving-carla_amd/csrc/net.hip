@@ -2877,6 +2877,23 @@ int cilrs_augment_u8(const uint8_t* frames, const cilrs_aug_params* params, int 
                              reinterpret_cast<hipStream_t>(stream));
 }
 
+int cilrs_batch_assemble(const uint8_t* cache, int64_t n_frames, const float* speed,
+                         const int64_t* command, const float* targets, const int64_t* index,
+                         const cilrs_aug_params* params, int batch, int height, int width,
+                         float* out_f32, uint8_t* out_u8, float* out_speed, int64_t* out_command,
+                         float* out_targets, void* stream) {
+    CILRS_CHECK(batch >= 1, "batch_assemble: batch must be at least 1");
+    CILRS_CHECK(cache && index && params && (out_f32 || out_u8), "batch_assemble: NULL argument");
+    CILRS_CHECK((!out_speed || speed) && (!out_command || command) && (!out_targets || targets),
+                "batch_assemble: a label output needs its label array");
+    return launch_batch_assemble(cache, n_frames, speed,
+                                 reinterpret_cast<const long long*>(command), targets,
+                                 reinterpret_cast<const long long*>(index), params, batch, height,
+                                 width, out_f32, out_u8, out_speed,
+                                 reinterpret_cast<long long*>(out_command), out_targets,
+                                 reinterpret_cast<hipStream_t>(stream));
+}
+
 // op-level nn.Linear (the kernels the heads launch, one group)
 int cilrs_linear_fwd(const float* x, const float* w, const float* bias, float* y, int batch,
                      int in_features, int out_features, int x_ld, int y_ld, int relu,

@@ -445,6 +445,24 @@ typedef struct {
 int cilrs_augment_u8(const uint8_t* frames, const cilrs_aug_params* params, int batch, int height,
                      int width, float* out_f32, uint8_t* out_u8, void* stream);
 
+/* A whole training batch from a device-resident dataset in one launch (the decoded frames stay on
+ * the device after the first epoch: no JPEG decode, staging buffer or host-to-device copy per step).
+ *   cache    uint8 [n_frames][H][W][3]; addressed in 64 bits, so it may exceed 4 GiB
+ *   speed    f32 [n_frames], command i64 [n_frames], targets f32 [n_frames][3]
+ *   index    i64 [B]: sample b is frame index[b]; values may repeat and come in any order.  Every
+ *            value must lie in [0, n_frames): that is the caller's contract (a value outside it
+ *            is never read, and that sample's outputs are left unwritten)
+ *   params   [B], as for cilrs_augment_u8
+ * -> out_f32 / out_u8 [B][H][W][3], element for element what cilrs_augment_u8 gives on the gathered
+ * frames (the kernels share their device code); either may be NULL, not both.  out_speed [B],
+ * out_command [B], out_targets [B][3] are gathered by the same index; each may be NULL, and a label
+ * input is only required when its output is asked for.  B*H*W < 2^31 as above. */
+int cilrs_batch_assemble(const uint8_t* cache, int64_t n_frames, const float* speed,
+                         const int64_t* command, const float* targets, const int64_t* index,
+                         const cilrs_aug_params* params, int batch, int height, int width,
+                         float* out_f32, uint8_t* out_u8, float* out_speed, int64_t* out_command,
+                         float* out_targets, void* stream);
+
 /* ---- evaluation report accumulators (metrics schema evaluation_report.json:1-73; the reference
  *      ships the report, not the code that made it) ---------------------------------------------
  * acc: cilrs_eval_acc_doubles() doubles on the device, zeroed by the caller before the first
