@@ -79,6 +79,9 @@ SIGNATURES = {
     "cilrs_net_forward_u8": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp, vp, vp]),
     "cilrs_net_forward_camera": (i32, [vp, C.POINTER(Buffers), vp, i32, i32, i32, C.c_long,
                                        C.c_long, vp, vp, vp, vp, vp]),
+    "cilrs_net_forward_frozen_u8": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp, vp, vp]),
+    "cilrs_net_forward_frozen_camera": (i32, [vp, C.POINTER(Buffers), vp, i32, i32, i32, C.c_long,
+                                              C.c_long, vp, vp, vp, vp, vp]),
     "cilrs_net_forward_u8_f16": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp, vp, vp]),
     "cilrs_net_forward_u8_f16_graph": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp, vp, vp]),
     "cilrs_net_forward_u8_graph": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp, vp, vp]),
@@ -99,6 +102,7 @@ SIGNATURES = {
     "cilrs_net_forward_u8_bf16_graph": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp, vp, vp]),
     "cilrs_loss_fwd_bwd": (i32, [vp, vp, vp, vp, i32, i32, c_float_p, f32, vp, vp, vp, vp]),
     "cilrs_net_backward": (i32, [vp, C.POINTER(Buffers), vp, vp, i32, i32, vp]),
+    "cilrs_net_backward_data": (i32, [vp, C.POINTER(Buffers), vp, vp, i32, i32, vp]),
     "cilrs_net_input_grads": (i32, [vp, C.POINTER(Buffers), vp, C.c_long, C.c_long, C.c_long,
                                     C.c_long, vp, vp]),
     "cilrs_stem_conv_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
@@ -160,6 +164,10 @@ SIGNATURES = {
                                  vp]),
     "cilrs_bn_eval_fwd": (i32, [vp, i32, i32, vp, vp, vp, vp, f32, vp, i32, vp, vp, vp]),
     "cilrs_bn_bwd": (i32, [vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "cilrs_bn_bwd_frozen": (i32, [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp]),
+    "cilrs_bn_bwd_pool_frozen": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "cilrs_saliency_map": (i32, [vp, C.c_long, C.c_long, C.c_long, C.c_long, i32, i32, i32,
+                                 c_float_p, vp, vp, vp, vp]),
     "cilrs_linear_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "cilrs_linear_bwd": (i32, [vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32,
                                vp]),

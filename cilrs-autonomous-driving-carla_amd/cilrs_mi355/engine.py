@@ -412,6 +412,64 @@ class Engine:
         self.last_plan = pl
         return controls, pred_speed, pl
 
+    def run_forward_frozen_u8(self, frames_u8, speed, command, height=None, width=None, out=None):
+        """run_forward_frozen fed with uint8 frames (device tensors): [B,H,W,3] at the network
+        resolution (height / width None), or raw camera frames [B,Hs,Ws,3|4] resized on the device
+        to (height, width) like run_forward_camera.  Returns (controls, pred_speed, plan)."""
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.size(3) not in (3, 4):
+            raise RuntimeError("frames must be uint8 [B,H,W,3] (camera frames: 3 or 4 bytes per pixel)")
+        camera = height is not None
+        if not camera and frames_u8.size(3) != 3:
+            raise RuntimeError("frames at the network resolution must be uint8 [B,H,W,3]")
+        b = frames_u8.size(0)
+        pl = self.plan(b, height, width) if camera else self.plan(b, frames_u8.size(1),
+                                                                  frames_u8.size(2))
+        frames_u8 = frames_u8.contiguous()
+        if out is None:
+            controls = torch.empty(b, 3, dtype=torch.float32, device=self.device)
+            pred_speed = torch.empty(b, dtype=torch.float32, device=self.device)
+        else:
+            controls, pred_speed = out
+        self._announce_weights(pl)
+        lib = L.lib()
+        if camera:
+            hs, ws, px = frames_u8.size(1), frames_u8.size(2), frames_u8.size(3)
+            L.check(lib.cilrs_net_forward_frozen_camera(
+                pl.handle, C.byref(pl.bufs), L.ptr(frames_u8), hs, ws, px, ws * px, hs * ws * px,
+                L.ptr(speed.contiguous()), L.ptr(command.contiguous()), L.ptr(controls),
+                L.ptr(pred_speed), self._stream()))
+        else:
+            L.check(lib.cilrs_net_forward_frozen_u8(
+                pl.handle, C.byref(pl.bufs), L.ptr(frames_u8), L.ptr(speed.contiguous()),
+                L.ptr(command.contiguous()), L.ptr(controls), L.ptr(pred_speed), self._stream()))
+        pl.generation += 1                    # the saved activations of earlier graphs are gone
+        self.last_plan = pl
+        return controls, pred_speed, pl
+
+    def run_saliency_map(self, dimage, chan_scale3=None, heat=None, heat_u8=None, peak=None):
+        """cilrs_saliency_map over an image gradient [B,3,H,W] (any strides): fills and returns
+        (heat float32 [B,H,W], peak float32 [B]); heat_u8 (uint8 [B,H,W]) is filled when given."""
+        if dimage.dtype != torch.float32 or dimage.dim() != 4 or dimage.size(1) != 3:
+            raise RuntimeError("dimage must be float32 [B,3,H,W]")
+        b, _, h, w = dimage.shape
+        if heat is None:
+            heat = torch.empty(b, h, w, dtype=torch.float32, device=self.device)
+        if peak is None:
+            peak = torch.empty(b, dtype=torch.float32, device=self.device)
+        for t, dt, shape in ((heat, torch.float32, (b, h, w)), (peak, torch.float32, (b,)),
+                             (heat_u8, torch.uint8, (b, h, w))):
+            if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()
+                                  or t.device != dimage.device):
+                raise RuntimeError(f"saliency map outputs must be contiguous {dt} {shape} on "
+                                   f"{dimage.device}")
+        scale = None
+        if chan_scale3 is not None:
+            scale = (C.c_float * 3)(*[float(v) for v in chan_scale3])
+        L.check(L.lib().cilrs_saliency_map(
+            L.ptr(dimage), *dimage.stride(), b, h, w, scale, L.ptr(heat), L.ptr(heat_u8),
+            L.ptr(peak), self._stream()))
+        return heat, peak
+
     def check_status(self):
         """Raise if the last forward saw an out-of-range command (one device->host read)."""
         if self.last_plan is not None:
@@ -477,9 +535,20 @@ class Engine:
         self.last_plan = pl
         return controls, pred_speed
 
-    def run_backward(self, pl, dcontrols, dpred_speed, seg_begin=0, seg_end=6, into=None):
+    def run_backward(self, pl, dcontrols, dpred_speed, seg_begin=0, seg_end=6, into=None,
+                     data_only=False, segments=None):
         """Writes the parameter gradients of segments [seg_begin, seg_end) into the gradient
-        arena, or into `into` (another arena of the same layout)."""
+        arena, or into `into` (another arena of the same layout).  `segments` = (begin, end)
+        overrides the two.  data_only=True: the data-gradient chain alone
+        (cilrs_net_backward_data) -- no weight gradient is computed and no gradient arena is
+        touched; run_input_grads follows it as usual."""
+        if segments is not None:
+            seg_begin, seg_end = segments
+        if data_only:
+            L.check(L.lib().cilrs_net_backward_data(
+                pl.handle, C.byref(pl.bufs), L.ptr(dcontrols), L.ptr(dpred_speed), seg_begin,
+                seg_end, self._stream()))
+            return
         bufs = pl.bufs
         if into is not None:
             bufs = L.Buffers(self.params.data_ptr(), into.data_ptr(), self.bn.data_ptr(),
@@ -550,11 +619,43 @@ class Engine:
             else:
                 c, s, _ = self.run_forward(image, speed, command, False, dropout_p, seed)
             return c, s
+        params = tuple(self.module.parameters())
+        gate = _ParamGate.apply(*params) if any(p.requires_grad for p in params) else None
         return _CILRSFunction.apply(self, image, speed, command, float(dropout_p), int(seed),
-                                    bool(training), e, g, *self.module.parameters())
+                                    bool(training), e, g, gate, *params)
 
 
-_N_LEADING = 9        # _CILRSFunction.forward arguments in front of the parameters
+_N_LEADING = 10       # _CILRSFunction.forward arguments in front of the parameters
+
+
+class _ParamGate(torch.autograd.Function):
+    """A node between the parameters and _CILRSFunction that computes nothing.  `needs_input_grad`
+    of a custom Function is fixed when the graph is built (does the input require grad), whatever
+    a later ``torch.autograd.grad(out, image)`` asks for; whether the autograd engine is going to
+    run THIS node -- it leads to the parameters only -- says whether the pass under way wants any
+    parameter gradient.  The gradients themselves go to the parameters directly, as before."""
+
+    @staticmethod
+    def forward(ctx, *params):
+        ctx.set_materialize_grads(False)
+        ctx.n = len(params)
+        return params[0].new_empty(())
+
+    @staticmethod
+    def backward(ctx, _g):
+        return (None,) * ctx.n
+
+
+def _pass_wants_params(gate_node) -> bool:
+    """Inside a backward: will the engine reach the parameters in this pass?  (True when it
+    cannot be told: the full backward is always correct.)"""
+    probe = getattr(torch._C, "_will_engine_execute_node", None)
+    if gate_node is None or probe is None:
+        return True
+    try:
+        return bool(probe(gate_node))
+    except RuntimeError:
+        return True
 
 
 class _CILRSFunction(torch.autograd.Function):
@@ -563,7 +664,7 @@ class _CILRSFunction(torch.autograd.Function):
     to the speed input) in train mode and -- through the frozen forward -- in eval mode."""
 
     @staticmethod
-    def forward(ctx, eng, image, speed, command, dropout_p, seed, training, e, g, *params):
+    def forward(ctx, eng, image, speed, command, dropout_p, seed, training, e, g, gate, *params):
         if training:
             controls, pred_speed, pl = eng.run_forward_ft(image, speed, command, e, g, dropout_p,
                                                           seed)
@@ -571,6 +672,7 @@ class _CILRSFunction(torch.autograd.Function):
             controls, pred_speed, pl = eng.run_forward_frozen(image, speed, command)
         ctx.eng, ctx.pl, ctx.generation = eng, pl, pl.generation
         ctx.n_params = len(params)
+        ctx.gate_node = gate.grad_fn if gate is not None else None
         ctx.frozen_groups = g if training else 0
         ctx.channels_last = (not image.is_contiguous()
                              and image.is_contiguous(memory_format=torch.channels_last))
@@ -585,7 +687,9 @@ class _CILRSFunction(torch.autograd.Function):
                 "later train-mode forward (or eval-mode forward with an input requiring grad) "
                 "with the same input shape (one graph per shape)")
         need_image, need_speed = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        need_params = any(ctx.needs_input_grad[_N_LEADING:])
+        # (parameters that require grad, AND a pass that asks for a parameter gradient:
+        #  torch.autograd.grad(out, image) on a trainable model does not)
+        need_params = any(ctx.needs_input_grad[_N_LEADING:]) and _pass_wants_params(ctx.gate_node)
         b = pl.batch
         if dcontrols is None:
             dcontrols = torch.zeros(b, 3, device=eng.device)
@@ -599,15 +703,19 @@ class _CILRSFunction(torch.autograd.Function):
         # views of the arena for loops that consume the gradients before the next backward
         # (optimizer.step() + zero_grad(set_to_none=True)); when some p.grad still lives in the
         # arena that backward is written to a second arena instead, so accumulation stays correct.
-        # (a backward for input gradients alone must not disturb parameter gradients that live
-        # in the arena either)
+        # (a backward for input gradients alone computes no parameter gradient at all: the
+        #  data-gradient chain, down to the stem only when the image asks)
         dst = eng.grads
-        if (eng.zero_copy_grads or not need_params) and eng.grads_aliased():
-            if eng._scratch_grads is None:
-                eng._scratch_grads = torch.zeros_like(eng.grads)
-            dst = eng._scratch_grads
-        eng.run_backward(pl, dcontrols.contiguous().float(), dpred_speed.contiguous().float(),
-                         into=None if dst is eng.grads else dst)
+        if not need_params:
+            eng.run_backward(pl, dcontrols.contiguous().float(), dpred_speed.contiguous().float(),
+                             data_only=True, segments=(0, 6) if need_image else (0, 1))
+        else:
+            if eng.zero_copy_grads and eng.grads_aliased():
+                if eng._scratch_grads is None:
+                    eng._scratch_grads = torch.zeros_like(eng.grads)
+                dst = eng._scratch_grads
+            eng.run_backward(pl, dcontrols.contiguous().float(), dpred_speed.contiguous().float(),
+                             into=None if dst is eng.grads else dst)
         dimage = dspeed = None
         if need_image or need_speed:
             if need_image:

@@ -321,6 +321,116 @@ class Predictor:
         c = self._ctrl_np[0]
         return (float(c[0]), float(c[1]), float(c[2]), float(self._spd_np[0]) * SPEED_NORM_FACTOR)
 
+    # ---- saliency ----------------------------------------------------------------------------
+    SALIENCY_OUTPUTS = {"steer": (1.0, 0.0, 0.0, 0.0), "throttle": (0.0, 1.0, 0.0, 0.0),
+                        "brake": (0.0, 0.0, 1.0, 0.0), "speed": (0.0, 0.0, 0.0, 1.0)}
+
+    @classmethod
+    def _saliency_weights(cls, output):
+        if isinstance(output, str):
+            if output not in cls.SALIENCY_OUTPUTS:
+                raise ValueError(f"saliency: unknown output {output!r} (one of "
+                                 f"{sorted(cls.SALIENCY_OUTPUTS)}, or four weights)")
+            return np.asarray(cls.SALIENCY_OUTPUTS[output], dtype=np.float32)
+        try:
+            w = np.asarray(output, dtype=np.float32)
+        except (TypeError, ValueError):
+            w = None
+        if w is None or w.shape != (4,) or not np.isfinite(w).all():
+            raise ValueError("saliency: output must be 'steer', 'throttle', 'brake', 'speed' or four "
+                             "finite weights over (steer, throttle, brake, speed)")
+        return w
+
+    def _saliency_buffers(self, shape):
+        """Pinned + device staging of one saliency call for frames of `shape` (cached)."""
+        sal = getattr(self, "_sal", None)
+        if sal is not None and sal["shape"] == shape and sal["eng"] is self.eng:
+            return sal
+        dev = self.eng.device
+        b, h, w = self.batch, self.frames_host.size(1), self.frames_host.size(2)
+        nfr = int(np.prod(shape))
+        # [frames | speed | d controls | d pred_speed | command]: one H2D copy
+        o_spd = (nfr + 15) // 16 * 16
+        o_dc = o_spd + 4 * b
+        o_ds = o_dc + 12 * b
+        o_cmd = (o_ds + 4 * b + 7) // 8 * 8
+        host = torch.zeros(o_cmd + 8 * b, dtype=torch.uint8).pin_memory()
+        dbuf = torch.zeros_like(host, device=dev)
+
+        def views(buf):
+            return (buf[:nfr].view(shape), buf[o_spd:o_dc].view(torch.float32),
+                    buf[o_dc:o_ds].view(torch.float32).view(b, 3),
+                    buf[o_ds:o_ds + 4 * b].view(torch.float32),
+                    buf[o_cmd:o_cmd + 8 * b].view(torch.int64))
+        # [controls | pred_speed | peak | heat]: one D2H copy
+        out_dev = torch.empty(b * 5 + b * h * w, dtype=torch.float32, device=dev)
+        out_host = torch.zeros(b * 5 + b * h * w, dtype=torch.float32).pin_memory()
+        sal = dict(shape=shape, eng=self.eng, host=host, dev=dbuf,
+                   host_np=[v.numpy() for v in views(host)], dev_views=views(dbuf),
+                   out_dev=out_dev, out_host=out_host, out_np=out_host.numpy(),
+                   ctrl=out_dev[:3 * b].view(b, 3), spd=out_dev[3 * b:4 * b],
+                   peak=out_dev[4 * b:5 * b], heat=out_dev[5 * b:].view(b, h, w),
+                   dimage=torch.empty(b, 3, h, w, dtype=torch.float32, device=dev))
+        self._sal = sal
+        return sal
+
+    @torch.no_grad()
+    def saliency(self, frames_u8, speeds_kmh, commands, output="steer"):
+        """Which pixels moved an output: (out [B,4], heat [B,H,W] float32, peak [B]).
+
+        `out` is what predict_batch returns.  `heat` is max over the colour channels of
+        |d (w . (steer, throttle, brake, pred_speed)) / d pixel| per 8-bit pixel level (the raw
+        network outputs, pred_speed not yet multiplied by 90), divided by its per-frame maximum
+        `peak`; `output` picks w: "steer" | "throttle" | "brake" | "speed", or four weights.
+        frames: uint8 [B,88,200,3] at the network resolution, or raw camera frames [B,Hs,Ws,3|4]
+        of any other size -- those are resized on the device like predict_camera does, and the
+        map is over the resized frame (upscaling it for display is the caller's).  The
+        eval-mode forward that keeps its graph, the data-gradient-only backward and the map
+        kernel run on this predictor's stream through the per-layer plan of the same shape; the
+        single-frame persistent state and later predict_batch calls are not disturbed."""
+        wts = self._saliency_weights(output)                       # ValueError before any launch
+        frames = np.asarray(frames_u8)
+        h, w = self.frames_host.size(1), self.frames_host.size(2)
+        if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[0] != self.batch or \
+                frames.shape[3] not in (3, 4):
+            raise RuntimeError(f"saliency: frames must be uint8 [{self.batch},H,W,3] (camera "
+                               "frames: 3 or 4 bytes per pixel)")
+        camera = frames.shape[1:] != (h, w, 3)
+        cmds = self._check_commands(commands)
+        speeds = np.minimum(np.asarray(speeds_kmh, dtype=np.float64) / SPEED_NORM_FACTOR, 1.0)
+        if cmds.shape != (self.batch,) or speeds.shape != (self.batch,):
+            raise RuntimeError(f"saliency: {self.batch} speeds and commands expected")
+        if self.model.engine() is not self.eng:
+            self.__init__(self.model, self.batch, h, w, self.use_graph, self.half, self.persistent)
+        if self.model.training:
+            self.model.eval()
+        sal = self._saliency_buffers(tuple(frames.shape))
+        f_np, s_np, dc_np, ds_np, c_np = sal["host_np"]
+        np.copyto(f_np, frames)
+        s_np[...] = speeds
+        dc_np[...] = wts[:3]
+        ds_np[...] = wts[3]
+        c_np[...] = cmds
+        f_dev, s_dev, dc_dev, ds_dev, c_dev = sal["dev_views"]
+        eng = self.eng
+        self._order_after_weight_updates()
+        with torch.cuda.stream(self.stream):
+            sal["dev"].copy_(sal["host"], non_blocking=True)
+            _, _, pl = eng.run_forward_frozen_u8(f_dev, s_dev, c_dev, h if camera else None,
+                                                 w if camera else None, out=(sal["ctrl"], sal["spd"]))
+            eng.run_backward(pl, dc_dev, ds_dev, data_only=True, segments=(0, 6))
+            eng.run_input_grads(pl, sal["dimage"], None)
+            eng.run_saliency_map(sal["dimage"], [1.0 / (255.0 * sd) for sd in IMG_STD],
+                                 heat=sal["heat"], peak=sal["peak"])
+            sal["out_host"].copy_(sal["out_dev"], non_blocking=True)
+            self.stream.synchronize()
+        b = self.batch
+        o = sal["out_np"]
+        out = np.empty((b, 4), dtype=np.float32)
+        out[:, :3] = o[:3 * b].reshape(b, 3)
+        out[:, 3] = o[3 * b:4 * b] * np.float32(SPEED_NORM_FACTOR)
+        return out, o[5 * b:].reshape(b, h, w).copy(), o[4 * b:5 * b].copy()
+
     def predict_controls(self, image_rgb_u8, speed_kmh, command_idx):
         """Same return tuple as the reference's predict_controls (:918-920).  Frames that are not
         already 88x200x3 go through the fused resize (predict_camera)."""

@@ -464,6 +464,57 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     }
 }
 
+// BatchNorm backward with FIXED statistics and nobody asking for dgamma / dbeta (the data-gradient-only
+// backward of a frozen graph, cilrs_net_backward_data): no column reductions, no finalize, no read
+// of the pre-BN tensor --
+//   g = relu ? (z > 0 ? dz : 0) : dz;   g_out = g (identity path, optional);
+//   dy = g * (gamma[c] * rstd[c])       (rstd = stats[C + c])
+// gamma * rstd is the fp32 product bwd_finalize_channel forms as c1, so dy has the value
+// bn_bwd_apply_kernel gives with c2 = c3 = 0.  Streams like bn_finalize_apply_kernel: the grid stride
+// is a multiple of C/4 (a thread keeps its channel quad), kU 16-byte loads per tensor in flight.
+__global__ __launch_bounds__(kApplyThreads) void bn_bwd_frozen_kernel(
+    const float* __restrict__ dz, const float* __restrict__ z, const float* __restrict__ gamma,
+    const float* __restrict__ stats, float* __restrict__ dy, float* __restrict__ g_out,
+    const size_t total4, const int C, const int relu) {
+    const int cq = C >> 2;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int q = (int)(i % cq);
+    const f32x4 sc = *reinterpret_cast<const f32x4*>(gamma + q * 4) *
+                     *reinterpret_cast<const f32x4*>(stats + C + q * 4);
+    constexpr int kU = 4;
+    f32x4 g[kU], zz[kU];
+    auto load_trip = [&](const size_t base) {
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const size_t j = base + u * stride;
+            g[u] = zz[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (j < total4) {
+                g[u] = *reinterpret_cast<const f32x4*>(dz + j * 4);
+                if (relu) zz[u] = *reinterpret_cast<const f32x4*>(z + j * 4);
+            }
+        }
+    };
+    if (i < total4) load_trip(i);
+    while (i < total4) {
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const size_t j = i + u * stride;
+            if (j < total4) {
+                f32x4 gg = g[u];
+                if (relu) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) gg[e] = zz[u][e] > 0.f ? gg[e] : 0.f;
+                }
+                if (g_out) *reinterpret_cast<f32x4*>(g_out + j * 4) = gg;
+                *reinterpret_cast<f32x4*>(dy + j * 4) = gg * sc;
+            }
+        }
+        i += kU * stride;
+        if (i < total4) load_trip(i);
+    }
+}
+
 struct BnBwdFinArgs {
     const float* partial; int nblk; int M;
     const float* gamma; float* dgamma; float* dbeta; int accumulate;
@@ -822,6 +873,41 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pool_kernel(
             if (!ok[k]) continue;
             const f32x4 xh = (pp.y[k] - mean) * rstd;
             *reinterpret_cast<f32x4*>(dy + off[k]) = (pp.g[k] - c2 - xh * c3) * c1;
+        }
+    }
+}
+
+// ... with fixed statistics and no dgamma / dbeta (see bn_bwd_frozen_kernel): argmax scatter + ReLU
+// mask (pool_patch; the stem's post-BN tensor is never stored, so the mask is rebuilt from y) + scale
+__global__ __launch_bounds__(256) void bn_bwd_frozen_pool_kernel(
+    const float* __restrict__ y, const float* __restrict__ dpool,
+    const unsigned char* __restrict__ argmax, const float* __restrict__ gamma,
+    const float* __restrict__ stats, float* __restrict__ dy, const int N, const int H, const int W,
+    const int C, const int Ho, const int Wo) {
+    const int cq = C >> 2;
+    const int PH = (H + 1) >> 1, PW = (W + 1) >> 1;
+    const size_t total = (size_t)N * PH * PW * cq;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (size_t)gridDim.x * blockDim.x) {
+        const int q = (int)(i % cq);
+        size_t p = i / cq;
+        const int b = (int)(p % PW); p /= PW;
+        const int a = (int)(p % PH);
+        const int n = (int)(p / PH);
+        const f32x4 sw = *reinterpret_cast<const f32x4*>(stats + 2 * C + q * 4);
+        const f32x4 sb = *reinterpret_cast<const f32x4*>(stats + 3 * C + q * 4);
+        const f32x4 sc = *reinterpret_cast<const f32x4*>(gamma + q * 4) *
+                         *reinterpret_cast<const f32x4*>(stats + C + q * 4);
+        PoolPatch pp;
+        pool_patch(y, dpool, argmax, sw, sb, n, a, b, q, H, W, C, Ho, Wo, pp);
+        const bool ph1 = 2 * a + 1 < H, pw1 = 2 * b + 1 < W;
+        const size_t p00 = (((size_t)n * H + 2 * a) * W + 2 * b) * C + q * 4;
+        const size_t off[4] = {p00, p00 + C, p00 + (size_t)W * C, p00 + (size_t)W * C + C};
+        const bool ok[4] = {true, pw1, ph1, ph1 && pw1};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!ok[k]) continue;
+            *reinterpret_cast<f32x4*>(dy + off[k]) = pp.g[k] * sc;
         }
     }
 }
@@ -1251,6 +1337,39 @@ int launch_bn_bwd_pool(const float* dpool, const unsigned char* argmax, const fl
     const size_t total = (size_t)NP * (C / 4);
     bn_bwd_apply_pool_kernel<<<grid_for(total), 256, 0, s>>>(y, dpool, argmax, stats, coef, dy, N,
                                                             H, W, C, Ho, Wo);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_bn_bwd_frozen(const float* dz, const float* z, int M, int C, const float* gamma,
+                         const float* stats, int relu, float* dy, float* g_out, hipStream_t s) {
+    if (check_c(C)) return 1;
+    CILRS_CHECK(dz && gamma && stats && dy && (!relu || z) && M >= 1, "bn_bwd_frozen: NULL tensor");
+    CILRS_CHECK(((((uintptr_t)dz | (uintptr_t)z | (uintptr_t)dy | (uintptr_t)g_out |
+                   (uintptr_t)gamma | (uintptr_t)stats) & 15) == 0),
+                "bn_bwd_frozen: pointers must be 16-byte aligned");
+    // the kernel fixes a thread's channel quad once: C/4 must divide the 1,024-thread block, hence
+    // every grid stride (of check_c's channel counts, 3072 does not)
+    CILRS_CHECK(kApplyThreads % (C / 4) == 0,
+                "bn_bwd_frozen: unsupported channel count %d (C/4 must divide %d)", C, kApplyThreads);
+    const size_t total4 = (size_t)M * C / 4;
+    bn_bwd_frozen_kernel<<<grid_for(total4, kApplyThreads, apply_grid_cap()), kApplyThreads, 0, s>>>(
+        dz, z, gamma, stats, dy, g_out, total4, C, relu);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_bn_bwd_pool_frozen(const float* dpool, const unsigned char* argmax, const float* y, int N,
+                              int H, int W, int C, const float* gamma, const float* stats, float* dy,
+                              hipStream_t s) {
+    if (check_c(C)) return 1;
+    CILRS_CHECK(C <= 1024, "bn_bwd_pool_frozen: at most 1024 channels (got %d)", C);
+    CILRS_CHECK(dpool && argmax && y && gamma && stats && dy && N >= 1 && H >= 1 && W >= 1,
+                "bn_bwd_pool_frozen: NULL tensor");
+    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    const size_t total = (size_t)N * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);
+    bn_bwd_frozen_pool_kernel<<<grid_for(total), 256, 0, s>>>(y, dpool, argmax, gamma, stats, dy, N,
+                                                              H, W, C, Ho, Wo);
     CILRS_LAUNCH_CHECK();
     return 0;
 }

@@ -264,8 +264,21 @@ int launch_bn_bwd_pool(const float* dpool, const unsigned char* argmax, const fl
                        int H, int W, int C, const float* gamma, const float* stats, float* dgamma,
                        float* dbeta, float* coef, float* partial, float* dy, hipStream_t s,
                        int frozen = 0);
+// BatchNorm backward with fixed statistics when nobody asks for dgamma / dbeta (the data-gradient-
+// only backward of a frozen graph): dy = g * (gamma * rstd), g = dz masked by z > 0 (relu), g_out = g
+// (optional) -- one streaming launch, no reductions, no finalize, the pre-BN tensor is not read.
+// launch_bn_bwd_pool_frozen: its max-pool form for the stem (the mask is rebuilt from y there)
+int launch_bn_bwd_frozen(const float* dz, const float* z, int M, int C, const float* gamma,
+                         const float* stats, int relu, float* dy, float* g_out, hipStream_t s);
+int launch_bn_bwd_pool_frozen(const float* dpool, const unsigned char* argmax, const float* y, int N,
+                              int H, int W, int C, const float* gamma, const float* stats, float* dy,
+                              hipStream_t s);
 int launch_maxpool_fwd(const float* x, float* out, unsigned char* argmax, int N, int H, int W,
                        int C, hipStream_t s);
+// saliency.hip: per-frame heat map of an image gradient (see cilrs_saliency_map)
+int launch_saliency_map(const float* dimage, long sn, long sc, long sh, long sw, int B, int H, int W,
+                        const float* chan_scale3, float* heat, unsigned char* heat_u8, float* peak,
+                        hipStream_t s);
 int launch_maxpool_bwd(const float* dout, const unsigned char* argmax, float* dx, int N, int H,
                        int W, int C, hipStream_t s);
 int launch_avgpool_fwd(const float* x, float* out, int N, int HW, int C, int out_ld,

@@ -1037,7 +1037,9 @@ int cilrs_net_create_ex(int variant, int batch, int height, int width, unsigned 
         n->bn_partial = bump.take(need);
         n->bn_partial2 = bump.take(need);      // (the down-sample branch of a block, built beside conv1)
     }
-    n->bn_coef = bump.take(3 * 2048);
+    // [0, 3 x 2048) the BatchNorm-backward coefficients; [3 x 2048, 5 x 2048) where the data-gradient-
+    // only backward of a train-mode graph leaves the dgamma / dbeta by-products of its reductions
+    n->bn_coef = bump.take(5 * 2048);
     n->slabs_floats = slabs_max;
     n->slabs = bump.take(slabs_max > 0 ? slabs_max : 4);
     n->ksplit_floats = ksplit_max;
@@ -1938,6 +1940,21 @@ int cilrs_net_forward_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_
     return forward_u8(net, bufs, frames, speed, command, controls, pred_speed, stream, 0);
 }
 
+int cilrs_net_forward_frozen_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
+                                const float* speed, const int64_t* command, float* controls,
+                                float* pred_speed, void* stream) {
+    if (check_bufs(net, bufs, false)) return 1;
+    CILRS_CHECK(frames && speed && command && controls && pred_speed, "forward_frozen_u8: NULL tensor");
+    CILRS_CHECK(!net->bf16_train, "forward_frozen: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan "
+                "rejects the frozen mode)");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
+    RUN(net, "transform", 0.0, 0.0, s,
+        launch_u8hwc_to_nhwc4(frames, ws + net->x4, (size_t)net->B * net->H * net->W, kImageMean,
+                              kImageStd, s));
+    return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s, 0, true);
+}
+
 int cilrs_net_forward_camera(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
                              int src_h, int src_w, int pixel_stride, long row_stride,
                              long frame_stride, const float* speed, const int64_t* command,
@@ -1951,6 +1968,24 @@ int cilrs_net_forward_camera(cilrs_net* net, const cilrs_buffers* bufs, const ui
         launch_camera_to_nhwc4(frames, ws + net->x4, net->B, src_h, src_w, pixel_stride,
                                row_stride, frame_stride, net->H, net->W, kImageMean, kImageStd, s));
     return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s);
+}
+
+int cilrs_net_forward_frozen_camera(cilrs_net* net, const cilrs_buffers* bufs,
+                                    const uint8_t* frames, int src_h, int src_w, int pixel_stride,
+                                    long row_stride, long frame_stride, const float* speed,
+                                    const int64_t* command, float* controls, float* pred_speed,
+                                    void* stream) {
+    if (check_bufs(net, bufs, false)) return 1;
+    CILRS_CHECK(frames && speed && command && controls && pred_speed,
+                "forward_frozen_camera: NULL tensor");
+    CILRS_CHECK(!net->bf16_train, "forward_frozen: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan "
+                "rejects the frozen mode)");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
+    RUN(net, "transform", 0.0, 0.0, s,
+        launch_camera_to_nhwc4(frames, ws + net->x4, net->B, src_h, src_w, pixel_stride,
+                               row_stride, frame_stride, net->H, net->W, kImageMean, kImageStd, s));
+    return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s, 0, true);
 }
 
 int cilrs_net_forward_u8_f16(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
@@ -2387,11 +2422,15 @@ int cilrs_net_forward_u8_bf16_graph(cilrs_net* net, const cilrs_buffers* bufs,
 // backward
 // ------------------------------------------------------------------------------------------------
 static int backward_heads(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
-                          const float* dps, const int64_t* command_unused, hipStream_t s);
+                          const float* dps, bool data_only, hipStream_t s);
 
-int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
-                       const float* dpred_speed, int seg_begin, int seg_end, void* stream) {
-    if (check_bufs(net, bufs, true)) return 1;
+// data_only (cilrs_net_backward_data): the data-gradient chain alone -- no weight gradient, no head
+// dW / db, nothing on the side stream, bufs->grads never touched; a frozen graph's BatchNorm
+// backward is then one reduction-free launch per layer
+static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
+                         const float* dpred_speed, int seg_begin, int seg_end, void* stream,
+                         const bool data_only) {
+    if (check_bufs(net, bufs, !data_only)) return 1;
     CILRS_CHECK(net->trained_fwd, "backward needs a preceding train-mode forward on this plan");
     CILRS_CHECK(0 <= seg_begin && seg_begin <= seg_end && seg_end <= 6, "bad segment range");
     // fine-tuning: the graph ends where the frozen prefix begins -- segments of frozen groups are
@@ -2404,8 +2443,15 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
     float* ws = reinterpret_cast<float*>(bufs->workspace);
     net->ws_base = ws;
     const float* P = bufs->params;
-    float* Gp = bufs->grads;
+    float* Gp = data_only ? nullptr : bufs->grads;
     const int B = net->B;
+    // data-only pass over a frozen graph: BatchNorm backward without reductions, data gradients
+    // without the BatchNorm-partials epilogue
+    const bool lean_bn = data_only && net->frozen_fwd;
+    // where a BatchNorm backward leaves dgamma / dbeta: the arena, or (data-only pass over a
+    // train-mode graph, whose reductions still feed dx) a scratch nobody reads
+    auto dgamma_of = [&](const BnT& b) { return data_only ? ws + net->bn_coef + 3 * 2048 : Gp + b.gamma; };
+    auto dbeta_of = [&](const BnT& b) { return data_only ? ws + net->bn_coef + 4 * 2048 : Gp + b.beta; };
     auto last_conv = [&](const BlockT& blk) { return blk.conv3 >= 0 ? blk.conv3 : blk.conv2; };
     // cilrs_net_backward_step: segment `seg`'s gradients are complete once the main stream reaches
     // this point (BatchNorm / head gradients) and the side stream has run what it holds (weight
@@ -2434,7 +2480,7 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
         if (seg == 0) {
             CILRS_CHECK(dcontrols && dpred_speed, "backward: output gradients missing");
             net->bwd_nblk_next = 0;
-            if (backward_heads(net, bufs, dcontrols, dpred_speed, nullptr, s)) return 1;
+            if (backward_heads(net, bufs, dcontrols, dpred_speed, data_only, s)) return 1;
             // d visual -> avgpool backward -> grad of the last block's output, in G[3]
             if (cut == 5) {
                 // (whole trunk frozen: nobody reads d(feature map))
@@ -2458,6 +2504,12 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
             for (int L = 1; L < layer; ++L) first += nblk[L - 1];
             for (int bi = first + nblk[layer - 1] - 1; bi >= first; --bi) {
                 const BlockT& blk = A.blocks[bi];
+                // (boundary block of a fine-tuning cut: no data gradient leaves it, and a data-only
+                //  pass wants none of its weight gradients)
+                if (data_only && layer == cut && bi == first) {
+                    net->bwd_nblk_next = 0;
+                    continue;
+                }
                 // conv-BN pairs of the main branch, in forward order (2: BasicBlock, 3: Bottleneck)
                 const int chain[3] = {blk.conv1, blk.conv2, blk.conv3};
                 const int nchain = blk.conv3 >= 0 ? 3 : 2;
@@ -2477,7 +2529,9 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
                 auto Gh = [&](int gi) { return h16(ws, net->G16[gi]); };
                 // (x: the conv's input activation; x16: its bf16 form)
                 auto wgrad_side = [&](const ConvT& c, const ConvG& g, const float* x,
-                                      const cilrs_half* x16, int gi, float* dwdst) -> int {
+                                      const cilrs_half* x16, int gi, size_t dw_off) -> int {
+                    if (data_only) return 0;
+                    float* const dwdst = Gp + dw_off;
                     if (gbuf_side_begin(net, s)) return 1;
                     if (bf16t) {
                         if (conv_wgrad16(net, c, g, x16, Gh(gi), dwdst, ws, side_or(net, s, 0)))
@@ -2494,6 +2548,7 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
                                  bool out32 = false) -> int {
                     const ConvT& c = A.convs[ci];
                     const ConvG& g = net->cg[ci];
+                    if (lean_bn) { bn_of = nullptr; nbp = nullptr; }
                     if (bf16t)
                         return conv_dgrad16(net, c, g, ci, Gh(gi), out32 ? nullptr : Gh(go),
                                             out32 ? Gf(go) : nullptr, gadd >= 0 ? Gh(gadd) : nullptr,
@@ -2508,18 +2563,24 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
                     const ConvT& c = A.convs[ci];
                     const ConvG& g = net->cg[ci];
                     const BnT& b = A.bns[c.bn];
-                    if (bf16t) {
+                    if (lean_bn) {
+                        RUN(net, "bn_bwd." + grp, 0.0,
+                            4.0 * g.M * c.cout * (2.0 + (relu ? 1.0 : 0.0) + (gg >= 0 ? 1.0 : 0.0)), s,
+                            launch_bn_bwd_frozen(Gf(gz), relu ? ws + g.z : nullptr, g.M, c.cout,
+                                                 P + b.gamma, ws + g.stats, relu, Gf(gdy),
+                                                 gg >= 0 ? Gf(gg) : nullptr, s));
+                    } else if (bf16t) {
                         RUN(net, "bn_bwd." + grp, 0.0, 2.0 * g.M * c.cout * passes, s,
                             launch_bn16_bwd(Gh(gz), relu ? h16(ws, net->z16[ci]) : nullptr,
                                             y16_of(net, ws, ci), g.M, c.cout, P + b.gamma,
-                                            ws + g.stats, relu, Gp + b.gamma, Gp + b.beta,
+                                            ws + g.stats, relu, dgamma_of(b), dbeta_of(b),
                                             ws + net->bn_coef, ws + net->bn_partial, Gh(gdy),
                                             gg >= 0 ? Gh(gg) : nullptr, pre_nblk, s));
                     } else {
                         RUN(net, "bn_bwd." + grp, 0.0, 4.0 * g.M * c.cout * passes, s,
                             launch_bn_bwd(Gf(gz), relu ? ws + g.z : nullptr, ws + g.y, g.M, c.cout,
-                                          P + b.gamma, ws + g.stats, relu, Gp + b.gamma,
-                                          Gp + b.beta, 0, ws + net->bn_coef, ws + net->bn_partial,
+                                          P + b.gamma, ws + g.stats, relu, dgamma_of(b),
+                                          dbeta_of(b), 0, ws + net->bn_coef, ws + net->bn_partial,
                                           Gf(gdy), gg >= 0 ? Gf(gg) : nullptr, pre_nblk, s, nullptr,
                                           bn_sync(net, ws, 1), net->frozen_fwd ? 1 : 0));
                     }
@@ -2544,7 +2605,7 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
                     const ConvT& c = A.convs[chain[i]];
                     const ConvG& g = net->cg[chain[i]];
                     const ConvG& gp = net->cg[chain[i - 1]];
-                    if (wgrad_side(c, g, ws + gp.z, z16_of(chain[i - 1]), ga, Gp + c.w)) return 1;
+                    if (wgrad_side(c, g, ws + gp.z, z16_of(chain[i - 1]), ga, c.w)) return 1;
                     if (gbuf_acquire(net, s, 2)) return 1;
                     int nbp = 0;    // the previous BatchNorm's reductions ride on this dgrad's epilogue
                     if (dgrad(chain[i], ga, 2, -1, &gp, &nbp)) return 1;
@@ -2553,7 +2614,7 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
                     if (bnb(chain[i - 1], 2, 1, ga, -1, nbp, 7.0)) return 1;
                 }
                 // 3. dW1 (side)
-                if (wgrad_side(c1, g1, xin, xin16, ga, Gp + c1.w)) return 1;
+                if (wgrad_side(c1, g1, xin, xin16, ga, c1.w)) return 1;
                 if (layer == cut && bi == first) {
                     // boundary block of a fine-tuning step: its input belongs to the frozen
                     // prefix -- no data gradient leaves it; the down-sample branch still takes
@@ -2565,12 +2626,15 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
                         const int gdn = next_ring();
                         if (gbuf_acquire(net, s, gdn)) return 1;
                         if (bnb(blk.down, 1, 0, gdn, -1, 0, 6.0)) return 1;
-                        if (wgrad_side(cd, gd, xin, xin16, gdn, Gp + cd.w)) return 1;
+                        if (wgrad_side(cd, gd, xin, xin16, gdn, cd.w)) return 1;
                     }
                 } else if (blk.down < 0) {
                     // 4. dx = dgrad(conv1) + identity grad [1] -> [3]
                     // ... and carries the reductions of the previous block's last BatchNorm
-                    const ConvG* prev = bi > 0 ? &net->cg[last_conv(A.blocks[bi - 1])] : nullptr;
+                    // (not for a block the data-only pass is going to skip: nobody would read them)
+                    const bool prev_skipped = data_only && layer == cut && bi - 1 == first;
+                    const ConvG* prev =
+                        bi > 0 && !prev_skipped ? &net->cg[last_conv(A.blocks[bi - 1])] : nullptr;
                     if (dgrad(blk.conv1, ga, 3, 1, prev, &net->bwd_nblk_next, bi == 0)) return 1;
                 } else {
                     const ConvT& cd = A.convs[blk.down];
@@ -2580,7 +2644,7 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
                     const int gdn = next_ring();
                     if (gbuf_acquire(net, s, gdn)) return 1;
                     if (bnb(blk.down, 1, 0, gdn, -1, 0, 6.0)) return 1;
-                    if (wgrad_side(cd, gd, xin, xin16, gdn, Gp + cd.w)) return 1;
+                    if (wgrad_side(cd, gd, xin, xin16, gdn, cd.w)) return 1;
                     // 6. dx += dgrad(conv_d)
                     if (dgrad(blk.down, gdn, 3, 3, nullptr, nullptr, bi == 0)) return 1;
                 }
@@ -2600,17 +2664,24 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
                 reinterpret_cast<const unsigned char*>(bufs->workspace) + net->argmax_b;
             // max-pool backward + ReLU mask are rebuilt inside the BatchNorm-backward passes
             if (gbuf_acquire(net, s, 1)) return 1;           // G[1] is rewritten below
-            RUN(net, "bn_bwd.stem", 0.0, 4.0 * g0.M * 64 * 3.0, s,
-                launch_bn_bwd_pool(ws + net->G[3], argmax, ws + g0.y, B, net->H0, net->W0, 64,
-                                   P + b0.gamma, ws + g0.stats, Gp + b0.gamma, Gp + b0.beta,
-                                   ws + net->bn_coef, ws + net->bn_partial, ws + net->G[1], s,
-                                   net->frozen_fwd ? 1 : 0));
+            if (lean_bn)
+                RUN(net, "bn_bwd.stem", 0.0, 4.0 * g0.M * 64 * 2.5, s,
+                    launch_bn_bwd_pool_frozen(ws + net->G[3], argmax, ws + g0.y, B, net->H0, net->W0,
+                                              64, P + b0.gamma, ws + g0.stats, ws + net->G[1], s));
+            else
+                RUN(net, "bn_bwd.stem", 0.0, 4.0 * g0.M * 64 * 3.0, s,
+                    launch_bn_bwd_pool(ws + net->G[3], argmax, ws + g0.y, B, net->H0, net->W0, 64,
+                                       P + b0.gamma, ws + g0.stats, dgamma_of(b0), dbeta_of(b0),
+                                       ws + net->bn_coef, ws + net->bn_partial, ws + net->G[1], s,
+                                       net->frozen_fwd ? 1 : 0));
             // the stem's weight gradient runs on the main stream and uses the same slab scratch as
             // the weight gradients of the side stream: those must have finished (between the
             // segments of one call nothing else joins the two streams any more)
             if (gbuf_join_all(net, s)) return 1;
             const size_t sw = stem_wgrad_f32_scratch_floats(B, net->H, net->W);
-            if (sw > 0 && sw <= net->slabs_floats) {
+            if (data_only) {
+                // (no weight gradient)
+            } else if (sw > 0 && sw <= net->slabs_floats) {
                 // (the reduction over pixels on the matrix pipe, dy from global memory, the input
                 //  rows in LDS: stem_f32.hip)
                 RUN(net, "conv_wgrad.stem", 2.0 * g0.M * 64 * 147,
@@ -2635,6 +2706,16 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
         CILRS_HIP(hipStreamWaitEvent(s, net->fork_ev, 0));
     }
     return 0;
+}
+
+int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
+                       const float* dpred_speed, int seg_begin, int seg_end, void* stream) {
+    return backward_impl(net, bufs, dcontrols, dpred_speed, seg_begin, seg_end, stream, false);
+}
+
+int cilrs_net_backward_data(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
+                            const float* dpred_speed, int seg_begin, int seg_end, void* stream) {
+    return backward_impl(net, bufs, dcontrols, dpred_speed, seg_begin, seg_end, stream, true);
 }
 
 // Backward of every segment with torch.optim.Adam.step() (notebook/notebook.ipynb:555) fused in:
@@ -2688,12 +2769,12 @@ int cilrs_net_input_grads(cilrs_net* net, const cilrs_buffers* bufs, float* dima
 }
 
 static int backward_heads(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
-                          const float* dps, const int64_t*, hipStream_t s) {
+                          const float* dps, const bool data_only, hipStream_t s) {
     const Arch& A = *net->A;
     const int feat = A.feat, comb = A.feat + 128;
     float* ws = reinterpret_cast<float*>(bufs->workspace);
     const float* P = bufs->params;
-    float* Gp = bufs->grads;
+    float* Gp = data_only ? nullptr : bufs->grads;
     const int B = net->B;
     const float dscale = net->last_dropout > 0.f ? 1.0f / (1.0f - net->last_dropout) : 1.0f;
     const long long* cmd = reinterpret_cast<const long long*>(
@@ -2704,6 +2785,7 @@ static int backward_heads(cilrs_net* net, const cilrs_buffers* bufs, const float
     auto wg = [&](HGemmGroup& g, const float* dy, int dy_ld, const float* x, int x_ld,
                   const LinT& l) {
         memset(&g, 0, sizeof(g));
+        if (data_only) return;       // (run(2, ...) launches nothing then)
         g.A = dy; g.lda = dy_ld; g.B = x; g.ldb = x_ld; g.C = Gp + l.w; g.ldc = l.in;
         g.dbias = Gp + l.b; g.M = l.out; g.N = l.in; g.K = B;
     };
@@ -2718,6 +2800,7 @@ static int backward_heads(cilrs_net* net, const cilrs_buffers* bufs, const float
     // stream (idle at this point of the backward pass, and these launches occupy a handful of
     // CUs), behind the output gradient they multiply; cilrs_net_backward joins them at its end
     auto run = [&](int mode, HGemmArgs& h, int n) -> int {
+        if (mode == 2 && data_only) return 0;
         h.ngroups = n; h.relu = 0; h.accumulate = 0; h.drop_p = 0.f; h.seed = 0;
         double fl = 0.0;
         for (int i = 0; i < n; ++i) fl += 2.0 * h.g[i].M * h.g[i].N * h.g[i].K;
@@ -3342,6 +3425,23 @@ int cilrs_bn_bwd(const float* dz, const float* z, const float* y, int M, int C,
                  float* coef3c, float* partial, float* dy, float* g_out, void* stream) {
     return launch_bn_bwd(dz, z, y, M, C, gamma, stats, relu, dgamma, dbeta, 0, coef3c, partial, dy,
                          g_out, 0, reinterpret_cast<hipStream_t>(stream));
+}
+int cilrs_bn_bwd_frozen(const float* dz, const float* z, int M, int C, const float* gamma,
+                        const float* stats, int relu, float* dy, float* g_out, void* stream) {
+    return launch_bn_bwd_frozen(dz, z, M, C, gamma, stats, relu, dy, g_out,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+int cilrs_bn_bwd_pool_frozen(const float* dpool, const uint8_t* argmax, const float* y, int N, int H,
+                             int W, int C, const float* gamma, const float* stats, float* dy,
+                             void* stream) {
+    return launch_bn_bwd_pool_frozen(dpool, argmax, y, N, H, W, C, gamma, stats, dy,
+                                     reinterpret_cast<hipStream_t>(stream));
+}
+int cilrs_saliency_map(const float* dimage, long sn, long sc, long sh, long sw, int B, int H, int W,
+                       const float* chan_scale3, float* heat, uint8_t* heat_u8, float* peak,
+                       void* stream) {
+    return launch_saliency_map(dimage, sn, sc, sh, sw, B, H, W, chan_scale3, heat, heat_u8, peak,
+                               reinterpret_cast<hipStream_t>(stream));
 }
 int cilrs_maxpool_fwd(const float* x, float* out, uint8_t* argmax, int N, int H, int W, int C,
                       void* stream) {

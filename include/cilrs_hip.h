@@ -219,6 +219,18 @@ int cilrs_net_forward_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_
                          const float* speed, const int64_t* command, float* controls,
                          float* pred_speed, void* stream);
 
+/* cilrs_net_forward_frozen (the eval-mode forward that keeps its graph) fed like
+ * cilrs_net_forward_u8 / cilrs_net_forward_camera (below): the same preprocessing launch, then the
+ * frozen forward.  fp32 plans only. */
+int cilrs_net_forward_frozen_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
+                                const float* speed, const int64_t* command, float* controls,
+                                float* pred_speed, void* stream);
+int cilrs_net_forward_frozen_camera(cilrs_net* net, const cilrs_buffers* bufs,
+                                    const uint8_t* frames, int src_h, int src_w, int pixel_stride,
+                                    long row_stride, long frame_stride, const float* speed,
+                                    const int64_t* command, float* controls, float* pred_speed,
+                                    void* stream);
+
 /* Same, fed with raw camera frames of any size: fuses preprocess_image completely --
  * cv2.resize(frame, (W, H)) (8-bit INTER_LINEAR, restated; cv2 is absent from the build image so
  * this step is parity-unpinned), /255, HWC->CHW, Normalize (autonomous_drive.py:897-902).
@@ -345,6 +357,22 @@ int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* d
  * (bit-identical from run to run). */
 int cilrs_net_input_grads(cilrs_net* net, const cilrs_buffers* bufs, float* dimage, long sn, long sc,
                           long sh, long sw, float* dspeed, void* stream);
+/* The data-gradient chain of cilrs_net_backward and nothing else -- torch.autograd.grad(out, image)
+ * or loss.backward() with every parameter frozen (requires_grad_(False)): the backward of a
+ * saliency map.  No weight-gradient launch of any kind (convolutions, the stem, the heads' dW / db),
+ * nothing on the weight-gradient stream, bufs->grads is never written and may be NULL.  Sets the
+ * same state as cilrs_net_backward, so cilrs_net_input_grads follows it unchanged, and handles a
+ * fine-tuning cut the same way (the chain stops at the cut; the image gradient is refused there).
+ *   train-mode graphs: the BatchNorm reductions stay (they feed dx); their dgamma / dbeta
+ *     by-products go to a workspace scratch.
+ *   frozen graphs (cilrs_net_forward_frozen*): every BatchNorm backward is one reduction-free
+ *     launch, dy = (z > 0 ? dz : 0) * (gamma * rstd), the pre-BN tensor is not read (the stem, whose
+ *     post-BN tensor is never stored, rebuilds its mask from it), and the data gradients run
+ *     without the BatchNorm-partials epilogue.
+ * The convolution plans are those of cilrs_net_backward: image and speed gradients are equal to
+ * what cilrs_net_backward + cilrs_net_input_grads give (element for element under torch.equal). */
+int cilrs_net_backward_data(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
+                            const float* dpred_speed, int seg_begin, int seg_end, void* stream);
 /* float range [begin,end) of the gradient arena that segment `seg` produces */
 int cilrs_segment_range(int seg, size_t* begin, size_t* end);
 /* the same for architecture variant `variant` (0 = the reference's ResNet-34, 1 = ResNet-50) */
@@ -526,6 +554,30 @@ size_t cilrs_conv2d_wgrad_16_scratch_floats(int N, int H, int W, int Cin, int Co
 int cilrs_conv2d_wgrad_16(const float* x, const float* dy, float* dw, float* scratch32, int N,
                           int H, int W, int Cin, int Cout, int K, int stride, int pad, int bf16,
                           void* scratch16, void* stream);
+
+/* BatchNorm backward with fixed statistics when no dgamma / dbeta is wanted (what
+ * cilrs_net_backward_data runs on a frozen graph): g = relu ? (z > 0 ? dz : 0) : dz;
+ * g_out = g (may be NULL); dy = g * (gamma[c] * stats[C + c]) -- stats = [mean | rstd | ...] as
+ * cilrs_bn_eval_fwd leaves it.  [M][C] dense tensors, 16-byte aligned; z may be NULL when relu == 0.
+ * C/4 must divide 1024 (the BatchNorm channel counts up to 1024, 2048 and 4096; 3072 is refused).
+ * cilrs_bn_bwd_pool_frozen: the stem's form, the backward of maxpool3x3/s2/p1(relu(bn(y))) given
+ * d(max-pool output) [N][Ho][Wo][C] and the forward's argmax -- scatter, mask by
+ * y * stats[2C + c] + stats[3C + c] > 0, scale; dy [N][H][W][C], every element written. */
+int cilrs_bn_bwd_frozen(const float* dz, const float* z, int M, int C, const float* gamma,
+                        const float* stats, int relu, float* dy, float* g_out, void* stream);
+int cilrs_bn_bwd_pool_frozen(const float* dpool, const uint8_t* argmax, const float* y, int N, int H,
+                             int W, int C, const float* gamma, const float* stats, float* dy,
+                             void* stream);
+
+/* Heat map of an image gradient (csrc/saliency.hip): dimage = logical NCHW f32 [B,3,H,W] with
+ * element strides (sn,sc,sh,sw), e.g. what cilrs_net_input_grads wrote.
+ *   s[b,h,w] = max_c |dimage[b,c,h,w]| * chan_scale3[c]   (three HOST floats; NULL = 1)
+ *   peak[b]  = max_hw s;   heat = s / peak (0 where peak == 0, never NaN) -- f32 [B,H,W];
+ *   heat_u8  = floor(heat * 255 + 0.5) -- uint8 [B,H,W].    heat_u8 and peak may be NULL.
+ * One launch, one workgroup per frame, fixed-order reduction: bit-identical from run to run. */
+int cilrs_saliency_map(const float* dimage, long sn, long sc, long sh, long sw, int B, int H, int W,
+                       const float* chan_scale3, float* heat, uint8_t* heat_u8, float* peak,
+                       void* stream);
 
 /* The bf16 training mode's operators on 16-bit tensors (round 4: every trunk tensor after the stem
  * -- activations, raw convolution outputs, gradients -- is stored in bf16; fp32 accumulation,

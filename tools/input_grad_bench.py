@@ -3,11 +3,14 @@
     (cilrs_stem_conv_fwd) of the same geometry, launched back to back in one process;
   * an eval-mode saliency pass: model.eval(), parameters frozen, image.requires_grad_(),
     forward (frozen BatchNorm) + torch.autograd.grad(controls.sum(), image), against the plain
-    eval forward under torch.no_grad().
-Per item: median of --rounds rounds of --iters launches each, timed with device events after
---warmup launches.  Prints one JSON line.
+    eval forward under torch.no_grad() -- the backward is the data-gradient-only one
+    (cilrs_net_backward_data); --profile adds its per-label device times (one serialised pass);
+  * one frame through Predictor.saliency (upload, frozen forward, data-only backward, heat map,
+    read-back) beside Predictor.predict_batch of the same frame, as host wall-clock per call.
+Per item: (median, min, max) of --rounds rounds of --iters launches each, timed with device events
+after --warmup launches.  Prints one JSON line.
 
-    python tools/input_grad_bench.py [--batch 128] [--height 88] [--width 200]
+    python tools/input_grad_bench.py [--batch 128] [--height 88] [--width 200] [--profile]
 """
 import argparse
 import ctypes as C
@@ -15,6 +18,7 @@ import json
 import os
 import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "cilrs-autonomous-driving-carla_amd"), os.path.join(ROOT, "oracle")):
@@ -40,6 +44,19 @@ def timed_ms(fn, iters, rounds, warmup):
     return statistics.median(out), min(out), max(out)
 
 
+def wall_ms(fn, iters, rounds, warmup):
+    """Synchronous calls (they end with their own stream synchronisation): host time per call."""
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(rounds):
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            fn()
+        out.append((time.perf_counter() - t0) * 1e3 / iters)
+    return statistics.median(out), min(out), max(out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=128)
@@ -48,6 +65,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--profile", action="store_true",
+                    help="per-label device times of one saliency pass (serialised launches)")
     a = ap.parse_args()
     import cilrs_oracle as O
     from cilrs_mi355 import CILRS, _lib as L
@@ -97,6 +116,26 @@ def main():
 
     res["eval_forward_ms"] = timed_ms(infer, max(1, a.iters // 4), a.rounds, a.warmup)
     res["saliency_fwd_bwd_ms"] = timed_ms(saliency, max(1, a.iters // 4), a.rounds, a.warmup)
+    if a.profile:
+        pl = m.engine().plan(B, H, W)
+        pl.profile(True)
+        try:
+            pl.profile_reset()
+            saliency()
+            torch.cuda.synchronize()
+            rows = pl.profile_table()
+        finally:
+            pl.profile(False)
+        res["saliency_profile_ms"] = {k: [r["calls"], round(r["ms"], 4)] for k, r in sorted(rows.items())}
+
+    # one frame: the control loop's tick beside its saliency map
+    from cilrs_mi355.predict import Predictor
+    pr = Predictor(m)
+    frame = O.synthetic_batch(1, seed=4)[4]
+    res["predict_batch_b1_ms"] = wall_ms(lambda: pr.predict_batch(frame, [30.0], [1]), a.iters,
+                                         a.rounds, a.warmup)
+    res["predictor_saliency_b1_ms"] = wall_ms(lambda: pr.saliency(frame, [30.0], [1]), a.iters,
+                                              a.rounds, a.warmup)
     print(json.dumps(res))
 
 
