@@ -3,9 +3,17 @@
 // (SURVEY.md 2b): torchvision BasicBlock = conv-BN-ReLU-conv-BN-(+id)-ReLU, stem = conv-BN-ReLU-
 // maxpool, tail = avgpool (reference model/autonomous_drive.py:366-370).
 //
-// Semantics follow torch.nn.BatchNorm2d exactly: batch mean / BIASED variance for normalisation,
-// UNBIASED variance into running_var, momentum 0.1, eps 1e-5, num_batches_tracked += 1; like
-// torch's CPU kernels the per-channel statistics are accumulated in double from fp32 partial sums.
+// Semantics are torch.nn.BatchNorm2d's: batch mean / BIASED variance for normalisation, UNBIASED
+// variance into running_var, momentum 0.1, eps 1e-5, num_batches_tracked += 1.  The statistics are
+// one pass: fp32 partial sums of d and d*d over at most a block's rows, summed in double, with
+// var = sum(d*d)/M - (sum(d)/M)^2.  The column reduces of this file take d = y - y[0][c] (the
+// channel's first row as pivot, a sample of the channel: |mean(d)|/std stays at a few units whatever
+// the channel's mean is); partials that a convolution epilogue wrote are sums of y and y*y themselves
+// (d = y).  Envelope of the normalised output against float64 (tests/test_ops_edges_gpu.py; DESIGN.md
+// section 3, "BatchNorm statistics away from zero mean"): with d = y the error is a few 2^-24 (up to
+// 11 x 2^-24 measured when one workgroup adds 21 rows in fp32) times 1 + (mean/std)^2 -- 1.7e-4 at
+// ratio 12, 1.45 at ratio 1000 -- with the pivot the ratio that counts is that of d, a few units.
+// torch's CPU kernel is two-pass.
 //
 // Every reduction is a fixed-shape tree (per-thread rows -> LDS -> per-block partial -> serial
 // double sum over blocks): deterministic, no atomics.  Channel is the fastest index, so a wave reads
@@ -27,7 +35,7 @@ __device__ __forceinline__ void store_bf16x4(__bf16* __restrict__ p, const size_
 }
 
 // partial[0][c][blk] = sum_rows v1, partial[1][c][blk] = sum_rows v2   (channel-major)
-// MODE 0: v1 = y, v2 = y*y                     (forward statistics)
+// MODE 0: v1 = d, v2 = d*d, d = y - y[0][c]     (forward statistics about the pivot row 0)
 // MODE 1: v1 = g, v2 = g * (y - mean) * rstd   (backward reductions), g = dz * (z > 0 if relu)
 template <int MODE>
 __global__ __launch_bounds__(256) void bn_colreduce_kernel(
@@ -50,13 +58,16 @@ __global__ __launch_bounds__(256) void bn_colreduce_kernel(
     if (MODE == 1) {
         mean = *reinterpret_cast<const f32x4*>(stats + c0 + q * 4);
         rstd = *reinterpret_cast<const f32x4*>(stats + C + c0 + q * 4);
+    } else {
+        mean = *reinterpret_cast<const f32x4*>(y + c0 + q * 4);      // the pivot: row 0 (see the header)
     }
     auto accum = [&](int r, f32x4& a1, f32x4& a2) {
         const size_t o = (size_t)r * C + c0 + q * 4;
         const f32x4 v = *reinterpret_cast<const f32x4*>(y + o);
         if (MODE == 0) {
-            a1 += v;
-            a2 += v * v;
+            const f32x4 d = v - mean;
+            a1 += d;
+            a2 += d * d;
         } else {
             f32x4 g = *reinterpret_cast<const f32x4*>(dz + o);
             if (relu) {
@@ -240,12 +251,17 @@ __device__ __forceinline__ void fwd_finalize_channel(
     const float* __restrict__ partial, const int nblk, const int M, const int C, const int c,
     const float* __restrict__ gamma, const float* __restrict__ beta, float* running_mean,
     float* running_var, long long* nbt, const float momentum, const float eps,
-    float* __restrict__ stats) {
+    float* __restrict__ stats, const void* __restrict__ pivot, const int pivot_bf16) {
     double s1, s2;
     if (SC1 ? !partial_sums4(partial, nblk, C, c, c < C, s1, s2)
             : !partial_sums(partial, nblk, C, c, s1, s2)) return;
-    const double mean = s1 / M;
-    double var = s2 / M - mean * mean;
+    // pivot: row 0 of the tensor whose column reduce took its sums about that row (NULL: about 0)
+    const double piv = !pivot ? 0.0
+                       : pivot_bf16 ? (double)(float)reinterpret_cast<const __bf16*>(pivot)[c]
+                                    : (double)reinterpret_cast<const float*>(pivot)[c];
+    const double dmean = s1 / M;
+    const double mean = piv + dmean;
+    double var = s2 / M - dmean * dmean;
     if (var < 0.0) var = 0.0;
     const float rstd = (float)(1.0 / sqrt(var + (double)eps));
     const float w = gamma[c] * rstd;
@@ -271,9 +287,9 @@ __global__ __launch_bounds__(kFinThreads) void bn_fwd_finalize_kernel(
     const float* __restrict__ partial, const int nblk, const int M, const int C,
     const float* __restrict__ gamma, const float* __restrict__ beta, float* running_mean,
     float* running_var, long long* nbt, const float momentum, const float eps,
-    float* __restrict__ stats) {
+    float* __restrict__ stats, const void* __restrict__ pivot, const int pivot_bf16) {
     fwd_finalize_channel<false>(partial, nblk, M, C, blockIdx.x, gamma, beta, running_mean,
-                                running_var, nbt, momentum, eps, stats);
+                                running_var, nbt, momentum, eps, stats, pivot, pivot_bf16);
 }
 
 // eval mode: stats from the running statistics
@@ -347,6 +363,7 @@ struct BnFinArgs {
     const float* gamma; const float* beta; float* running_mean; float* running_var;
     long long* nbt; float momentum; float eps;
     int* sync; int target;
+    const float* pivot;              // row 0 of y when the partials are sums about it, else NULL
 };
 __global__ __launch_bounds__(kApplyThreads) void bn_finalize_apply_kernel(
     const BnFinArgs f, const float* __restrict__ y, float* __restrict__ stats,
@@ -355,7 +372,7 @@ __global__ __launch_bounds__(kApplyThreads) void bn_finalize_apply_kernel(
     for (int base = blockIdx.x * 4; base < C; base += gridDim.x * 4) {       // block-uniform trips
         const int c = base + (threadIdx.x >> 8);
         fwd_finalize_channel<true>(f.partial, f.nblk, f.M, C, c, f.gamma, f.beta, f.running_mean,
-                                   f.running_var, f.nbt, f.momentum, f.eps, stats);
+                                   f.running_var, f.nbt, f.momentum, f.eps, stats, f.pivot, 0);
         if ((threadIdx.x & 255) == 0 && c < C) publish_channel(f.sync, c);
     }
     const int cq = C >> 2;
@@ -988,6 +1005,8 @@ __global__ __launch_bounds__(256) void bn16_colreduce_kernel(
         mhi = *reinterpret_cast<const f32x4*>(stats + c0 + q * 8 + 4);
         rlo = *reinterpret_cast<const f32x4*>(stats + C + c0 + q * 8);
         rhi = *reinterpret_cast<const f32x4*>(stats + C + c0 + q * 8 + 4);
+    } else {
+        cvt8(*reinterpret_cast<const bf16x8*>(y + c0 + q * 8), mlo, mhi);   // the pivot: row 0
     }
     f32x4 a1lo[2], a1hi[2], a2lo[2], a2hi[2];
 #pragma unroll
@@ -997,8 +1016,9 @@ __global__ __launch_bounds__(256) void bn16_colreduce_kernel(
         f32x4 vlo, vhi;
         cvt8(*reinterpret_cast<const bf16x8*>(y + o), vlo, vhi);
         if (MODE == 0) {
-            a1lo[u] += vlo; a1hi[u] += vhi;
-            a2lo[u] += vlo * vlo; a2hi[u] += vhi * vhi;
+            const f32x4 dlo = vlo - mlo, dhi = vhi - mhi;
+            a1lo[u] += dlo; a1hi[u] += dhi;
+            a2lo[u] += dlo * dlo; a2hi[u] += dhi * dhi;
         } else {
             f32x4 glo, ghi;
             cvt8(*reinterpret_cast<const bf16x8*>(dz + o), glo, ghi);
@@ -1216,8 +1236,10 @@ int launch_bn_train_fwd(const float* y, int M, int C, const float* gamma, const 
                         float* z, int pre_nblk, hipStream_t s, void* z16, BnSync* sync) {
     if (check_c(C)) return 1;
     int nblk = pre_nblk;
+    const float* pivot = nullptr;      // partials from a convolution epilogue: sums of y, y*y
     if (nblk <= 0) {
         const ColPlan p = col_plan(M, C);
+        pivot = y;
         bn_colreduce_kernel<0><<<dim3(p.nblk, col_groups(C)), 256, 0, s>>>(y, nullptr, nullptr, nullptr, partial, M, C,
                                                       0, p.rows_per_block);
         CILRS_LAUNCH_CHECK();
@@ -1227,7 +1249,7 @@ int launch_bn_train_fwd(const float* y, int M, int C, const float* gamma, const 
         const size_t total4 = (size_t)M * C / 4;
         sync->total = (int)((unsigned)sync->total + (unsigned)(C / 8));
         const BnFinArgs f{partial, nblk, M, gamma, beta, running_mean, running_var, nbt, momentum, eps,
-                          sync->dev, sync->total};
+                          sync->dev, sync->total, pivot};
         bn_finalize_apply_kernel<<<grid_for(total4, kApplyThreads, apply_grid_cap()), kApplyThreads, 0, s>>>(
             f, y, stats, residual, z, total4, C, relu, reinterpret_cast<__bf16*>(z16));
         CILRS_LAUNCH_CHECK();
@@ -1235,7 +1257,7 @@ int launch_bn_train_fwd(const float* y, int M, int C, const float* gamma, const 
     }
     bn_fwd_finalize_kernel<<<C, kFinThreads, 0, s>>>(partial, nblk, M, C, gamma, beta,
                                                         running_mean, running_var, nbt, momentum,
-                                                        eps, stats);
+                                                        eps, stats, pivot, 0);
     CILRS_LAUNCH_CHECK();
     if (z) {
         const size_t total4 = (size_t)M * C / 4;
@@ -1433,15 +1455,17 @@ int launch_bn16_train_fwd(const void* y16, int M, int C, const float* gamma, con
     if (check_c16(C)) return 1;
     const __bf16* y = reinterpret_cast<const __bf16*>(y16);
     int nblk = pre_nblk;
+    const __bf16* pivot = nullptr;     // partials from a convolution epilogue: sums of y, y*y
     if (nblk <= 0) {
         const ColPlan p = col_plan16(M, C);
+        pivot = y;
         bn16_colreduce_kernel<0><<<dim3(p.nblk, C > 2048 ? C / 2048 : 1), 256, 0, s>>>(
             y, nullptr, nullptr, nullptr, partial, M, C, 0, p.rows_per_block);
         CILRS_LAUNCH_CHECK();
         nblk = p.nblk;
     }
     bn_fwd_finalize_kernel<<<C, kFinThreads, 0, s>>>(partial, nblk, M, C, gamma, beta, running_mean,
-                                                     running_var, nbt, momentum, eps, stats);
+                                                     running_var, nbt, momentum, eps, stats, pivot, 1);
     CILRS_LAUNCH_CHECK();
     if (z16) {
         const size_t total8 = (size_t)M * C / 8;
