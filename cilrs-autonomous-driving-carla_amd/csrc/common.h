@@ -61,7 +61,7 @@ constexpr float kImageStd[3] = {0.229f, 0.224f, 0.225f};
 // are COMPILED OUT of the product library: experiment_env() is the constant default unless the
 // library is built with -DCILRS_EXPERIMENTS (make CXXEXTRA=-DCILRS_EXPERIMENTS; tools/README.md).
 // Switches a test exercises (CILRS_WINO, CILRS_WINO_TAIL, CILRS_WINO_WGRAD, CILRS_OVERLAP,
-// CILRS_BN_FUSED, CILRS_SPLITK_INKERNEL, CILRS_CONV16_TILE, CILRS_B1_STAMPS) stay run-time.
+// CILRS_CONV16_TILE, CILRS_B1_STAMPS) stay run-time.
 #ifdef CILRS_EXPERIMENTS
 int experiment_env(const char* name, int dflt);
 #else
@@ -119,8 +119,6 @@ struct ConvArgs {
     // fused into the epilogue: per M-tile [2][Cout] partial sums of g and g*xhat
     const float* bwd_z; const float* bwd_y; const float* bwd_stats; int bwd_relu;
     float* bwd_partial; int* bwd_nblk;     // host out: tiles written (0 = not fused)
-    int* tile_counters;    // optional: zeroed ticket counters (one per output tile) for the
-    int tile_counters_cap; //   in-kernel split-K reduction; NULL => carved from `scratch`
     float* scratch;        // optional split-K scratch (>= 2*M*y_ld floats to be considered)
     size_t scratch_floats;
     int force_cfg;         // -1 auto; 0/1/2: 128x128, 128x64, 64x64 register-staged; 3/4/5: the
@@ -145,7 +143,6 @@ struct DgradArgs {
     int N, H, W, Cin, Ho, Wo, Cout, K, stride, pad;
     int dy_ld, dx_ld;
     float* scratch; size_t scratch_floats; int force_cfg, force_splitk;
-    int* tile_counters; int tile_counters_cap;     // see ConvArgs
     const float* bwd_z; const float* bwd_y; const float* bwd_stats; int bwd_relu;
     float* bwd_partial; int* bwd_nblk;
 };
@@ -204,19 +201,11 @@ int launch_conv_wgrad(const WgradArgs& a, hipStream_t s);
 // ---- BatchNorm / pooling (bn_pool.hip) --------------------------------------------------------
 // stats: 4*C floats (mean | rstd | w | b); coef: 3*C floats; partial: bn_partial_floats(C) floats
 size_t bn_partial_floats(int C);
-// counters of the finalize-inside-apply launches: 8 shards x 32 ints of device memory, zero when
-// `total` is zero; the launchers advance `total` (cumulative arrivals per shard) -- one object per
-// stream of BatchNorm launches, never shared between two launches that may overlap
-struct BnSync { int* dev; int total; };
-constexpr int kBnSyncInts = 8 * 32;
 // pre_nblk > 0: `partial` already holds pre_nblk per-tile partial sums (fused into the conv)
 int launch_bn_train_fwd(const float* y, int M, int C, const float* gamma, const float* beta,
                         float* running_mean, float* running_var, long long* nbt, float momentum,
                         float eps, const float* residual, int relu, float* stats, float* partial,
-                        float* z, int pre_nblk, hipStream_t s, void* z16 = nullptr,
-                        BnSync* sync = nullptr);
-// (sync != NULL: the per-channel finalize runs inside the apply launch instead of a launch of its
-//  own -- bn_pool.hip, "finalize inside the apply launch")
+                        float* z, int pre_nblk, hipStream_t s, void* z16 = nullptr);
 // (z16 / dy16 / out16: optional bf16 shadow of the fp32 result -- the 16-bit operand of the next
 //  convolution in the bf16 training mode; launch_bn_bwd: dy may then be NULL)
 // eval-mode scale/shift of up to kMaxConvs BatchNorm layers in one launch (offsets in floats);
@@ -238,8 +227,7 @@ int launch_bn_eval_fwd(const float* y, int M, int C, const float* gamma, const f
 int launch_bn_bwd(const float* dz, const float* z, const float* y, int M, int C,
                   const float* gamma, const float* stats, int relu, float* dgamma, float* dbeta,
                   int accumulate, float* coef, float* partial, float* dy, float* g_out,
-                  int pre_nblk, hipStream_t s, void* dy16 = nullptr, BnSync* sync = nullptr,
-                  int frozen = 0);
+                  int pre_nblk, hipStream_t s, void* dy16 = nullptr, int frozen = 0);
 // frozen != 0 (launch_bn_bwd, launch_bn_bwd_pool): BatchNorm with FIXED statistics (eval mode,
 // `stats` from the running buffers): dy = gamma * rstd * g -- the batch-statistics terms vanish --
 // while dgamma = sum g * xhat and dbeta = sum g come from the same column reductions

@@ -40,7 +40,6 @@ namespace {
 
 constexpr int BK = 32;
 constexpr int APITCH = BK + 4;
-constexpr int kSplitKInKernelDefault = 0;      // see launch_conv_igemm
 
 __device__ float g_zero_page[64];   // zero-initialised; target of out-of-image gathers
 
@@ -464,72 +463,9 @@ void conv_igemm_kernel(const ConvArgs a, const int M_, const int Krow, const int
     }
     }
 
-    // ---- split-K: every K-slice block parks its partial tile in a slab; the block that draws the
-    // last ticket of the tile sums the slabs in slice order (deterministic) and runs the epilogue.
-    // Hand-off WITHOUT release / acquire fences (cdna guide G16, "every load sc1" form; the same
-    // protocol as csrc/infer_b1.hip): slab stores are write-through (`sc1`: a whole 128-B line per
-    // wave instruction), every storing wave drains them, a workgroup barrier, ONE relaxed
-    // agent-scope ticket add whose returned value tells the last arriver, which then reads every
-    // slab with `sc1` loads.  (Round 1's version fenced -- an agent release per block writes back
-    // the XCD's whole L2, ~20 MB of dirty output here -- and lost to a separate reduce launch.)
-    bool inkernel_reduce = false;
-    if (a.splitk > 1 && a.tile_counters != nullptr) {
-        inkernel_reduce = true;
-        float* slab = a.scratch + (size_t)blockIdx.z * M * a.y_ld;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int co = n0 + wn * WTN + j * 32 + l31;
-                const int mbase = m0 + wm * WTM + i * 32 + 4 * lh;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = mbase + (r & 3) + 8 * (r >> 2);
-                    if (m < M)
-                        __hip_atomic_store(&slab[(size_t)m * a.y_ld + co], acc[i][j][r],
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        volatile int* flag = reinterpret_cast<volatile int*>(smem);
-        if (tid == 0) {
-            const int prev = __hip_atomic_fetch_add(&a.tile_counters[logical], 1, __ATOMIC_RELAXED,
-                                                    __HIP_MEMORY_SCOPE_AGENT);
-            const int last = (prev == a.splitk - 1) ? 1 : 0;
-            if (last)       // leave the counter ready for the next launch; nobody else touches it
-                __hip_atomic_store(&a.tile_counters[logical], 0, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-            flag[0] = last;
-        }
-        __syncthreads();
-        const int is_last = flag[0];
-        __syncthreads();                         // flag word is reused as scratch below
-        if (!is_last) return;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int co = n0 + wn * WTN + j * 32 + l31;
-                const int mbase = m0 + wm * WTM + i * 32 + 4 * lh;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-                for (int z = 0; z < a.splitk; ++z) {
-                    const float* sl = a.scratch + (size_t)z * M * a.y_ld;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int m = mbase + (r & 3) + 8 * (r >> 2);
-                        if (m < M)
-                            acc[i][j][r] += __hip_atomic_load(&sl[(size_t)m * a.y_ld + co],
-                                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-            }
-    }
-
     // ---- fused BatchNorm statistics: per-channel sum / sum of squares of this M-tile's rows
     // (rows >= M are exact zeros).  Fixed summation order => deterministic.
-    if (a.bn_partial != nullptr && (a.splitk <= 1 || inkernel_reduce)) {
+    if (a.bn_partial != nullptr && a.splitk <= 1) {
         float* red = smem;                       // [WM][BN][2]; the K loop ended on a barrier
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
@@ -567,7 +503,7 @@ void conv_igemm_kernel(const ConvArgs a, const int M_, const int Krow, const int
     // ---- epilogue: C/D map of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
     // Optional operands are fetched as 16 independent loads per tile (clamped row, no per-element
     // branch) so their latency overlaps instead of serialising.
-    const bool partial = a.splitk > 1 && !inkernel_reduce;
+    const bool partial = a.splitk > 1;
     const bool dense = (a.out_sh == 1) && (a.out_sw == 1) && (a.out_H == P_Ho) &&
                        (a.out_W == P_Wo);
     float* yout = partial ? a.y + (size_t)blockIdx.z * M * a.y_ld : a.y;
@@ -1034,37 +970,11 @@ int launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     CILRS_CHECK(ch.cfg >= 0 && ch.cfg < kNumCfg && a.Cout % kCfg[ch.cfg].bn == 0,
                 "conv_igemm: tile config %d does not fit Cout=%d", ch.cfg, a.Cout);
     a.splitk = ch.splitk;
-    // in-kernel reduction needs one ticket counter per output tile (zero before the launch; the
-    // last arriver re-zeroes it).  Counters live at the head of the scratch unless given.
-    const int n_tiles = cdiv(M, kCfg[ch.cfg].bm) * (a.Cout / kCfg[ch.cfg].bn);
-    // Round 1 measured the FENCED in-kernel combine slower than a separate reduce launch (train
-    // step +9 %); the fence-free form (sc1 slabs + ticket) is A/B'd with CILRS_SPLITK_INKERNEL=0|1
-    // (profiles/r03_splitk_ab.log).
-    static const int inkernel_on =
-        getenv("CILRS_SPLITK_INKERNEL") ? atoi(getenv("CILRS_SPLITK_INKERNEL")) : kSplitKInKernelDefault;
-    bool inkernel = false;
-    if (!inkernel_on) a.tile_counters = nullptr;
-    if (a.splitk > 1 && inkernel_on) {
-        if (a.tile_counters == nullptr) {
-            // carve [counters | slabs] out of the caller's scratch and zero the counters
-            const size_t cnt_floats = ((size_t)n_tiles + 63) / 64 * 64;
-            if (a.scratch_floats >= cnt_floats + (size_t)a.splitk * slab) {
-                a.tile_counters = reinterpret_cast<int*>(a.scratch);
-                CILRS_HIP(hipMemsetAsync(a.tile_counters, 0, cnt_floats * sizeof(float), s));
-                a.scratch += cnt_floats;
-                a.scratch_floats -= cnt_floats;
-                inkernel = true;
-            }
-        } else {
-            inkernel = n_tiles <= a.tile_counters_cap;
-            if (!inkernel) a.tile_counters = nullptr;
-        }
-    }
     const bool dense_out = a.out_sh == 1 && a.out_sw == 1 && a.out_H == a.Ho && a.out_W == a.Wo;
     // split-K + separate reduce: the reduce kernel can emit the BatchNorm column partials itself
     // when the output is dense and the channel count tiles a 256-thread block
     const int tpr = a.Cout >> 2;
-    const bool cols_ok = a.splitk > 1 && !inkernel && dense_out && a.Cout % 4 == 0 && tpr <= 256 &&
+    const bool cols_ok = a.splitk > 1 && dense_out && a.Cout % 4 == 0 && tpr <= 256 &&
                          256 % tpr == 0 && a.y_ld % 4 == 0 && (!a.mask || a.mask_ld % 4 == 0);
     int cols_rows = 0, cols_nblk = 0;
     if (cols_ok && (a.bn_partial || a.bwd_partial)) {
@@ -1076,12 +986,12 @@ int launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     float* const bwd_partial = a.bwd_partial;
     if (a_in.bn_nblk)
         *a_in.bn_nblk = !a.bn_partial ? 0
-                        : (a.splitk == 1 || inkernel) ? cdiv(M, kCfg[ch.cfg].bm) : cols_nblk;
+                        : a.splitk == 1 ? cdiv(M, kCfg[ch.cfg].bm) : cols_nblk;
     if (!(a.splitk == 1 && dense_out)) a.bwd_partial = nullptr;
     if (a_in.bwd_nblk)
         *a_in.bwd_nblk = a.bwd_partial ? cdiv(M, kCfg[ch.cfg].bm) : (bwd_partial ? cols_nblk : 0);
     float* final_y = a.y;
-    if (a.splitk > 1 && !inkernel) a.y = a.scratch;      // legacy: partials + separate reduce
+    if (a.splitk > 1) a.y = a.scratch;      // partials, summed by the reduce launch below
 
     int rc = 1;
 #define CILRS_DISPATCH(BM_, BN_, DMA_)                                                          \
@@ -1101,7 +1011,7 @@ int launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
 #undef CILRS_DISPATCH
     if (rc) return rc;
 
-    if (a.splitk > 1 && !inkernel) {
+    if (a.splitk > 1) {
         const float* part = a.scratch;
         a.y = final_y;
         const size_t total4 = (size_t)M * (a.Cout / 4);
@@ -1163,7 +1073,6 @@ int launch_conv_dgrad(const DgradArgs& d, hipStream_t s) {
     a.x_ld = d.dy_ld; a.y_ld = d.dx_ld; a.w_mode = 1; a.w_cin = d.Cin;
     a.scratch = d.scratch; a.scratch_floats = d.scratch_floats;
     a.force_cfg = d.force_cfg; a.force_splitk = d.force_splitk;
-    a.tile_counters = d.tile_counters; a.tile_counters_cap = d.tile_counters_cap;
     if (d.bwd_nblk) *d.bwd_nblk = 0;
     if (d.stride == 1) {
         a.bwd_z = d.bwd_z; a.bwd_y = d.bwd_y; a.bwd_stats = d.bwd_stats; a.bwd_relu = d.bwd_relu;
@@ -1189,7 +1098,7 @@ int launch_conv_dgrad(const DgradArgs& d, hipStream_t s) {
         c.stride = 1; c.pad = 0;
         c.out_H = d.H; c.out_W = d.W; c.out_sh = 2; c.out_sw = 2; c.out_h0 = c.out_w0 = 0;
         c.Ho = (d.H + 1) / 2; c.Wo = (d.W + 1) / 2;          // class (0,0): never empty
-        c.splitk = 1; c.scratch = nullptr; c.tile_counters = nullptr;
+        c.splitk = 1; c.scratch = nullptr;
         c.prio_mode = wave_priority_mode();
         struct Cls { int ph, pw, nt, Ho, Wo; int dh[4], dw[4], tw[4]; } cl[4];
         int ncl = 0;

@@ -284,7 +284,6 @@ using namespace cilrs;
 // The plan
 // ------------------------------------------------------------------------------------------------
 struct ConvG { int H, W, Ho, Wo, M; size_t y, z, stats; };
-constexpr int kTileCounters = 16384;
 // The frozen prefix of a fine-tuning step sends the layers the train plan gives to the Winograd
 // kernel through its folded-epilogue variant (conv_wino.hip FOLD) instead of the implicit GEMM
 // (DESIGN.md "Fine-tuning" has the per-shape measurement; CILRS_FT_WINO=0 of an experiments
@@ -293,17 +292,11 @@ constexpr int kTileCounters = 16384;
 static bool ft_wino_fold() { return experiment_env("CILRS_FT_WINO", 1) != 0; }
 
 // dy ring: bn_bwd writes each conv's output gradient into the next ring slot; the weight-gradient
-// GEMM that consumes it runs on side stream 0 and may lag the data-gradient chain by up to
-// depth - 1 convolutions.  Measured on MI355X (tools/overlap_sweep.sh): depth 2/4/8 all give
-// 14.58-14.65 ms/step, and a LOW-PRIORITY side stream (CILRS_SIDE_PRIO=1) starves the weight
-// gradients outright (25.3 ms/step) -- so the defaults are depth 2, default priority.
-constexpr int kDyRing = 8;
-constexpr int kNumG = 5 + kDyRing - 2;
-constexpr int kRingIdx[kDyRing] = {0, 4, 5, 6, 7, 8, 9, 10};
-static int dy_ring_depth() {
-    static const int d = experiment_env("CILRS_DY_RING", 2);
-    return d < 2 ? 2 : d > kDyRing ? kDyRing : d;
-}
+// GEMM that consumes it runs on side stream 0 and may lag the data-gradient chain by one
+// convolution (deeper rings were measured and bought nothing: DESIGN.md section 3).
+constexpr int kDyRing = 2;
+constexpr int kNumG = 5;
+constexpr int kRingIdx[kDyRing] = {0, 4};
 
 struct cilrs_net {
     const Arch* A = nullptr;               // architecture variant of this plan
@@ -316,11 +309,8 @@ struct cilrs_net {
     size_t x4, w4, pool, argmax_b /*bytes offset*/, combined, s1, p1, p2, h1[kMaxCmd], h2[kMaxCmd], all_out;
     size_t dcombined, ds1, dp1, dp2, dh1[kMaxCmd], dh2[kMaxCmd], dcomb_part[kMaxCmd + 1], d_all, speed_in,
         cmd_b /*bytes offset*/;
-    size_t tile_cnt;                       // split-K ticket counters (ints), then 2 x kBnSyncInts ints:
-                                           // forward / backward finalize-in-apply counters
-    BnSync bn_sync[2] = {{nullptr, 0}, {nullptr, 0}};
-    const void* cnt_zeroed_for = nullptr;  // workspace whose counters have been zeroed
-    size_t G[kNumG];                       // gradient buffers: [1..3] fixed roles, the rest = dy ring
+    const void* status_cleared_for = nullptr;   // workspace whose status words have been cleared
+    size_t G[kNumG];                       // gradient buffers: [1..3] fixed roles, [0] and [4] = dy ring
     size_t gmax;
     size_t bn_partial, bn_partial2, bn_coef, slabs, slabs_floats, ksplit, ksplit_floats, status_b;
     size_t ws_bytes;
@@ -432,28 +422,12 @@ struct Bump {
         }                                                                             \
     } while (0)
 
-static BnSync* bn_sync(cilrs_net* net, float* ws, int bwd);
-// split-K ticket counters start at zero; every reducer block re-zeroes its own afterwards
-// counters of the finalize-inside-apply BatchNorm launches (bn_pool.hip).  OFF by default: measured
-// at B=128 the in-launch hand-off (partials -> coefficients -> sc1 publish -> counter -> poll ->
-// sc1 read: four memory-side round trips) costs MORE than the 5.4 us finalize launch + its gap --
-// BatchNorm 1.33 ms/step with the separate launches, 1.70 ms fused (profiles/r03_bn_fused.log).
-// CILRS_BN_FUSED=1 selects it (tests/test_model_gpu.py runs one step that way).
-static BnSync* bn_sync(cilrs_net* net, float* ws, int bwd) {
-    static const int on = getenv("CILRS_BN_FUSED") ? atoi(getenv("CILRS_BN_FUSED")) : 0;
-    if (!on) return nullptr;
-    net->bn_sync[bwd].dev = reinterpret_cast<int*>(ws + net->tile_cnt) + kTileCounters + kBnSyncInts * bwd;
-    return &net->bn_sync[bwd];
-}
-int zero_counters_once(cilrs_net* net, void* workspace, hipStream_t s) {
-    if (net->cnt_zeroed_for == workspace) return 0;
-    float* ws = reinterpret_cast<float*>(workspace);
-    CILRS_HIP(hipMemsetAsync(ws + net->tile_cnt, 0, (kTileCounters + 2 * kBnSyncInts) * sizeof(int), s));
-    // the int32[4] status words start at zero in every workspace (a C-ABI caller brings its own,
-    // uninitialised one); afterwards the kernels only ever SET them: "since the caller last cleared"
+// the int32[4] status words start at zero in every workspace (a C-ABI caller brings its own,
+// uninitialised one); afterwards the kernels only ever SET them: "since the caller last cleared"
+int clear_status_once(cilrs_net* net, void* workspace, hipStream_t s) {
+    if (net->status_cleared_for == workspace) return 0;
     CILRS_HIP(hipMemsetAsync(reinterpret_cast<char*>(workspace) + net->status_b, 0, 16, s));
-    net->bn_sync[0].total = net->bn_sync[1].total = 0;
-    net->cnt_zeroed_for = workspace;
+    net->status_cleared_for = workspace;
     return 0;
 }
 
@@ -470,26 +444,8 @@ unsigned stream_event_flags() {
 }
 int ensure_streams(cilrs_net* net) {
     if (net->streams_ready) return 0;
-    int prio_least = 0, prio_greatest = 0;
-    CILRS_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    // side stream 0 carries the weight-gradient GEMMs (CILRS_SIDE_PRIO=1: lowest priority -- an
-    // experiment that starves them, see kDyRing)
-    static const int side_prio = experiment_env("CILRS_SIDE_PRIO", 0);
-    // experiment (CILRS_SIDE_CUS=n, CILRS_SIDE_CU_MODE=0|1): confine the weight-gradient stream to n
-    // CUs (mode 0: CU ids 0..n-1; mode 1: ids with (id % 32) < n / 8, i.e. n / 8 per group of 32)
-    static const int side_cus = experiment_env("CILRS_SIDE_CUS", 0);
-    static const int side_cu_mode = experiment_env("CILRS_SIDE_CU_MODE", 0);
-    if (side_cus > 0) {
-        uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int id = 0; id < 256; ++id) {
-            const bool on = side_cu_mode == 0 ? id < side_cus : (id % 32) < side_cus / 8;
-            if (on) mask[id >> 5] |= 1u << (id & 31);
-        }
-        CILRS_HIP(hipExtStreamCreateWithCUMask(&net->side[0], 8, mask));
-    } else if (side_prio)
-        CILRS_HIP(hipStreamCreateWithPriority(&net->side[0], hipStreamNonBlocking, prio_least));
-    else
-        CILRS_HIP(hipStreamCreateWithFlags(&net->side[0], hipStreamNonBlocking));
+    // side stream 0 carries the weight-gradient GEMMs
+    CILRS_HIP(hipStreamCreateWithFlags(&net->side[0], hipStreamNonBlocking));
     for (int i = 0; i < kNumG; ++i)
         CILRS_HIP(hipEventCreateWithFlags(&net->gbuf_ev[i], stream_event_flags()));
     CILRS_HIP(hipEventCreateWithFlags(&net->fork_ev, stream_event_flags()));
@@ -593,8 +549,6 @@ int conv_fwd(cilrs_net* net, const ConvT& c, const ConvG& g, const float* x, int
     a.x_ld = x_cin; a.y_ld = c.cout; a.w_mode = 0; a.w_cin = x_cin;
     a.scratch = ws + net->ksplit; a.scratch_floats = net->ksplit_floats;
     if (net->side_branch) { a.scratch = nullptr; a.scratch_floats = 0; }     // (no split-K beside the main stream's)
-    a.tile_counters = reinterpret_cast<int*>(ws + net->tile_cnt);
-    a.tile_counters_cap = kTileCounters;
     a.force_cfg = -1;
     if (bn_nblk) {
         a.bn_partial = ws + (net->side_branch == 1 ? net->bn_partial2 : net->bn_partial);
@@ -657,8 +611,6 @@ int conv_dgrad(cilrs_net* net, const ConvT& c, const ConvG& g, const float* dy, 
     a.Ho = g.Ho; a.Wo = g.Wo; a.Cout = c.cout; a.K = c.k; a.stride = c.stride; a.pad = c.pad;
     a.dy_ld = c.cout; a.dx_ld = c.cin;
     a.scratch = ws + net->ksplit; a.scratch_floats = net->ksplit_floats;
-    a.tile_counters = reinterpret_cast<int*>(ws + net->tile_cnt);
-    a.tile_counters_cap = kTileCounters;
     a.force_cfg = -1;
     const double flops = 2.0 * g.M * c.cout * c.k * c.k * c.cin;
     const double bytes = 4.0 * ((double)net->B * g.H * g.W * c.cin + (double)g.M * c.cout +
@@ -918,7 +870,6 @@ int cilrs_net_create_ex(int variant, int batch, int height, int width, unsigned 
         n->H1 = out_dim(g.Ho, 3, 2, 1); n->W1 = out_dim(g.Wo, 3, 2, 1);
     }
     size_t gmax = (size_t)n->cg[0].M * 64;
-    size_t dymax = 0;
     size_t actmax = (size_t)B * n->H1 * n->W1 * 64;       // largest trunk tensor (elements)
     n->pool = bump.take((size_t)B * n->H1 * n->W1 * 64);
     const size_t argmax_floats = ((size_t)B * n->H1 * n->W1 * 64 + 3) / 4;
@@ -977,7 +928,6 @@ int cilrs_net_create_ex(int variant, int batch, int height, int width, unsigned 
             if (ci < 0) continue;
             const size_t o = (size_t)n->cg[ci].M * A.convs[ci].cout;
             if (o > gmax) gmax = o;
-            if (o > dymax) dymax = o;                                         // trunk dy tensors
         }
         h = oh; w = ow;
     }
@@ -1016,10 +966,9 @@ int cilrs_net_create_ex(int variant, int batch, int height, int width, unsigned 
         if (sf > slabs_max) slabs_max = sf;
     }
     (void)feat;
-    if (!trainable) { gmax = 4; dymax = 4; }
+    if (!trainable) gmax = 4;
     n->gmax = gmax;
-    for (int i = 0; i < 5; ++i) n->G[i] = bump.take(gmax);
-    for (int i = 5; i < kNumG; ++i) n->G[i] = bump.take(dymax);
+    for (int i = 0; i < kNumG; ++i) n->G[i] = bump.take(gmax);
     {
         size_t need = bn_partial_floats(512);
         if (trainable)
@@ -1045,7 +994,6 @@ int cilrs_net_create_ex(int variant, int batch, int height, int width, unsigned 
     n->ksplit_floats = ksplit_max;
     n->ksplit = bump.take(ksplit_max > 0 ? ksplit_max : 4);
     n->status_b = bump.take(64) * sizeof(float);
-    n->tile_cnt = bump.take(kTileCounters + 2 * kBnSyncInts);  // + the BatchNorm finalize counters
     CILRS_CHECK((int)A.convs.size() <= kMaxConvs, "too many convolutions for the BN tables");
     n->bn_table.n = (int)A.convs.size();
     for (size_t ci = 0; ci < A.convs.size(); ++ci) {
@@ -1346,7 +1294,7 @@ static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train,
                 launch_bn_train_fwd(ws + g.y, g.M, c.cout, P + b.gamma, P + b.beta, R + b.rm,
                                     R + b.rv, reinterpret_cast<long long*>(bufs->bn_nbt) + c.bn,
                                     mom, eps, residual, relu, ws + g.stats, partial,
-                                    ws + g.z, pre_nblk, st, nullptr, side_branch ? nullptr : bn_sync(net, ws, 0)));
+                                    ws + g.z, pre_nblk, st));
         } else {
             RUN(net, std::string("bn_fwd.") + kGroupName[c.group], 0.0, bytes, st,
                 launch_bn_eval_fwd(ws + g.y, g.M, c.cout, P + b.gamma, P + b.beta, R + b.rm,
@@ -1443,7 +1391,7 @@ static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train,
         // the side stream beside conv1 / bn1 / conv2, with column-partial scratch of its own
         // and no split-K scratch; the block's last BatchNorm -- which adds it -- waits for it.
         bool branch_pending = false;
-        const bool branch_aside = blk.down >= 0 && use_overlap(net) && bn_sync(net, ws, 0) == nullptr;
+        const bool branch_aside = blk.down >= 0 && use_overlap(net);
         auto down_branch = [&](hipStream_t st, bool aside) -> int {
             const ConvT& cd = A.convs[blk.down];
             const ConvG& gd = net->cg[blk.down];
@@ -1756,7 +1704,7 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
     net->ws_base = reinterpret_cast<float*>(bufs->workspace);
     CILRS_CHECK(!(frozen && (train || half || net->bf16_train)),
                 "frozen forward: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan rejects it)");
-    if (zero_counters_once(net, bufs->workspace, s)) return 1;
+    if (clear_status_once(net, bufs->workspace, s)) return 1;
     net->bwd_done = 0;
     if (train || frozen) net->ft_bn = net->ft_grad = 0;
     if (train) {
@@ -1822,7 +1770,7 @@ static int forward_ft_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const f
                               const int64_t* command, int k, uint64_t prefix_key, float dropout_p,
                               uint64_t seed, float* controls, float* pred_speed, hipStream_t s) {
     net->ws_base = reinterpret_cast<float*>(bufs->workspace);
-    if (zero_counters_once(net, bufs->workspace, s)) return 1;
+    if (clear_status_once(net, bufs->workspace, s)) return 1;
     net->bwd_done = 0;
     // the trainable weights / BatchNorm buffers are about to change: the cached eval state goes stale
     net->prep_key = 0; net->fold_key = 0;
@@ -2215,7 +2163,7 @@ static int b1_launch(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* f
         if (b1_build(net, blocks)) return 1;
         net->b1_blocks = blocks;
     }
-    if (zero_counters_once(net, bufs->workspace, s)) return 1;     // (also: status words of a fresh workspace)
+    if (clear_status_once(net, bufs->workspace, s)) return 1;
     if (eval_prep(net, bufs, s)) return 1;
     if (net->b1_ready_for != bufs->workspace) {
         CILRS_HIP(hipMemsetAsync(ws + net->b1_sync, 0, kB1SyncInts * sizeof(int), s));
@@ -2582,7 +2530,7 @@ static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float*
                                           P + b.gamma, ws + g.stats, relu, dgamma_of(b),
                                           dbeta_of(b), 0, ws + net->bn_coef, ws + net->bn_partial,
                                           Gf(gdy), gg >= 0 ? Gf(gg) : nullptr, pre_nblk, s, nullptr,
-                                          bn_sync(net, ws, 1), net->frozen_fwd ? 1 : 0));
+                                          net->frozen_fwd ? 1 : 0));
                     }
                     return 0;
                 };
@@ -2591,7 +2539,7 @@ static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float*
                     bi == 0 ? h16(ws, net->pool16) : z16_of(last_conv(A.blocks[bi - 1]));
                 auto next_ring = [&]() {
                     const int gi = kRingIdx[net->dy_pos];
-                    net->dy_pos = (net->dy_pos + 1) % dy_ring_depth();
+                    net->dy_pos = (net->dy_pos + 1) % kDyRing;
                     return gi;
                 };
                 // 1. out = relu(bn_last(y_last) + identity): masked grad -> [1], dy_last -> ga

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-label hipEvent times of the BatchNorm launches of a B=128 train step (the plan's own
-profile table): `CILRS_BN_FUSED=0 python tools/bn_profile.py` for the separate-finalize form."""
+profile table)."""
 import os
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,4 +29,4 @@ for k, r in sorted(t.items()):
     if k.startswith("bn_"):
         tot += r["ms"] / 5
         print(f"{k:20s} calls/step {r['calls'] // 5:3d}  us/call {r['ms'] / r['calls'] * 1e3:7.2f}")
-print(f"BatchNorm total {tot:.3f} ms/step  (CILRS_BN_FUSED={os.environ.get('CILRS_BN_FUSED', '0')})")
+print(f"BatchNorm total {tot:.3f} ms/step")
