@@ -168,6 +168,11 @@ SIGNATURES = {
     "cilrs_bn_bwd_pool_frozen": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "cilrs_saliency_map": (i32, [vp, C.c_long, C.c_long, C.c_long, C.c_long, i32, i32, i32,
                                  c_float_p, vp, vp, vp, vp]),
+    "cilrs_attr_samples": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, u64, vp, vp]),
+    "cilrs_attr_accumulate": (i32, [vp, C.c_long, C.c_long, C.c_long, C.c_long, i32, i32, i32, i32,
+                                    i32, vp, vp]),
+    "cilrs_attr_finalize": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, c_float_p, vp, vp, vp, vp]),
+    "cilrs_attr_finalize_threads": (i32, []),
     "cilrs_linear_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "cilrs_linear_bwd": (i32, [vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32,
                                vp]),

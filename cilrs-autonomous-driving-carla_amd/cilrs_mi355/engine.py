@@ -470,6 +470,76 @@ class Engine:
             L.ptr(peak), self._stream()))
         return heat, peak
 
+    # ---- SmoothGrad / integrated gradients (csrc/attribution.hip) ------------------------------
+    def _check_attr_frames(self, frames_u8, baseline_u8):
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.size(3) != 3 or \
+                not frames_u8.is_contiguous() or frames_u8.device != self.device:
+            raise RuntimeError(f"frames must be contiguous uint8 [B,H,W,3] on {self.device}")
+        if baseline_u8 is not None and (baseline_u8.dtype != torch.uint8 or
+                                        baseline_u8.shape != frames_u8.shape or
+                                        not baseline_u8.is_contiguous() or
+                                        baseline_u8.device != self.device):
+            raise RuntimeError(f"baseline must be contiguous uint8 {tuple(frames_u8.shape)} on "
+                               f"{self.device}")
+        return frames_u8.size(0), frames_u8.size(1), frames_u8.size(2)
+
+    def run_attr_samples(self, frames_u8, baseline_u8, mode, samples, s_begin, s_count, sigma255,
+                         seed, out=None):
+        """cilrs_attr_samples: samples [s_begin, s_begin + s_count) of `samples` per frame of
+        uint8 [B,H,W,3] -> float32 NCHW [B*s_count,3,H,W] (frame-major); fills and returns `out`."""
+        b, h, w = self._check_attr_frames(frames_u8, baseline_u8)
+        if out is None:
+            out = torch.empty(b * s_count, 3, h, w, dtype=torch.float32, device=self.device)
+        elif (out.dtype != torch.float32 or tuple(out.shape) != (b * s_count, 3, h, w) or
+              not out.is_contiguous() or out.device != self.device):
+            raise RuntimeError(f"samples must be contiguous float32 [{b * s_count},3,{h},{w}] on "
+                               f"{self.device}")
+        L.check(L.lib().cilrs_attr_samples(
+            L.ptr(frames_u8), L.ptr(baseline_u8), b, h, w, int(mode), int(samples), int(s_begin),
+            int(s_count), float(sigma255), int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(out),
+            self._stream()))
+        return out
+
+    def run_attr_accumulate(self, dimage, acc, s_count, first):
+        """cilrs_attr_accumulate: acc [B,3,H,W] (+)= the gradients [B*s_count,3,H,W] (any
+        strides) of each frame's samples in sample order; `first` starts the sum at zero."""
+        if acc.dtype != torch.float32 or acc.dim() != 4 or acc.size(1) != 3 or \
+                not acc.is_contiguous() or acc.device != self.device:
+            raise RuntimeError(f"acc must be contiguous float32 [B,3,H,W] on {self.device}")
+        b, _, h, w = acc.shape
+        if dimage.dtype != torch.float32 or tuple(dimage.shape) != (b * s_count, 3, h, w) or \
+                dimage.device != self.device:
+            raise RuntimeError(f"dimage must be float32 [{b * s_count},3,{h},{w}] on {self.device}")
+        L.check(L.lib().cilrs_attr_accumulate(
+            L.ptr(dimage), *dimage.stride(), b, int(s_count), h, w, 1 if first else 0, L.ptr(acc),
+            self._stream()))
+        return acc
+
+    def run_attr_finalize(self, acc, frames_u8, baseline_u8, mode, samples, chan_scale3=None,
+                          attr=None, signed_map=None, total=None):
+        """cilrs_attr_finalize over the gradient sum acc [B,3,H,W]: fills and returns attr
+        float32 [B,3,H,W]; signed_map [B,H,W] and total [B] are filled when given."""
+        if acc.dtype != torch.float32 or acc.dim() != 4 or acc.size(1) != 3 or \
+                not acc.is_contiguous() or acc.device != self.device:
+            raise RuntimeError(f"acc must be contiguous float32 [B,3,H,W] on {self.device}")
+        b, _, h, w = acc.shape
+        if frames_u8 is not None and self._check_attr_frames(frames_u8, baseline_u8) != (b, h, w):
+            raise RuntimeError(f"frames must be uint8 [{b},{h},{w},3]")
+        if attr is None:
+            attr = torch.empty(b, 3, h, w, dtype=torch.float32, device=self.device)
+        for t, shape in ((attr, (b, 3, h, w)), (signed_map, (b, h, w)), (total, (b,))):
+            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or
+                                  not t.is_contiguous() or t.device != self.device):
+                raise RuntimeError(f"attribution outputs must be contiguous float32 {shape} on "
+                                   f"{self.device}")
+        scale = None
+        if chan_scale3 is not None:
+            scale = (C.c_float * 3)(*[float(v) for v in chan_scale3])
+        L.check(L.lib().cilrs_attr_finalize(
+            L.ptr(acc), L.ptr(frames_u8), L.ptr(baseline_u8), b, h, w, int(mode), int(samples),
+            scale, L.ptr(attr), L.ptr(signed_map), L.ptr(total), self._stream()))
+        return attr
+
     def check_status(self):
         """Raise if the last forward saw an out-of-range command (one device->host read)."""
         if self.last_plan is not None:

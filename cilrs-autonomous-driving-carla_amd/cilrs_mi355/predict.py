@@ -431,6 +431,200 @@ class Predictor:
         out[:, 3] = o[3 * b:4 * b] * np.float32(SPEED_NORM_FACTOR)
         return out, o[5 * b:].reshape(b, h, w).copy(), o[4 * b:5 * b].copy()
 
+    # ---- SmoothGrad / integrated gradients --------------------------------------------------------
+    ATTRIBUTION_METHODS = {"smoothgrad": 0, "integrated": 1}      # CILRS_ATTR_* of the library
+    # samples per pass when `chunk` is None: min(samples, this).  Measured on an MI355X, one frame,
+    # 32 samples (tools/input_grad_bench.py --attribution): chunk 8 / 16 / 32
+    # = 8.7 / 5.9 / 4.2 ms per SmoothGrad call
+    ATTRIBUTION_CHUNK = 32
+
+    @classmethod
+    def _attribution_args(cls, method, samples, sigma, baseline, seed, chunk, frames_shape):
+        """Host-side check of attribution's own arguments (ValueError before any launch):
+        returns (mode, samples, sigma255, baseline uint8 array or None, seed, chunk)."""
+        if not isinstance(method, str) or method not in cls.ATTRIBUTION_METHODS:
+            raise ValueError(f"attribution: unknown method {method!r} (one of "
+                             f"{sorted(cls.ATTRIBUTION_METHODS)})")
+        mode = cls.ATTRIBUTION_METHODS[method]
+
+        def whole(v, name, least):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < least:
+                raise ValueError(f"attribution: {name} must be an integer >= {least}, got {v!r}")
+            return int(v)
+        samples = whole(samples, "samples", 1)
+        if samples >= 1 << 24:
+            raise ValueError("attribution: samples must stay below 2^24 (the midpoint rule's "
+                             "(s + 0.5) / S is evaluated in float32)")
+        try:
+            sigma = float(sigma)
+        except (TypeError, ValueError):
+            sigma = float("nan")
+        if not (np.isfinite(sigma) and sigma >= 0.0 and 255.0 * sigma <= 3e38):
+            raise ValueError("attribution: sigma (the noise's standard deviation as a fraction of "
+                             "the 8-bit range) must be finite and >= 0")
+        if baseline is not None:
+            if mode != cls.ATTRIBUTION_METHODS["integrated"]:
+                raise ValueError("attribution: a baseline belongs to method='integrated'")
+            baseline = np.asarray(baseline)
+            if baseline.dtype != np.uint8 or baseline.shape != tuple(frames_shape):
+                raise ValueError(f"attribution: baseline must be None (a black frame) or a uint8 "
+                                 f"array of the frames' shape {tuple(frames_shape)}")
+        seed = whole(seed, "seed", 0)
+        if seed >= 1 << 64:
+            raise ValueError("attribution: seed must fit 64 bits")
+        chunk = min(samples, cls.ATTRIBUTION_CHUNK) if chunk is None else \
+            min(samples, whole(chunk, "chunk", 1))
+        return mode, samples, 255.0 * sigma, baseline, seed, chunk
+
+    def _attribution_buffers(self, chunk):
+        """Pinned + device staging and the device tensors of one attribution call with `chunk`
+        samples per pass (cached)."""
+        att = getattr(self, "_att", None)
+        if att is not None and att["chunk"] == chunk and att["eng"] is self.eng:
+            return att
+        dev = self.eng.device
+        b, h, w = self.batch, self.frames_host.size(1), self.frames_host.size(2)
+        r = b * chunk
+        nfr = b * h * w * 3
+        # [frames | baseline | speed | d controls x r | d pred_speed x r | command]: one H2D copy
+        o_base = (nfr + 15) // 16 * 16
+        o_spd = o_base + o_base
+        o_dc = o_spd + 4 * b
+        o_ds = o_dc + 12 * r
+        o_cmd = (o_ds + 4 * r + 7) // 8 * 8
+        host = torch.zeros(o_cmd + 8 * b, dtype=torch.uint8).pin_memory()
+        dbuf = torch.zeros_like(host, device=dev)
+
+        def views(buf):
+            return (buf[:nfr].view(b, h, w, 3), buf[o_base:o_base + nfr].view(b, h, w, 3),
+                    buf[o_spd:o_dc].view(torch.float32),
+                    buf[o_dc:o_ds].view(torch.float32).view(r, 3),
+                    buf[o_ds:o_ds + 4 * r].view(torch.float32),
+                    buf[o_cmd:o_cmd + 8 * b].view(torch.int64))
+        # [controls | pred_speed | the same at the baseline | peak | total | heat | signed]: one D2H
+        n_out = b * 10 + 2 * b * h * w
+        out_dev = torch.empty(n_out, dtype=torch.float32, device=dev)
+        out_host = torch.zeros(n_out, dtype=torch.float32).pin_memory()
+        o_heat = 10 * b
+        att = dict(chunk=chunk, eng=self.eng, host=host, dev=dbuf,
+                   host_np=[v.numpy() for v in views(host)], dev_views=views(dbuf),
+                   out_dev=out_dev, out_host=out_host, out_np=out_host.numpy(),
+                   ctrl=out_dev[:3 * b].view(b, 3), spd=out_dev[3 * b:4 * b],
+                   bctrl=out_dev[4 * b:7 * b].view(b, 3), bspd=out_dev[7 * b:8 * b],
+                   peak=out_dev[8 * b:9 * b], total=out_dev[9 * b:10 * b],
+                   heat=out_dev[o_heat:o_heat + b * h * w].view(b, h, w),
+                   signed=out_dev[o_heat + b * h * w:].view(b, h, w),
+                   x=torch.empty(r, 3, h, w, dtype=torch.float32, device=dev),
+                   dimage=torch.empty(r, 3, h, w, dtype=torch.float32, device=dev),
+                   acc=torch.empty(b, 3, h, w, dtype=torch.float32, device=dev),
+                   attr=torch.empty(b, 3, h, w, dtype=torch.float32, device=dev))
+        self._att = att
+        return att
+
+    @torch.no_grad()
+    def attribution(self, frames_u8, speeds_kmh, commands, output="steer", method="smoothgrad",
+                    samples=32, sigma=0.15, baseline=None, seed=0, chunk=None):
+        """SmoothGrad or integrated gradients of one output: (out [B,4], heat [B,H,W] float32,
+        peak [B], info) -- out / heat / peak shaped as `saliency` returns them.
+
+        method="smoothgrad": the mean of saliency's gradient over `samples` noisy copies of each
+        frame, Gaussian noise of standard deviation `sigma` (a fraction of the 8-bit range) added
+        to the network input and drawn on the device from `seed`; heat is saliency's definition
+        applied to the mean gradient, so samples=1, sigma=0 is `saliency` itself.
+        method="integrated": the mean gradient over `samples` points of the straight path from
+        `baseline` (None: a black frame, or uint8 frames of the same shape) to the frame, midpoint
+        rule, times (frame - baseline) in the network's input units; heat = max over the colour
+        channels of |attribution| / peak.  info then also holds `signed` [B,H,W] (attributions
+        summed over the channels), `total` [B] (summed over the frame), `baseline_out` [B]
+        (w . outputs at the baseline) and `delta` [B] = total - (w . outputs - baseline_out),
+        the completeness gap (raw network outputs: pred_speed not multiplied by 90).
+        frames: uint8 [B,88,200,3] at the network resolution only.  `chunk` samples per frame go
+        through one forward / data-gradient pass of batch B * chunk on this predictor's stream;
+        nothing per sample touches the host, and the gradient sum is the same sequential
+        chain whatever `chunk` is.  The persistent single-frame state is not disturbed."""
+        wts = self._saliency_weights(output)                       # ValueError before any launch
+        frames = np.asarray(frames_u8)
+        h, w = self.frames_host.size(1), self.frames_host.size(2)
+        mode, samples, sigma255, baseline, seed, chunk = self._attribution_args(
+            method, samples, sigma, baseline, seed, chunk, frames.shape)
+        if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[0] != self.batch or \
+                frames.shape[3] not in (3, 4):
+            raise RuntimeError(f"attribution: frames must be uint8 [{self.batch},{h},{w},3]")
+        if frames.shape[1:] != (h, w, 3):
+            raise RuntimeError(f"attribution: frames must be at the network resolution "
+                               f"[{self.batch},{h},{w},3]; raw camera frames are not served (there "
+                               "is no stand-alone device resize to build the sample batch from) "
+                               "-- resize them first, or use saliency()")
+        cmds = self._check_commands(commands)
+        speeds = np.minimum(np.asarray(speeds_kmh, dtype=np.float64) / SPEED_NORM_FACTOR, 1.0)
+        if cmds.shape != (self.batch,) or speeds.shape != (self.batch,):
+            raise RuntimeError(f"attribution: {self.batch} speeds and commands expected")
+        if self.model.engine().train_precision != "fp32":
+            raise RuntimeError("attribution: fp32 plans only (the model's training plan is "
+                               f"{self.model.engine().train_precision}; the eval-mode graph it "
+                               "differentiates needs train_precision='fp32')")
+        if self.model.engine() is not self.eng:
+            self.__init__(self.model, self.batch, h, w, self.use_graph, self.half, self.persistent)
+        if self.model.training:
+            self.model.eval()
+        integrated = mode == self.ATTRIBUTION_METHODS["integrated"]
+        b = self.batch
+        att = self._attribution_buffers(chunk)
+        f_np, b_np, s_np, dc_np, ds_np, c_np = att["host_np"]
+        np.copyto(f_np, frames)
+        b_np[...] = 0 if baseline is None else baseline
+        s_np[...] = speeds
+        dc_np[...] = wts[:3]
+        ds_np[...] = wts[3]
+        c_np[...] = cmds
+        f_dev, b_dev, s_dev, dc_dev, ds_dev, c_dev = att["dev_views"]
+        base_dev = b_dev if baseline is not None else None         # NULL: a black frame
+        scale = [1.0 / (255.0 * sd) for sd in IMG_STD]
+        eng = self.eng
+
+        def per_sample(t, n):                                      # repeat_interleave, no sync
+            return t.view(b, 1).expand(b, n).reshape(-1)
+        self._order_after_weight_updates()
+        with torch.cuda.stream(self.stream):
+            att["dev"].copy_(att["host"], non_blocking=True)
+            eng.run_forward_frozen_u8(f_dev, s_dev, c_dev, out=(att["ctrl"], att["spd"]))
+            if integrated:
+                eng.run_forward_frozen_u8(b_dev, s_dev, c_dev, out=(att["bctrl"], att["bspd"]))
+            s_rep, c_rep = per_sample(s_dev, chunk), per_sample(c_dev, chunk)
+            for s0 in range(0, samples, chunk):
+                n = min(chunk, samples - s0)                       # a short last chunk: its own plan
+                if n != chunk:
+                    s_rep, c_rep = per_sample(s_dev, n), per_sample(c_dev, n)
+                x, dimg = att["x"][:b * n], att["dimage"][:b * n]
+                eng.run_attr_samples(f_dev, base_dev, mode, samples, s0, n, sigma255, seed, out=x)
+                _, _, pl = eng.run_forward_frozen(x, s_rep, c_rep)
+                eng.run_backward(pl, dc_dev[:b * n], ds_dev[:b * n], data_only=True, segments=(0, 6))
+                eng.run_input_grads(pl, dimg, None)
+                eng.run_attr_accumulate(dimg, att["acc"], n, first=s0 == 0)
+            if integrated:
+                eng.run_attr_finalize(att["acc"], f_dev, base_dev, mode, samples, scale,
+                                      attr=att["attr"], signed_map=att["signed"], total=att["total"])
+                eng.run_saliency_map(att["attr"], None, heat=att["heat"], peak=att["peak"])
+            else:
+                eng.run_attr_finalize(att["acc"], None, None, mode, samples, attr=att["attr"])
+                eng.run_saliency_map(att["attr"], scale, heat=att["heat"], peak=att["peak"])
+            att["out_host"].copy_(att["out_dev"], non_blocking=True)
+            self.stream.synchronize()
+        o = att["out_np"]
+        out = np.empty((b, 4), dtype=np.float32)
+        out[:, :3] = o[:3 * b].reshape(b, 3)
+        out[:, 3] = o[3 * b:4 * b] * np.float32(SPEED_NORM_FACTOR)
+        info = dict(method=method, samples=samples, chunk=chunk)
+        hw = b * h * w
+        if integrated:
+            w64 = wts.astype(np.float64)
+            f_x = o[:3 * b].reshape(b, 3).astype(np.float64) @ w64[:3] + o[3 * b:4 * b] * w64[3]
+            f_0 = o[4 * b:7 * b].reshape(b, 3).astype(np.float64) @ w64[:3] + o[7 * b:8 * b] * w64[3]
+            total = o[9 * b:10 * b].copy()
+            info.update(signed=o[10 * b + hw:].reshape(b, h, w).copy(), total=total,
+                        baseline_out=f_0, delta=total - (f_x - f_0))
+        return out, o[10 * b:10 * b + hw].reshape(b, h, w).copy(), o[8 * b:9 * b].copy(), info
+
     def predict_controls(self, image_rgb_u8, speed_kmh, command_idx):
         """Same return tuple as the reference's predict_controls (:918-920).  Frames that are not
         already 88x200x3 go through the fused resize (predict_camera)."""

@@ -267,6 +267,17 @@ int launch_maxpool_fwd(const float* x, float* out, unsigned char* argmax, int N,
 int launch_saliency_map(const float* dimage, long sn, long sc, long sh, long sw, int B, int H, int W,
                         const float* chan_scale3, float* heat, unsigned char* heat_u8, float* peak,
                         hipStream_t s);
+// attribution.hip: sample batch, gradient sum and final maps of SmoothGrad / integrated gradients
+// (see cilrs_attr_samples)
+int launch_attr_samples(const unsigned char* frames, const unsigned char* baseline, int B, int H,
+                        int W, int mode, int S, int s_begin, int s_count, float sigma255,
+                        unsigned long long seed, float* out, hipStream_t s);
+int launch_attr_accumulate(const float* dimage, long sn, long sc, long sh, long sw, int B,
+                           int s_count, int H, int W, int first, float* acc, hipStream_t s);
+int launch_attr_finalize(const float* acc, const unsigned char* frames, const unsigned char* baseline,
+                         int B, int H, int W, int mode, int S, const float* chan_scale3, float* attr,
+                         float* signed_map, float* total, hipStream_t s);
+int attr_finalize_threads();
 int launch_maxpool_bwd(const float* dout, const unsigned char* argmax, float* dx, int N, int H,
                        int W, int C, hipStream_t s);
 int launch_avgpool_fwd(const float* x, float* out, int N, int HW, int C, int out_ld,

@@ -3391,6 +3391,24 @@ int cilrs_saliency_map(const float* dimage, long sn, long sc, long sh, long sw, 
     return launch_saliency_map(dimage, sn, sc, sh, sw, B, H, W, chan_scale3, heat, heat_u8, peak,
                                reinterpret_cast<hipStream_t>(stream));
 }
+int cilrs_attr_samples(const uint8_t* frames_u8, const uint8_t* baseline_u8, int B, int H, int W,
+                       int mode, int S, int s_begin, int s_count, float sigma255, uint64_t seed,
+                       float* out, void* stream) {
+    return launch_attr_samples(frames_u8, baseline_u8, B, H, W, mode, S, s_begin, s_count, sigma255,
+                               seed, out, reinterpret_cast<hipStream_t>(stream));
+}
+int cilrs_attr_accumulate(const float* dimage, long sn, long sc, long sh, long sw, int B, int s_count,
+                          int H, int W, int first, float* acc, void* stream) {
+    return launch_attr_accumulate(dimage, sn, sc, sh, sw, B, s_count, H, W, first, acc,
+                                  reinterpret_cast<hipStream_t>(stream));
+}
+int cilrs_attr_finalize(const float* acc, const uint8_t* frames_u8, const uint8_t* baseline_u8, int B,
+                        int H, int W, int mode, int S, const float* chan_scale3, float* attr,
+                        float* signed_map, float* total, void* stream) {
+    return launch_attr_finalize(acc, frames_u8, baseline_u8, B, H, W, mode, S, chan_scale3, attr,
+                                signed_map, total, reinterpret_cast<hipStream_t>(stream));
+}
+int cilrs_attr_finalize_threads(void) { return attr_finalize_threads(); }
 int cilrs_maxpool_fwd(const float* x, float* out, uint8_t* argmax, int N, int H, int W, int C,
                       void* stream) {
     return launch_maxpool_fwd(x, out, argmax, N, H, W, C, reinterpret_cast<hipStream_t>(stream));

@@ -579,6 +579,48 @@ int cilrs_saliency_map(const float* dimage, long sn, long sc, long sh, long sw, 
                        const float* chan_scale3, float* heat, uint8_t* heat_u8, float* peak,
                        void* stream);
 
+/* SmoothGrad and integrated gradients around that pass (csrc/attribution.hip; Predictor.attribution
+ * drives them): S samples per frame go through cilrs_net_forward_frozen + cilrs_net_backward_data +
+ * cilrs_net_input_grads a chunk at a time, and these three launches keep every sample on the
+ * device.  Streaming kernels, no atomics, every sum in a fixed order, every float operation
+ * rounded once (no FMA contraction): each result is the torch fp32 expression bit for bit.
+ *
+ * cilrs_attr_samples: frames_u8 uint8 [B,H,W,3] -> out f32 contiguous NCHW [B*s_count,3,H,W];
+ *   row b*s_count + j is global sample s = s_begin + j of frame b (a frame's samples are adjacent).
+ *   With c the 8-bit value as a float and m, d the channel's mean / std:
+ *     CILRS_ATTR_SMOOTHGRAD   v = c + sigma255 * n   (no clipping, no rounding: the noise is on the
+ *       network input, not on the camera); n = sqrtf(-2 logf u1) * cosf(2 pi u2), u1 / u2 the
+ *       24-bit fields of splitmix64(seed + counter * 0xD1B54A32D192ED03) exactly as the GaussNoise
+ *       of cilrs_augment_u8 extracts them, counter = (b*S + s)*3HW + (y*W + x)*3 + k: keyed on the
+ *       global sample index, so a sample is the same whichever chunk produces it.
+ *     CILRS_ATTR_INTEGRATED   v = c0 + alpha_s * (c - c0), c0 the baseline_u8 pixel (NULL: 0, a
+ *       black frame), alpha_s = ((float)s + 0.5f) / (float)S  (midpoint rule).
+ *   out = (v / 255 - m) / d.  sigma255 = 0, or alpha = 1, is the preprocessing of
+ *   cilrs_net_forward_u8 bit for bit.  Refused: NULL tensors, S < 1, a chunk outside [0, S), a
+ *   negative or non-finite sigma255, 3*H*W*B*S >= 2^63.
+ * cilrs_attr_accumulate: dimage = logical f32 [B*s_count,3,H,W] with non-negative element strides
+ *   (what cilrs_net_input_grads wrote for the chunk), acc f32 contiguous [B,3,H,W].  Per element
+ *   a = first ? +0 : acc;  a = a + g_j for j = 0 .. s_count-1 in that order;  acc = a -- one
+ *   sequential chain, so any split of the S samples into chunks gives the same bits.
+ * cilrs_attr_finalize: invS = 1 / (float)S.
+ *     SMOOTHGRAD  attr = acc * invS   (chan_scale3, frames_u8, baseline_u8 unused, may be NULL)
+ *     INTEGRATED  attr_c = (acc_c * invS) * ((float)(c - c0) * chan_scale3[c]); chan_scale3 = three
+ *       HOST floats, 1 / (255 * std_c) for attributions in the network's input units
+ *   attr f32 [B,3,H,W]; signed_map (may be NULL) f32 [B,H,W] = (attr_0 + attr_1) + attr_2;
+ *   total (may be NULL) f32 [B] = the frame's sum of signed_map, one workgroup of
+ *   cilrs_attr_finalize_threads() threads per frame: per-thread chain, wave shuffles, LDS. */
+#define CILRS_ATTR_SMOOTHGRAD 0
+#define CILRS_ATTR_INTEGRATED 1
+int cilrs_attr_samples(const uint8_t* frames_u8, const uint8_t* baseline_u8, int B, int H, int W,
+                       int mode, int S, int s_begin, int s_count, float sigma255, uint64_t seed,
+                       float* out, void* stream);
+int cilrs_attr_accumulate(const float* dimage, long sn, long sc, long sh, long sw, int B, int s_count,
+                          int H, int W, int first, float* acc, void* stream);
+int cilrs_attr_finalize(const float* acc, const uint8_t* frames_u8, const uint8_t* baseline_u8, int B,
+                        int H, int W, int mode, int S, const float* chan_scale3, float* attr,
+                        float* signed_map, float* total, void* stream);
+int cilrs_attr_finalize_threads(void);
+
 /* The bf16 training mode's operators on 16-bit tensors (round 4: every trunk tensor after the stem
  * -- activations, raw convolution outputs, gradients -- is stored in bf16; fp32 accumulation,
  * statistics and coefficients).  No reference counterpart (the reference trains in fp32,

@@ -9,8 +9,12 @@
     read-back) beside Predictor.predict_batch of the same frame, as host wall-clock per call.
 Per item: (median, min, max) of --rounds rounds of --iters launches each, timed with device events
 after --warmup launches.  Prints one JSON line.
+--attribution runs, instead of all that, Predictor.attribution (SmoothGrad and integrated
+gradients, one frame, --samples samples) per candidate chunk against a Python loop of as many
+Predictor.saliency calls -- see attribution_bench.
 
     python tools/input_grad_bench.py [--batch 128] [--height 88] [--width 200] [--profile]
+    python tools/input_grad_bench.py --attribution [--samples 32]
 """
 import argparse
 import ctypes as C
@@ -57,8 +61,63 @@ def wall_ms(fn, iters, rounds, warmup):
     return statistics.median(out), min(out), max(out)
 
 
+def attribution_bench(samples, rounds, reps):
+    """One 88x200 frame, `samples` samples: Predictor.attribution per candidate `chunk` beside the
+    documented workaround it replaces, a Python loop of `samples` Predictor.saliency calls.  Per
+    candidate the two are alternated for `rounds` rounds in this one process; a round times the
+    loop once and the mean of `reps` attribution calls (host wall-clock: both end in their own
+    stream synchronisation).  The batched call counts as faster only if it beats the loop by more
+    than the loop's own max - min over the rounds."""
+    import cilrs_oracle as O
+    from cilrs_mi355 import CILRS
+    from cilrs_mi355.predict import Predictor
+    m = CILRS(4, 0.0)
+    m.load_state_dict(O.portable_state_dict(m.state_dict(), 0))
+    m = m.cuda().eval().requires_grad_(False)
+    pr = Predictor(m)
+    frame = O.synthetic_batch(1, seed=4)[4]
+
+    def loop():
+        for _ in range(samples):
+            pr.saliency(frame, [30.0], [1])
+
+    def once(fn, n=1):
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        return (time.perf_counter() - t0) * 1e3 / n
+
+    res = {"samples": samples, "rounds": rounds, "reps": reps, "default_chunk": Predictor.ATTRIBUTION_CHUNK,
+           "chunks": {}}
+    for chunk in sorted({min(samples, c) for c in (8, 16, 32)}):
+        def smooth():
+            pr.attribution(frame, [30.0], [1], method="smoothgrad", samples=samples, chunk=chunk)
+
+        def integrated():
+            pr.attribution(frame, [30.0], [1], method="integrated", samples=samples, chunk=chunk)
+        for fn in (loop, smooth, integrated, loop, smooth, integrated):     # plans, code objects
+            fn()
+        row = {"saliency_loop_ms": [], "smoothgrad_ms": [], "integrated_ms": []}
+        for _ in range(rounds):
+            row["saliency_loop_ms"].append(once(loop))
+            row["smoothgrad_ms"].append(once(smooth, reps))
+            row["integrated_ms"].append(once(integrated, reps))
+        lp = row["saliency_loop_ms"]
+        spread = max(lp) - min(lp)
+        row["loop_spread_ms"] = spread
+        for k in ("smoothgrad_ms", "integrated_ms"):
+            row[k.replace("_ms", "_faster_beyond_spread")] = \
+                statistics.median(lp) - statistics.median(row[k]) > spread
+        res["chunks"][str(chunk)] = row
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--attribution", action="store_true",
+                    help="only: Predictor.attribution (one frame, --samples samples, chunk 8 / 16 / "
+                         "32) against a loop of Predictor.saliency calls, alternated, three rounds")
+    ap.add_argument("--samples", type=int, default=32)
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--height", type=int, default=88)
     ap.add_argument("--width", type=int, default=200)
@@ -68,6 +127,9 @@ def main():
     ap.add_argument("--profile", action="store_true",
                     help="per-label device times of one saliency pass (serialised launches)")
     a = ap.parse_args()
+    if a.attribution:
+        print(json.dumps(attribution_bench(a.samples, 3, 5)))
+        return
     import cilrs_oracle as O
     from cilrs_mi355 import CILRS, _lib as L
     lib = L.lib()
