@@ -91,6 +91,7 @@ SIGNATURES = {
     "cilrs_net_forward_u8_b1_post": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp, vp, vp, i32, vp]),
     "cilrs_net_forward_u8_b1_sync": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp, vp, vp]),
     "cilrs_net_b1_stages": (i32, [vp]),
+    "cilrs_net_b1_stage_info": (i32, [vp, i32] + [C.POINTER(i32)] * 8),
     "cilrs_net_b1_set_epoch": (i32, [vp, C.POINTER(Buffers), i32, vp]),
     "cilrs_net_wino_convs": (i32, [vp]),
     "cilrs_net_forward_ft": (i32, [vp, C.POINTER(Buffers), vp, C.c_long, C.c_long, C.c_long,

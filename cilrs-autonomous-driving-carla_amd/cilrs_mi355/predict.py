@@ -33,6 +33,9 @@ class _FastTick:
 # ticks served through the per-layer launches after a barrier timeout before the persistent launch
 # is tried again (10 s of a 20 Hz control loop)
 DEGRADED_TICKS = 200
+# what the library says when the persistent launch's planner has no tiling for a frame size (it
+# needs every stage in one pass of the resident grid); said before anything is launched
+PLANNER_REFUSALS = ("no one-pass tiling", "frame too large for", "division constants do not cover")
 
 
 class Predictor:
@@ -147,9 +150,17 @@ class Predictor:
                 self.stream.synchronize()
             else:
                 self.in_dev.copy_(self.in_host, non_blocking=True)
-                self.eng.run_forward_u8(self.frames_dev, self.speed_dev, self.cmd_dev,
-                                        out=(self.ctrl_dev, self.spd_out_dev), graph=self.use_graph,
-                                        half=self.half, persistent=self.persistent)
+                try:
+                    self.eng.run_forward_u8(self.frames_dev, self.speed_dev, self.cmd_dev,
+                                            out=(self.ctrl_dev, self.spd_out_dev),
+                                            graph=self.use_graph, half=self.half,
+                                            persistent=self.persistent)
+                except RuntimeError:
+                    if not (self.persistent and self._planner_refused()):
+                        raise
+                    self.eng.run_forward_u8(self.frames_dev, self.speed_dev, self.cmd_dev,
+                                            out=(self.ctrl_dev, self.spd_out_dev),
+                                            graph=self.use_graph, half=self.half, persistent=False)
                 self.out_host[:self.batch * 4].copy_(self.out_dev, non_blocking=True)   # pinned; no torch kernels
                 self.stream.synchronize()
         if self.persistent and not np.isfinite(self._ctrl_np).all():
@@ -193,6 +204,8 @@ class Predictor:
             self._seq = seq = (self._seq % 0x3FFFFFFF) + 1
             if fast.post_fn(fast.handle, fast.bufs, fast.frame, fast.speed, fast.cmd, fast.ctrl,
                             fast.spd, fast.done, seq, fast.stream) != 0:
+                if self._planner_refused():
+                    return self._tick_per_layer()
                 _L.check(1)
             done, n = self._done_np, 0
             while done[0] != seq:
@@ -202,6 +215,8 @@ class Predictor:
                     break
         elif fast.sync_fn(fast.handle, fast.bufs, fast.frame, fast.speed, fast.cmd, fast.ctrl,
                           fast.spd, fast.stream) != 0:
+            if self._planner_refused():
+                return self._tick_per_layer()
             _L.check(1)
         if self._inject_timeout > 0:      # test hook: what the kernel leaves behind on a timeout
             self._inject_timeout -= 1
@@ -215,6 +230,23 @@ class Predictor:
         out[:, :3] = self._ctrl_np
         out[:, 3] = self._spd_np * np.float32(SPEED_NORM_FACTOR)                # :920
         return out
+
+    def _planner_refused(self):
+        """A persistent call just failed.  If the library's planner said that it has no tiling
+        for this frame size (nothing was launched, the status words are untouched), that is
+        not an error of the frame either: this predictor serves every tick through the per-layer
+        launches from now on, reports ``persistent`` False, and says so once."""
+        msg = _L.lib().cilrs_last_error()
+        msg = msg.decode() if msg else ""
+        if not any(r in msg for r in PLANNER_REFUSALS):
+            return False
+        self.persistent = False
+        self._fast = None
+        import warnings
+        warnings.warn("CILRS Predictor: the persistent single-frame launch does not serve "
+                      f"{self.frames_host.size(1)}x{self.frames_host.size(2)} frames ({msg}); "
+                      "serving them through per-layer launches", RuntimeWarning)
+        return True
 
     def _barrier_gave_up(self, plan):
         """Non-finite outputs of the persistent launch.  If its status word says a grid barrier
@@ -301,15 +333,19 @@ class Predictor:
             pl = eng.plan(1, self.frames_host.size(1), self.frames_host.size(2))
             eng.last_plan = pl
             hs, ws_, px = frame.shape
-            _L.check(_L.lib().cilrs_net_forward_camera_b1(
-                pl.handle, _C.byref(pl.bufs), _L.ptr(cam[0]), hs, ws_, px, ws_ * px,
-                _L.ptr(cam[4][0]), _L.ptr(cam[4][1]), _L.ptr(self._ctrl_host),
-                _L.ptr(self._spd_host), 1, _C.c_void_p(self.stream.cuda_stream)))
-            if np.isfinite(self._ctrl_np).all() or not self._barrier_gave_up(pl):
+            refused = False
+            if _L.lib().cilrs_net_forward_camera_b1(
+                    pl.handle, _C.byref(pl.bufs), _L.ptr(cam[0]), hs, ws_, px, ws_ * px,
+                    _L.ptr(cam[4][0]), _L.ptr(cam[4][1]), _L.ptr(self._ctrl_host),
+                    _L.ptr(self._spd_host), 1, _C.c_void_p(self.stream.cuda_stream)) != 0:
+                refused = self._planner_refused()
+                if not refused:
+                    _L.check(1)
+            if not refused and (np.isfinite(self._ctrl_np).all() or not self._barrier_gave_up(pl)):
                 c = self._ctrl_np[0]
                 return (float(c[0]), float(c[1]), float(c[2]),
                         float(self._spd_np[0]) * SPEED_NORM_FACTOR)
-            # (barrier timeout: fall through to the per-layer camera path below)
+            # (barrier timeout, or no tiling for this size: the per-layer camera path below)
         self._order_after_weight_updates()
         with torch.cuda.stream(self.stream):
             cam[2][0].copy_(cam[0], non_blocking=True)               # frame | speed | command

@@ -473,7 +473,8 @@ struct B1Stage {
     unsigned src_off, dst_off; int pH, pW, pC, pHo, pWo;    // B1_PRE / B1_POOL geometry
     unsigned cmd_off;        // where stage 0 parks the command for the head stages (ws bytes)
     int same_shape;          // conv stage laid out exactly like the previous one (only bases differ)
-    int pad_[3];
+    int conv_no[2];          // host only (cilrs_net_b1_stage_info): the plan's numbers of c[0] / c[1]
+    int pad_;
 };
 constexpr int kB1MaxStages = 48;
 constexpr int kB1Tickets = 512;            // split-K arrival tickets (one per output tile of a stage)

@@ -843,7 +843,9 @@ int cilrs_net_create_ex(int variant, int batch, int height, int width, unsigned 
     CILRS_CHECK(out != nullptr, "cilrs_net_create: out is NULL");
     CILRS_CHECK((flags & ~1u) == 0, "cilrs_net_create: unknown flags 0x%x", flags);
     CILRS_CHECK(variant_ok(variant), "cilrs_net_create: variant %d out of range", variant);
-    CILRS_CHECK(batch >= 1 && height >= 32 && width >= 32, "cilrs_net_create: bad geometry %d %d %d",
+    // 17: every one of the five stride-2 steps (stem, max-pool, layer2-4) still reads a map of at
+    // least two rows and columns, as at 32 x 32 (17 -> 9 -> 5 -> 3 -> 2 -> 1)
+    CILRS_CHECK(batch >= 1 && height >= 17 && width >= 17, "cilrs_net_create: bad geometry %d %d %d",
                 batch, height, width);
     const Arch& A = arch(variant);
     const bool trainable = true;
@@ -2004,7 +2006,7 @@ static int b1_build(cilrs_net* net, int nblk) {
     // count half; 2 KB each at ~70 GB/s per CU: 35 per microsecond) + ~50 for a ticketed combine.
     constexpr int kB1MaxK = 8;
     bool plan_ok = true;
-    auto push_conv_stage = [&](int type, const B1Conv& c0, const B1Conv* c1) {
+    auto push_conv_stage = [&](int type, int n0, const B1Conv& c0, int n1, const B1Conv* c1) {
         B1Stage st;
         memset(&st, 0, sizeof(st));
         st.type = type;
@@ -2049,6 +2051,8 @@ static int b1_build(cilrs_net* net, int nblk) {
         st.c[0] = fin(c0, opts[b0], 0, net->b1_slabs);
         if (c1) st.c[1] = fin(*c1, opts[b1], c0.ntiles, net->b1_slabs + net->b1_slab_floats / 2);
         st.wpt = bw;
+        st.conv_no[0] = n0;
+        st.conv_no[1] = c1 ? n1 : -1;
         st.nunits0 = st.c[0].nunits;
         st.total_units = st.c[0].nunits + (c1 ? st.c[1].nunits : 0);
         // same lane-level plan as the previous stage?  (everything but the tensor bases, the
@@ -2081,7 +2085,7 @@ static int b1_build(cilrs_net* net, int nblk) {
         st.cmd_off = fb(net->b1_cmd);
         T.push_back(st);
     }
-    push_conv_stage(B1_STEM, conv_desc(0, net->x4, false, 0, 1, 0), nullptr);
+    push_conv_stage(B1_STEM, 0, conv_desc(0, net->x4, false, 0, 1, 0), -1, nullptr);
     {   // max-pool 3x3/s2/p1
         B1Stage st;
         memset(&st, 0, sizeof(st));
@@ -2099,13 +2103,13 @@ static int b1_build(cilrs_net* net, int nblk) {
         size_t identity = cur;
         if (blk.down >= 0) {
             const B1Conv cd = conv_desc(blk.down, cur, false, 0, 0, 0);
-            push_conv_stage(B1_CONV, c1, &cd);
+            push_conv_stage(B1_CONV, blk.conv1, c1, blk.down, &cd);
             identity = net->cg[blk.down].z;
         } else {
-            push_conv_stage(B1_CONV, c1, nullptr);
+            push_conv_stage(B1_CONV, blk.conv1, c1, -1, nullptr);
         }
-        push_conv_stage(B1_CONV, conv_desc(blk.conv2, net->cg[blk.conv1].z, true, identity, 0, 1),
-                        nullptr);
+        push_conv_stage(B1_CONV, blk.conv2,
+                        conv_desc(blk.conv2, net->cg[blk.conv1].z, true, identity, 0, 1), -1, nullptr);
         cur = net->cg[blk.conv2].z;
     }
     // heads: commanded branch (chain 0) and speed predictor (chain 1), layer by layer
@@ -2137,8 +2141,10 @@ static int b1_build(cilrs_net* net, int nblk) {
                     "infer_b1: head width");
         T.push_back(st);
     }
-    CILRS_CHECK(magic_ok, "infer_b1: division constants do not cover this geometry");
+    // (the tiling first: a stage without one keeps a placeholder whose unit counts may also be
+    // beyond the division constants, and the missing tiling is what the caller needs to hear)
     CILRS_CHECK(plan_ok, "infer_b1: no one-pass tiling of a stage on %d workgroups", nblk);
+    CILRS_CHECK(magic_ok, "infer_b1: division constants do not cover this geometry");
     CILRS_CHECK(A.convs[0].k == 7 && A.convs[0].pad == 3 && A.convs[0].stride == 2,
                 "infer_b1: stem geometry");
     CILRS_CHECK((int)T.size() <= kB1MaxStages, "infer_b1: %d stages", (int)T.size());
@@ -2296,6 +2302,28 @@ int cilrs_net_b1_stages(cilrs_net* net) {
     if (!net || net->b1_table == 0) return 0;
     if (net->b1_blocks < 0) return -1;             // not launched yet
     return (int)net->b1_host.size();
+}
+
+int cilrs_net_b1_stage_info(const cilrs_net* net, int stage, int* type, int* wpt, int* same_shape,
+                            int* workgroups, int* nconv, int* conv, int* ksplit, int* nt) {
+    CILRS_CHECK(net != nullptr, "b1_stage_info: net is NULL");
+    CILRS_CHECK(net->b1_table != 0 && net->b1_blocks > 0, "b1_stage_info: no persistent launch yet");
+    CILRS_CHECK(stage >= 0 && stage < (int)net->b1_host.size(), "b1_stage_info: stage %d out of range",
+                stage);
+    const B1Stage& st = net->b1_host[stage];
+    const bool is_conv = st.type == B1_CONV || st.type == B1_STEM;
+    const int n = !is_conv ? 0 : st.total_units != st.nunits0 ? 2 : 1;
+    if (type) *type = st.type;
+    if (wpt) *wpt = is_conv ? st.wpt : 0;
+    if (same_shape) *same_shape = st.same_shape;
+    if (workgroups) *workgroups = net->b1_blocks;
+    if (nconv) *nconv = n;
+    for (int i = 0; i < 2; ++i) {
+        if (conv) conv[i] = i < n ? st.conv_no[i] : -1;
+        if (ksplit) ksplit[i] = i < n ? st.c[i].ksplit : 0;
+        if (nt) nt[i] = i < n ? st.c[i].nt : 0;
+    }
+    return 0;
 }
 
 // Same as cilrs_net_forward_u8, replayed from a cached hipGraph (one launch per frame instead of

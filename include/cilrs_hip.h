@@ -84,7 +84,8 @@ typedef struct {
     void* workspace;        /* cilrs_net_workspace_bytes() bytes              */
 } cilrs_buffers;
 
-/* plan for a fixed batch / frame size (reference: B x 3 x 88 x 200) */
+/* plan for a fixed batch / frame size (reference: B x 3 x 88 x 200); height and width at least 17
+ * (smaller frames would leave a stride-2 step a one-pixel map to halve) */
 int cilrs_net_create(int batch, int height, int width, cilrs_net** out);
 int cilrs_net_create_variant(int variant, int batch, int height, int width, cilrs_net** out);
 /* The same with plan options.  CILRS_PLAN_BF16_TRAIN: "bf16 MFMA path" training (BASELINE.json
@@ -319,6 +320,16 @@ int cilrs_net_wino_convs(cilrs_net* net);
 /* number of stages (= grid barriers + 1) of that launch; -1 before the first call, 0 if the plan
  * has no persistent path */
 int cilrs_net_b1_stages(cilrs_net* net);
+/* test aid: how the planner tiled stage `stage` (0 .. cilrs_net_b1_stages - 1) of that launch, read
+ * from the host copy of the stage table.  type: 0 preprocess, 1 convolution, 2 stem, 3 max-pool,
+ * 4 head layer; workgroups: the resident grid the table was planned for.  Convolution and stem
+ * stages: wpt = waves per unit (2, 4, 8 or 16), same_shape = 1 if the stage reuses the previous
+ * stage's lane plan, nconv = 1 or 2 convolutions in the stage, and for each of them (arrays of two,
+ * unused entries -1 / 0) its number as in cilrs_net_activation_info, ksplit = workgroups per
+ * output tile and nt = channel tiles per unit.  Other stages: wpt 0, nconv 0.  Any pointer may be
+ * NULL.  Fails before the plan's first persistent launch. */
+int cilrs_net_b1_stage_info(const cilrs_net* net, int stage, int* type, int* wpt, int* same_shape,
+                            int* workgroups, int* nconv, int* conv, int* ksplit, int* nt);
 /* Re-base the launch's monotonic barrier counters (the eight arrival shards and the epoch word,
  * which are equal between launches) to `value`, after synchronising `stream`.  The counters are
  * compared wrap-safe (unsigned difference), so a long-running control loop never needs this; it
