@@ -67,6 +67,9 @@ SIGNATURES = {
     "cilrs_net_set_weights_key": (i32, [vp, u64]),
     "cilrs_net_activation_info": (i32, [vp, i32, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),
                                         C.POINTER(i32)]),
+    "cilrs_net_pool_argmax_info": (i32, [vp, C.POINTER(sz), C.POINTER(sz)]),
+    "cilrs_net_head_activation_info": (i32, [vp, i32, i32, C.POINTER(sz), C.POINTER(i32),
+                                             C.POINTER(i32), C.POINTER(i32)]),
     "cilrs_dropout": (i32, [vp, i32, i32, i32, f32, u64, i32, vp]),
     "cilrs_net_infer16_conv_info": (i32, [vp, i32, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),
                                           C.POINTER(i32), C.POINTER(i32)]),

@@ -1140,6 +1140,29 @@ int cilrs_net_activation_info(const cilrs_net* net, int conv, size_t* y_offset, 
     return 0;
 }
 
+int cilrs_net_pool_argmax_info(const cilrs_net* net, size_t* byte_offset, size_t* numel) {
+    CILRS_CHECK(net != nullptr, "pool_argmax_info: net is NULL");
+    if (byte_offset) *byte_offset = net->argmax_b;
+    if (numel) *numel = (size_t)net->B * net->H1 * net->W1 * 64;
+    return 0;
+}
+
+int cilrs_net_head_activation_info(const cilrs_net* net, int which, int branch, size_t* offset,
+                                   int* rows, int* cols, int* ld) {
+    CILRS_CHECK(net != nullptr, "head_activation_info: net is NULL");
+    CILRS_CHECK(which >= 0 && which <= 5, "head_activation_info: tensor %d out of range", which);
+    CILRS_CHECK(which < 4 || (branch >= 0 && branch < net->A->ncmd),
+                "head_activation_info: branch %d out of range", branch);
+    const int comb = net->A->feat + 128;
+    const size_t off[6] = {net->s1, net->combined + (size_t)net->A->feat, net->p1, net->p2,
+                           which == 4 ? net->h1[branch] : 0, which == 5 ? net->h2[branch] : 0};
+    if (offset) *offset = off[which];
+    if (rows) *rows = net->B;
+    if (cols) *cols = which < 2 ? 128 : 256;
+    if (ld) *ld = which == 1 ? comb : which == 0 ? 128 : 256;
+    return 0;
+}
+
 int cilrs_net_infer16_conv_info(const cilrs_net* net, int conv, size_t* w16_offset,
                                 size_t* bias_offset, size_t* w16_numel, int* channels,
                                 int* folded_half) {

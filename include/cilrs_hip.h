@@ -187,6 +187,22 @@ int cilrs_net_set_weights_key(cilrs_net* net, uint64_t key);
  * count the ReLU decisions on which the engine and the oracle differ. */
 int cilrs_net_activation_info(const cilrs_net* net, int conv, size_t* y_offset, size_t* z_offset,
                               size_t* numel, int* channels);
+/* The other decisions a graph-keeping forward (cilrs_net_forward with train != 0, _frozen, or _ft
+ * with no eval-mode prefix) left for the backward pass -- test aids like the one above: offsets,
+ * no launch, no state.  The mask-matched gradient tests hand them to the float64 oracle.
+ * cilrs_net_pool_argmax_info: BYTE offset and element count of the stem max-pool's argmax, uint8
+ * [B][Ho][Wo][64], value kh * 3 + kw of the window tap (input row 2 * oh - 1 + kh, column
+ * 2 * ow - 1 + kw) the window kept (the first of equal values, kh-major).  A forward with an
+ * eval-mode prefix (bn_frozen_groups > 0) does not write it.
+ * cilrs_net_head_activation_info: float offset, rows (= batch), columns and row pitch of a head
+ * activation the backward re-reads (post-ReLU, and post-dropout where a Dropout follows).  which:
+ * 0 s1 (speed_encoder.1 output, 128 wide); 1 the speed-feature columns of `combined`
+ * (speed_encoder.4 output, 128 wide, pitch features + 128); 2 p1, 3 p2 (speed_predictor.1 / .4);
+ * 4 h1[branch], 5 h2[branch] (control_branches.<branch>.1 / .4; branch < num_commands, ignored
+ * for which < 4). */
+int cilrs_net_pool_argmax_info(const cilrs_net* net, size_t* byte_offset, size_t* numel);
+int cilrs_net_head_activation_info(const cilrs_net* net, int which, int branch, size_t* offset,
+                                   int* rows, int* cols, int* ld);
 
 /* Where a 16-bit eval forward (cilrs_net_forward_u8_f16 / _bf16) keeps what its kernels read and
  * write, as BYTE offsets into the workspace -- test aid: the layer-by-layer tests of the 16-bit

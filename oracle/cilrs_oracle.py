@@ -72,6 +72,23 @@ class BasicBlock(nn.Module):
         out = out + identity
         return self.relu(out)
 
+    def forward_decided(self, x, f, ci):
+        """forward() with BatchNorm and ReLU handed to `f` (forward_with_decisions); ci = number of
+        conv1 in the engine's order conv1, conv2[, downsample].  Returns (out, next ci)."""
+        out = f.relu(ci, f.bn(ci, self.bn1, self.conv1(x)))
+        identity, nxt = x, ci + 2
+        if self.downsample is not None:
+            identity, nxt = f.bn(ci + 2, self.downsample[1], self.downsample[0](x)), ci + 3
+        out = f.bn(ci + 1, self.bn2, self.conv2(out)) + identity
+        return f.relu(ci + 1, out), nxt
+
+    def convs_in_order(self):
+        """[(conv, bn, ends in a ReLU)] in the engine's order."""
+        out = [(self.conv1, self.bn1, True), (self.conv2, self.bn2, True)]
+        if self.downsample is not None:
+            out.append((self.downsample[0], self.downsample[1], False))
+        return out
+
 
 class ResNet34Trunk(nn.Module):
     """Attribute names follow torchvision so the reference's nn.Sequential re-wrapping
@@ -180,6 +197,115 @@ def forward_with_dropout_masks(model: CILRSOracle, image, speed, command, masks)
     b = image.size(0)
     all_out = torch.stack([_seq_with_masks(br, combined, masks,
                                            DROPOUT_SITES[f"control_branches.{k}"])
+                           for k, br in enumerate(model.control_branches)], dim=0)
+    idx = command.unsqueeze(0).unsqueeze(2).expand(1, b, 3)
+    controls = all_out.gather(0, idx).squeeze(0)
+    return controls, pred_speed
+
+
+# --------------------------------------------------------------------------------------
+# Forward under GIVEN decisions (the mask-matched gradient tests, tests/_masked_grads.py)
+# --------------------------------------------------------------------------------------
+# Keys of the ReLU decisions: the engine's convolution number (parameter order: 0 the stem, then
+# every block's conv1, conv2[, conv3][, downsample]) for a trunk ReLU; for the heads "s1" / "s2"
+# (speed_encoder.1 / .4), "p1" / "p2" (speed_predictor.1 / .4), "h1.<k>" / "h2.<k>"
+# (control_branches.<k>.1 / .4).
+def trunk_blocks(model):
+    return [b for layer in list(model.visual_encoder)[4:8] for b in layer]
+
+
+def trunk_convs(model):
+    """[(conv number, trunk group 0..4, conv, bn, ends in a ReLU)] in the engine's order."""
+    ve = model.visual_encoder
+    out = [(0, 0, ve[0], ve[1], True)]
+    for gi in range(4):
+        for blk in ve[4 + gi]:
+            for conv, bn, relu in blk.convs_in_order():
+                out.append((len(out), gi + 1, conv, bn, relu))
+    return out
+
+
+class ForcedDecisions:
+    """BatchNorm, ReLU and the stem's pooling as forward_with_decisions asks for them, every
+    decision read from a record instead of being taken:
+      relu[key]     bool mask of the key's ReLU (shape of its activation): relu(x) becomes x * mask;
+      stem_argmax   integer [B,64,Ho,Wo], kh * 3 + kw of the 3x3/s2/p1 window tap each pooled
+                    element takes (input row 2 * oh - 1 + kh, column 2 * ow - 1 + kw);
+      stem_on       bool [B,64,Ho,Wo]: the stem ReLU's decision on the element the window took;
+      bn_batch[ci]  True: BatchNorm of convolution ci on the batch statistics (train mode), False:
+                    on the running statistics (frozen graph, eval-mode prefix of a fine-tuning cut).
+    No running buffer is ever updated.  `taps`, when a dict, receives every ReLU's detached
+    pre-activation under its key and the stem's BatchNorm output under "stem"."""
+
+    def __init__(self, relu, stem_argmax, stem_on, bn_batch, taps=None):
+        self.relu_masks, self.stem_argmax, self.stem_on = relu, stem_argmax, stem_on
+        self.bn_batch, self.taps = bn_batch, taps
+
+    def bn(self, ci, m, x):
+        if self.bn_batch[ci]:
+            return nn.functional.batch_norm(x, None, None, m.weight, m.bias, True, 0.0, m.eps)
+        return nn.functional.batch_norm(x, m.running_mean, m.running_var, m.weight, m.bias, False,
+                                        0.0, m.eps)
+
+    def relu(self, key, x):
+        if self.taps is not None:
+            self.taps[key] = x.detach()
+        mask = self.relu_masks[key]
+        assert mask.shape == x.shape, (key, tuple(mask.shape), tuple(x.shape))
+        return x * mask.to(x.dtype)
+
+    def stem(self, z):
+        """pooled = gather(z, argmax) * stem_on: neither a relu nor a max_pool2d call."""
+        if self.taps is not None:
+            self.taps["stem"] = z.detach()
+        return pool_gather(z, self.stem_argmax) * self.stem_on.to(z.dtype)
+
+
+def pool_index(argmax, h, w):
+    """Flat index row * w + col into an [h, w] map of the taps argmax [B,C,Ho,Wo] (kh * 3 + kw) of
+    the 3x3/s2/p1 windows, [B,C,Ho*Wo]."""
+    ho, wo = argmax.shape[2:]
+    a = argmax.long()
+    row = torch.arange(ho).view(1, 1, ho, 1) * 2 - 1 + a // 3
+    col = torch.arange(wo).view(1, 1, 1, wo) * 2 - 1 + a % 3
+    if bool((a > 8).any() | (row < 0).any() | (row >= h).any() | (col < 0).any() | (col >= w).any()):
+        raise ValueError("pool_index: a window's tap lies outside the map")
+    return (row * w + col).flatten(2)
+
+
+def pool_gather(z, argmax):
+    """z [B,C,H,W] at the taps argmax [B,C,Ho,Wo] of the 3x3/s2/p1 windows."""
+    return z.flatten(2).gather(2, pool_index(argmax, z.size(2), z.size(3))).view(argmax.shape)
+
+
+def _seq_decided(seq, x, f, keys):
+    it = iter(keys)
+    for layer in seq:
+        if isinstance(layer, nn.ReLU):
+            x = f.relu(next(it), x)
+        elif isinstance(layer, nn.Dropout):
+            assert layer.p == 0.0, "forward_with_decisions: dropout 0 only"
+        else:
+            x = layer(x)
+    return x
+
+
+def forward_with_decisions(model, image, speed, command, f):
+    """CILRSOracle.forward (autonomous_drive.py:389-399) as a function of the module's parameters
+    and buffers, in whatever dtype they have, with every BatchNorm mode, ReLU and the stem's
+    ReLU + max-pool delegated to `f` (ForcedDecisions: given, not taken).  Serves every class
+    whose blocks have forward_decided: ResNet-34, the ResNet-50 variant, any num_commands."""
+    ve = model.visual_encoder
+    x = f.stem(f.bn(0, ve[1], ve[0](image)))
+    ci = 1
+    for blk in trunk_blocks(model):
+        x, ci = blk.forward_decided(x, f, ci)
+    visual = ve[9](ve[8](x))
+    speed_feat = _seq_decided(model.speed_encoder, speed.unsqueeze(1), f, ("s1", "s2"))
+    combined = torch.cat([visual, speed_feat], dim=1)
+    pred_speed = _seq_decided(model.speed_predictor, visual, f, ("p1", "p2")).squeeze(1)
+    b = image.size(0)
+    all_out = torch.stack([_seq_decided(br, combined, f, (f"h1.{k}", f"h2.{k}"))
                            for k, br in enumerate(model.control_branches)], dim=0)
     idx = command.unsqueeze(0).unsqueeze(2).expand(1, b, 3)
     controls = all_out.gather(0, idx).squeeze(0)

@@ -51,6 +51,24 @@ class Bottleneck(nn.Module):
             identity = self.downsample(x)
         return self.relu(out + identity)
 
+    def forward_decided(self, x, f, ci):
+        """forward() with BatchNorm and ReLU handed to `f` (cilrs_oracle.forward_with_decisions);
+        ci = number of conv1 in the engine's order conv1, conv2, conv3[, downsample]."""
+        out = f.relu(ci, f.bn(ci, self.bn1, self.conv1(x)))
+        out = f.relu(ci + 1, f.bn(ci + 1, self.bn2, self.conv2(out)))
+        identity, nxt = x, ci + 3
+        if self.downsample is not None:
+            identity, nxt = f.bn(ci + 3, self.downsample[1], self.downsample[0](x)), ci + 4
+        out = f.bn(ci + 2, self.bn3, self.conv3(out)) + identity
+        return f.relu(ci + 2, out), nxt
+
+    def convs_in_order(self):
+        out = [(self.conv1, self.bn1, True), (self.conv2, self.bn2, True),
+               (self.conv3, self.bn3, True)]
+        if self.downsample is not None:
+            out.append((self.downsample[0], self.downsample[1], False))
+        return out
+
 
 def _layer(inplanes, planes, blocks, stride):
     down = None
