@@ -226,6 +226,7 @@ class Engine:
         self.plans = {}
         self.bufs = {}
         self.last_plan = None
+        self._mc_bufs = {}                # run_heads_mc: (owner, B, S) -> scratch + pinned outputs
         # "fp32" (the reference's arithmetic) or "bf16": train-mode trunk convolutions on the bf16
         # matrix pipe (include/cilrs_hip.h CILRS_PLAN_BF16_TRAIN); set through
         # Trainer(..., precision=) or directly before the first train-mode forward
@@ -582,6 +583,48 @@ class Engine:
                    L.ptr(pred_speed), self._stream()))
         self.last_plan = pl
         return controls, pred_speed
+
+    MC_MAX_SAMPLES, MC_MAX_ROWS = 4096, 65536
+
+    MC_CACHE_ENTRIES = 8
+
+    def run_heads_mc(self, speed, command, samples, p, seed=0, return_samples=False, owner=None):
+        """Monte-Carlo dropout through the heads (include/cilrs_hip.h, cilrs_net_heads_mc) on the
+        features the last eval-mode forward left in its plan: enqueues the launches on the current
+        stream and returns (mean [B,4], std [B,4], samples [B,S,4] or None) as views of a PINNED
+        host buffer that the kernels write -- valid after the stream is synchronised and until the
+        next call with the same (B, S).  speed / command: the tensors the forward was given
+        (device or pinned host).  Scratch and outputs are cached per (owner, B, S), the
+        MC_CACHE_ENTRIES most recent: callers that may run at the same time on different streams
+        (two Predictors on one model) pass themselves as `owner` and so never share a buffer."""
+        pl = self.last_plan
+        if pl is None:
+            raise RuntimeError("run_heads_mc: no forward yet")
+        samples, p, b = int(samples), float(p), pl.batch
+        if not 1 <= samples <= self.MC_MAX_SAMPLES:
+            raise ValueError(f"samples must be in 1..{self.MC_MAX_SAMPLES}")
+        if b * samples > self.MC_MAX_ROWS:
+            raise ValueError(f"batch * samples must not exceed {self.MC_MAX_ROWS}")
+        if not 0.0 <= p < 1.0:                       # (NaN fails both comparisons)
+            raise ValueError("dropout probability must be in [0, 1)")
+        cache, key = self._mc_bufs, (id(owner) if owner is not None else None, b, samples)
+        bufs = cache.pop(key, None)
+        if bufs is None:
+            while len(cache) >= self.MC_CACHE_ENTRIES:
+                cache.pop(next(iter(cache)))             # the least recently used
+            n = L.lib().cilrs_heads_mc_scratch_floats(self.variant, b, samples)
+            scratch = torch.empty(n, dtype=torch.float32, device=self.device)
+            host = torch.zeros(b * 8 + b * samples * 4, dtype=torch.float32).pin_memory()
+            bufs = (scratch, host, host[:b * 4].view(b, 4), host[b * 4:b * 8].view(b, 4),
+                    host[b * 8:].view(b, samples, 4))
+        cache[key] = bufs                                # (re-inserted: most recently used last)
+        scratch, _host, mean, std, smp = bufs
+        L.check(L.lib().cilrs_net_heads_mc(
+            pl.handle, C.byref(pl.bufs), L.ptr(speed), L.ptr(command), samples, p,
+            int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(mean), L.ptr(std),
+            L.ptr(smp) if return_samples else None, L.ptr(scratch), scratch.numel(),
+            self._stream()))
+        return mean, std, (smp if return_samples else None)
 
     def run_forward_camera(self, frames_u8, speed, command, height=88, width=200, out=None):
         """Raw camera frames uint8 [B,Hs,Ws,3|4] (device) -> eval forward with the whole of

@@ -671,3 +671,91 @@ class Predictor:
         # the reference multiplies the float32 .item() by 90.0 in Python (double)
         return (float(r[0]), float(r[1]), float(r[2]),
                 float(self._spd_np[0]) * SPEED_NORM_FACTOR)
+
+    # ---- Monte-Carlo dropout -----------------------------------------------------------------
+    def _mc_args(self, samples, p, seed):
+        """Validated (samples, p, seed) of the uncertainty calls; raises ValueError before any
+        launch."""
+        if isinstance(samples, bool) or int(samples) != samples:
+            raise ValueError("samples must be an integer")
+        samples = int(samples)
+        if not 1 <= samples <= self.eng.MC_MAX_SAMPLES:
+            raise ValueError(f"samples must be in 1..{self.eng.MC_MAX_SAMPLES}")
+        if self.batch * samples > self.eng.MC_MAX_ROWS:
+            raise ValueError(f"batch * samples must not exceed {self.eng.MC_MAX_ROWS}")
+        if p is None:
+            p = float(getattr(self.model, "dropout", 0.0))
+            if p == 0.0:
+                raise ValueError(
+                    "the model was built with dropout=0.0 (the reference agent does so and loads a "
+                    "checkpoint trained at 0.5): pass the training dropout probability as p")
+        p = float(p)
+        if not 0.0 <= p < 1.0:
+            raise ValueError("p must be in [0, 1)")
+        if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("seed must be an integer in 0..2**64-1")
+        return samples, p, int(seed)
+
+    def _mc_inputs(self, camera=False):
+        """(speed, command) tensors of the tick that just ran, as the MC launches read them.  Every
+        tick stages them in pinned host memory first, and a persistent zero-copy predictor keeps
+        reading them there (as its forward does, also on a degraded tick, which copies them to the
+        device besides); every other predictor passes the device copies its forward read."""
+        host = self.persistent and self.zero_copy
+        if camera:
+            cam = self._cam
+            return cam[4] if host else (cam[2][2], cam[2][3])
+        return (self.speed_host, self.cmd_host) if host else (self.speed_dev, self.cmd_dev)
+
+    def _mc_run(self, speed, command, samples, p, seed, return_samples):
+        """The MC launches on this predictor's stream, on the plan the tick just used, into a
+        pinned buffer; one synchronise.  Returns km/h-scaled copies (mean, std, samples)."""
+        eng = self.eng
+        eng.last_plan = eng.plan(self.batch, self.frames_host.size(1), self.frames_host.size(2))
+        with torch.cuda.stream(self.stream):
+            mean, std, smp = eng.run_heads_mc(speed, command, samples, p, seed, return_samples,
+                                              owner=self)
+            self.stream.synchronize()
+        scale = np.array([1.0, 1.0, 1.0, SPEED_NORM_FACTOR], dtype=np.float32)
+        return (mean.numpy() * scale, std.numpy() * scale,
+                smp.numpy() * scale if return_samples else None)
+
+    @torch.no_grad()
+    def predict_uncertain(self, frames_u8, speeds_kmh, commands, samples=32, p=None, seed=0,
+                          return_samples=False):
+        """predict_batch plus a Monte-Carlo dropout estimate of how far its outputs can be trusted:
+        BatchNorm stays in eval mode, the trunk runs once, the heads run ``samples`` times under
+        their training Dropout masks (include/cilrs_hip.h, cilrs_net_heads_mc).  Returns a dict of
+        np.float32 arrays: "point" [B,4] (exactly predict_batch's result), "mean" and "std" [B,4]
+        over the samples (std: torch's unbiased estimate), and "samples" [B,S,4] when
+        return_samples is set; column 3 of each is in km/h.  ``p`` defaults to the model's dropout
+        probability; a model built with dropout=0.0 must pass it.  ``seed=0`` draws the same masks
+        on every tick -- a fixed ensemble without tick-to-tick flicker; vary ``seed`` for fresh
+        masks.  Bad arguments raise ValueError before anything is launched."""
+        samples, p, seed = self._mc_args(samples, p, seed)
+        point = self.predict_batch(frames_u8, speeds_kmh, commands)
+        speed, cmd = self._mc_inputs()
+        mean, std, smp = self._mc_run(speed, cmd, samples, p, seed, return_samples)
+        out = {"point": point, "mean": mean, "std": std}
+        if return_samples:
+            out["samples"] = smp
+        return out
+
+    @torch.no_grad()
+    def predict_controls_uncertain(self, image_rgb_u8, speed_kmh, command_idx, samples=32, p=None,
+                                   seed=0):
+        """predict_controls with error bars: ((steer, throttle, brake, speed_kmh), (std_steer,
+        std_throttle, std_brake, std_speed_kmh)), the first tuple being the MC-dropout mean (see
+        predict_uncertain).  Frames that are not 88x200x3 go through predict_camera's path first."""
+        if self.batch != 1:
+            raise RuntimeError("predict_controls_uncertain is the single-frame control-loop path")
+        samples, p, seed = self._mc_args(samples, p, seed)
+        image_rgb_u8 = np.asarray(image_rgb_u8)
+        if image_rgb_u8.shape != tuple(self.frames_host.shape[1:]):
+            self.predict_camera(image_rgb_u8, speed_kmh, command_idx)
+            speed, cmd = self._mc_inputs(camera=True)
+        else:
+            self.predict_batch(image_rgb_u8[None], [speed_kmh], [command_idx])
+            speed, cmd = self._mc_inputs()
+        mean, std, _ = self._mc_run(speed, cmd, samples, p, seed, False)
+        return tuple(float(x) for x in mean[0]), tuple(float(x) for x in std[0])

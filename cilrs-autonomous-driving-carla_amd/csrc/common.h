@@ -659,4 +659,42 @@ int launch_scale(float* g, size_t n, const float* coef_ptr, float c, hipStream_t
 int launch_keep_head_inputs(const float* speed, const long long* cmd, float* speed_dst,
                             long long* cmd_dst, int B, hipStream_t s);
 
+// ---- Monte-Carlo dropout through the heads (mc_heads.hip; cilrs_heads_mc) -----------------------
+#if defined(__HIPCC__)
+// The dropout hash of the heads (dropout_kernel, hgemm_kernel): the fp32 in [0, 1) from the top 24
+// bits of splitmix64's finaliser over seed * 0x2545F4914F6CDD1D + (site << 40) + row * cols + col;
+// an element is kept where it is >= p.
+__device__ __forceinline__ float dropout_u(const unsigned long long seed, const unsigned long long site,
+                                           const unsigned int index) {
+    unsigned long long x = seed * 0x2545F4914F6CDD1Dull + (site << 40) + index;
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return (float)((unsigned int)(x >> 32) >> 8) * (1.0f / 16777216.0f);
+}
+#endif
+constexpr int kMcMaxFeat = 2048;          // widest trunk feature vector (ResNet-50 variant)
+constexpr int kMcSharedFloats = 640;      // per frame: a0[128] | hv[256] | pp[256] (mc_pre_kernel)
+constexpr int kMcMaxSamples = 4096, kMcMaxRows = 65536;
+struct McHeadsArgs {
+    const float* se0_w; const float* se0_b; const float* se3_w; const float* se3_b;
+    const float* br_w[kMaxCmd][3]; const float* br_b[kMaxCmd][3];
+    const float* sp0_w; const float* sp0_b; const float* sp3_w; const float* sp3_b;
+    const float* sp5_w; const float* sp5_b;
+    int ncmd, F;
+    const float* pooled; int pooled_ld;   // [B][pooled_ld] features, or NULL:
+    const float* featmap; int HW;         //   [B][HW][F] last feature map, pooled by the pre launch
+    const float* speed; const long long* cmd;
+    int B, S;
+    float p; unsigned long long seed;
+    float* mean; float* stdv;             // [B][4]
+    float* samples_out;                   // [B][S][4] or NULL (a copy of `samples`)
+    int* status;                          // may be NULL
+    float* shared; float* samples;        // set by the launcher: inside the caller's scratch
+    int nchunks;
+};
+size_t mc_heads_scratch_floats(int batch, int samples);
+int launch_mc_heads(McHeadsArgs& a, float* scratch, hipStream_t s);
+
 }  // namespace cilrs

@@ -348,6 +348,13 @@ struct cilrs_net {
     const void* prep_bufs[3] = {nullptr, nullptr, nullptr};     // params, bn_running, workspace
     bool trained_fwd = false;
     float last_dropout = 0.f;
+    // where the last forward left what cilrs_net_heads_mc reads: 0 no forward yet (every forward
+    // sets 0 on entry and its own value at its successful end, so a forward that failed midway
+    // leaves nothing to sample from); 1 pooled fp32
+    // features in `combined` (every eval-mode forward but the persistent launch); 2 the last feature
+    // map (the persistent launch pools inside its head stage and keeps no pooled copy); -1 a
+    // train-mode forward (batch statistics: refused)
+    int mc_src = 0;
     // the last graph-keeping forward was cilrs_net_forward_frozen (BatchNorm on the running
     // statistics: its backward drops the batch-statistics terms)
     bool frozen_fwd = false;
@@ -1727,6 +1734,7 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
                            float* controls, float* pred_speed, hipStream_t s, int half = 0,
                            bool frozen = false) {
     net->ws_base = reinterpret_cast<float*>(bufs->workspace);
+    net->mc_src = 0;          // until this forward has finished, its features are not there
     CILRS_CHECK(!(frozen && (train || half || net->bf16_train)),
                 "frozen forward: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan rejects it)");
     if (clear_status_once(net, bufs->workspace, s)) return 1;
@@ -1755,6 +1763,7 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
     net->trained_fwd = graph;
     net->frozen_fwd = frozen;
     net->last_dropout = pdrop;
+    net->mc_src = train ? -1 : 1;
     return 0;
 }
 
@@ -1795,6 +1804,7 @@ static int forward_ft_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const f
                               const int64_t* command, int k, uint64_t prefix_key, float dropout_p,
                               uint64_t seed, float* controls, float* pred_speed, hipStream_t s) {
     net->ws_base = reinterpret_cast<float*>(bufs->workspace);
+    net->mc_src = 0;
     if (clear_status_once(net, bufs->workspace, s)) return 1;
     net->bwd_done = 0;
     // the trainable weights / BatchNorm buffers are about to change: the cached eval state goes stale
@@ -1813,6 +1823,7 @@ static int forward_ft_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const f
     net->trained_fwd = true;
     net->frozen_fwd = false;
     net->last_dropout = dropout_p;
+    net->mc_src = -1;
     return 0;
 }
 
@@ -2185,6 +2196,7 @@ static int b1_launch(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* f
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float* ws = reinterpret_cast<float*>(bufs->workspace);
     net->ws_base = ws;
+    net->mc_src = 0;
     if (net->b1_blocks < 0) {
         int blocks = 0;
         if (infer_b1_grid(&blocks)) return 1;
@@ -2219,6 +2231,7 @@ static int b1_launch(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* f
     RUN(net, "infer_b1", 2.0 * 2.798e9 / 2.0, 0.0, s, launch_infer_b1(a, net->b1_blocks, s));
     net->trained_fwd = false;
     net->last_dropout = 0.f;
+    net->mc_src = 2;
     return 0;
 }
 
@@ -2358,6 +2371,7 @@ static int forward_u8_graph(cilrs_net* net, const cilrs_buffers* bufs, const uin
     if (check_bufs(net, bufs, false)) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     CILRS_CHECK(s != nullptr, "forward_u8_graph: capture needs a non-default stream");
+    net->mc_src = 0;
     const void* key[8] = {bufs->params, bufs->bn_running, bufs->workspace, frames, speed, command,
                           controls, pred_speed};
     bool same = net->graph_exec != nullptr && net->graph_half == half &&
@@ -2394,6 +2408,7 @@ static int forward_u8_graph(cilrs_net* net, const cilrs_buffers* bufs, const uin
         net->graph_wkey = net->weights_key;
     }
     CILRS_HIP(hipGraphLaunch(net->graph_exec, s));
+    net->mc_src = 1;
     return 0;
 }
 
@@ -2415,6 +2430,87 @@ int cilrs_net_forward_u8_bf16_graph(cilrs_net* net, const cilrs_buffers* bufs,
                                     const int64_t* command, float* controls, float* pred_speed,
                                     void* stream) {
     return forward_u8_graph(net, bufs, frames, speed, command, controls, pred_speed, stream, 2);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Monte-Carlo dropout through the heads (mc_heads.hip)
+// ------------------------------------------------------------------------------------------------
+static int mc_check(const char* who, int batch, int samples, float p, const float* scratch,
+                    size_t scratch_floats) {
+    CILRS_CHECK(batch >= 1, "%s: batch %d", who, batch);
+    CILRS_CHECK(samples >= 1 && samples <= kMcMaxSamples, "%s: samples %d outside 1..%d", who,
+                samples, kMcMaxSamples);
+    CILRS_CHECK((long long)batch * samples <= kMcMaxRows, "%s: batch * samples %lld above %d", who,
+                (long long)batch * samples, kMcMaxRows);
+    CILRS_CHECK(p >= 0.f && p < 1.f, "%s: dropout probability %f outside [0, 1)", who, (double)p);
+    CILRS_CHECK(scratch != nullptr && scratch_floats >= mc_heads_scratch_floats(batch, samples),
+                "%s: scratch of %zu floats, %zu needed", who, scratch_floats,
+                mc_heads_scratch_floats(batch, samples));
+    return 0;
+}
+
+static void mc_fill(McHeadsArgs& a, const Arch& A, const float* P) {
+    memset(&a, 0, sizeof(a));
+    a.se0_w = P + A.se0.w; a.se0_b = P + A.se0.b; a.se3_w = P + A.se3.w; a.se3_b = P + A.se3.b;
+    for (int k = 0; k < A.ncmd; ++k)
+        for (int l = 0; l < 3; ++l) { a.br_w[k][l] = P + A.br[k][l].w; a.br_b[k][l] = P + A.br[k][l].b; }
+    a.sp0_w = P + A.sp0.w; a.sp0_b = P + A.sp0.b; a.sp3_w = P + A.sp3.w; a.sp3_b = P + A.sp3.b;
+    a.sp5_w = P + A.sp5.w; a.sp5_b = P + A.sp5.b;
+    a.ncmd = A.ncmd; a.F = A.feat;
+}
+
+size_t cilrs_heads_mc_scratch_floats(int variant, int batch, int samples) {
+    if (!variant_ok(variant) || batch < 1 || samples < 1) return 0;
+    return mc_heads_scratch_floats(batch, samples);
+}
+
+int cilrs_heads_mc(int variant, const float* params, const float* pooled, int pooled_ld,
+                   const float* speed, const int64_t* command, int batch, int samples, float p,
+                   uint64_t seed, float* mean, float* std, float* samples_out, float* scratch,
+                   size_t scratch_floats, int* status, void* stream) {
+    CILRS_CHECK(variant_ok(variant), "heads_mc: unknown architecture code %d", variant);
+    CILRS_CHECK(params && pooled && speed && command && mean && std, "heads_mc: NULL tensor");
+    if (mc_check("heads_mc", batch, samples, p, scratch, scratch_floats)) return 1;
+    const Arch& A = arch(variant);
+    CILRS_CHECK(pooled_ld >= A.feat, "heads_mc: pooled_ld %d below the %d features", pooled_ld, A.feat);
+    CILRS_CHECK(((uintptr_t)params & 15) == 0, "heads_mc: params must be 16-byte aligned");
+    McHeadsArgs a;
+    mc_fill(a, A, params);
+    a.pooled = pooled; a.pooled_ld = pooled_ld;
+    a.speed = speed; a.cmd = reinterpret_cast<const long long*>(command);
+    a.B = batch; a.S = samples; a.p = p; a.seed = seed;
+    a.mean = mean; a.stdv = std; a.samples_out = samples_out; a.status = status;
+    return launch_mc_heads(a, scratch, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cilrs_net_heads_mc(cilrs_net* net, const cilrs_buffers* bufs, const float* speed,
+                       const int64_t* command, int samples, float p, uint64_t seed, float* mean,
+                       float* std, float* samples_out, float* scratch, size_t scratch_floats,
+                       void* stream) {
+    if (check_bufs(net, bufs, false)) return 1;
+    CILRS_CHECK(speed && command && mean && std, "net_heads_mc: NULL tensor");
+    if (mc_check("net_heads_mc", net->B, samples, p, scratch, scratch_floats)) return 1;
+    CILRS_CHECK(net->mc_src != 0, "net_heads_mc: no forward on this plan yet");
+    CILRS_CHECK(net->mc_src > 0, "net_heads_mc: the plan's last forward ran in train mode (batch "
+                "statistics); run an eval-mode forward first");
+    const Arch& A = *net->A;
+    const float* ws = reinterpret_cast<const float*>(bufs->workspace);
+    McHeadsArgs a;
+    mc_fill(a, A, bufs->params);
+    if (net->mc_src == 2) {
+        a.featmap = ws + net->cg[A.blocks.back().conv3 >= 0 ? A.blocks.back().conv3
+                                                            : A.blocks.back().conv2].z;
+        a.HW = net->featHW;
+    } else {
+        a.pooled = ws + net->combined; a.pooled_ld = A.feat + 128;
+    }
+    a.speed = speed; a.cmd = reinterpret_cast<const long long*>(command);
+    a.B = net->B; a.S = samples; a.p = p; a.seed = seed;
+    a.mean = mean; a.stdv = std; a.samples_out = samples_out;
+    a.status = reinterpret_cast<int*>(reinterpret_cast<char*>(bufs->workspace) + net->status_b);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    RUN(net, "heads_mc", 2.0 * net->B * samples * 180480.0, 0.0, s, launch_mc_heads(a, scratch, s));
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

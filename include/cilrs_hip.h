@@ -230,6 +230,61 @@ int cilrs_net_infer16_io_info(const cilrs_net* net, size_t* x4_offset, size_t* x
 int cilrs_dropout(float* a, int rows, int cols, int ld, float p, uint64_t seed, int site,
                   void* stream);
 
+/* ---- Monte-Carlo dropout through the heads (csrc/mc_heads.hip) ---------------------------------
+ * The executed configuration trains with a Dropout after speed_encoder.1, control_branches.k.1,
+ * control_branches.k.4 and speed_predictor.1 (autonomous_drive.py:371-387); every Dropout sits in
+ * the heads, so in eval mode the trunk is deterministic.  MC dropout keeps BatchNorm in eval mode,
+ * draws S dropout masks and reports the mean and spread of the S outputs: the trunk runs once, only
+ * the heads run S times.  The reference has no such path; parity is pinned by this definition
+ * (restated in float64 by tests/_mc_dropout.py):
+ *   Inputs   per frame: pooled features v (fp32, F = 512 / 2048 for the ResNet-34 / ResNet-50
+ *            trunk), normalised speed x, command k, architecture code trunk | num_commands << 8
+ *            (NC commands).  Call parameters: S samples, dropout probability p in [0, 1), a 64-bit
+ *            seed.
+ *   Row      sample s of frame b is row r = b * S + s.
+ *   Mask     keep(site, r, c, cols) = u >= p, u the fp32 in [0, 1) from the top 24 bits of the hash
+ *            of seed * 0x2545F4914F6CDD1D + (site << 40) + (r * cols + c), exactly as cilrs_dropout
+ *            computes it.  A kept value is value / (1.0f - p) (an fp32 division), a dropped one 0.
+ *   Sites    0: speed_encoder.2 (128 columns); 1 + 2k and 2 + 2k: control_branches.k.2 and .5 (256
+ *            columns each); 2 NC + 1: speed_predictor.2 (256 columns; 9 for the reference).
+ *   Per row  s1 = drop_0(relu(W_se0 x + b));  f = relu(W_se3 s1 + b);
+ *            h1 = drop_{1+2k}(relu(W_k0 [v | f] + b));  h2 = drop_{2+2k}(relu(W_k3 h1 + b));
+ *            controls = W_k5 h2 + b;
+ *            p1 = drop_{2NC+1}(relu(W_p0 v + b));  p2 = relu(W_p3 p1 + b);  pred_speed = W_p5 p2 + b.
+ *   Branch   only the commanded branch is evaluated; a command outside 0..NC-1 uses branch 0 and
+ *            sets the status word, as everywhere else in the library.
+ *   Stats    per frame and output, over its S stored fp32 sample values: mean = (sum x_s) / S,
+ *            std = sqrt(sum (x_s - mean)^2 / (S - 1)) (torch's default unbiased estimate; 0 for
+ *            S = 1); both passes in double in sample order, the results rounded once to fp32.
+ *   p = 0    every sample is the eval-mode output and std is exactly 0 (the double sum of
+ *            S <= 4,096 equal fp32 values is exact).
+ * A sample's four values depend only on (seed, r, inputs), not on how many samples the call asks
+ * for.  At most three launches, no atomics, every sum in a fixed order.
+ *
+ * mean, std: [B][4] = steer, throttle, brake, pred_speed; samples_out: [B][S][4] or NULL; all three
+ * may be pinned host memory.  status: a device int (set to 1 on an out-of-range command) or NULL.
+ * scratch: caller's device memory of cilrs_heads_mc_scratch_floats(variant, batch, samples) floats
+ * (0 for an unknown code or a non-positive size).
+ * cilrs_heads_mc: the op-level form on caller-supplied pooled features [B][pooled_ld], features
+ * first; `variant` is the architecture code (both trunks, 1..8 commands).
+ * cilrs_net_heads_mc: the same on the features of the plan's last eval-mode forward -- `combined`
+ * after cilrs_net_forward(train = 0), _frozen*, _u8, _camera, the _graph forms and the 16-bit forms;
+ * after a persistent single-frame forward, which pools inside its head stage and keeps no pooled
+ * copy, the average pool of the last feature map it stored.  Batch = the plan's; status = the
+ * plan's word 0.  No launch of any forward entry changes, nor does the workspace layout.
+ * Refused (non-zero, text in cilrs_last_error, nothing launched): NULL tensors; samples < 1 or
+ * > 4096; batch * samples > 65536; p outside [0, 1) or not finite; a scratch smaller than asked; an
+ * unknown architecture code; at plan level no forward yet, or a train-mode forward last. */
+size_t cilrs_heads_mc_scratch_floats(int variant, int batch, int samples);
+int cilrs_heads_mc(int variant, const float* params, const float* pooled, int pooled_ld,
+                   const float* speed, const int64_t* command, int batch, int samples, float p,
+                   uint64_t seed, float* mean, float* std, float* samples_out,
+                   float* scratch, size_t scratch_floats, int* status, void* stream);
+int cilrs_net_heads_mc(cilrs_net* net, const cilrs_buffers* bufs, const float* speed,
+                       const int64_t* command, int samples, float p, uint64_t seed,
+                       float* mean, float* std, float* samples_out,
+                       float* scratch, size_t scratch_floats, void* stream);
+
 /* Same, fed with uint8 RGB HWC frames [B,H,W,3]: fuses preprocess_image's /255, HWC->CHW and
  * Normalize(mean,std) (autonomous_drive.py:897-902; the cv2.resize is the caller's). */
 int cilrs_net_forward_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
