@@ -75,6 +75,13 @@ SIGNATURES = {
     "cilrs_heads_mc": (i32, [i32, vp, vp, i32, vp, vp, i32, i32, f32, u64, vp, vp, vp, vp, sz, vp, vp]),
     "cilrs_net_heads_mc": (i32, [vp, C.POINTER(Buffers), vp, vp, i32, f32, u64, vp, vp, vp, vp, sz,
                                  vp]),
+    "cilrs_heads_input_grad": (i32, [i32, vp, vp, i32, vp, i32, vp, vp, c_float_p, i32, vp, vp, vp, vp]),
+    "cilrs_gradcam_map": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "cilrs_gradcam_scratch_floats": (sz, [i32, i32]),
+    "cilrs_net_gradcam_info": (i32, [vp, i32, C.POINTER(sz), C.POINTER(sz), C.POINTER(i32),
+                                     C.POINTER(i32), C.POINTER(i32)]),
+    "cilrs_net_gradcam": (i32, [vp, C.POINTER(Buffers), vp, vp, c_float_p, i32, vp, vp, vp, vp, vp, sz,
+                                vp]),
     "cilrs_net_infer16_conv_info": (i32, [vp, i32, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),
                                           C.POINTER(i32), C.POINTER(i32)]),
     "cilrs_net_infer16_io_info": (i32, [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),

@@ -17,6 +17,7 @@ Memory layout (all fp32, on one device):
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -227,6 +228,7 @@ class Engine:
         self.bufs = {}
         self.last_plan = None
         self._mc_bufs = {}                # run_heads_mc: (owner, B, S) -> scratch + pinned outputs
+        self._gc_bufs = {}                # run_gradcam: (owner, B, H, W, layer) -> the same
         # "fp32" (the reference's arithmetic) or "bf16": train-mode trunk convolutions on the bf16
         # matrix pipe (include/cilrs_hip.h CILRS_PLAN_BF16_TRAIN); set through
         # Trainer(..., precision=) or directly before the first train-mode forward
@@ -625,6 +627,105 @@ class Engine:
             L.ptr(smp) if return_samples else None, L.ptr(scratch), scratch.numel(),
             self._stream()))
         return mean, std, (smp if return_samples else None)
+
+    # ---- Grad-CAM (csrc/gradcam.hip) ---------------------------------------------------------------
+    GRADCAM_CHANNELS = (64, 128, 256, 512, 1024, 2048)
+
+    @staticmethod
+    def _gradcam_weights(weights4):
+        w = [float(v) for v in weights4]
+        if len(w) != 4 or not all(math.isfinite(v) for v in w):
+            raise ValueError("four finite output weights expected")
+        return (C.c_float * 4)(*w)
+
+    def run_heads_input_grad(self, speed, command, weights4, pooled=None, featmap=None, g=None,
+                             out4=None, status=None):
+        """cilrs_heads_input_grad on this engine's weights: d (w . outputs) / d pooled features of
+        the eval-mode heads, float32 [B, F].  Features: `pooled` [B, ld >= F] (features first) or
+        `featmap` [B, HW, F], which the kernel pools.  Returns (g, out4 [B, 4] raw outputs)."""
+        if (pooled is None) == (featmap is None):
+            raise ValueError("exactly one of pooled and featmap must be given")
+        src = pooled if pooled is not None else featmap
+        feat = L.lib().cilrs_variant_feature_width(self.variant)
+        want = 2 if pooled is not None else 3
+        if src.dtype != torch.float32 or src.dim() != want or not src.is_contiguous() or \
+                src.size(-1) < feat or (featmap is not None and src.size(-1) != feat):
+            raise RuntimeError(f"features must be contiguous float32 [B,ld>={feat}] or [B,HW,{feat}]")
+        b = src.size(0)
+        if tuple(speed.shape) != (b,) or tuple(command.shape) != (b,):
+            raise RuntimeError(f"{b} speeds and commands expected")
+        w = self._gradcam_weights(weights4)
+        if g is None:
+            g = torch.empty(b, feat, dtype=torch.float32, device=self.device)
+        if out4 is None:
+            out4 = torch.empty(b, 4, dtype=torch.float32, device=self.device)
+        L.check(L.lib().cilrs_heads_input_grad(
+            self.variant, L.ptr(self.params), L.ptr(pooled), src.size(1) if pooled is not None else 0,
+            L.ptr(featmap), src.size(1) if featmap is not None else 0, L.ptr(speed.contiguous()),
+            L.ptr(command.contiguous()), w, b, L.ptr(g), L.ptr(out4), L.ptr(status), self._stream()))
+        return g, out4
+
+    def run_gradcam_map(self, act, height, width, dact=None, g=None, cam=None, peak=None, heat=None,
+                        heat_u8=None):
+        """cilrs_gradcam_map: act float32 [B,h,w,C] (NHWC) with its gradient `dact` (same shape) or
+        the pooled gradient `g` [B,C] -> (cam [B,h,w], peak [B], heat [B,height,width]); heat_u8
+        (uint8 [B,height,width]) is filled when given."""
+        if (dact is None) == (g is None):
+            raise ValueError("exactly one of dact and g must be given")
+        if act.dtype != torch.float32 or act.dim() != 4 or not act.is_contiguous():
+            raise RuntimeError("act must be contiguous float32 [B,h,w,C]")
+        b, h, w, c = act.shape
+        other, shape = (dact, (b, h, w, c)) if dact is not None else (g, (b, c))
+        if other.dtype != torch.float32 or tuple(other.shape) != shape or not other.is_contiguous():
+            raise RuntimeError(f"the gradient must be contiguous float32 {shape}")
+        if cam is None:
+            cam = torch.empty(b, h, w, dtype=torch.float32, device=self.device)
+        if peak is None:
+            peak = torch.empty(b, dtype=torch.float32, device=self.device)
+        if heat is None:
+            heat = torch.empty(b, height, width, dtype=torch.float32, device=self.device)
+        L.check(L.lib().cilrs_gradcam_map(
+            L.ptr(act), L.ptr(dact), L.ptr(g), b, h, w, c, int(height), int(width), L.ptr(cam),
+            L.ptr(peak), L.ptr(heat), L.ptr(heat_u8), self._stream()))
+        return cam, peak, heat
+
+    def run_gradcam(self, speed, command, weights4, layer=4, want_u8=False, owner=None):
+        """cilrs_net_gradcam on what the last forward left in its plan (layer 4: any fp32 eval-mode
+        forward; layers 1..3: run_forward_frozen* followed by run_backward over segments
+        (0, 5 - layer)).  Enqueues the launches on the current stream and returns (cam [B,h,w],
+        heat [B,H,W], peak [B], heat_u8 [B,H,W] or None) as views of PINNED host buffers that the
+        kernels write -- valid after the stream is synchronised and until the next call with the
+        same (owner, plan shape, layer).  speed / command: the tensors the forward was given."""
+        pl = self.last_plan
+        if pl is None:
+            raise RuntimeError("run_gradcam: no forward yet")
+        layer = int(layer)
+        if not 1 <= layer <= 4:
+            raise ValueError("layer must be in 1..4")
+        w = self._gradcam_weights(weights4)
+        cache = self._gc_bufs
+        key = (id(owner) if owner is not None else None, pl.batch, pl.h, pl.w, layer)
+        bufs = cache.pop(key, None)
+        if bufs is None:
+            while len(cache) >= self.MC_CACHE_ENTRIES:
+                cache.pop(next(iter(cache)))             # the least recently used
+            h, wd, ch = L.i32(), L.i32(), L.i32()
+            L.check(L.lib().cilrs_net_gradcam_info(pl.handle, layer, None, None, C.byref(h),
+                                                   C.byref(wd), C.byref(ch)))
+            b, ncam, nheat = pl.batch, pl.batch * h.value * wd.value, pl.batch * pl.h * pl.w
+            n = L.lib().cilrs_gradcam_scratch_floats(self.variant, b)
+            scratch = torch.empty(n, dtype=torch.float32, device=self.device)
+            host = torch.zeros(ncam + b + nheat, dtype=torch.float32).pin_memory()
+            u8 = torch.zeros(nheat, dtype=torch.uint8).pin_memory().view(b, pl.h, pl.w)
+            bufs = (scratch, host, host[:ncam].view(b, h.value, wd.value), host[ncam:ncam + b],
+                    host[ncam + b:].view(b, pl.h, pl.w), u8)
+        cache[key] = bufs                                # (re-inserted: most recently used last)
+        scratch, _host, cam, peak, heat, u8 = bufs
+        L.check(L.lib().cilrs_net_gradcam(
+            pl.handle, C.byref(pl.bufs), L.ptr(speed), L.ptr(command), w, layer, L.ptr(cam),
+            L.ptr(heat), L.ptr(u8) if want_u8 else None, L.ptr(peak), L.ptr(scratch),
+            scratch.numel(), self._stream()))
+        return cam, heat, peak, (u8 if want_u8 else None)
 
     def run_forward_camera(self, frames_u8, speed, command, height=88, width=200, out=None):
         """Raw camera frames uint8 [B,Hs,Ws,3|4] (device) -> eval forward with the whole of

@@ -759,3 +759,88 @@ class Predictor:
             speed, cmd = self._mc_inputs()
         mean, std, _ = self._mc_run(speed, cmd, samples, p, seed, False)
         return tuple(float(x) for x in mean[0]), tuple(float(x) for x in std[0])
+
+    # ---- Grad-CAM --------------------------------------------------------------------------------
+    GRADCAM_LAYERS = {"layer1": 1, "layer2": 2, "layer3": 3, "layer4": 4}
+
+    @torch.no_grad()
+    def gradcam(self, frames_u8, speeds_kmh, commands, output="steer", layer="layer4", want_u8=False):
+        """Which region of the feature map carried an output: (out [B,4], heat [B,H,W] float32 in
+        [0,1] -- or uint8 0..255 with ``want_u8`` --, cam [B,h,w] float32, peak [B]).
+
+        Grad-CAM of trunk group ``layer`` ("layer1" .. "layer4"; 22x50, 11x25, 6x13 and 3x7 cells
+        at 88x200) for y = w . (steer, throttle, brake, pred_speed), ``output`` picking w as in
+        ``saliency``: cam is the signed channel-weighted sum of the group's output, peak the maximum
+        of its positive part, heat that part divided by peak and interpolated bilinearly to the
+        frame (include/cilrs_hip.h, cilrs_net_gradcam).  ``"layer4"`` is an unchanged predict_batch
+        -- persistent launch, degraded mode and all; predict_camera for a camera-sized frame on a
+        batch-1 predictor -- followed by two small launches on this predictor's stream and one more
+        synchronise: cheap enough for every tick, and ``out`` is exactly predict_batch's result.
+        The deeper, finer layers reuse ``saliency``'s staging: the eval-mode forward that keeps its
+        graph, then the data-gradient chain down to the group's boundary only.  fp32 predictors
+        only.  Bad arguments raise ValueError / RuntimeError before anything is launched."""
+        wts = self._saliency_weights(output)
+        if not isinstance(layer, str) or layer not in self.GRADCAM_LAYERS:
+            raise ValueError(f"gradcam: unknown layer {layer!r} (one of {sorted(self.GRADCAM_LAYERS)})")
+        lnum = self.GRADCAM_LAYERS[layer]
+        if self.half:
+            raise RuntimeError("gradcam: fp32 predictors only (a 16-bit trunk keeps 16-bit feature "
+                               "maps)")
+        frames = np.asarray(frames_u8)
+        h, w = self.frames_host.size(1), self.frames_host.size(2)
+        b = self.batch
+        if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[0] != b or \
+                frames.shape[3] not in (3, 4):
+            raise RuntimeError(f"gradcam: frames must be uint8 [{b},H,W,3] (camera frames: 3 or 4 "
+                               "bytes per pixel)")
+        camera = frames.shape[1:] != (h, w, 3)
+        cmds = self._check_commands(commands)
+        speeds = np.asarray(speeds_kmh, dtype=np.float64)
+        if cmds.shape != (b,) or speeds.shape != (b,):
+            raise RuntimeError(f"gradcam: {b} speeds and commands expected")
+        if camera and lnum == 4 and b != 1:
+            raise RuntimeError("gradcam: camera-sized frames at layer4 take predict_camera's path, "
+                               "which is the single-frame one")
+        eng = self.eng
+        if lnum == 4:
+            if camera:
+                r = self.predict_camera(frames[0], float(speeds[0]), int(cmds[0]))
+                out = np.asarray([r], dtype=np.float32)
+            else:
+                out = self.predict_batch(frames, speeds, cmds)
+            eng = self.eng                                   # (a re-attached model re-initialises)
+            speed, cmd = self._mc_inputs(camera)
+            eng.last_plan = eng.plan(b, h, w)
+            with torch.cuda.stream(self.stream):
+                cam, heat, peak, u8 = eng.run_gradcam(speed, cmd, wts, 4, want_u8, owner=self)
+                self.stream.synchronize()
+        else:
+            if self.model.engine() is not self.eng:
+                self.__init__(self.model, b, h, w, self.use_graph, self.half, self.persistent)
+                eng = self.eng
+            if self.model.training:
+                self.model.eval()
+            sal = self._saliency_buffers(tuple(frames.shape))
+            f_np, s_np, dc_np, ds_np, c_np = sal["host_np"]
+            np.copyto(f_np, frames)
+            s_np[...] = np.minimum(speeds / SPEED_NORM_FACTOR, 1.0)
+            dc_np[...] = wts[:3]
+            ds_np[...] = wts[3]
+            c_np[...] = cmds
+            f_dev, s_dev, dc_dev, ds_dev, c_dev = sal["dev_views"]
+            self._order_after_weight_updates()
+            with torch.cuda.stream(self.stream):
+                sal["dev"].copy_(sal["host"], non_blocking=True)
+                _, _, pl = eng.run_forward_frozen_u8(f_dev, s_dev, c_dev, h if camera else None,
+                                                     w if camera else None,
+                                                     out=(sal["ctrl"], sal["spd"]))
+                eng.run_backward(pl, dc_dev, ds_dev, data_only=True, segments=(0, 5 - lnum))
+                cam, heat, peak, u8 = eng.run_gradcam(s_dev, c_dev, wts, lnum, want_u8, owner=self)
+                sal["out_host"][:4 * b].copy_(sal["out_dev"][:4 * b], non_blocking=True)
+                self.stream.synchronize()
+            o = sal["out_np"]
+            out = np.empty((b, 4), dtype=np.float32)
+            out[:, :3] = o[:3 * b].reshape(b, 3)
+            out[:, 3] = o[3 * b:4 * b] * np.float32(SPEED_NORM_FACTOR)
+        return (out, (u8 if want_u8 else heat).numpy().copy(), cam.numpy().copy(),
+                peak.numpy().copy())

@@ -697,4 +697,32 @@ struct McHeadsArgs {
 size_t mc_heads_scratch_floats(int batch, int samples);
 int launch_mc_heads(McHeadsArgs& a, float* scratch, hipStream_t s);
 
+// ---- Grad-CAM (gradcam.hip; cilrs_heads_input_grad, cilrs_gradcam_map) --------------------------
+constexpr int kGcMaxC = 2048;             // widest trunk group (layer4 of the ResNet-50 variant)
+constexpr int kGcMaxHW = 4096;            // cells of the coarse map kept in LDS
+struct HeadsGradArgs {
+    const float* se0_w; const float* se0_b; const float* se3_w; const float* se3_b;
+    const float* br_w[kMaxCmd][3]; const float* br_b[kMaxCmd][3];
+    const float* sp0_w; const float* sp0_b; const float* sp3_w; const float* sp3_b;
+    const float* sp5_w; const float* sp5_b;
+    int ncmd, F;
+    const float* pooled; int pooled_ld;   // [B][pooled_ld] features, or NULL:
+    const float* featmap; int HW;         //   [B][HW][F] last feature map, pooled by the kernel
+    const float* speed; const long long* cmd;
+    float w[4];                           // y = w . (steer, throttle, brake, pred_speed)
+    int B;
+    float* g;                             // [B][F] dy / d pooled
+    float* out4;                          // [B][4] raw eval-mode outputs, or NULL
+    int* status;                          // may be NULL
+};
+int launch_heads_input_grad(const HeadsGradArgs& a, hipStream_t s);
+struct GradcamMapArgs {
+    const float* A;                       // [B][h][w][C]
+    const float* dA;                      // [B][h][w][C], or NULL:
+    const float* g;                       //   [B][C], dA = g / (h * w) in every cell
+    int B, h, w, C, H, W;
+    float* cam; float* peak; float* heat; unsigned char* heat_u8;
+};
+int launch_gradcam_map(const GradcamMapArgs& a, hipStream_t s);
+
 }  // namespace cilrs

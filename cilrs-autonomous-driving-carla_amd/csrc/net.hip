@@ -355,6 +355,14 @@ struct cilrs_net {
     // map (the persistent launch pools inside its head stage and keeps no pooled copy); -1 a
     // train-mode forward (batch statistics: refused)
     int mc_src = 0;
+    // cilrs_net_gradcam: arithmetic of the last forward (0 fp32, 1 fp16, 2 bf16: set with mc_src);
+    // a count of the forwards this plan has begun; the segment the last unbroken run of backward
+    // calls from segment 0 stopped at (G[3] then holds the gradient of trunk group 5 - gc_bwd_end's
+    // output; -1: none, or a call that failed midway) and the forward count it belonged to
+    int fwd_half = 0;
+    uint64_t fwd_serial = 0;
+    int gc_bwd_end = -1;
+    uint64_t gc_bwd_fwd = 0;
     // the last graph-keeping forward was cilrs_net_forward_frozen (BatchNorm on the running
     // statistics: its backward drops the batch-statistics terms)
     bool frozen_fwd = false;
@@ -1735,6 +1743,7 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
                            bool frozen = false) {
     net->ws_base = reinterpret_cast<float*>(bufs->workspace);
     net->mc_src = 0;          // until this forward has finished, its features are not there
+    ++net->fwd_serial;
     CILRS_CHECK(!(frozen && (train || half || net->bf16_train)),
                 "frozen forward: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan rejects it)");
     if (clear_status_once(net, bufs->workspace, s)) return 1;
@@ -1764,6 +1773,7 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
     net->frozen_fwd = frozen;
     net->last_dropout = pdrop;
     net->mc_src = train ? -1 : 1;
+    net->fwd_half = half;
     return 0;
 }
 
@@ -1804,7 +1814,7 @@ static int forward_ft_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const f
                               const int64_t* command, int k, uint64_t prefix_key, float dropout_p,
                               uint64_t seed, float* controls, float* pred_speed, hipStream_t s) {
     net->ws_base = reinterpret_cast<float*>(bufs->workspace);
-    net->mc_src = 0;
+    net->mc_src = 0; ++net->fwd_serial;
     if (clear_status_once(net, bufs->workspace, s)) return 1;
     net->bwd_done = 0;
     // the trainable weights / BatchNorm buffers are about to change: the cached eval state goes stale
@@ -1824,6 +1834,7 @@ static int forward_ft_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const f
     net->frozen_fwd = false;
     net->last_dropout = dropout_p;
     net->mc_src = -1;
+    net->fwd_half = 0;
     return 0;
 }
 
@@ -2196,7 +2207,7 @@ static int b1_launch(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* f
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float* ws = reinterpret_cast<float*>(bufs->workspace);
     net->ws_base = ws;
-    net->mc_src = 0;
+    net->mc_src = 0; ++net->fwd_serial;
     if (net->b1_blocks < 0) {
         int blocks = 0;
         if (infer_b1_grid(&blocks)) return 1;
@@ -2232,6 +2243,7 @@ static int b1_launch(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* f
     net->trained_fwd = false;
     net->last_dropout = 0.f;
     net->mc_src = 2;
+    net->fwd_half = 0;
     return 0;
 }
 
@@ -2371,7 +2383,7 @@ static int forward_u8_graph(cilrs_net* net, const cilrs_buffers* bufs, const uin
     if (check_bufs(net, bufs, false)) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     CILRS_CHECK(s != nullptr, "forward_u8_graph: capture needs a non-default stream");
-    net->mc_src = 0;
+    net->mc_src = 0; ++net->fwd_serial;
     const void* key[8] = {bufs->params, bufs->bn_running, bufs->workspace, frames, speed, command,
                           controls, pred_speed};
     bool same = net->graph_exec != nullptr && net->graph_half == half &&
@@ -2409,6 +2421,7 @@ static int forward_u8_graph(cilrs_net* net, const cilrs_buffers* bufs, const uin
     }
     CILRS_HIP(hipGraphLaunch(net->graph_exec, s));
     net->mc_src = 1;
+    net->fwd_half = half;
     return 0;
 }
 
@@ -2514,6 +2527,145 @@ int cilrs_net_heads_mc(cilrs_net* net, const cilrs_buffers* bufs, const float* s
 }
 
 // ------------------------------------------------------------------------------------------------
+// Grad-CAM (gradcam.hip)
+// ------------------------------------------------------------------------------------------------
+static void hg_fill(HeadsGradArgs& a, const Arch& A, const float* P) {
+    memset(&a, 0, sizeof(a));
+    a.se0_w = P + A.se0.w; a.se0_b = P + A.se0.b; a.se3_w = P + A.se3.w; a.se3_b = P + A.se3.b;
+    for (int k = 0; k < A.ncmd; ++k)
+        for (int l = 0; l < 3; ++l) { a.br_w[k][l] = P + A.br[k][l].w; a.br_b[k][l] = P + A.br[k][l].b; }
+    a.sp0_w = P + A.sp0.w; a.sp0_b = P + A.sp0.b; a.sp3_w = P + A.sp3.w; a.sp3_b = P + A.sp3.b;
+    a.sp5_w = P + A.sp5.w; a.sp5_b = P + A.sp5.b;
+    a.ncmd = A.ncmd; a.F = A.feat;
+}
+
+static int gc_weights(const char* who, const float* weights4, float* w) {
+    CILRS_CHECK(weights4 != nullptr, "%s: NULL tensor (weights4)", who);
+    for (int i = 0; i < 4; ++i) {
+        CILRS_CHECK(std::isfinite(weights4[i]), "%s: output weight %d is not finite", who, i);
+        w[i] = weights4[i];
+    }
+    return 0;
+}
+
+int cilrs_heads_input_grad(int variant, const float* params, const float* pooled, int pooled_ld,
+                           const float* featmap, int hw, const float* speed, const int64_t* command,
+                           const float* weights4, int batch, float* g, float* out4, int* status,
+                           void* stream) {
+    CILRS_CHECK(variant_ok(variant), "heads_input_grad: unknown architecture code %d", variant);
+    CILRS_CHECK(params && speed && command && g, "heads_input_grad: NULL tensor");
+    CILRS_CHECK((pooled != nullptr) != (featmap != nullptr),
+                "heads_input_grad: exactly one of pooled and featmap must be given");
+    CILRS_CHECK(batch >= 1, "heads_input_grad: batch %d", batch);
+    const Arch& A = arch(variant);
+    if (pooled) CILRS_CHECK(pooled_ld >= A.feat, "heads_input_grad: pooled_ld %d below the %d features",
+                            pooled_ld, A.feat);
+    else CILRS_CHECK(hw >= 1, "heads_input_grad: feature map of %d cells", hw);
+    CILRS_CHECK(((uintptr_t)params & 15) == 0, "heads_input_grad: params must be 16-byte aligned");
+    HeadsGradArgs a;
+    hg_fill(a, A, params);
+    if (gc_weights("heads_input_grad", weights4, a.w)) return 1;
+    a.pooled = pooled; a.pooled_ld = pooled_ld; a.featmap = featmap; a.HW = hw;
+    a.speed = speed; a.cmd = reinterpret_cast<const long long*>(command);
+    a.B = batch; a.g = g; a.out4 = out4; a.status = status;
+    return launch_heads_input_grad(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cilrs_gradcam_map(const float* A, const float* dA, const float* g, int batch, int h, int w,
+                      int channels, int H, int W, float* cam, float* peak, float* heat,
+                      uint8_t* heat_u8, void* stream) {
+    GradcamMapArgs a;
+    a.A = A; a.dA = dA; a.g = g;
+    a.B = batch; a.h = h; a.w = w; a.C = channels; a.H = H; a.W = W;
+    a.cam = cam; a.peak = peak; a.heat = heat; a.heat_u8 = heat_u8;
+    return launch_gradcam_map(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t cilrs_gradcam_scratch_floats(int variant, int batch) {
+    if (!variant_ok(variant) || batch < 1) return 0;
+    return (size_t)batch * (arch(variant).feat + 4);
+}
+
+// last convolution of trunk group `layer` (1..4)
+static int gc_group_conv(const Arch& A, int layer) {
+    const int nblk[4] = {3, 4, 6, 3};
+    int last = -1;
+    for (int L = 1; L <= layer; ++L) last += nblk[L - 1];
+    const BlockT& blk = A.blocks[last];
+    return blk.conv3 >= 0 ? blk.conv3 : blk.conv2;
+}
+
+int cilrs_net_gradcam_info(const cilrs_net* net, int layer, size_t* a_offset, size_t* da_offset,
+                           int* h, int* w, int* channels) {
+    CILRS_CHECK(net != nullptr, "gradcam_info: net is NULL");
+    CILRS_CHECK(layer >= 1 && layer <= 4, "gradcam_info: layer %d outside 1..4", layer);
+    const int ci = gc_group_conv(*net->A, layer);
+    if (a_offset) *a_offset = net->cg[ci].z;
+    if (da_offset) *da_offset = net->G[3];
+    if (h) *h = net->cg[ci].Ho;
+    if (w) *w = net->cg[ci].Wo;
+    if (channels) *channels = net->A->convs[ci].cout;
+    return 0;
+}
+
+int cilrs_net_gradcam(cilrs_net* net, const cilrs_buffers* bufs, const float* speed,
+                      const int64_t* command, const float* weights4, int layer, float* cam,
+                      float* heat, uint8_t* heat_u8, float* peak, float* scratch,
+                      size_t scratch_floats, void* stream) {
+    if (check_bufs(net, bufs, false)) return 1;
+    CILRS_CHECK(speed && command && cam && heat && peak, "net_gradcam: NULL tensor");
+    CILRS_CHECK(layer >= 1 && layer <= 4, "net_gradcam: layer %d outside 1..4", layer);
+    const Arch& A = *net->A;
+    const size_t need = (size_t)net->B * (A.feat + 4);
+    CILRS_CHECK(scratch != nullptr && scratch_floats >= need,
+                "net_gradcam: scratch of %zu floats, %zu needed", scratch_floats, need);
+    HeadsGradArgs ha;
+    hg_fill(ha, A, bufs->params);
+    if (gc_weights("net_gradcam", weights4, ha.w)) return 1;
+    CILRS_CHECK(!net->bf16_train, "net_gradcam: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan keeps "
+                "16-bit feature maps)");
+    CILRS_CHECK(net->mc_src != 0, "net_gradcam: no forward on this plan yet");
+    CILRS_CHECK(!(net->mc_src < 0 && (net->ft_grad > 0 || net->ft_bn > 0)),
+                "net_gradcam: the plan's last forward was a fine-tuning step behind a frozen prefix; "
+                "run an eval-mode forward first");
+    CILRS_CHECK(net->mc_src > 0, "net_gradcam: the plan's last forward ran in train mode (batch "
+                "statistics); run an eval-mode forward first");
+    CILRS_CHECK(net->fwd_half == 0, "net_gradcam: the plan's last forward ran a 16-bit (fp16 / bf16) "
+                "trunk, whose feature maps are 16-bit; run an fp32 forward first");
+    const int ci = gc_group_conv(A, layer);
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
+    GradcamMapArgs ma;
+    ma.A = ws + net->cg[ci].z; ma.dA = nullptr; ma.g = nullptr;
+    ma.B = net->B; ma.h = net->cg[ci].Ho; ma.w = net->cg[ci].Wo; ma.C = A.convs[ci].cout;
+    ma.H = net->H; ma.W = net->W;
+    ma.cam = cam; ma.peak = peak; ma.heat = heat; ma.heat_u8 = heat_u8;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (layer == 4) {
+        // the fast path: average pooling sits on layer4, so dA = (dy / d pooled) / (h * w)
+        if (net->mc_src == 2) {
+            ha.featmap = ma.A; ha.HW = net->featHW;
+        } else {
+            ha.pooled = ws + net->combined; ha.pooled_ld = A.feat + 128;
+        }
+        ha.speed = speed; ha.cmd = reinterpret_cast<const long long*>(command);
+        ha.B = net->B; ha.g = scratch; ha.out4 = scratch + (size_t)net->B * A.feat;
+        ha.status = reinterpret_cast<int*>(reinterpret_cast<char*>(bufs->workspace) + net->status_b);
+        ma.g = scratch;
+        RUN(net, "gradcam", 4.0 * net->B * 180480.0, 0.0, s, launch_heads_input_grad(ha, s));
+    } else {
+        // the graph path: the data-gradient chain stopped at this group's boundary, G[3] holds dA
+        CILRS_CHECK(net->trained_fwd && net->frozen_fwd && net->gc_bwd_fwd == net->fwd_serial &&
+                    net->gc_bwd_end == 5 - layer,
+                    "net_gradcam: layer %d needs cilrs_net_forward_frozen* followed by "
+                    "cilrs_net_backward[_data] over segments [0, %d) on this plan: no matching "
+                    "backward", layer, 5 - layer);
+        ma.dA = ws + net->G[3];
+    }
+    RUN(net, "gradcam", 2.0 * net->B * ma.h * ma.w * ma.C, 0.0, s, launch_gradcam_map(ma, s));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------
 static int backward_heads(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
@@ -2571,6 +2723,11 @@ static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float*
     //  leaves d(stem conv output) in)
     if (seg_begin == 0) net->bwd_done = 0;
     if (seg_begin <= 5 && seg_end > 1) net->bwd_done &= ~(1u << 5);
+    // where G[3] stands once this call has gone through (cilrs_net_gradcam): a run from segment 0,
+    // or the continuation of one on the same forward; until then nothing
+    const bool gc_run = seg_begin == 0 || (net->gc_bwd_fwd == net->fwd_serial &&
+                                           net->gc_bwd_end == seg_begin);
+    net->gc_bwd_end = -1;
     for (int seg = seg_begin; seg < seg_end; ++seg) {
         if (seg == 0) {
             CILRS_CHECK(dcontrols && dpred_speed, "backward: output gradients missing");
@@ -2800,6 +2957,7 @@ static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float*
         CILRS_HIP(hipEventRecord(net->fork_ev, net->side[0]));
         CILRS_HIP(hipStreamWaitEvent(s, net->fork_ev, 0));
     }
+    if (gc_run) { net->gc_bwd_end = seg_end; net->gc_bwd_fwd = net->fwd_serial; }
     return 0;
 }
 

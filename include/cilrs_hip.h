@@ -285,6 +285,78 @@ int cilrs_net_heads_mc(cilrs_net* net, const cilrs_buffers* bufs, const float* s
                        float* mean, float* std, float* samples_out,
                        float* scratch, size_t scratch_floats, void* stream);
 
+/* ---- Grad-CAM: class-activation maps of a trunk group (csrc/gradcam.hip) -----------------------
+ * Which region of the feature map carried an output.  The reference has no such path (its
+ * DashboardHUD, autonomous_drive.py:178-355, draws the outputs only); parity is pinned by this
+ * definition (restated in float64 by tests/_gradcam.py).  Per frame:
+ *   y        = w . (steer, throttle, brake, pred_speed) on the raw eval-mode outputs (no dropout,
+ *            the commanded branch only; pred_speed not multiplied by 90), w four finite weights.
+ *            A command outside 0..NC-1 uses branch 0 and sets status word 0, as everywhere else.
+ *   A        the post-ReLU output of trunk group L (layer1..layer4), NHWC [h][w][C]; at 88x200
+ *            layer4 is 3x7x512.
+ *   dA       dy / dA.  For layer4, where AdaptiveAvgPool2d sits directly on A
+ *            (autonomous_drive.py:365-370), dA[c,i,j] = g[c] / (h*w) with g = dy / d pooled, which
+ *            the heads give alone: dh2 = relu'(h2) W_k5^T w[0..2], dh1 = relu'(h1) W_k3^T dh2, the
+ *            first F columns of W_k0^T dh1; dp2 = relu'(p2) W_p5^T w[3], dp1 = relu'(p1) W_p3^T dp2,
+ *            W_p0^T dp1; g = branch part + speed-predictor part, added in that order (names as in
+ *            the Monte-Carlo section above, k the commanded branch; relu'(x) = 1 where x > 0).
+ *   alpha[c] = (1/(h*w)) sum_ij dA[c,i,j]          (given g: g[c] / (h*w), one fp32 division)
+ *   cam[i,j] = sum_c alpha[c] A[c,i,j]             signed, returned as it is
+ *   peak     = max_ij max(cam, 0)
+ *   n        = max(cam, 0) / peak, and 0 everywhere when peak == 0 (never NaN)
+ *   heat[y,x] float32 [H][W]: the bilinear interpolation of n at the network resolution with
+ *            half-pixel centres -- source coordinate (y + 0.5) * h / H - 0.5 clamped to [0, h-1], the
+ *            upper neighbour clamped to h-1, likewise in x: F.interpolate(mode="bilinear",
+ *            align_corners=False).  Coordinates and blend in double, rounded to fp32 once.
+ *   heat_u8  = floor(heat * 255 + 0.5) in fp32; optional.
+ * Every sum runs in a fixed order without atomics: results are bit-identical from run to run and a
+ * frame's result does not depend on the batch it sits in.
+ *
+ * cilrs_heads_input_grad: the eval-mode heads forward and backward to g [B][F] (F = 512 / 2048), one
+ * launch.  Features: exactly one of `pooled` ([B][pooled_ld], features first) and `featmap` (an
+ * fp32 map [B][hw][F], which the kernel pools in cell order).  out4 [B][4]: the raw outputs, or
+ * NULL.  weights4: HOST memory.  `variant`: the architecture code trunk | num_commands << 8, both
+ * trunks, 1..8 commands.  status: a device int (set to 1 on an out-of-range command) or NULL.
+ * cilrs_gradcam_map: alpha, cam [B][h][w], peak [B], heat [B][H][W] and optionally heat_u8 from
+ * A [B][h][w][C] and exactly one of dA (same shape) and g [B][C]; one launch, one workgroup per
+ * frame.  C in {64, 128, 256, 512, 1024, 2048}; h * w <= 4096.
+ * cilrs_net_gradcam: the map of trunk group `layer` (1..4) on what the plan's last forward left.
+ *   layer 4  after any fp32 eval-mode forward -- cilrs_net_forward(train = 0), _frozen*, _u8, _camera,
+ *            _u8_graph, the persistent single-frame forms: A is the stored last feature map, g comes
+ *            from cilrs_heads_input_grad on the plan's pooled features (after a persistent launch:
+ *            on the stored map); two launches, no backward pass needed.
+ *   any other layer  after cilrs_net_forward_frozen* followed by cilrs_net_backward[_data] calls
+ *            that began at segment 0 and ended exactly at segment 5 - layer: dA is the gradient the
+ *            chain left at that group's boundary; y is then whatever dcontrols / dpred_speed that
+ *            backward was given, and weights4 is only checked.  One launch.
+ *   cam [B][h][w] (h, w, C: cilrs_net_gradcam_info), heat [B][H][W] and heat_u8 at the plan's frame
+ *   size, peak [B]; heat_u8 may be NULL; outputs may be pinned host memory.  scratch: caller's device
+ *   memory of cilrs_gradcam_scratch_floats(variant, batch) floats (0 for an unknown code or a
+ *   non-positive batch); after a layer-4 call it holds g [B][F] followed by the raw outputs [B][4].
+ *   No launch of any other entry changes, nor does the workspace layout.
+ * cilrs_net_gradcam_info: workspace offsets (in floats) of A and of the boundary gradient, and the
+ * map's shape, for trunk group `layer`.
+ * Refused (non-zero, text in cilrs_last_error, nothing launched): NULL tensors; non-positive sizes;
+ * an unknown architecture code; both or neither of pooled / featmap, of dA / g; non-finite weights;
+ * a channel count or a cell count outside the above; a scratch smaller than asked; at plan level a
+ * layer outside 1..4, no forward yet, a train-mode forward last, a fine-tuning step (frozen prefix)
+ * last, a 16-bit (fp16 / bf16) forward last (its maps are 16-bit), a CILRS_PLAN_BF16_TRAIN plan, and
+ * layers 1..3 without a matching backward (none, another forward since, or another end segment). */
+int cilrs_heads_input_grad(int variant, const float* params, const float* pooled, int pooled_ld,
+                           const float* featmap, int hw, const float* speed, const int64_t* command,
+                           const float* weights4, int batch, float* g, float* out4, int* status,
+                           void* stream);
+int cilrs_gradcam_map(const float* A, const float* dA, const float* g, int batch, int h, int w,
+                      int channels, int H, int W, float* cam, float* peak, float* heat,
+                      uint8_t* heat_u8, void* stream);
+size_t cilrs_gradcam_scratch_floats(int variant, int batch);
+int cilrs_net_gradcam_info(const cilrs_net* net, int layer, size_t* a_offset, size_t* da_offset,
+                           int* h, int* w, int* channels);
+int cilrs_net_gradcam(cilrs_net* net, const cilrs_buffers* bufs, const float* speed,
+                      const int64_t* command, const float* weights4, int layer, float* cam,
+                      float* heat, uint8_t* heat_u8, float* peak, float* scratch,
+                      size_t scratch_floats, void* stream);
+
 /* Same, fed with uint8 RGB HWC frames [B,H,W,3]: fuses preprocess_image's /255, HWC->CHW and
  * Normalize(mean,std) (autonomous_drive.py:897-902; the cv2.resize is the caller's). */
 int cilrs_net_forward_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
