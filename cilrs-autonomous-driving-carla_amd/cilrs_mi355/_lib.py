@@ -134,6 +134,12 @@ SIGNATURES = {
     "cilrs_adam_step_groups": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, vp, f64, f64, f64, f64, vp, f32,
                                      vp]),
     "cilrs_scale": (i32, [vp, sz, vp, f32, vp]),
+    "cilrs_ema_update": (i32, [vp, vp, sz, f32, vp]),
+    "cilrs_adam_step_ema": (i32, [vp, vp, vp, vp, sz, f64, f64, f64, f64, f64, i64, vp, f32, vp, f32,
+                                  vp]),
+    "cilrs_adam_step_groups_ema": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, vp, f64, f64, f64, f64, vp,
+                                         f32, vp, f32, vp]),
+    "cilrs_swap": (i32, [vp, vp, sz, vp]),
     "cilrs_augment_u8": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
     "cilrs_batch_assemble": (i32, [vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,
                                    vp]),

@@ -8,6 +8,12 @@ reference stored numpy scalars, which is why its loader needs a numpy._core shim
 ``optimizer_state_dict`` is in torch.optim.Adam's own format (142 entries, parameters() order);
 ``step`` is per parameter, as there: a tensor that sat out fine-tuning steps while frozen has a
 smaller one (and zero moments if it never stepped).
+
+With an EMA of the weights (TrainConfig.ema_decay) ``checkpoint_latest.pth`` also carries
+``ema_state_dict`` (the averaged parameters, keyed like the model's) and ``ema_updates``, and
+``save_best(..., ema=True)`` stores the averaged parameters as ``model_state_dict`` -- same 250
+keys, BatchNorm buffers from the live model, so the reference's strict load is unchanged -- plus
+``"ema": {"decay", "updates"}``.  Without an EMA every file has the keys it always had.
 """
 from __future__ import annotations
 
@@ -63,16 +69,32 @@ def load_optimizer_state_dict(trainer, sd):
     trainer.lr = float(sd["param_groups"][0]["lr"])
 
 
-def save_best(path, model, trainer, epoch, val_loss, val_steer, cmd_steer_errors, config=None):
-    """notebook/notebook.ipynb:631-636."""
-    cfg = config if config is not None else dict(trainer.cfg.__dict__)
-    torch.save({
-        "epoch": int(epoch), "model_state_dict": model_state_dict(model),
+def _config_dict(trainer):
+    """TrainConfig as a plain dict; the EMA fields appear only when the EMA is on."""
+    cfg = dict(trainer.cfg.__dict__)
+    if cfg.get("ema_decay") is None:
+        cfg.pop("ema_decay", None)
+        cfg.pop("ema_warmup", None)
+    return cfg
+
+
+def save_best(path, model, trainer, epoch, val_loss, val_steer, cmd_steer_errors, config=None,
+              ema=False):
+    """notebook/notebook.ipynb:631-636.  ema=True: the averaged parameters (trainer.ema) take the
+    place of the raw ones in ``model_state_dict``; BatchNorm buffers are the live model's."""
+    cfg = config if config is not None else _config_dict(trainer)
+    sd = model_state_dict(model)
+    d = {
+        "epoch": int(epoch), "model_state_dict": sd,
         "optimizer_state_dict": optimizer_state_dict(trainer),
         "val_loss": float(val_loss), "val_steer": float(val_steer),
         "config": {k: (list(v) if isinstance(v, tuple) else v) for k, v in cfg.items()},
         "cmd_steer_errors": {k: float(v) for k, v in cmd_steer_errors.items()},
-    }, path)
+    }
+    if ema:
+        sd.update(trainer.ema_state_dict())        # parameters only: the key set stays the model's
+        d["ema"] = {"decay": float(trainer.ema_decay), "updates": int(trainer.ema_updates)}
+    torch.save(d, path)
 
 
 def save_latest(path, model, trainer, epoch, loop_state=None):
@@ -87,6 +109,9 @@ def save_latest(path, model, trainer, epoch, loop_state=None):
     }
     if loop_state is not None:
         d["loop_state"] = loop_state
+    if getattr(trainer, "ema", None) is not None:       # raw weights above, the average beside them
+        d["ema_state_dict"] = trainer.ema_state_dict()
+        d["ema_updates"] = int(trainer.ema_updates)
     torch.save(d, path)
 
 
@@ -126,6 +151,12 @@ def load(path, model, trainer=None, map_location=None):
         load_optimizer_state_dict(trainer, ck["optimizer_state_dict"])
         if "scheduler_state_dict" in ck:
             trainer.epoch = int(ck["scheduler_state_dict"]["last_epoch"])
+    if trainer is not None and getattr(trainer, "ema", None) is not None:
+        if "ema_state_dict" in ck:
+            trainer.load_ema_state_dict(ck["ema_state_dict"])
+            trainer.ema_updates = int(ck.get("ema_updates", 0))
+        else:                       # a file without an average: it starts from the loaded weights
+            trainer.ema_reset()
     return ck
 
 

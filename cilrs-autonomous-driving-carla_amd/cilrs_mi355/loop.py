@@ -59,9 +59,18 @@ def train_one_epoch(trainer, batches):
 
 
 def fit(trainer, train_batches, val_batches, epochs=20, patience=6, out_dir=".", resume=None,
-        log=print):
+        log=print, validate_ema=None):
     """``train_batches`` / ``val_batches``: callables returning an iterable of
-    (imgs, speeds, cmds, tgts) device batches for one epoch."""
+    (imgs, speeds, cmds, tgts) device batches for one epoch.
+
+    validate_ema (None = on when the trainer keeps an EMA of the weights, TrainConfig.ema_decay):
+    the validation pass, the early-stopping decision and ``checkpoint_best.pth`` use the averaged
+    weights.  ``checkpoint_latest.pth`` always holds the raw weights, with the average beside
+    them, so that a resume continues the same trajectory."""
+    has_ema = getattr(trainer, "ema", None) is not None
+    use_ema = has_ema if validate_ema is None else bool(validate_ema)
+    if use_ema and not has_ema:
+        raise ValueError("fit(validate_ema=True): the trainer keeps no EMA (TrainConfig.ema_decay)")
     # data parallel: metrics are all-reduced (Trainer.validate / train_one_epoch), so every rank
     # takes the same decisions; rank 0 alone writes the checkpoints and the history
     writer = trainer.rank == 0
@@ -89,7 +98,8 @@ def fit(trainer, train_batches, val_batches, epochs=20, patience=6, out_dir=".",
         t0 = time.time()
         lr = trainer.lr
         tr = train_one_epoch(trainer, train_batches())
-        va, cmd = trainer.validate(val_batches())
+        va, cmd = trainer.validate(val_batches(), ema=True) if use_ema else \
+            trainer.validate(val_batches())
         trainer.scheduler_step()                                   # nb:604
         dt = time.time() - t0
         row = {"epoch": epoch, "lr": lr, "time": dt}
@@ -104,7 +114,7 @@ def fit(trainer, train_batches, val_batches, epochs=20, patience=6, out_dir=".",
             best_val, best_epoch, bad = va["total"], epoch, 0
             if writer:
                 checkpoint.save_best(best_path, trainer.model, trainer, epoch, va["total"],
-                                     va["steer"], cmd)
+                                     va["steer"], cmd, ema=use_ema)
         else:
             bad += 1
         if writer:

@@ -7,7 +7,9 @@ Also the evaluation loop body (``validate``, nb:563-585) and StepLR (nb:535-536,
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import math
 from dataclasses import dataclass, field
 
 import torch
@@ -37,6 +39,14 @@ class TrainConfig:
     # "heads"; missing = 1.0) -- the lower trunk rate that is usual on top of a pretrained trunk.
     # None, or all 1.0: the step is the single-rate step, launch for launch.
     lr_mult: dict = None
+    # exponential moving average of the weights, updated on every optimizer step by a streaming
+    # pass behind the Adam launch (Trainer.ema; Trainer.ema_fused moves it into the launch;
+    # include/cilrs_hip.h "exponential moving average"): the decay d, 0 <= d < 1;
+    # None = off, and then no launch, file or checkpoint differs.  ema_warmup: the decay of update
+    # t (1-based) is min(d, (1 + t) / (10 + t)), so that the first steps are not averaged with the
+    # initialisation at full weight.
+    ema_decay: float = None
+    ema_warmup: bool = True
 
 
 GROUP_NAMES = ("stem", "layer1", "layer2", "layer3", "layer4", "heads")
@@ -53,6 +63,28 @@ def steplr(cfg: TrainConfig, epoch: int) -> float:
     return cfg.lr * (cfg.lr_gamma ** (epoch // cfg.lr_step_size))
 
 
+def ema_decay_at(decay: float, t: int, warmup: bool = True) -> float:
+    """Decay of the t-th EMA update (1-based), in double."""
+    d = float(decay)
+    return min(d, (1.0 + t) / (10.0 + t)) if warmup else d
+
+
+def ema_weight(decay: float, t: int, warmup: bool = True) -> float:
+    """w of `ema = ema + w * (p - ema)` for update t: 1 - d_t in double, rounded to fp32 once."""
+    return C.c_float(1.0 - ema_decay_at(decay, t, warmup)).value
+
+
+def check_ema_decay(decay):
+    """float(decay) if it is a usable decay (finite, 0 <= d < 1), else ValueError."""
+    try:
+        d = float(decay)
+    except (TypeError, ValueError):
+        raise ValueError(f"ema_decay must be a number in [0, 1) or None, got {decay!r}") from None
+    if not (math.isfinite(d) and 0.0 <= d < 1.0):
+        raise ValueError(f"ema_decay must be finite and in [0, 1), got {decay!r}")
+    return d
+
+
 CONFIG_A = TrainConfig()
 CONFIG_B = TrainConfig(name="B", lr=1e-4, loss="l1", loss_weights=(5.0, 1.0, 1.0, 0.5),
                        grad_clip=1.0, dropout=0.5)
@@ -66,6 +98,7 @@ class Trainer:
         to bf16 rounding, not to 1e-4."""
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16'")
+        ema_decay = None if cfg.ema_decay is None else check_ema_decay(cfg.ema_decay)
         self.model = model
         self.cfg = cfg
         self.eng = model.engine()
@@ -106,6 +139,24 @@ class Trainer:
         # averaged gradient is there (the last, small bucket's collective runs under the first two
         # buckets' updates)
         self.bucket_optimizer = True
+        # EMA of the weights: fp32 over the fp32 master arena in every precision mode, a copy of the
+        # parameters now.  BatchNorm buffers are not averaged (running statistics already are
+        # moving averages; the averaged weights are evaluated with the live model's buffers).
+        self.ema_decay = ema_decay
+        self.ema = self.eng.params.clone() if ema_decay is not None else None
+        self.ema_updates = 0
+        # False: Adam, then cilrs_ema_update over the same range; True: the average is updated
+        # inside the Adam launch (cilrs_adam_step_ema) -- the same numbers bit for bit.  By bytes
+        # the fused launch should win (9 arena-sized arrays against 10 and a launch); measured it
+        # does not: 0.157 ms against 0.147 ms over the arena (Adam alone 0.107; a hypothesis, no
+        # counters taken: the separate pass finds the parameters Adam has just written in the
+        # last-level cache).  In the B=128 step the fused route reads 0.022 ms faster, inside the
+        # larger spread of 0.025 ms (profiles/ema_bench.log).  By the rule
+        # set before measuring -- fused only if it wins over the arena -- the separate pass is
+        # the default.
+        self.ema_fused = False
+        self._ema_w = 0.0
+        self._in_ema = False
         self.reducer = None
         self.rank = 0
         if process_group is not None:
@@ -153,15 +204,36 @@ class Trainer:
         return e, g
 
     def _advance_steps(self, frozen_groups):
-        """One optimizer step begins: the trainable groups count it, the frozen ones sit it out."""
+        """One optimizer step begins: the trainable groups count it, the frozen ones sit it out.
+        With EMA on it is also one EMA update: its weight is fixed here, once, for every range the
+        step updates, and the frozen prefix -- which no Adam launch visits -- is averaged by a
+        pass of its own (a group that was trained, then frozen, keeps converging to its
+        parameters; where ema == p already the pass changes nothing)."""
         self.step_count += 1
         for i in range(frozen_groups):
             self.group_lag[i] += 1
+        if self.ema is None:
+            return
+        self.ema_updates += 1
+        self._ema_w = ema_weight(self.ema_decay, self.ema_updates, self.cfg.ema_warmup)
+        begin = self.eng.trainable_begin(frozen_groups)
+        if begin > 0:
+            self._ema_pass(0, begin)
+
+    def _ema_pass(self, b, e):
+        L.check(L.lib().cilrs_ema_update(L.ptr(self.ema[b:e]), L.ptr(self.eng.params[b:e]), e - b,
+                                         self._ema_w, self._stream()))
+
+    def _refuse_inside_ema_weights(self, what):
+        if self._in_ema:
+            raise RuntimeError(f"Trainer.{what} inside `with trainer.ema_weights():` -- the arena "
+                               "holds the averaged weights there; leave the context first")
 
     def optimizer_step(self, grad_scale=1.0):
         """clip_grad_norm_ (nb:553-554) + Adam.step (nb:555) over the flat arena -- over its
         trainable range when a prefix of the trunk is frozen (frozen parameters and their moments
         are not touched and take no weight decay, like torch.optim.Adam's `grad is None`)."""
+        self._refuse_inside_ema_weights("optimizer_step")
         lib = L.lib()
         eng, cfg = self.eng, self.cfg
         e, g = self._freeze_state()
@@ -186,6 +258,11 @@ class Trainer:
     # -- one iteration of train_one_epoch's loop (nb:549-555) ------------------------------------
     def train_step(self, imgs, speeds, cmds, tgts):
         """Returns the device loss buffer [>=6] (LOSS_KEYS order); reading it is the only sync."""
+        self._refuse_inside_ema_weights("train_step")
+        if self.ema is not None and self.fuse_optimizer:
+            raise RuntimeError("Trainer.fuse_optimizer cannot serve ema_decay: cilrs_net_backward_"
+                               "step's per-segment Adam launches carry no average (leave "
+                               "fuse_optimizer off, the default)")
         eng = self._ensure_engine()
         if not self.model.training:
             self.model.train()
@@ -235,7 +312,9 @@ class Trainer:
         already advanced).  Adjacent parameter groups that share learning rate and step
         count form one run; one run is the plain cilrs_adam_step launch, several (lr_mult, or
         an earlier freeze that tells the groups' step counts apart) go to the table-driven
-        launch."""
+        launch.  With EMA on, each of the two is followed by cilrs_ema_update over the same
+        range, or (ema_fused) replaced by its form with the average fused in (cilrs_adam_step_ema /
+        _groups_ema); this step's weight on every range."""
         eng, cfg = self.eng, self.cfg
         steps = self.group_steps
         runs = []                             # [begin, end, lr, step]
@@ -252,12 +331,22 @@ class Trainer:
         if not runs:
             return
         b, e = runs[0][0], runs[-1][1]
+        fused_ema = self.ema is not None and self.ema_fused
         if len(runs) == 1:
             _, _, lr, step = runs[0]
+            if fused_ema:
+                L.check(L.lib().cilrs_adam_step_ema(
+                    L.ptr(eng.params[b:e]), L.ptr(eng.grads[b:e]), L.ptr(self.exp_avg[b:e]),
+                    L.ptr(self.exp_avg_sq[b:e]), e - b, lr, cfg.betas[0], cfg.betas[1], cfg.eps,
+                    cfg.weight_decay, step, clip_ptr, float(grad_scale), L.ptr(self.ema[b:e]),
+                    self._ema_w, self._stream()))
+                return
             L.check(L.lib().cilrs_adam_step(
                 L.ptr(eng.params[b:e]), L.ptr(eng.grads[b:e]), L.ptr(self.exp_avg[b:e]),
                 L.ptr(self.exp_avg_sq[b:e]), e - b, lr, cfg.betas[0], cfg.betas[1], cfg.eps,
                 cfg.weight_decay, step, clip_ptr, float(grad_scale), self._stream()))
+            if self.ema is not None:
+                self._ema_pass(b, e)
             return
         # several rates / step counts: still one launch, the kernel looks them up per range
         # (range launches cost 0.044 ms per step at B=128, DESIGN.md "Fine-tuning")
@@ -265,10 +354,90 @@ class Trainer:
         ends = (C.c_size_t * k)(*[r[1] - b for r in runs])
         lrs = (C.c_double * k)(*[r[2] for r in runs])
         steps = (C.c_int64 * k)(*[r[3] for r in runs])
+        if fused_ema:
+            L.check(L.lib().cilrs_adam_step_groups_ema(
+                L.ptr(eng.params[b:e]), L.ptr(eng.grads[b:e]), L.ptr(self.exp_avg[b:e]),
+                L.ptr(self.exp_avg_sq[b:e]), e - b, k, ends, lrs, steps, cfg.betas[0],
+                cfg.betas[1], cfg.eps, cfg.weight_decay, clip_ptr, float(grad_scale),
+                L.ptr(self.ema[b:e]), self._ema_w, self._stream()))
+            return
         L.check(L.lib().cilrs_adam_step_groups(
             L.ptr(eng.params[b:e]), L.ptr(eng.grads[b:e]), L.ptr(self.exp_avg[b:e]),
             L.ptr(self.exp_avg_sq[b:e]), e - b, k, ends, lrs, steps, cfg.betas[0], cfg.betas[1],
             cfg.eps, cfg.weight_decay, clip_ptr, float(grad_scale), self._stream()))
+        if self.ema is not None:
+            self._ema_pass(b, e)
+
+    # -- EMA of the weights ------------------------------------------------------------------------
+    def _need_ema(self):
+        if self.ema is None:
+            raise RuntimeError("this Trainer keeps no EMA of the weights (TrainConfig.ema_decay)")
+
+    def ema_reset(self):
+        """The average starts over: a copy of the parameters as they are now, no updates made."""
+        self._need_ema()
+        self._refuse_inside_ema_weights("ema_reset")
+        self.ema.copy_(self.eng.params)
+        self.ema_updates = 0
+
+    def ema_state_dict(self):
+        """The averaged parameters, keyed and shaped like ``model.state_dict()``'s parameter
+        entries (CPU clones).  BatchNorm buffers are not averaged and not in it."""
+        self._need_ema()
+        from .engine import _arena_view
+        src = self.eng.params if self._in_ema else self.ema    # swapped inside ema_weights()
+        return {name: _arena_view(src, off, numel, shape).detach().cpu().contiguous().clone()
+                for name, off, numel, shape in self.eng.params_layout}
+
+    def load_ema_state_dict(self, sd):
+        """Inverse of ema_state_dict (the update count is `ema_updates`, set by the caller)."""
+        self._need_ema()
+        self._refuse_inside_ema_weights("load_ema_state_dict")
+        from .engine import _arena_view
+        want = [p[0] for p in self.eng.params_layout]
+        missing, extra = [k for k in want if k not in sd], [k for k in sd if k not in set(want)]
+        if missing or extra:
+            raise KeyError(f"ema_state_dict: missing {missing[:3]}, unexpected {extra[:3]}")
+        with torch.no_grad():
+            for name, off, numel, shape in self.eng.params_layout:
+                if tuple(sd[name].shape) != tuple(shape):
+                    raise ValueError(f"ema_state_dict: {name} has shape {tuple(sd[name].shape)}, "
+                                     f"expected {tuple(shape)}")
+                _arena_view(self.ema, off, numel, shape).copy_(sd[name])
+
+    def _swap_ema(self):
+        # Predictor and the inference lanes run on streams of their own: the exchange is fenced
+        # against the whole device on both sides (it happens once per validation, not per step)
+        dev = self.eng.device
+        torch.cuda.synchronize(dev)
+        L.check(L.lib().cilrs_swap(L.ptr(self.eng.params), L.ptr(self.ema), self.eng.n_arena,
+                                   self._stream()))
+        torch.cuda.synchronize(dev)
+        self.model.weights_changed()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with trainer.ema_weights():`` -- the model IS the averaged model inside: the averaged
+        parameters are swapped into the arena (cilrs_swap; the plans keep their pointers) and the
+        weights epoch is bumped, so ``model(...)``, Predictor and evaluate.py work unchanged, with
+        the live BatchNorm buffers.  On exit, also on an exception, the raw parameters are swapped
+        back.  No train_step / optimizer_step inside; not re-entrant."""
+        self._need_ema()
+        self._ensure_engine()
+        if self._in_ema:
+            raise RuntimeError("Trainer.ema_weights() is not re-entrant")
+        self._swap_ema()
+        self._in_ema = True
+        try:
+            yield self
+        finally:
+            try:
+                self._swap_ema()
+            finally:
+                # also when the exchange back itself failed (a device error): the Trainer is not
+                # left locked; the arena may then still hold the averaged weights, and the error
+                # that says so propagates
+                self._in_ema = False
 
     def next_dropout_seed(self):
         """Seed of the next train step's dropout masks: torch's seed, the step count and the
@@ -298,9 +467,16 @@ class Trainer:
         self.lr = steplr(self.cfg, self.epoch)
 
     # -- validate() (nb:563-585) -------------------------------------------------------------------
+    def validate(self, batches, ema=False):
+        """mean of batch means + per-command mean |steer error|, like the reference.  ema=True:
+        of the averaged weights (inside ``ema_weights()``)."""
+        if ema:
+            with self.ema_weights():
+                return self._validate(batches)
+        return self._validate(batches)
+
     @torch.no_grad()
-    def validate(self, batches):
-        """mean of batch means + per-command mean |steer error|, like the reference."""
+    def _validate(self, batches):
         self.model.eval()
         sums = torch.zeros(6, dtype=torch.float64)
         # (the reference's validate is written for its four commands, nb:566; a model built with more

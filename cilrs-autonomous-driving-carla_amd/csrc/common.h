@@ -656,6 +656,18 @@ int launch_adam_groups(float* p, const float* g, float* m, float* v, size_t n, i
                        double beta2, double eps, double wd, const float* clip_out, float gscale,
                        hipStream_t s);
 int launch_scale(float* g, size_t n, const float* coef_ptr, float c, hipStream_t s);
+// exponential moving average of the weights (heads_optim.hip): the stand-alone pass, the in-place
+// exchange of two arrays, and launch_adam / launch_adam_groups with the average fused in
+int launch_ema_update(float* ema, const float* p, size_t n, float w, hipStream_t s);
+int launch_swap(float* a, float* b, size_t n, hipStream_t s);
+int launch_adam_ema(float* p, const float* g, float* m, float* v, size_t n, double lr,
+                    double beta1, double beta2, double eps, double wd, long long step,
+                    const float* clip_out, float gscale, float* ema, float ema_w, hipStream_t s);
+int launch_adam_groups_ema(float* p, const float* g, float* m, float* v, size_t n, int ngroups,
+                           const size_t* ends, const double* lrs, const long long* steps,
+                           double beta1, double beta2, double eps, double wd,
+                           const float* clip_out, float gscale, float* ema, float ema_w,
+                           hipStream_t s);
 int launch_keep_head_inputs(const float* speed, const long long* cmd, float* speed_dst,
                             long long* cmd_dst, int B, hipStream_t s);
 

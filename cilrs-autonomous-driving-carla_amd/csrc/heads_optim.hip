@@ -645,6 +645,113 @@ __global__ __launch_bounds__(256) void adam_table_kernel(float* __restrict__ p,
     }
 }
 
+// ---- exponential moving average of the weights ---------------------------------------------------
+// Rides on the optimizer step (notebook/notebook.ipynb:555); the reference keeps no such average,
+// include/cilrs_hip.h states the definition: ema = ema + w * (p - ema), three separately rounded
+// fp32 operations.  hipcc contracts a * b + c to an FMA by default, hence plain operators under
+// `#pragma clang fp contract(off)` (attribution.hip has the measurement); the pragma is scoped to
+// this function so that the Adam arithmetic around it contracts exactly as adam_kernel's does.
+__device__ __forceinline__ float ema_lerp(const float e, const float p, const float w) {
+#pragma clang fp contract(off)
+    const float d = p - e;
+    const float s = w * d;
+    return e + s;
+}
+
+// The stand-alone pass: one read of p, one read and one write of ema.
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema,
+                                                  const float* __restrict__ p, const size_t n4,
+                                                  const float w) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+         i += (size_t)gridDim.x * blockDim.x) {
+        const f32x4 pv = *reinterpret_cast<const f32x4*>(p + i * 4);
+        f32x4 ev = *reinterpret_cast<const f32x4*>(ema + i * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ev[e] = ema_lerp(ev[e], pv[e], w);
+        *reinterpret_cast<f32x4*>(ema + i * 4) = ev;
+    }
+}
+
+// a <-> b in one pass (the averaged weights go into the parameter arena and out again: the plans
+// cache the arena's address)
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b,
+                                                   const size_t n4) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+         i += (size_t)gridDim.x * blockDim.x) {
+        const f32x4 av = *reinterpret_cast<const f32x4*>(a + i * 4);
+        const f32x4 bv = *reinterpret_cast<const f32x4*>(b + i * 4);
+        *reinterpret_cast<f32x4*>(a + i * 4) = bv;
+        *reinterpret_cast<f32x4*>(b + i * 4) = av;
+    }
+}
+
+// adam_kernel / adam_table_kernel with the average fused in: their loop bodies restated statement
+// for statement (so that the compiler contracts the Adam expressions exactly as it does there),
+// then the EMA line on the just-computed parameter while it is still in a register.
+__global__ __launch_bounds__(256) void adam_ema_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+    float* __restrict__ v, float* __restrict__ ema, const size_t n4, const float omb1,
+    const float beta2, const float omb2, const float eps, const float wd,
+    const float neg_step_size, const float bc2_sqrt, const float* __restrict__ gscale_ptr,
+    const float gscale_const, const float ema_w) {
+    const float gs = gscale_ptr ? gscale_ptr[1] * gscale_const : gscale_const;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+         i += (size_t)gridDim.x * blockDim.x) {
+        f32x4 pv = *reinterpret_cast<const f32x4*>(p + i * 4);
+        f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
+        f32x4 mv = *reinterpret_cast<const f32x4*>(m + i * 4);
+        f32x4 vv = *reinterpret_cast<const f32x4*>(v + i * 4);
+        f32x4 ev = *reinterpret_cast<const f32x4*>(ema + i * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float gg = gv[e] * gs;                             // clip_grad_norm_ scaling
+            gg = gg + wd * pv[e];                              // grad.add(param, alpha=wd)
+            mv[e] = mv[e] + omb1 * (gg - mv[e]);               // exp_avg.lerp_(grad, 1-beta1)
+            vv[e] = vv[e] * beta2 + (omb2 * gg) * gg;          // mul_(beta2).addcmul_(g,g,1-beta2)
+            const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
+            pv[e] = pv[e] + (neg_step_size * mv[e]) / denom;   // addcdiv_(exp_avg, denom, -step)
+            ev[e] = ema_lerp(ev[e], pv[e], ema_w);
+        }
+        *reinterpret_cast<f32x4*>(p + i * 4) = pv;
+        *reinterpret_cast<f32x4*>(m + i * 4) = mv;
+        *reinterpret_cast<f32x4*>(v + i * 4) = vv;
+        *reinterpret_cast<f32x4*>(ema + i * 4) = ev;
+    }
+}
+
+__global__ __launch_bounds__(256) void adam_table_ema_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+    float* __restrict__ v, float* __restrict__ ema, const size_t n4, const float omb1,
+    const float beta2, const float omb2, const float eps, const float wd, const AdamTable t,
+    const float* __restrict__ gscale_ptr, const float gscale_const, const float ema_w) {
+    const float gs = gscale_ptr ? gscale_ptr[1] * gscale_const : gscale_const;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+         i += (size_t)gridDim.x * blockDim.x) {
+        int r = 0;
+        while (r + 1 < t.n && i >= t.end4[r]) ++r;
+        const float neg_step_size = t.neg_step_size[r], bc2_sqrt = t.bc2_sqrt[r];
+        f32x4 pv = *reinterpret_cast<const f32x4*>(p + i * 4);
+        f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
+        f32x4 mv = *reinterpret_cast<const f32x4*>(m + i * 4);
+        f32x4 vv = *reinterpret_cast<const f32x4*>(v + i * 4);
+        f32x4 ev = *reinterpret_cast<const f32x4*>(ema + i * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float gg = gv[e] * gs;
+            gg = gg + wd * pv[e];
+            mv[e] = mv[e] + omb1 * (gg - mv[e]);
+            vv[e] = vv[e] * beta2 + (omb2 * gg) * gg;
+            const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
+            pv[e] = pv[e] + (neg_step_size * mv[e]) / denom;
+            ev[e] = ema_lerp(ev[e], pv[e], ema_w);
+        }
+        *reinterpret_cast<f32x4*>(p + i * 4) = pv;
+        *reinterpret_cast<f32x4*>(m + i * 4) = mv;
+        *reinterpret_cast<f32x4*>(v + i * 4) = vv;
+        *reinterpret_cast<f32x4*>(ema + i * 4) = ev;
+    }
+}
+
 __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ g, const size_t n4,
                                                     const float* __restrict__ coef_ptr,
                                                     const float c) {
@@ -889,6 +996,100 @@ int launch_adam_groups(float* p, const float* g, float* m, float* v, size_t n, i
     adam_table_kernel<<<grid1d(n4, 4096), 256, 0, s>>>(p, g, m, v, n4, (float)(1.0 - beta1),
                                                        (float)beta2, (float)(1.0 - beta2),
                                                        (float)eps, (float)wd, t, clip_out, gscale);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
+namespace {
+// [a, a+n) and [b, b+n) share no float
+bool disjoint(const float* a, const float* b, size_t n) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    const uintptr_t bytes = (uintptr_t)n * sizeof(float);
+    return x + bytes <= y || y + bytes <= x;
+}
+bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+}  // namespace
+
+int launch_ema_update(float* ema, const float* p, size_t n, float w, hipStream_t s) {
+    CILRS_CHECK(ema && p, "ema: NULL argument");
+    CILRS_CHECK(n % 4 == 0, "ema: n must be a multiple of 4");
+    CILRS_CHECK(aligned16(ema) && aligned16(p), "ema: pointers must be 16-byte aligned");
+    CILRS_CHECK(w >= 0.f && w <= 1.f, "ema: weight %g outside [0, 1]", (double)w);
+    CILRS_CHECK(disjoint(ema, p, n), "ema: ema may not alias the parameters");
+    ema_kernel<<<grid1d(n / 4, 4096), 256, 0, s>>>(ema, p, n / 4, w);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_swap(float* a, float* b, size_t n, hipStream_t s) {
+    CILRS_CHECK(a && b, "swap: NULL argument");
+    CILRS_CHECK(n % 4 == 0, "swap: n must be a multiple of 4");
+    CILRS_CHECK(aligned16(a) && aligned16(b), "swap: pointers must be 16-byte aligned");
+    CILRS_CHECK(disjoint(a, b, n), "swap: the two arrays may not overlap");
+    swap_kernel<<<grid1d(n / 4, 4096), 256, 0, s>>>(a, b, n / 4);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
+namespace {
+int check_adam_ema(const float* p, const float* g, const float* m, const float* v, const float* ema,
+                   size_t n, float ema_w) {
+    CILRS_CHECK(ema != nullptr, "adam+ema: NULL ema");
+    CILRS_CHECK(n % 4 == 0, "adam: n must be a multiple of 4");
+    CILRS_CHECK(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(ema),
+                "adam+ema: pointers must be 16-byte aligned");
+    CILRS_CHECK(ema_w >= 0.f && ema_w <= 1.f, "adam+ema: weight %g outside [0, 1]", (double)ema_w);
+    CILRS_CHECK(disjoint(ema, p, n) && disjoint(ema, m, n) && disjoint(ema, v, n) &&
+                    disjoint(ema, g, n),
+                "adam+ema: ema may not alias the parameters, the gradients or the moments");
+    return 0;
+}
+}  // namespace
+
+int launch_adam_ema(float* p, const float* g, float* m, float* v, size_t n, double lr,
+                    double beta1, double beta2, double eps, double wd, long long step,
+                    const float* clip_out, float gscale, float* ema, float ema_w, hipStream_t s) {
+    if (check_adam_ema(p, g, m, v, ema, n, ema_w)) return 1;
+    CILRS_CHECK(step >= 1, "adam: step must be >= 1");
+    // the scalars of launch_adam
+    const double bc1 = 1.0 - pow(beta1, (double)step);
+    const double bc2 = 1.0 - pow(beta2, (double)step);
+    const float neg_step_size = (float)(-(lr / bc1));
+    const float bc2_sqrt = (float)sqrt(bc2);
+    const size_t n4 = n / 4;
+    adam_ema_kernel<<<grid1d(n4, 4096), 256, 0, s>>>(
+        p, g, m, v, ema, n4, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
+        (float)wd, neg_step_size, bc2_sqrt, clip_out, gscale, ema_w);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_adam_groups_ema(float* p, const float* g, float* m, float* v, size_t n, int ngroups,
+                           const size_t* ends, const double* lrs, const long long* steps,
+                           double beta1, double beta2, double eps, double wd,
+                           const float* clip_out, float gscale, float* ema, float ema_w,
+                           hipStream_t s) {
+    if (check_adam_ema(p, g, m, v, ema, n, ema_w)) return 1;
+    CILRS_CHECK(ngroups >= 1 && ngroups <= kAdamTableMax && ends && lrs && steps,
+                "adam: 1..%d ranges", kAdamTableMax);
+    AdamTable t = {};                                     // the table of launch_adam_groups
+    t.n = ngroups;
+    size_t prev = 0;
+    for (int r = 0; r < ngroups; ++r) {
+        CILRS_CHECK(ends[r] > prev && ends[r] % 4 == 0 && ends[r] <= n && steps[r] >= 1,
+                    "adam: range ends must increase in multiples of 4 up to n, steps >= 1");
+        prev = ends[r];
+        const double bc1 = 1.0 - pow(beta1, (double)steps[r]);
+        const double bc2 = 1.0 - pow(beta2, (double)steps[r]);
+        t.end4[r] = ends[r] / 4;
+        t.neg_step_size[r] = (float)(-(lrs[r] / bc1));
+        t.bc2_sqrt[r] = (float)sqrt(bc2);
+    }
+    CILRS_CHECK(prev == n, "adam: the last range must end at n");
+    const size_t n4 = n / 4;
+    adam_table_ema_kernel<<<grid1d(n4, 4096), 256, 0, s>>>(
+        p, g, m, v, ema, n4, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
+        (float)wd, t, clip_out, gscale, ema_w);
     CILRS_LAUNCH_CHECK();
     return 0;
 }

@@ -3172,6 +3172,40 @@ int cilrs_adam_step_groups(float* params, const float* grads, float* exp_avg, fl
                               reinterpret_cast<hipStream_t>(stream));
 }
 
+// exponential moving average of the weights, on the optimizer step (notebook/notebook.ipynb:555)
+int cilrs_ema_update(float* ema, const float* params, size_t n, float w, void* stream) {
+    return launch_ema_update(ema, params, n, w, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cilrs_swap(float* a, float* b, size_t n, void* stream) {
+    return launch_swap(a, b, n, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cilrs_adam_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                        size_t n, double lr, double beta1, double beta2, double eps,
+                        double weight_decay, int64_t step, const float* clip_out2,
+                        float grad_scale, float* ema, float ema_w, void* stream) {
+    CILRS_CHECK(params && grads && exp_avg && exp_avg_sq, "adam: NULL argument");
+    return launch_adam_ema(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
+                           weight_decay, (long long)step, clip_out2, grad_scale, ema, ema_w,
+                           reinterpret_cast<hipStream_t>(stream));
+}
+
+int cilrs_adam_step_groups_ema(float* params, const float* grads, float* exp_avg,
+                               float* exp_avg_sq, size_t n, int ngroups, const size_t* ends,
+                               const double* lrs, const int64_t* steps, double beta1, double beta2,
+                               double eps, double weight_decay, const float* clip_out2,
+                               float grad_scale, float* ema, float ema_w, void* stream) {
+    CILRS_CHECK(params && grads && exp_avg && exp_avg_sq, "adam: NULL argument");
+    CILRS_CHECK(ngroups >= 1 && ngroups <= kAdamTableMax && steps, "adam: 1..%d ranges",
+                kAdamTableMax);
+    long long st[kAdamTableMax];
+    for (int r = 0; r < ngroups; ++r) st[r] = (long long)steps[r];
+    return launch_adam_groups_ema(params, grads, exp_avg, exp_avg_sq, n, ngroups, ends, lrs, st,
+                                  beta1, beta2, eps, weight_decay, clip_out2, grad_scale, ema,
+                                  ema_w, reinterpret_cast<hipStream_t>(stream));
+}
+
 int cilrs_stem_conv_fwd(const float* x4, const float* w, float* y, float* bn_partial, int N, int H,
                         int W, int* partial_rows, void* stream) {
     CILRS_CHECK(x4 && w && y, "stem_conv_fwd: NULL argument");

@@ -559,6 +559,39 @@ int cilrs_adam_step_groups(float* params, const float* grads, float* exp_avg, fl
                            void* stream);
 int cilrs_scale(float* x, size_t n, const float* clip_out2, float c, void* stream);
 
+/* ---- exponential moving average (EMA) of the weights ---------------------------------------------
+ * Rides on optimizer.step() (notebook/notebook.ipynb:555); the reference keeps no such average, so
+ * this text is the definition.  After the Adam update of a step, for every element
+ *     ema = ema + w * (p_new - ema)
+ * as three separately rounded fp32 operations (no FMA contraction); where ema == p the element
+ * comes back bit-identical.  w = float32(1 - d_t) is computed by the caller in double and rounded
+ * once; 0 <= w <= 1.  All arrays: 16-byte aligned, n a multiple of 4.  Every refusal happens
+ * before any launch.
+ *
+ * cilrs_ema_update: the stand-alone streaming pass (reads params, reads and writes ema); ema may
+ * not overlap params. */
+int cilrs_ema_update(float* ema, const float* params, size_t n, float w, void* stream);
+/* cilrs_adam_step / cilrs_adam_step_groups with the average fused in: the Adam arithmetic is
+ * element for element theirs, the EMA line runs on the just-computed parameter while it is still
+ * in a register (one more read and one more write of an arena-sized array instead of the two reads,
+ * one write and one launch of a separate pass; measured on an MI355X that does not pay --
+ * possibly because the separate pass finds the just-written parameters in the last-level cache,
+ * which was not confirmed with counters: DESIGN.md section 5c).  ema: n floats, may not be NULL and may not overlap
+ * params, grads, exp_avg or exp_avg_sq. */
+int cilrs_adam_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                        size_t n, double lr, double beta1, double beta2, double eps,
+                        double weight_decay, int64_t step, const float* clip_out2,
+                        float grad_scale, float* ema, float ema_w, void* stream);
+int cilrs_adam_step_groups_ema(float* params, const float* grads, float* exp_avg,
+                               float* exp_avg_sq, size_t n, int ngroups, const size_t* ends,
+                               const double* lrs, const int64_t* steps, double beta1, double beta2,
+                               double eps, double weight_decay, const float* clip_out2,
+                               float grad_scale, float* ema, float ema_w, void* stream);
+/* In-place exchange of two arrays of n floats that do not overlap, in one pass.  The plans cache the
+ * parameter arena's address: averaged weights are evaluated by swapping them into the arena and
+ * out again, never by re-binding pointers. */
+int cilrs_swap(float* a, float* b, size_t n, void* stream);
+
 /* op-level stem convolution of the TRAINING step (visual_encoder.0 = torchvision resnet34.conv1,
  * model/autonomous_drive.py:366; trained by notebook/notebook.ipynb:549-555): conv 7x7 / stride 2 /
  * pad 3, fp32, x4 = the channel-padded NHWC image [N,H,W,4], w = OHWI [64,7,7,3], y = [N,Ho,Wo,64];
