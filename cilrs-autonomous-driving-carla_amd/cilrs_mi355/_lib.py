@@ -82,6 +82,12 @@ SIGNATURES = {
                                      C.POINTER(i32), C.POINTER(i32)]),
     "cilrs_net_gradcam": (i32, [vp, C.POINTER(Buffers), vp, vp, c_float_p, i32, vp, vp, vp, vp, vp, sz,
                                 vp]),
+    "cilrs_feature_moments_doubles": (sz, [i32, i32]),
+    "cilrs_feature_moments": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "cilrs_feature_novelty_scratch_floats": (sz, [i32, i32]),
+    "cilrs_feature_novelty": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp, vp]),
+    "cilrs_net_feature_moments": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp]),
+    "cilrs_net_novelty": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp, vp, sz, vp]),
     "cilrs_net_infer16_conv_info": (i32, [vp, i32, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),
                                           C.POINTER(i32), C.POINTER(i32)]),
     "cilrs_net_infer16_io_info": (i32, [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),

@@ -229,6 +229,7 @@ class Engine:
         self.last_plan = None
         self._mc_bufs = {}                # run_heads_mc: (owner, B, S) -> scratch + pinned outputs
         self._gc_bufs = {}                # run_gradcam: (owner, B, H, W, layer) -> the same
+        self._nov_bufs = {}               # run_novelty: (owner, B) -> scratch + pinned d2
         # "fp32" (the reference's arithmetic) or "bf16": train-mode trunk convolutions on the bf16
         # matrix pipe (include/cilrs_hip.h CILRS_PLAN_BF16_TRAIN); set through
         # Trainer(..., precision=) or directly before the first train-mode forward
@@ -726,6 +727,54 @@ class Engine:
             L.ptr(heat), L.ptr(u8) if want_u8 else None, L.ptr(peak), L.ptr(scratch),
             scratch.numel(), self._stream()))
         return cam, heat, peak, (u8 if want_u8 else None)
+
+    # ---- feature-space novelty (csrc/novelty.hip) --------------------------------------------------
+    def feature_width(self) -> int:
+        return int(L.lib().cilrs_variant_feature_width(self.variant))
+
+    def plan_features(self, pl):
+        """View [B, F] of the fp32 pooled features (`combined`) in a plan's workspace: what every
+        eval-mode forward but the persistent single-frame launch leaves there."""
+        co, ld, feat = L.sz(), L.i32(), L.i32()
+        L.check(L.lib().cilrs_net_infer16_io_info(pl.handle, None, None, C.byref(co), C.byref(ld),
+                                                  C.byref(feat)))
+        comb = pl.workspace[co.value:co.value + 4 * pl.batch * ld.value].view(torch.float32)
+        return comb.view(pl.batch, ld.value)[:, :feat.value]
+
+    def run_feature_moments(self, command, pivot, table):
+        """cilrs_net_feature_moments: add the pooled features the last eval-mode forward left in
+        its plan, one row per frame, to the float64 moment table (include/cilrs_hip.h).  One
+        launch on the current stream; nothing is copied to the host."""
+        pl = self.last_plan
+        if pl is None:
+            raise RuntimeError("run_feature_moments: no forward yet")
+        L.check(L.lib().cilrs_net_feature_moments(
+            pl.handle, C.byref(pl.bufs), L.ptr(command), L.ptr(pivot), L.ptr(table), self._stream()))
+
+    def run_novelty(self, command, mean, W, d2=None, owner=None):
+        """cilrs_net_novelty on the features the last eval-mode forward left in its plan: enqueues
+        the three launches on the current stream and returns d2 [B].  Without `d2` the kernels
+        write a PINNED host buffer, valid after the stream is synchronised and until the next call
+        with the same (owner, B); the scratch is cached the same way (see run_heads_mc)."""
+        pl = self.last_plan
+        if pl is None:
+            raise RuntimeError("run_novelty: no forward yet")
+        b = pl.batch
+        cache, key = self._nov_bufs, (id(owner) if owner is not None else None, b)
+        bufs = cache.pop(key, None)
+        if bufs is None:
+            while len(cache) >= self.MC_CACHE_ENTRIES:
+                cache.pop(next(iter(cache)))             # the least recently used
+            n = L.lib().cilrs_feature_novelty_scratch_floats(self.feature_width(), b)
+            bufs = (torch.empty(n, dtype=torch.float32, device=self.device),
+                    torch.zeros(b, dtype=torch.float32).pin_memory())
+        cache[key] = bufs
+        scratch, host = bufs
+        out = host if d2 is None else d2
+        L.check(L.lib().cilrs_net_novelty(
+            pl.handle, C.byref(pl.bufs), L.ptr(command), L.ptr(mean), L.ptr(W), L.ptr(out),
+            L.ptr(scratch), scratch.numel(), self._stream()))
+        return out
 
     def run_forward_camera(self, frames_u8, speed, command, height=88, width=200, out=None):
         """Raw camera frames uint8 [B,Hs,Ws,3|4] (device) -> eval forward with the whole of

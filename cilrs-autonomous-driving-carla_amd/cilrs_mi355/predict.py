@@ -760,8 +760,57 @@ class Predictor:
         mean, std, _ = self._mc_run(speed, cmd, samples, p, seed, False)
         return tuple(float(x) for x in mean[0]), tuple(float(x) for x in std[0])
 
+    # ---- feature-space novelty --------------------------------------------------------------------
+    def _novelty_check(self, density, commands, who):
+        """What the novelty calls refuse before anything is launched."""
+        if self.half:
+            raise RuntimeError(f"{who}: fp32 predictors only (a density fitted on fp32 features does "
+                               "not describe a 16-bit trunk's)")
+        density.check_model(self.model, who)
+        density.check_commands(self._check_commands(commands), who)
+
+    def _novelty_run(self, command, density):
+        """The score launches on this predictor's stream, on the plan the tick just used, into a
+        pinned buffer; one synchronise."""
+        eng = self.eng
+        eng.last_plan = eng.plan(self.batch, self.frames_host.size(1), self.frames_host.size(2))
+        with torch.cuda.stream(self.stream):
+            d2 = eng.run_novelty(command, density.mean, density.W, owner=self)
+            self.stream.synchronize()
+        return d2.numpy().copy()
+
+    @torch.no_grad()
+    def predict_novelty(self, frames_u8, speeds_kmh, commands, density):
+        """predict_batch plus a score of how unlike the training set the frames look to the trunk:
+        returns (controls [B,3], pred_speed [B] in km/h, d2 [B]), np.float32; the first two are
+        exactly predict_batch's columns.  d2 is the squared Mahalanobis distance of the pooled
+        features to ``density`` (a finalised cilrs_mi355.novelty.FeatureDensity; include/cilrs_hip.h,
+        cilrs_net_novelty): an unchanged predict_batch -- persistent launch, degraded mode and all --
+        then three small launches on this predictor's stream and one more synchronise.
+        ``density.percentile(d2)`` turns it into a threshold with a meaning.  fp32 predictors only;
+        a density of another feature width or command count, and a command its fit never saw,
+        raise RuntimeError before anything is launched."""
+        self._novelty_check(density, commands, "predict_novelty")
+        out = self.predict_batch(frames_u8, speeds_kmh, commands)
+        _speed, cmd = self._mc_inputs()
+        d2 = self._novelty_run(cmd, density)
+        return out[:, :3].copy(), out[:, 3].copy(), d2
+
+    @torch.no_grad()
+    def predict_controls_novelty(self, image_rgb_u8, speed_kmh, command_idx, density):
+        """predict_controls with the novelty score: ((steer, throttle, brake, speed_kmh), d2).
+        Frames that are not 88x200x3 go through predict_camera's path first."""
+        if self.batch != 1:
+            raise RuntimeError("predict_controls_novelty is the single-frame control-loop path")
+        self._novelty_check(density, [int(command_idx)], "predict_controls_novelty")
+        image_rgb_u8 = np.asarray(image_rgb_u8)
+        camera = image_rgb_u8.shape != tuple(self.frames_host.shape[1:])
+        point = self.predict_controls(image_rgb_u8, speed_kmh, command_idx)
+        _speed, cmd = self._mc_inputs(camera)
+        return point, float(self._novelty_run(cmd, density)[0])
+
     # ---- Grad-CAM --------------------------------------------------------------------------------
-    GRADCAM_LAYERS = {"layer1": 1, "layer2": 2, "layer3": 3, "layer4": 4}
+    GRADCAM_LAYERS ={"layer1": 1, "layer2": 2, "layer3": 3, "layer4": 4}
 
     @torch.no_grad()
     def gradcam(self, frames_u8, speeds_kmh, commands, output="steer", layer="layer4", want_u8=False):

@@ -737,4 +737,30 @@ struct GradcamMapArgs {
 };
 int launch_gradcam_map(const GradcamMapArgs& a, hipStream_t s);
 
+// ---- feature-space novelty (novelty.hip; cilrs_feature_moments, cilrs_feature_novelty) ----------
+struct NoveltyMomentsArgs {
+    const float* features; int ld;        // [B][ld] features, or NULL:
+    const float* featmap; int HW;         //   [B][HW][F] last feature map, pooled by the kernel
+    const long long* cmd;
+    int B, F, NC;
+    const float* pivot;                   // [F]
+    double* table;                        // n[NC] | s[NC][F] | G[F][F] (lower triangle)
+    int* status;                          // may be NULL
+};
+size_t novelty_moments_doubles(int F, int NC);
+int launch_novelty_moments(const NoveltyMomentsArgs& a, hipStream_t s);
+struct NoveltyScoreArgs {
+    const float* features; int ld;        // as above
+    const float* featmap; int HW;
+    const long long* cmd;
+    int B, F, NC;
+    const float* mean;                    // [NC][F]
+    const float* W;                       // [F][F], lower triangle read
+    float* d2;                            // [B]
+    int* status;                          // may be NULL
+    float* u; float* part;                // set by the launcher: inside the caller's scratch
+};
+size_t novelty_scratch_floats(int F, int batch);
+int launch_novelty_score(NoveltyScoreArgs& a, float* scratch, hipStream_t s);
+
 }  // namespace cilrs

@@ -2666,6 +2666,128 @@ int cilrs_net_gradcam(cilrs_net* net, const cilrs_buffers* bufs, const float* sp
 }
 
 // ------------------------------------------------------------------------------------------------
+// Feature-space novelty (novelty.hip)
+// ------------------------------------------------------------------------------------------------
+constexpr int kNovMaxBatch = 65536;
+
+// what both op-level entries check of their feature source and sizes
+static int nov_check(const char* who, const float* features, int ld, const float* featmap, int hw,
+                     const int64_t* command, int batch, int F, int NC) {
+    CILRS_CHECK(command != nullptr, "%s: NULL tensor (command)", who);
+    CILRS_CHECK(batch >= 1 && batch <= kNovMaxBatch, "%s: batch %d outside 1..%d", who, batch,
+                kNovMaxBatch);
+    CILRS_CHECK(F == 512 || F == 2048, "%s: feature width %d (512 or 2048)", who, F);
+    CILRS_CHECK(NC >= 1 && NC <= kMaxCmd, "%s: %d commands outside 1..%d", who, NC, kMaxCmd);
+    CILRS_CHECK((features != nullptr) != (featmap != nullptr),
+                "%s: exactly one of features and featmap must be given", who);
+    if (features) CILRS_CHECK(ld >= F, "%s: ld %d below the %d features", who, ld, F);
+    else CILRS_CHECK(hw >= 1 && hw <= 65536, "%s: feature map of %d cells", who, hw);
+    return 0;
+}
+
+static int nov_score_check(const char* who, const float* mean, const float* W, const float* d2,
+                           const float* scratch, size_t scratch_floats, int F, int batch) {
+    CILRS_CHECK(mean && W && d2, "%s: NULL tensor", who);
+    CILRS_CHECK(scratch != nullptr && scratch_floats >= novelty_scratch_floats(F, batch),
+                "%s: scratch of %zu floats, %zu needed", who, scratch_floats,
+                novelty_scratch_floats(F, batch));
+    CILRS_CHECK(((uintptr_t)W & 15) == 0 && ((uintptr_t)scratch & 15) == 0,
+                "%s: W and scratch must be 16-byte aligned", who);
+    return 0;
+}
+
+size_t cilrs_feature_moments_doubles(int F, int NC) {
+    if ((F != 512 && F != 2048) || NC < 1 || NC > kMaxCmd) return 0;
+    return novelty_moments_doubles(F, NC);
+}
+
+int cilrs_feature_moments(const float* features, int ld, const float* featmap, int hw,
+                          const int64_t* command, int batch, int F, int NC, const float* pivot,
+                          double* table, int* status, void* stream) {
+    CILRS_CHECK(pivot && table, "feature_moments: NULL tensor");
+    if (nov_check("feature_moments", features, ld, featmap, hw, command, batch, F, NC)) return 1;
+    NoveltyMomentsArgs a;
+    a.features = features; a.ld = ld; a.featmap = featmap; a.HW = hw;
+    a.cmd = reinterpret_cast<const long long*>(command);
+    a.B = batch; a.F = F; a.NC = NC; a.pivot = pivot; a.table = table; a.status = status;
+    return launch_novelty_moments(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t cilrs_feature_novelty_scratch_floats(int F, int batch) {
+    if ((F != 512 && F != 2048) || batch < 1 || batch > kNovMaxBatch) return 0;
+    return novelty_scratch_floats(F, batch);
+}
+
+int cilrs_feature_novelty(const float* features, int ld, const float* featmap, int hw,
+                          const int64_t* command, int batch, int F, int NC, const float* mean,
+                          const float* W, float* d2, float* scratch, size_t scratch_floats,
+                          int* status, void* stream) {
+    if (nov_check("feature_novelty", features, ld, featmap, hw, command, batch, F, NC)) return 1;
+    if (nov_score_check("feature_novelty", mean, W, d2, scratch, scratch_floats, F, batch)) return 1;
+    NoveltyScoreArgs a;
+    a.features = features; a.ld = ld; a.featmap = featmap; a.HW = hw;
+    a.cmd = reinterpret_cast<const long long*>(command);
+    a.B = batch; a.F = F; a.NC = NC; a.mean = mean; a.W = W; a.d2 = d2; a.status = status;
+    return launch_novelty_score(a, scratch, reinterpret_cast<hipStream_t>(stream));
+}
+
+// the features the plan's last eval-mode forward left, resolved as cilrs_net_heads_mc does
+static int nov_plan_source(const char* who, const cilrs_net* net, const cilrs_buffers* bufs,
+                           const float** features, int* ld, const float** featmap, int* hw) {
+    CILRS_CHECK(net->mc_src != 0, "%s: no forward on this plan yet", who);
+    CILRS_CHECK(net->mc_src > 0, "%s: the plan's last forward ran in train mode (batch statistics); "
+                "run an eval-mode forward first", who);
+    const Arch& A = *net->A;
+    const float* ws = reinterpret_cast<const float*>(bufs->workspace);
+    *features = nullptr; *featmap = nullptr; *ld = 0; *hw = 0;
+    if (net->mc_src == 2) {
+        *featmap = ws + net->cg[A.blocks.back().conv3 >= 0 ? A.blocks.back().conv3
+                                                           : A.blocks.back().conv2].z;
+        *hw = net->featHW;
+    } else {
+        *features = ws + net->combined; *ld = A.feat + 128;
+    }
+    return 0;
+}
+
+int cilrs_net_feature_moments(cilrs_net* net, const cilrs_buffers* bufs, const int64_t* command,
+                              const float* pivot, double* table, void* stream) {
+    if (check_bufs(net, bufs, false)) return 1;
+    CILRS_CHECK(command && pivot && table, "net_feature_moments: NULL tensor");
+    NoveltyMomentsArgs a;
+    if (nov_plan_source("net_feature_moments", net, bufs, &a.features, &a.ld, &a.featmap, &a.HW))
+        return 1;
+    const Arch& A = *net->A;
+    CILRS_CHECK(net->B <= kNovMaxBatch, "net_feature_moments: batch %d above %d", net->B, kNovMaxBatch);
+    a.cmd = reinterpret_cast<const long long*>(command);
+    a.B = net->B; a.F = A.feat; a.NC = A.ncmd; a.pivot = pivot; a.table = table;
+    a.status = reinterpret_cast<int*>(reinterpret_cast<char*>(bufs->workspace) + net->status_b);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    RUN(net, "feature_moments", (double)net->B * A.feat * (A.feat + 1), 0.0, s,
+        launch_novelty_moments(a, s));
+    return 0;
+}
+
+int cilrs_net_novelty(cilrs_net* net, const cilrs_buffers* bufs, const int64_t* command,
+                      const float* mean, const float* W, float* d2, float* scratch,
+                      size_t scratch_floats, void* stream) {
+    if (check_bufs(net, bufs, false)) return 1;
+    CILRS_CHECK(command != nullptr, "net_novelty: NULL tensor (command)");
+    const Arch& A = *net->A;
+    CILRS_CHECK(net->B <= kNovMaxBatch, "net_novelty: batch %d above %d", net->B, kNovMaxBatch);
+    if (nov_score_check("net_novelty", mean, W, d2, scratch, scratch_floats, A.feat, net->B)) return 1;
+    NoveltyScoreArgs a;
+    if (nov_plan_source("net_novelty", net, bufs, &a.features, &a.ld, &a.featmap, &a.HW)) return 1;
+    a.cmd = reinterpret_cast<const long long*>(command);
+    a.B = net->B; a.F = A.feat; a.NC = A.ncmd; a.mean = mean; a.W = W; a.d2 = d2;
+    a.status = reinterpret_cast<int*>(reinterpret_cast<char*>(bufs->workspace) + net->status_b);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    RUN(net, "novelty", (double)net->B * A.feat * (A.feat + 1), 0.0, s,
+        launch_novelty_score(a, scratch, s));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------
 static int backward_heads(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,

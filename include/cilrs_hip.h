@@ -357,6 +357,74 @@ int cilrs_net_gradcam(cilrs_net* net, const cilrs_buffers* bufs, const float* sp
                       float* heat, uint8_t* heat_u8, float* peak, float* scratch,
                       size_t scratch_floats, void* stream);
 
+/* ---- Feature-space novelty: Mahalanobis distance of the pooled features (csrc/novelty.hip) ------
+ * Monte-Carlo dropout measures how much the heads disagree about a feature vector; it cannot see
+ * that the vector itself is unlike anything the trunk produced during training.  This score can:
+ * the squared Mahalanobis distance of the eval-mode pooled features to command-conditional
+ * Gaussians with one tied covariance (Lee et al., 2018), the classes being the navigation commands.
+ * The reference has no such path; parity is pinned by this definition (restated in float64 by
+ * tests/_novelty.py).
+ *   Inputs   of a fit: N frames, each with v (fp32 pooled features, F = 512 / 2048: the first F
+ *            columns of a row, or the cell-order average s / (float)hw of an fp32 map [hw][F],
+ *            s += map[p][c] for p = 0..hw-1) and a command k in 0..NC-1, NC <= 8.  A command outside
+ *            that range counts as command 0 and sets the status word, as everywhere else.
+ *   Pivot    c: a fixed fp32 vector [F] chosen once per fit.  All moments are taken of
+ *            x = (double)v - (double)c; the result is algebraically independent of c, which only
+ *            keeps G - sum n mu mu^T from cancelling.
+ *   Table    float64, cilrs_feature_moments_doubles(F, NC) = NC + NC F + F F values:
+ *            n[NC] | s[NC][F] | G[F][F].  n_k counts the rows of command k, s_k sums their x,
+ *            G[i][j] = sum_n x_ni x_nj for j <= i, tied over all commands; entries j > i are never
+ *            read or written.  Every entry is ONE sequential chain over the rows in row order that
+ *            continues from the value already in the table: t = table; per row t = fma(x_bi, x_bj, t)
+ *            (s: t = t + x_bi for the rows of command k; n: t = t + 1); table = t.  Updates of 2 + 3
+ *            rows are therefore bit for bit one update of 5.  The caller zeroes the table before
+ *            the first update.  No atomics.
+ *   Finalise (host, float64): mu_k = c + s_k / n_k for the K' commands that occurred;
+ *            S_w = G - sum_k n_k (s_k/n_k)(s_k/n_k)^T;  Sigma = S_w / (N - K');
+ *            Sigma_l = (1 - l) Sigma + l (tr Sigma / F) I  (shrinkage l > 0 makes it positive
+ *            definite whatever dead channels the post-ReLU features have, and for N < F);
+ *            Sigma_l = L L^T (Cholesky), W = L^-1 lower triangular; W [F][F] and mean [NC][F] are
+ *            rounded once to fp32.
+ *   Score    per frame b: u = v - mean[k] in fp32; y_i = sum_{j <= i} W_ij u_j; d2 = sum_i y_i^2,
+ *            all in fp32.  Columns j > i of W are never read.  Order of the sums: lane l of a wave
+ *            runs a = fmaf(W_ij, u_j, a) from a = 0 over its columns j = 256 q + 4 l + e <= i
+ *            (q ascending, then e = 0..3); the 64 lane sums are combined by the xor butterfly
+ *            a += shfl_xor(a, o), o = 32, 16, .., 1.  Workgroup g of F / 8 owns rows g + (F / 8) r,
+ *            r = 0..7; wave w gives q_w = fmaf(y', y', y y) for rows r = 2w (y) and 2w + 1 (y'); the
+ *            workgroup's part is ((q_0 + q_1) + q_2) + q_3; d2 adds the parts from 0 in workgroup
+ *            order.  No atomics: results are bit-identical from run to run and a frame's score
+ *            does not depend on the batch it sits in.
+ * cilrs_feature_moments: one launch; adds `batch` rows into `table`.  Features: exactly one of
+ * `features` ([batch][ld], features first) and `featmap` ([batch][hw][F]).
+ * cilrs_feature_novelty: three launches (u into the scratch; the triangular product with the rows
+ * of W split over F / 8 workgroups; the per-frame sum).  d2 [batch] may be pinned host memory.
+ * scratch: caller's device memory of cilrs_feature_novelty_scratch_floats(F, batch) floats (0 for a
+ * width other than 512 / 2048 or a batch outside 1..65536), 16-byte aligned like W.
+ * status: a device int (set to 1 on an out-of-range command) or NULL.
+ * cilrs_net_feature_moments / cilrs_net_novelty: the same on the features the plan's last
+ * eval-mode forward left, resolved exactly as cilrs_net_heads_mc resolves them (`combined`, or after
+ * a persistent single-frame forward the stored last feature map); F, NC and the batch are the
+ * plan's, status its word 0.  16-bit forwards are accepted (`combined` is fp32 there).  No launch of
+ * any forward entry changes, nor does the workspace layout.
+ * Refused (non-zero, text in cilrs_last_error, nothing launched): NULL tensors; a batch outside
+ * 1..65536; F outside {512, 2048}; NC outside 1..8; both or neither of features / featmap; ld < F;
+ * hw outside 1..65536; a scratch smaller than asked; a W or scratch that is not 16-byte aligned;
+ * at plan level no forward yet, or a train-mode forward last. */
+size_t cilrs_feature_moments_doubles(int F, int NC);
+int cilrs_feature_moments(const float* features, int ld, const float* featmap, int hw,
+                          const int64_t* command, int batch, int F, int NC, const float* pivot,
+                          double* table, int* status, void* stream);
+size_t cilrs_feature_novelty_scratch_floats(int F, int batch);
+int cilrs_feature_novelty(const float* features, int ld, const float* featmap, int hw,
+                          const int64_t* command, int batch, int F, int NC, const float* mean,
+                          const float* W, float* d2, float* scratch, size_t scratch_floats,
+                          int* status, void* stream);
+int cilrs_net_feature_moments(cilrs_net* net, const cilrs_buffers* bufs, const int64_t* command,
+                              const float* pivot, double* table, void* stream);
+int cilrs_net_novelty(cilrs_net* net, const cilrs_buffers* bufs, const int64_t* command,
+                      const float* mean, const float* W, float* d2, float* scratch,
+                      size_t scratch_floats, void* stream);
+
 /* Same, fed with uint8 RGB HWC frames [B,H,W,3]: fuses preprocess_image's /255, HWC->CHW and
  * Normalize(mean,std) (autonomous_drive.py:897-902; the cv2.resize is the caller's). */
 int cilrs_net_forward_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
