@@ -187,6 +187,13 @@ SIGNATURES = {
     "cilrs_conv2d_wino_wgrad_scratch_floats": (sz, [i32, i32, i32, i32, i32]),
     "cilrs_conv2d_wino_wgrad": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
     "cilrs_bn_partial_floats": (sz, [i32]),
+    "cilrs_variant_bn_stats_doubles": (sz, [i32]),
+    "cilrs_variant_bn_stats_info": (i32, [i32, i32, C.POINTER(i32), C.POINTER(sz), C.POINTER(sz)]),
+    "cilrs_net_bn_layer_info": (i32, [vp, i32, C.POINTER(sz), C.POINTER(i32), C.POINTER(i32),
+                                      C.POINTER(i32)]),
+    "cilrs_net_forward_bn_stats": (i32, [vp, C.POINTER(Buffers), vp, C.c_long, C.c_long, C.c_long, C.c_long, vp, vp]),
+    "cilrs_bn_stats_finalize": (i32, [i32, vp, i32, vp, vp, vp]),
+    "cilrs_bn_train_stats": (i32, [vp, i32, i32, vp, vp, vp]),
     "cilrs_bn_train_fwd": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, f32, f32, vp, i32, vp, vp, vp,
                                  vp]),
     "cilrs_bn_eval_fwd": (i32, [vp, i32, i32, vp, vp, vp, vp, f32, vp, i32, vp, vp, vp]),

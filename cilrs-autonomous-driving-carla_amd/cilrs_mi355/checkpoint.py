@@ -14,6 +14,11 @@ With an EMA of the weights (TrainConfig.ema_decay) ``checkpoint_latest.pth`` als
 ``save_best(..., ema=True)`` stores the averaged parameters as ``model_state_dict`` -- same 250
 keys, BatchNorm buffers from the live model, so the reference's strict load is unchanged -- plus
 ``"ema": {"decay", "updates"}``.  Without an EMA every file has the keys it always had.
+
+Once the averaged weights have BatchNorm buffers of their own (Trainer.update_bn(ema=True), fit's
+``ema_bn_batches``) ``checkpoint_latest.pth`` also carries them as ``ema_bn_state_dict`` (keyed
+like the model's buffer entries) and ``save_best(..., ema=True)`` stores them in place of the live
+model's, with ``"ema"["bn"] = True``.  Before that, no key differs.
 """
 from __future__ import annotations
 
@@ -94,6 +99,10 @@ def save_best(path, model, trainer, epoch, val_loss, val_steer, cmd_steer_errors
     if ema:
         sd.update(trainer.ema_state_dict())        # parameters only: the key set stays the model's
         d["ema"] = {"decay": float(trainer.ema_decay), "updates": int(trainer.ema_updates)}
+        ema_bn = trainer.ema_bn_state_dict()
+        if ema_bn is not None:                     # the averaged weights' own re-estimated buffers
+            sd.update(ema_bn)
+            d["ema"]["bn"] = True
     torch.save(d, path)
 
 
@@ -112,6 +121,9 @@ def save_latest(path, model, trainer, epoch, loop_state=None):
     if getattr(trainer, "ema", None) is not None:       # raw weights above, the average beside them
         d["ema_state_dict"] = trainer.ema_state_dict()
         d["ema_updates"] = int(trainer.ema_updates)
+        ema_bn = trainer.ema_bn_state_dict()
+        if ema_bn is not None:
+            d["ema_bn_state_dict"] = ema_bn
     torch.save(d, path)
 
 
@@ -157,6 +169,8 @@ def load(path, model, trainer=None, map_location=None):
             trainer.ema_updates = int(ck.get("ema_updates", 0))
         else:                       # a file without an average: it starts from the loaded weights
             trainer.ema_reset()
+        if "ema_bn_state_dict" in ck:
+            trainer.load_ema_bn_state_dict(ck["ema_bn_state_dict"])
     return ck
 
 

@@ -342,6 +342,35 @@ class Engine:
         self.last_plan = pl
         return controls, pred_speed, pl
 
+    def run_forward_bn_stats(self, image, table):
+        """Enqueue the train-mode trunk on `image` with every BatchNorm's batch statistics added to
+        the float64 device `table` (cilrs_net_forward_bn_stats; bn_estimate.py): no heads, the
+        running buffers and the parameters untouched, no host synchronisation.  Returns the plan."""
+        if image.dim() != 4 or image.size(1) != 3:
+            raise RuntimeError(f"image must be [B,3,H,W], got {tuple(image.shape)}")
+        if image.dtype != torch.float32:
+            raise RuntimeError("image must be float32")
+        if image.device != self.device or table.device != self.device:
+            raise RuntimeError(f"image on {image.device}, table on {table.device}, model on "
+                               f"{self.device}")
+        n = L.lib().cilrs_variant_bn_stats_doubles(self.variant)
+        if table.dtype != torch.float64 or table.numel() != n or not table.is_contiguous():
+            raise RuntimeError(f"table must be a contiguous float64 tensor of {n} entries")
+        if self.train_precision != "fp32":
+            raise RuntimeError("BatchNorm re-estimation: fp32 plans only")
+        pl = self.plan(image.size(0), image.size(2), image.size(3))
+        sn, sc, sh, sw = image.stride()
+        # the plan's per-layer scale / shift tables are about to hold batch statistics: what any
+        # plan cached from them (eval state, a fine-tuning prefix) is rebuilt on its next use
+        self.weights_epoch += 1
+        self._announce_weights(pl)
+        L.check(L.lib().cilrs_net_forward_bn_stats(
+            pl.handle, C.byref(pl.bufs), L.ptr(image), sn, sc, sh, sw, L.ptr(table),
+            self._stream()))
+        pl.generation += 1                    # the saved activations of earlier graphs are gone
+        self.last_plan = pl
+        return pl
+
     def trainable_begin(self, frozen_groups) -> int:
         """First arena float of the trainable range behind `frozen_groups` frozen trunk groups."""
         return self.group_ranges[frozen_groups][0]

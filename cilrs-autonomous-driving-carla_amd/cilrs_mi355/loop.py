@@ -59,14 +59,21 @@ def train_one_epoch(trainer, batches):
 
 
 def fit(trainer, train_batches, val_batches, epochs=20, patience=6, out_dir=".", resume=None,
-        log=print, validate_ema=None):
+        log=print, validate_ema=None, ema_bn_batches=None):
     """``train_batches`` / ``val_batches``: callables returning an iterable of
     (imgs, speeds, cmds, tgts) device batches for one epoch.
 
     validate_ema (None = on when the trainer keeps an EMA of the weights, TrainConfig.ema_decay):
     the validation pass, the early-stopping decision and ``checkpoint_best.pth`` use the averaged
     weights.  ``checkpoint_latest.pth`` always holds the raw weights, with the average beside
-    them, so that a resume continues the same trajectory."""
+    them, so that a resume continues the same trajectory.
+
+    ema_bn_batches: a callable returning batches (images, or tuples starting with them).  When it is
+    given and the EMA is validated, every BatchNorm's statistics are re-estimated on the averaged
+    weights (``trainer.update_bn(ema_bn_batches(), ema=True)``) before each EMA validation, and
+    the checkpoints carry the result: ``checkpoint_best.pth`` in its ``model_state_dict``'s buffer
+    entries, ``checkpoint_latest.pth`` under ``ema_bn_state_dict``.  Without it every file has
+    the keys it always had."""
     has_ema = getattr(trainer, "ema", None) is not None
     use_ema = has_ema if validate_ema is None else bool(validate_ema)
     if use_ema and not has_ema:
@@ -98,6 +105,8 @@ def fit(trainer, train_batches, val_batches, epochs=20, patience=6, out_dir=".",
         t0 = time.time()
         lr = trainer.lr
         tr = train_one_epoch(trainer, train_batches())
+        if use_ema and ema_bn_batches is not None:
+            trainer.update_bn(ema_bn_batches(), ema=True)
         va, cmd = trainer.validate(val_batches(), ema=True) if use_ema else \
             trainer.validate(val_batches())
         trainer.scheduler_step()                                   # nb:604

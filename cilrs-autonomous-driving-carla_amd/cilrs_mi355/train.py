@@ -141,9 +141,13 @@ class Trainer:
         self.bucket_optimizer = True
         # EMA of the weights: fp32 over the fp32 master arena in every precision mode, a copy of the
         # parameters now.  BatchNorm buffers are not averaged (running statistics already are
-        # moving averages; the averaged weights are evaluated with the live model's buffers).
+        # moving averages): until update_bn(ema=True) has run, the averaged weights are evaluated
+        # with the live model's buffers; from then on with buffers of their own (ema_bn / ema_nbt,
+        # re-estimated on the averaged weights and exchanged together with the parameters).
         self.ema_decay = ema_decay
         self.ema = self.eng.params.clone() if ema_decay is not None else None
+        self.ema_bn = None
+        self.ema_nbt = None
         self.ema_updates = 0
         # False: Adam, then cilrs_ema_update over the same range; True: the average is updated
         # inside the Adam launch (cilrs_adam_step_ema) -- the same numbers bit for bit.  By bytes
@@ -412,6 +416,13 @@ class Trainer:
         torch.cuda.synchronize(dev)
         L.check(L.lib().cilrs_swap(L.ptr(self.eng.params), L.ptr(self.ema), self.eng.n_arena,
                                    self._stream()))
+        if self.ema_bn is not None:           # the averaged weights' own BatchNorm buffers
+            L.check(L.lib().cilrs_swap(L.ptr(self.eng.bn), L.ptr(self.ema_bn), self.eng.bn.numel(),
+                                       self._stream()))
+            with torch.no_grad():
+                live = self.eng.nbt.clone()
+                self.eng.nbt.copy_(self.ema_nbt)
+                self.ema_nbt.copy_(live)
         torch.cuda.synchronize(dev)
         self.model.weights_changed()
 
@@ -438,6 +449,76 @@ class Trainer:
                 # left locked; the arena may then still hold the averaged weights, and the error
                 # that says so propagates
                 self._in_ema = False
+
+    # -- BatchNorm re-estimation (bn_estimate.py) --------------------------------------------------
+    def update_bn(self, batches, ema=False, estimator="batch_mean"):
+        """Re-estimate every BatchNorm's running statistics on `batches` (image tensors, or tuples
+        starting with one): ``torch.optim.swa_utils.update_bn`` for this module, and AdaBN.
+
+        ema=False: of the live weights, into the module's buffers.  ema=True: of the averaged
+        weights -- runs inside ``ema_weights()`` and leaves the result in a Trainer-owned pair
+        (ema_bn / ema_nbt, created on first use as a copy of the live buffers) that every later
+        ``ema_weights()`` exchanges together with the parameters; the live buffers and parameters
+        are bit for bit what they were.  Data parallel: every rank passes its own shard, the
+        tables are summed over the ranks (they add entry by entry) before the buffers are
+        written, so all ranks end with identical buffers.  Returns the estimator."""
+        from .bn_estimate import BatchNormEstimator
+        self._ensure_engine()
+        if not ema:
+            self._refuse_inside_ema_weights("update_bn")
+            return self._update_bn(BatchNormEstimator(self.model, estimator), batches)
+        self._need_ema()
+        est = BatchNormEstimator(self.model, estimator)       # (raises before anything is created)
+        if self.ema_bn is None:
+            self.ema_bn = self.eng.bn.clone()
+            self.ema_nbt = self.eng.nbt.clone()
+        with self.ema_weights():
+            return self._update_bn(est, batches)
+
+    @torch.no_grad()
+    def _update_bn(self, est, batches):
+        for b in batches:
+            est.update(b)
+        est.table = self.all_reduce_sum(est.table)
+        if self.reducer is not None:
+            est.batches = max(est.batches, 1)         # a rank without a batch still writes the sum
+        est.finalize()
+        return est
+
+    def ema_bn_state_dict(self):
+        """The averaged weights' BatchNorm buffers (update_bn(ema=True)), keyed like the model's
+        buffer entries (CPU clones); None before the first such call."""
+        self._need_ema()
+        if self.ema_bn is None:
+            return None
+        bn, nbt = (self.eng.bn, self.eng.nbt) if self._in_ema else (self.ema_bn, self.ema_nbt)
+        out = {}
+        for j, (prefix, ch, rm, rv) in enumerate(self.eng.bn_layout):
+            out[f"{prefix}.running_mean"] = bn[rm:rm + ch].detach().cpu().clone()
+            out[f"{prefix}.running_var"] = bn[rv:rv + ch].detach().cpu().clone()
+            out[f"{prefix}.num_batches_tracked"] = nbt[j].detach().cpu().clone()
+        return out
+
+    def load_ema_bn_state_dict(self, sd):
+        """Inverse of ema_bn_state_dict."""
+        self._need_ema()
+        self._refuse_inside_ema_weights("load_ema_bn_state_dict")
+        want = [f"{p}.{k}" for p, *_ in self.eng.bn_layout
+                for k in ("running_mean", "running_var", "num_batches_tracked")]
+        missing, extra = [k for k in want if k not in sd], [k for k in sd if k not in set(want)]
+        if missing or extra:
+            raise KeyError(f"ema_bn_state_dict: missing {missing[:3]}, unexpected {extra[:3]}")
+        bn, nbt = self.eng.bn.clone(), self.eng.nbt.clone()
+        with torch.no_grad():
+            for j, (prefix, ch, rm, rv) in enumerate(self.eng.bn_layout):
+                for key, off in (("running_mean", rm), ("running_var", rv)):
+                    t = sd[f"{prefix}.{key}"]
+                    if tuple(t.shape) != (ch,):
+                        raise ValueError(f"ema_bn_state_dict: {prefix}.{key} has shape "
+                                         f"{tuple(t.shape)}, expected {(ch,)}")
+                    bn[off:off + ch].copy_(t)
+                nbt[j].copy_(sd[f"{prefix}.num_batches_tracked"])
+        self.ema_bn, self.ema_nbt = bn, nbt
 
     def next_dropout_seed(self):
         """Seed of the next train step's dropout masks: torch's seed, the step count and the

@@ -160,11 +160,22 @@ __device__ __forceinline__ bool partial_sums(const float* __restrict__ partial, 
 }
 
 // stats layout (floats): [0,C) mean | [C,2C) rstd | [2C,3C) w = gamma*rstd | [3C,4C) b = beta-mean*w
+// ACC (BatchNorm re-estimation, cilrs_bn_train_stats): the same thread also continues the layer's
+// four double chains in acc = [4][C] from the values already there --
+//   acc[0][c] += mean_b,  acc[1][c] += var_b * M / (M - 1),  acc[2][c] += M * mean_b,
+//   acc[3][c] += M * (var_b + mean_b^2)
+// -- and channel 0's thread the layer's acc_head = {t += 1, rows += M}.  Every term is rounded on its
+// own (no contraction of a product into the chain's addition), so a table is the same sequence
+// of double additions whatever the calls were that fed it the batches, and the sum of two tables on
+// the host continues a chain exactly as one more batch would.  A kernel of its own instantiation: the
+// ACC = false code is the code every other launch has always run.
+template <bool ACC>
 __device__ __forceinline__ void fwd_finalize_channel(
     const float* __restrict__ partial, const int nblk, const int M, const int C, const int c,
     const float* __restrict__ gamma, const float* __restrict__ beta, float* running_mean,
     float* running_var, long long* nbt, const float momentum, const float eps,
-    float* __restrict__ stats, const void* __restrict__ pivot, const int pivot_bf16) {
+    float* __restrict__ stats, const void* __restrict__ pivot, const int pivot_bf16,
+    double* __restrict__ acc_head = nullptr, double* __restrict__ acc = nullptr) {
     double s1, s2;
     if (!partial_sums(partial, nblk, C, c, s1, s2)) return;
     // pivot: row 0 of the tensor whose column reduce took its sums about that row (NULL: about 0)
@@ -175,26 +186,86 @@ __device__ __forceinline__ void fwd_finalize_channel(
     const double mean = piv + dmean;
     double var = s2 / M - dmean * dmean;
     if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float w = gamma[c] * rstd;
-    stats[c] = (float)mean;
-    stats[C + c] = rstd;
-    stats[2 * C + c] = w;
-    stats[3 * C + c] = beta[c] - (float)mean * w;
+    if (!ACC || stats) {             // (stats == NULL: cilrs_bn_train_stats keeps the table only)
+        const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+        const float w = gamma[c] * rstd;
+        stats[c] = (float)mean;
+        stats[C + c] = rstd;
+        stats[2 * C + c] = w;
+        stats[3 * C + c] = beta[c] - (float)mean * w;
+    }
     if (running_mean) {
         const double unbiased = M > 1 ? var * ((double)M / (double)(M - 1)) : var;
         running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
         running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unbiased);
     }
     if (nbt && c == 0) *nbt += 1;
+    if (ACC) {
+        // (contraction off: with it the compiler fuses a term's product into the chain's addition --
+        //  one rounding instead of two, and no longer what adding two tables on the host does)
+#pragma clang fp contract(off)
+        const double dM = (double)M;
+        const double unb = var * (dM / (double)(M - 1));                // (M >= 2: the launcher)
+        const double mm = mean * mean;
+        const double ex2 = var + mm;
+        const double t2 = dM * mean, t3 = dM * ex2;
+        acc[c] = acc[c] + mean;
+        acc[C + c] = acc[C + c] + unb;
+        acc[2 * C + c] = acc[2 * C + c] + t2;
+        acc[3 * C + c] = acc[3 * C + c] + t3;
+        if (c == 0) {
+            acc_head[0] = acc_head[0] + 1.0;
+            acc_head[1] = acc_head[1] + dM;
+        }
+    }
 }
 __global__ __launch_bounds__(kFinThreads) void bn_fwd_finalize_kernel(
     const float* __restrict__ partial, const int nblk, const int M, const int C,
     const float* __restrict__ gamma, const float* __restrict__ beta, float* running_mean,
     float* running_var, long long* nbt, const float momentum, const float eps,
     float* __restrict__ stats, const void* __restrict__ pivot, const int pivot_bf16) {
-    fwd_finalize_channel(partial, nblk, M, C, blockIdx.x, gamma, beta, running_mean, running_var,
-                         nbt, momentum, eps, stats, pivot, pivot_bf16);
+    fwd_finalize_channel<false>(partial, nblk, M, C, blockIdx.x, gamma, beta, running_mean,
+                                running_var, nbt, momentum, eps, stats, pivot, pivot_bf16);
+}
+// ... with the re-estimation table (stats may be NULL: cilrs_bn_train_stats keeps the table only)
+__global__ __launch_bounds__(kFinThreads) void bn_fwd_finalize_acc_kernel(
+    const float* __restrict__ partial, const int nblk, const int M, const int C,
+    const float* __restrict__ gamma, const float* __restrict__ beta, float* running_mean,
+    float* running_var, long long* nbt, const float momentum, const float eps,
+    float* __restrict__ stats, const void* __restrict__ pivot, const int pivot_bf16,
+    double* __restrict__ acc_head, double* __restrict__ acc) {
+    fwd_finalize_channel<true>(partial, nblk, M, C, blockIdx.x, gamma, beta, running_mean,
+                               running_var, nbt, momentum, eps, stats, pivot, pivot_bf16, acc_head,
+                               acc);
+}
+
+// running_mean / running_var / num_batches_tracked of every layer from the re-estimation table
+// (block b = layer b; each value rounded once from double)
+__global__ __launch_bounds__(256) void bn_stats_finalize_kernel(const BnStatsTable t,
+                                                                const double* __restrict__ table,
+                                                                const int estimator,
+                                                                float* __restrict__ running,
+                                                                long long* __restrict__ nbt) {
+    const int l = blockIdx.x;
+    const int C = t.C[l];
+    const double* head = table + t.head[l];
+    const double* a = table + t.sums[l];
+    float* rm = running + t.rm[l];
+    float* rv = running + t.rv[l];
+    const double tb = head[0], N = head[1];
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        if (estimator == 0) {
+            rm[c] = (float)(a[c] / tb);
+            rv[c] = (float)(a[C + c] / tb);
+        } else {
+            const double m = a[2 * C + c] / N;
+            double v = a[3 * C + c] / N - m * m;
+            if (v < 0.0) v = 0.0;
+            rm[c] = (float)m;
+            rv[c] = (float)(v * (N / (N - 1.0)));
+        }
+    }
+    if (threadIdx.x == 0) nbt[l] = (long long)tb;
 }
 
 // eval mode: stats from the running statistics
@@ -1001,8 +1072,14 @@ static int check_c(int C) {
 int launch_bn_train_fwd(const float* y, int M, int C, const float* gamma, const float* beta,
                         float* running_mean, float* running_var, long long* nbt, float momentum,
                         float eps, const float* residual, int relu, float* stats, float* partial,
-                        float* z, int pre_nblk, hipStream_t s, void* z16) {
+                        float* z, int pre_nblk, hipStream_t s, void* z16, double* acc_head,
+                        double* acc) {
     if (check_c(C)) return 1;
+    CILRS_CHECK((acc == nullptr) == (acc_head == nullptr), "bn_train_fwd: acc_head and acc go together");
+    CILRS_CHECK(!acc || M >= 2, "bn_train_fwd: statistics table needs M >= 2 rows per channel (got "
+                "%d): an unbiased variance does not exist", M);
+    CILRS_CHECK(!acc || ((((uintptr_t)acc | (uintptr_t)acc_head) & 7) == 0),
+                "bn_train_fwd: statistics table must be 8-byte aligned");
     int nblk = pre_nblk;
     const float* pivot = nullptr;      // partials from a convolution epilogue: sums of y, y*y
     if (nblk <= 0) {
@@ -1013,9 +1090,16 @@ int launch_bn_train_fwd(const float* y, int M, int C, const float* gamma, const 
         CILRS_LAUNCH_CHECK();
         nblk = p.nblk;
     }
-    bn_fwd_finalize_kernel<<<C, kFinThreads, 0, s>>>(partial, nblk, M, C, gamma, beta,
-                                                        running_mean, running_var, nbt, momentum,
-                                                        eps, stats, pivot, 0);
+    if (acc) {
+        bn_fwd_finalize_acc_kernel<<<C, kFinThreads, 0, s>>>(partial, nblk, M, C, gamma, beta,
+                                                             running_mean, running_var, nbt,
+                                                             momentum, eps, stats, pivot, 0,
+                                                             acc_head, acc);
+    } else {
+        bn_fwd_finalize_kernel<<<C, kFinThreads, 0, s>>>(partial, nblk, M, C, gamma, beta,
+                                                         running_mean, running_var, nbt, momentum,
+                                                         eps, stats, pivot, 0);
+    }
     CILRS_LAUNCH_CHECK();
     if (z) {
         const size_t total4 = (size_t)M * C / 4;
@@ -1029,6 +1113,34 @@ int launch_bn_train_fwd(const float* y, int M, int C, const float* gamma, const 
 int launch_bn_eval_stats_all(const BnEvalTable& t, const float* params, const float* bn_running,
                              float* ws, float eps, hipStream_t s) {
     bn_eval_stats_all_kernel<<<t.n, 256, 0, s>>>(t, params, bn_running, ws, eps);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
+// the stand-alone column reduce (about the pivot row) + the accumulating finalise, nothing else:
+// acc = {t, sum M} | [4][C]; no scale / shift table is written (stats == NULL)
+int launch_bn_train_stats(const float* y, int M, int C, double* acc, float* partial, hipStream_t s) {
+    if (check_c(C)) return 1;
+    CILRS_CHECK(y && acc && partial, "bn_train_stats: NULL tensor");
+    CILRS_CHECK(M >= 2, "bn_train_stats: M >= 2 rows per channel needed (got %d): an unbiased "
+                "variance does not exist", M);
+    CILRS_CHECK(((uintptr_t)acc & 7) == 0 && (((uintptr_t)y | (uintptr_t)partial) & 15) == 0,
+                "bn_train_stats: table must be 8-byte, y / partial 16-byte aligned");
+    const ColPlan p = col_plan(M, C);
+    bn_colreduce_kernel<0><<<dim3(p.nblk, col_groups(C)), 256, 0, s>>>(y, nullptr, nullptr, nullptr,
+                                                                     partial, M, C, 0,
+                                                                     p.rows_per_block);
+    CILRS_LAUNCH_CHECK();
+    bn_fwd_finalize_acc_kernel<<<C, kFinThreads, 0, s>>>(partial, p.nblk, M, C, nullptr, nullptr,
+                                                         nullptr, nullptr, nullptr, 0.f, 1e-5f,
+                                                         nullptr, y, 0, acc, acc + kBnStatsHead);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_bn_stats_finalize(const BnStatsTable& t, const double* table, int estimator,
+                             float* bn_running, long long* bn_nbt, hipStream_t s) {
+    bn_stats_finalize_kernel<<<t.n, 256, 0, s>>>(t, table, estimator, bn_running, bn_nbt);
     CILRS_LAUNCH_CHECK();
     return 0;
 }

@@ -205,7 +205,15 @@ size_t bn_partial_floats(int C);
 int launch_bn_train_fwd(const float* y, int M, int C, const float* gamma, const float* beta,
                         float* running_mean, float* running_var, long long* nbt, float momentum,
                         float eps, const float* residual, int relu, float* stats, float* partial,
-                        float* z, int pre_nblk, hipStream_t s, void* z16 = nullptr);
+                        float* z, int pre_nblk, hipStream_t s, void* z16 = nullptr,
+                        double* acc_head = nullptr, double* acc = nullptr);
+// acc_head / acc (both or neither; launch_bn_train_fwd, the fp32 form only): the BatchNorm re-estimation
+// table of this layer (cilrs_bn_train_stats) -- acc_head = {t, sum M}, acc = [4][C] running sums of
+// the batch mean | unbiased variance | M * mean | M * (variance + mean^2), continued in double by the
+// thread that finalises the channel (no atomics: the table depends on the batches and their order
+// only).  Meant for running_mean == NULL: the running buffers are then not touched.
+constexpr int kBnStatsHead = 2, kBnStatsRows = 4;
+int launch_bn_train_stats(const float* y, int M, int C, double* acc, float* partial, hipStream_t s);
 // (z16 / dy16 / out16: optional bf16 shadow of the fp32 result -- the 16-bit operand of the next
 //  convolution in the bf16 training mode; launch_bn_bwd: dy may then be NULL)
 // eval-mode scale/shift of up to kMaxConvs BatchNorm layers in one launch (offsets in floats);
@@ -220,6 +228,16 @@ struct BnEvalTable {
 };
 int launch_bn_eval_stats_all(const BnEvalTable& t, const float* params, const float* bn_running,
                              float* ws, float eps, hipStream_t s);
+// all layers' running_mean / running_var / num_batches_tracked from a table, in one launch
+// (block b = layer b); estimator 0: mean of the batch statistics, 1: pooled moments of all rows
+struct BnStatsTable {
+    int n;
+    int C[kMaxConvs];
+    unsigned rm[kMaxConvs], rv[kMaxConvs];           // into the BN buffer arena (floats)
+    unsigned head[kMaxConvs], sums[kMaxConvs];       // into the table (doubles)
+};
+int launch_bn_stats_finalize(const BnStatsTable& t, const double* table, int estimator,
+                             float* bn_running, long long* bn_nbt, hipStream_t s);
 int launch_bn_eval_fwd(const float* y, int M, int C, const float* gamma, const float* beta,
                        const float* running_mean, const float* running_var, float eps,
                        const float* residual, int relu, float* stats, float* z, hipStream_t s);

@@ -329,6 +329,7 @@ struct cilrs_net {
     int dy_pos = 0;
     int bwd_nblk_next = 0;                 // fused BN-backward partials waiting for their BN
     BnEvalTable bn_table;
+    BnStatsTable bn_stats;                 // re-estimation table layout, indexed by BatchNorm layer
     FoldF16Table f16_table;                // fp16 inference: folded weights / biases / activations
     size_t f16_w, f16_bias, f16_act[5], f16_act_floats;
     size_t stem16_w = 0, stem16_b = 0;     // folded 16-bit stem weights [64][7][8][4] / fp32 shift
@@ -756,6 +757,20 @@ int conv_wgrad16(cilrs_net* net, const ConvT& c, const ConvG& g, const cilrs_hal
 
 }  // namespace
 
+static void bn_stats_layout(const Arch& A, BnStatsTable& t) {
+    memset(&t, 0, sizeof(t));
+    t.n = (int)A.bns.size();
+    size_t off = (size_t)kBnStatsHead * A.bns.size();
+    for (int j = 0; j < t.n; ++j) {
+        const BnT& b = A.bns[j];
+        t.C[j] = b.C;
+        t.rm[j] = (unsigned)b.rm; t.rv[j] = (unsigned)b.rv;
+        t.head[j] = (unsigned)(kBnStatsHead * j);
+        t.sums[j] = (unsigned)off;
+        off += (size_t)kBnStatsRows * b.C;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // C-ABI: layout queries
 // ------------------------------------------------------------------------------------------------
@@ -827,6 +842,27 @@ int cilrs_variant_bn_info(int variant, int j, char* prefix, int prefix_cap, int*
     if (channels) *channels = b.C;
     if (rm_offset) *rm_offset = b.rm;
     if (rv_offset) *rv_offset = b.rv;
+    return 0;
+}
+
+// BatchNorm re-estimation table of a variant (doubles): {t, sum M} of layer 0, 1, ... and then the
+// layers' [4][C] blocks, in cilrs_variant_bn_info order
+size_t cilrs_variant_bn_stats_doubles(int variant) {
+    if (!variant_ok(variant)) return 0;
+    const Arch& A = arch(variant);
+    return (size_t)kBnStatsHead * A.bns.size() + (size_t)(kBnStatsRows / 2) * A.bn_floats;
+}
+
+int cilrs_variant_bn_stats_info(int variant, int j, int* channels, size_t* head_offset,
+                                size_t* sums_offset) {
+    CILRS_CHECK(variant_ok(variant), "variant %d out of range", variant);
+    const Arch& A = arch(variant);
+    CILRS_CHECK(j >= 0 && j < (int)A.bns.size(), "bn index %d out of range", j);
+    BnStatsTable t;
+    bn_stats_layout(A, t);
+    if (channels) *channels = t.C[j];
+    if (head_offset) *head_offset = t.head[j];
+    if (sums_offset) *sums_offset = t.sums[j];
     return 0;
 }
 
@@ -1012,6 +1048,7 @@ int cilrs_net_create_ex(int variant, int batch, int height, int width, unsigned 
     n->ksplit = bump.take(ksplit_max > 0 ? ksplit_max : 4);
     n->status_b = bump.take(64) * sizeof(float);
     CILRS_CHECK((int)A.convs.size() <= kMaxConvs, "too many convolutions for the BN tables");
+    bn_stats_layout(A, n->bn_stats);
     n->bn_table.n = (int)A.convs.size();
     for (size_t ci = 0; ci < A.convs.size(); ++ci) {
         const BnT& b = A.bns[A.convs[ci].bn];
@@ -1152,6 +1189,19 @@ int cilrs_net_activation_info(const cilrs_net* net, int conv, size_t* y_offset, 
     if (z_offset) *z_offset = g.z;
     if (numel) *numel = (size_t)g.M * net->A->convs[conv].cout;
     if (channels) *channels = net->A->convs[conv].cout;
+    return 0;
+}
+
+// where convolution `conv`'s BatchNorm keeps its 4*C floats mean | rstd | scale | shift in the
+// workspace (floats), the rows M it sees in this plan, and its layer number (cilrs_variant_bn_info)
+int cilrs_net_bn_layer_info(const cilrs_net* net, int conv, size_t* stats_offset, int* channels,
+                            int* rows, int* bn_index) {
+    CILRS_CHECK(net != nullptr, "bn_layer_info: net is NULL");
+    CILRS_CHECK(conv >= 0 && conv < (int)net->cg.size(), "bn_layer_info: conv %d out of range", conv);
+    if (stats_offset) *stats_offset = net->cg[conv].stats;
+    if (channels) *channels = net->A->convs[conv].cout;
+    if (rows) *rows = net->cg[conv].M;
+    if (bn_index) *bn_index = net->A->convs[conv].bn;
     return 0;
 }
 
@@ -1301,13 +1351,17 @@ static WinoWeightTable wino_subtable(const cilrs_net* net, int g0, int g1) {
 // argmax).  *feat: the last feature map, or nullptr when it is already pooled into `combined`.
 // ft_groups > 0 (fine-tuning): the first ft_groups trunk groups were already computed in eval mode
 // (trunk_fwd_eval32 up to that group, last output in `start`); this function builds the rest.
+// bn_acc (cilrs_net_forward_bn_stats; fp32 train mode, no frozen prefix): the BatchNorm
+// re-estimation table -- every layer's batch statistics are added to it and the running buffers /
+// num_batches_tracked are left alone; every launch is otherwise the train step's.
 static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train, bool frozen,
                            hipStream_t s, const float** feat, int ft_groups = 0,
-                           const float* start = nullptr) {
+                           const float* start = nullptr, double* bn_acc = nullptr) {
     const Arch& A = *net->A;
     float* ws = reinterpret_cast<float*>(bufs->workspace);
     const float* P = bufs->params;
     float* R = bufs->bn_running;
+    long long* const NBT = reinterpret_cast<long long*>(bufs->bn_nbt);
     const int B = net->B;
     const float eps = 1e-5f, mom = 0.1f;
     const bool bf16t = train && net->bf16_train;      // trunk convolutions on the bf16 matrix pipe
@@ -1331,10 +1385,12 @@ static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train,
                                       h16(ws, net->z16[ci]), pre_nblk, st));
         } else if (train) {
             RUN(net, std::string("bn_fwd.") + kGroupName[c.group], 0.0, bytes, st,
-                launch_bn_train_fwd(ws + g.y, g.M, c.cout, P + b.gamma, P + b.beta, R + b.rm,
-                                    R + b.rv, reinterpret_cast<long long*>(bufs->bn_nbt) + c.bn,
-                                    mom, eps, residual, relu, ws + g.stats, partial,
-                                    ws + g.z, pre_nblk, st));
+                launch_bn_train_fwd(ws + g.y, g.M, c.cout, P + b.gamma, P + b.beta,
+                                    bn_acc ? nullptr : R + b.rm, bn_acc ? nullptr : R + b.rv,
+                                    bn_acc ? nullptr : NBT + c.bn, mom, eps, residual, relu,
+                                    ws + g.stats, partial, ws + g.z, pre_nblk, st, nullptr,
+                                    bn_acc ? bn_acc + net->bn_stats.head[c.bn] : nullptr,
+                                    bn_acc ? bn_acc + net->bn_stats.sums[c.bn] : nullptr));
         } else {
             RUN(net, std::string("bn_fwd.") + kGroupName[c.group], 0.0, bytes, st,
                 launch_bn_eval_fwd(ws + g.y, g.M, c.cout, P + b.gamma, P + b.beta, R + b.rm,
@@ -1399,10 +1455,11 @@ static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train,
         const BnT& b0 = A.bns[c0.bn];
         RUN(net, "bn_fwd.stem", 0.0, 0.0, s,
             launch_bn_train_fwd(ws + g0.y, g0.M, c0.cout, P + b0.gamma, P + b0.beta,
-                                R + b0.rm, R + b0.rv,
-                                reinterpret_cast<long long*>(bufs->bn_nbt) + c0.bn, mom, eps,
+                                bn_acc ? nullptr : R + b0.rm, bn_acc ? nullptr : R + b0.rv,
+                                bn_acc ? nullptr : NBT + c0.bn, mom, eps,
                                 nullptr, 1, ws + g0.stats, ws + net->bn_partial, nullptr, nb,
-                                s));
+                                s, nullptr, bn_acc ? bn_acc + net->bn_stats.head[c0.bn] : nullptr,
+                                bn_acc ? bn_acc + net->bn_stats.sums[c0.bn] : nullptr));
     }
     unsigned char* argmax = reinterpret_cast<unsigned char*>(bufs->workspace) + net->argmax_b;
     if (ft_groups == 0)
@@ -1860,6 +1917,79 @@ int cilrs_net_forward(cilrs_net* net, const cilrs_buffers* bufs, const float* im
         launch_nchw3_to_nhwc4(image, ws + net->x4, net->B, net->H, net->W, sn, sc, sh, sw, s));
     return forward_from_x4(net, bufs, speed, command, train, dropout_p, seed, controls,
                            pred_speed, s);
+}
+
+// The train-mode trunk of cilrs_net_forward(train = 1) -- the same convolution, BatchNorm and
+// max-pool launches in the same order -- with every layer's batch statistics added to `table`
+// instead of moving the running buffers (see include/cilrs_hip.h).
+int cilrs_net_forward_bn_stats(cilrs_net* net, const cilrs_buffers* bufs, const float* image,
+                               long sn, long sc, long sh, long sw, double* table, void* stream) {
+    if (check_bufs(net, bufs, false)) return 1;
+    CILRS_CHECK(image != nullptr, "forward_bn_stats: NULL image");
+    CILRS_CHECK(!net->bf16_train, "forward_bn_stats: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan "
+                "takes its statistics from bf16 tensors)");
+    CILRS_CHECK(table != nullptr && ((uintptr_t)table & 7) == 0,
+                "forward_bn_stats: the table is NULL or not 8-byte aligned");
+    for (size_t ci = 0; ci < net->A->convs.size(); ++ci)
+        CILRS_CHECK(net->cg[ci].M >= 2, "forward_bn_stats: BatchNorm %s sees %d value per channel in "
+                    "this plan; more than 1 is needed (torch: 'Expected more than 1 value per "
+                    "channel when training')", net->A->bns[net->A->convs[ci].bn].prefix.c_str(),
+                    net->cg[ci].M);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
+    net->ws_base = ws;
+    net->mc_src = 0; ++net->fwd_serial;
+    if (clear_status_once(net, bufs->workspace, s)) return 1;
+    net->bwd_done = 0;
+    net->ft_bn = net->ft_grad = 0;
+    // no heads run: nothing here is a graph cilrs_net_backward could walk
+    net->trained_fwd = false;
+    net->frozen_fwd = false;
+    // the per-layer scale / shift tables are about to hold batch statistics: the cached eval state
+    // goes stale
+    net->prep_key = 0; net->fold_key = 0;
+    RUN(net, "transform", 0.0, 0.0, s,
+        launch_nchw3_to_nhwc4(image, ws + net->x4, net->B, net->H, net->W, sn, sc, sh, sw, s));
+    RUN(net, "transform", 0.0, 0.0, s,
+        launch_pad_cin3_to_4(bufs->params + net->A->convs[0].w, ws + net->w4, 64 * 49, s));
+    const float* feat = nullptr;
+    if (trunk_fwd_graph(net, bufs, 1, false, s, &feat, 0, nullptr, table)) return 1;
+    net->last_dropout = 0.f;
+    net->mc_src = -1;         // a train-mode forward: the tick-following entries refuse
+    net->fwd_half = 0;
+    return 0;
+}
+
+int cilrs_bn_stats_finalize(int variant, const double* table, int estimator, float* bn_running,
+                            int64_t* bn_nbt, void* stream) {
+    CILRS_CHECK(variant_ok(variant), "bn_stats_finalize: variant %d out of range", variant);
+    CILRS_CHECK(table && bn_running && bn_nbt, "bn_stats_finalize: NULL tensor");
+    CILRS_CHECK(((uintptr_t)table & 7) == 0 && ((uintptr_t)bn_nbt & 7) == 0 &&
+                    ((uintptr_t)bn_running & 3) == 0, "bn_stats_finalize: misaligned tensor");
+    CILRS_CHECK(estimator == 0 || estimator == 1, "bn_stats_finalize: estimator %d (0 batch_mean, "
+                "1 pooled)", estimator);
+    const Arch& A = arch(variant);
+    BnStatsTable t;
+    bn_stats_layout(A, t);
+    // a layer that saw no batch has no statistics: the {t, sum M} heads are read back first (this
+    // call synchronises the stream; it runs once per re-estimation, not per batch)
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    std::vector<double> head((size_t)kBnStatsHead * t.n);
+    CILRS_HIP(hipMemcpyAsync(head.data(), table, head.size() * sizeof(double),
+                             hipMemcpyDeviceToHost, s));
+    CILRS_HIP(hipStreamSynchronize(s));
+    for (int j = 0; j < t.n; ++j) {
+        const double tb = head[(size_t)kBnStatsHead * j], rows = head[(size_t)kBnStatsHead * j + 1];
+        CILRS_CHECK(tb >= 1.0 && rows >= 2.0 * tb && tb == (double)(long long)tb,
+                    "bn_stats_finalize: BatchNorm %s has seen %g batches / %g rows; at least one "
+                    "batch is needed", A.bns[j].prefix.c_str(), tb, rows);
+    }
+    return launch_bn_stats_finalize(t, table, estimator, bn_running,
+                                    reinterpret_cast<long long*>(bn_nbt), s);
+}
+
+int cilrs_bn_train_stats(const float* y, int M, int C, double* acc, float* partial, void* stream) {
+    return launch_bn_train_stats(y, M, C, acc, partial, reinterpret_cast<hipStream_t>(stream));
 }
 
 int cilrs_net_forward_frozen(cilrs_net* net, const cilrs_buffers* bufs, const float* image, long sn,

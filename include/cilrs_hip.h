@@ -122,6 +122,58 @@ int cilrs_net_forward_frozen(cilrs_net* net, const cilrs_buffers* bufs, const fl
                              long sc, long sh, long sw, const float* speed, const int64_t* command,
                              float* controls, float* pred_speed, void* stream);
 
+/* BatchNorm re-estimation ("update_bn" of averaged weights; AdaBN, the label-free domain adaptation:
+ * every BatchNorm's statistics re-estimated on frames of the target domain).
+ *
+ * The table (doubles, on the device, zeroed by the caller before the first batch):
+ *   cilrs_variant_bn_stats_doubles(variant) entries -- for layer j of cilrs_variant_bn_info, at
+ *   head_offset {t, sum_b M_b} (batches and rows seen), and at sums_offset four rows of C_j:
+ *     [0] sum_b mean_b   [1] sum_b var_b * M_b / (M_b - 1)   [2] sum_b M_b * mean_b
+ *     [3] sum_b M_b * (var_b + mean_b^2)
+ *   with mean_b / var_b the batch mean and biased variance the train-mode BatchNorm normalises
+ *   with, taken in double where it forms them.  Each chain is continued by one thread, one batch
+ *   after the other, every term rounded on its own: no atomics, the table is a function of the
+ *   batches and their order alone, and tables of disjoint batch sets add entry by entry (data
+ *   parallel ranks all-reduce them).
+ *
+ * cilrs_net_forward_bn_stats: the train-mode trunk of cilrs_net_forward(train = 1) on batch
+ *   statistics -- the same convolution, BatchNorm and max-pool launches in the same order, hence bit
+ *   for bit the same per-layer statistics and activations -- adding each layer's batch to `table`.
+ *   No heads, no dropout, no loss; bn_running, bn_nbt and the parameters are not written; no host
+ *   synchronisation.  Afterwards the plan counts as "train-mode forward last" (the tick-following
+ *   entries refuse as after a train step) and holds no graph (cilrs_net_backward refuses).  fp32
+ *   plans of every variant.  Refused, nothing launched: a CILRS_PLAN_BF16_TRAIN plan; a NULL or
+ *   misaligned table; a plan in which some BatchNorm sees fewer than 2 values per channel (torch
+ *   raises "Expected more than 1 value per channel when training"; an unbiased variance does not
+ *   exist).
+ * cilrs_bn_stats_finalize: ONE launch writes every layer's running_mean / running_var into
+ *   bn_running and t into bn_nbt, each value rounded once from double.
+ *     estimator 0 ("batch_mean"): running_mean = sum mean_b / t, running_var = sum unbiased var_b / t
+ *       -- what torch leaves after reset_running_stats(), momentum = None and the same train-mode
+ *       forwards (the cumulative moving average).
+ *     estimator 1 ("pooled"): with N = sum M_b, mean = sum M_b mean_b / N,
+ *       var = (sum M_b (var_b + mean_b^2) / N - mean^2) * N / (N - 1): the moments of all rows seen;
+ *       a short last batch weighs by its rows, and for the stem's BatchNorm the result does not
+ *       depend on how the frames were batched.
+ *   Reads the {t, sum M} heads back first (synchronises `stream`; not capturable): a layer with
+ *   t == 0 is refused, like NULL / misaligned tensors and an unknown estimator, with nothing launched.
+ * cilrs_bn_train_stats: the op-level twin -- the stand-alone column reduce of y[M][C] (about its
+ *   pivot row, as cilrs_bn_train_fwd) plus the accumulating finalise, nothing else; acc = {t, sum M}
+ *   followed by the four rows of C (2 + 4 C doubles), partial: cilrs_bn_partial_floats(C) floats.
+ *   M >= 2. */
+size_t cilrs_variant_bn_stats_doubles(int variant);
+int cilrs_variant_bn_stats_info(int variant, int j, int* channels, size_t* head_offset,
+                                size_t* sums_offset);
+/* where convolution `conv`'s BatchNorm keeps mean | rstd | scale | shift (4 C floats) in the
+ * workspace, in floats; the rows M it sees in this plan; its layer number j */
+int cilrs_net_bn_layer_info(const cilrs_net* net, int conv, size_t* stats_offset, int* channels,
+                            int* rows, int* bn_index);
+int cilrs_net_forward_bn_stats(cilrs_net* net, const cilrs_buffers* bufs, const float* image,
+                               long sn, long sc, long sh, long sw, double* table, void* stream);
+int cilrs_bn_stats_finalize(int variant, const double* table, int estimator, float* bn_running,
+                            int64_t* bn_nbt, void* stream);
+int cilrs_bn_train_stats(const float* y, int M, int C, double* acc, float* partial, void* stream);
+
 /* Fine-tuning on top of a pretrained trunk -- the reference's own first remedy for its failure on
  * the campus map: "collect a small CUSAT-specific dataset and fine-tune the checkpoint" (reference
  * README.md, "Why Results Degraded on CUSAT Map"; configs/train_config.json has a `pretrained`
