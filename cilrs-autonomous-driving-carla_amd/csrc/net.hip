@@ -347,29 +347,34 @@ struct cilrs_net {
     uint64_t weights_key = 0, prep_key = 0, fold_key = 0, graph_wkey = 0;
     int fold_half = 0;
     const void* prep_bufs[3] = {nullptr, nullptr, nullptr};     // params, bn_running, workspace
-    bool trained_fwd = false;
-    float last_dropout = 0.f;
-    // where the last forward left what cilrs_net_heads_mc reads: 0 no forward yet (every forward
-    // sets 0 on entry and its own value at its successful end, so a forward that failed midway
-    // leaves nothing to sample from); 1 pooled fp32
-    // features in `combined` (every eval-mode forward but the persistent launch); 2 the last feature
-    // map (the persistent launch pools inside its head stage and keeps no pooled copy); -1 a
-    // train-mode forward (batch statistics: refused)
-    int mc_src = 0;
-    // cilrs_net_gradcam: arithmetic of the last forward (0 fp32, 1 fp16, 2 bf16: set with mc_src);
-    // a count of the forwards this plan has begun; the segment the last unbroken run of backward
-    // calls from segment 0 stopped at (G[3] then holds the gradient of trunk group 5 - gc_bwd_end's
-    // output; -1: none, or a call that failed midway) and the forward count it belonged to
-    int fwd_half = 0;
-    uint64_t fwd_serial = 0;
-    int gc_bwd_end = -1;
-    uint64_t gc_bwd_fwd = 0;
-    // the last graph-keeping forward was cilrs_net_forward_frozen (BatchNorm on the running
-    // statistics: its backward drops the batch-statistics terms)
-    bool frozen_fwd = false;
-    // segments of the last backward whose outputs cilrs_net_input_grads reads are still in the
-    // workspace: bit 0 = d(speed encoder) of segment 0, bit 5 = d(stem conv output) in G[1]
-    unsigned bwd_done = 0;
+    // What the plan's last forward left in the workspace; what may follow it is decided from here.
+    // Written by fwd_begin (reset, before a forward's first launch) and fwd_commit (at its
+    // successful end) alone, but for the two backward fields, which backward_impl keeps.
+    struct LastForward {
+        enum Kind {
+            None,        // no forward yet, or one that did not finish
+            Eval,        // z of every layer, pooled fp32 features in `combined`
+            EvalB1,      // the persistent launch: pools inside its head stage, keeps no pooled copy
+            Train,       // batch statistics, graph kept (cilrs_net_forward train != 0, _ft)
+            Frozen,      // running statistics, graph kept (cilrs_net_forward_frozen*)
+            StatsOnly    // cilrs_net_forward_bn_stats: the train-mode trunk, no heads, no graph
+        } kind = None;
+        int half = 0;              // Eval: arithmetic of the trunk (0 fp32, 1 fp16, 2 bf16)
+        float dropout = 0.f;       // Train: the heads' dropout probability
+        // segments of the backward on this forward whose outputs cilrs_net_input_grads reads:
+        // bit 0 = d(speed encoder) of segment 0, bit 5 = d(stem conv output) in G[1]
+        unsigned bwd_done = 0;
+        // where an unbroken run of backward calls from segment 0 on this forward stopped (G[3] then
+        // holds the gradient of trunk group 5 - gc_bwd_end's output; -1: none, or a failed call)
+        int gc_bwd_end = -1;
+        bool keeps_graph() const { return kind == Train || kind == Frozen; }   // cilrs_net_backward*
+        bool frozen() const { return kind == Frozen; }
+        // the features of the tick-following entries (heads_mc, gradcam, feature_moments, novelty):
+        // none, a train-mode forward's (refused), the last feature map only, else pooled
+        bool no_features() const { return kind == None; }
+        bool train_features() const { return kind == Train || kind == StatsOnly; }
+        bool featmap_only() const { return kind == EvalB1; }
+    } last;
     // bf16 training mode (CILRS_PLAN_BF16_TRAIN): the trunk convolutions after the stem multiply
     // bf16 operands on v_mfma_f32_32x32x16_bf16 (fp32 accumulation, fp32 results); everything
     // else -- BatchNorm, residual adds, the stem, the heads, loss, Adam, master weights -- stays
@@ -390,7 +395,8 @@ struct cilrs_net {
     // Fine-tuning (cilrs_net_forward_ft): leading trunk groups (stem, layer1..layer4) of the last
     // graph-keeping forward that ran in eval mode (ft_bn: BatchNorm folded into the convolution
     // epilogues, nothing kept for a backward pass) / whose parameters take no gradient (ft_grad:
-    // where cilrs_net_backward stops).  The prefix's weight-derived state -- scale / shift of its
+    // where cilrs_net_backward stops); fwd_commit clears the cut for every kind but Eval / EvalB1,
+    // cilrs_net_forward_ft sets it.  The prefix's weight-derived state -- scale / shift of its
     // BatchNorms, the padded stem weights, the Winograd filter images of its layers -- is cached
     // under the caller's prefix key.  ft_wino: folded-epilogue Winograd launches of that forward.
     int ft_bn = 0, ft_grad = 0, ft_wino = 0;
@@ -446,6 +452,21 @@ int clear_status_once(cilrs_net* net, void* workspace, hipStream_t s) {
     net->status_cleared_for = workspace;
     return 0;
 }
+
+// The two writers of cilrs_net::last: every forward calls fwd_begin before its first launch (from
+// there on the workspace no longer holds the previous forward) and fwd_commit at its successful end.
+int fwd_begin(cilrs_net* net, const cilrs_buffers* bufs, hipStream_t s) {
+    net->ws_base = reinterpret_cast<float*>(bufs->workspace);
+    net->last = cilrs_net::LastForward();
+    return clear_status_once(net, bufs->workspace, s);
+}
+void fwd_commit(cilrs_net* net, cilrs_net::LastForward::Kind kind, int half = 0, float dropout = 0.f) {
+    net->last.kind = kind; net->last.half = half; net->last.dropout = dropout;
+    if (kind != cilrs_net::LastForward::Eval && kind != cilrs_net::LastForward::EvalB1)
+        net->ft_bn = net->ft_grad = 0;
+}
+// weights or BatchNorm tables are about to change: the cached eval state goes stale
+void drop_eval_state(cilrs_net* net) { net->prep_key = net->fold_key = 0; }
 
 // Events that only order one stream of this device behind another (hipStreamWaitEvent; the host
 // never inspects them).  hipEventDisableSystemFence: by default a HIP event performs a SYSTEM-scope
@@ -1791,27 +1812,60 @@ static int heads_fwd(cilrs_net* net, const cilrs_buffers* bufs, const float* fea
     return 0;
 }
 
-// Every forward entry ends here, with the input image in x4.  Modes: train (batch-statistics
-// BatchNorm, dropout), frozen (running statistics, activations kept for the backward pass), else
-// eval in fp32 (half = 0), fp16 (1) or bf16 (2).
-static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const float* speed,
-                           const int64_t* command, int train, float dropout_p, uint64_t seed,
-                           float* controls, float* pred_speed, hipStream_t s, int half = 0,
-                           bool frozen = false) {
-    net->ws_base = reinterpret_cast<float*>(bufs->workspace);
-    net->mc_src = 0;          // until this forward has finished, its features are not there
-    ++net->fwd_serial;
+// Where a forward takes its image from: strided float NCHW (already normalised), uint8 HWC frames
+// of the plan's size, or raw camera frames (resized on the way).  stage_input brings it into x4.
+struct ImageSrc {
+    enum Kind { FloatNCHW, U8HWC, Camera } kind;
+    const void* data;
+    long sn = 0, sc = 0, sh = 0, sw = 0;                  // FloatNCHW: strides in floats
+    int src_h = 0, src_w = 0, pixel_stride = 0;           // Camera: frame size, bytes per pixel
+    long row_stride = 0, frame_stride = 0;                // Camera: bytes
+};
+static ImageSrc camera_src(const uint8_t* frames, int h, int w, int px, long row, long frame) {
+    return {ImageSrc::Camera, frames, 0, 0, 0, 0, h, w, px, row, frame};
+}
+static int stage_input(cilrs_net* net, const cilrs_buffers* bufs, const ImageSrc& src, hipStream_t s) {
+    float* x4 = reinterpret_cast<float*>(bufs->workspace) + net->x4;
+    const uint8_t* u8 = static_cast<const uint8_t*>(src.data);
+    RUN(net, "transform", 0.0, 0.0, s,
+        src.kind == ImageSrc::FloatNCHW
+            ? launch_nchw3_to_nhwc4(static_cast<const float*>(src.data), x4, net->B, net->H, net->W,
+                                    src.sn, src.sc, src.sh, src.sw, s)
+        : src.kind == ImageSrc::U8HWC
+            ? launch_u8hwc_to_nhwc4(u8, x4, (size_t)net->B * net->H * net->W, kImageMean, kImageStd, s)
+            : launch_camera_to_nhwc4(u8, x4, net->B, src.src_h, src.src_w, src.pixel_stride,
+                                     src.row_stride, src.frame_stride, net->H, net->W, kImageMean,
+                                     kImageStd, s));
+    return 0;
+}
+
+// What the public forward entries differ in.
+struct FwdMode {
+    int train = 0; float dropout_p = 0.f; uint64_t seed = 0;
+    int half = 0; bool frozen = false;
+    // cilrs_net_forward_ft: eval-mode / gradient-free leading trunk groups, the prefix key
+    bool ft = false; int ft_e = 0, ft_g = 0; uint64_t ft_key = 0;
+};
+static const FwdMode kFrozenMode{0, 0.f, 0, 0, true};
+
+// The forward of every entry but the persistent launch and the statistics pass.  Modes: train
+// (batch-statistics BatchNorm, dropout), frozen (running statistics, activations kept for the
+// backward pass), else eval in fp32 (half = 0), fp16 (1) or bf16 (2).
+static int forward_run(cilrs_net* net, const cilrs_buffers* bufs, const ImageSrc& src,
+                       const float* speed, const int64_t* command, float* controls,
+                       float* pred_speed, hipStream_t s, const FwdMode& m) {
+    const int train = m.train, half = m.half;
+    const bool frozen = m.frozen;
+    if (fwd_begin(net, bufs, s)) return 1;
     CILRS_CHECK(!(frozen && (train || half || net->bf16_train)),
                 "frozen forward: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan rejects it)");
-    if (clear_status_once(net, bufs->workspace, s)) return 1;
-    net->bwd_done = 0;
-    if (train || frozen) net->ft_bn = net->ft_grad = 0;
+    if (stage_input(net, bufs, src, s)) return 1;
     if (train) {
         // the stem weights are padded every step; the cached eval state goes stale as the
         // weights / BN buffers are about to change
         RUN(net, "transform", 0.0, 0.0, s,
             launch_pad_cin3_to_4(bufs->params + net->A->convs[0].w, net->ws_base + net->w4, 64 * 49, s));
-        net->prep_key = 0; net->fold_key = 0;
+        drop_eval_state(net);
     } else {
         if (eval_prep(net, bufs, s)) return 1;
         if (half && fold_prep(net, bufs, half, s)) return 1;
@@ -1823,14 +1877,11 @@ static int forward_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const floa
     const int rc = graph  ? trunk_fwd_graph(net, bufs, train, frozen, s, &feat)
                    : half ? trunk_fwd_eval16(net, bufs, half, s, &feat)
                           : trunk_fwd_eval32(net, bufs, s, &feat);
-    const float pdrop = train ? dropout_p : 0.f;
-    if (rc || heads_fwd(net, bufs, feat, speed, command, graph, pdrop, seed, controls, pred_speed, s))
+    const float pdrop = train ? m.dropout_p : 0.f;
+    if (rc || heads_fwd(net, bufs, feat, speed, command, graph, pdrop, m.seed, controls, pred_speed, s))
         return 1;
-    net->trained_fwd = graph;
-    net->frozen_fwd = frozen;
-    net->last_dropout = pdrop;
-    net->mc_src = train ? -1 : 1;
-    net->fwd_half = half;
+    using LF = cilrs_net::LastForward;
+    fwd_commit(net, train ? LF::Train : frozen ? LF::Frozen : LF::Eval, half, pdrop);
     return 0;
 }
 
@@ -1867,16 +1918,14 @@ static int ft_prep(cilrs_net* net, const cilrs_buffers* bufs, int groups, uint64
 // Train-mode forward behind a frozen prefix of k trunk groups: the prefix like trunk_fwd_eval32
 // (z only; eligible 3x3 layers on the Winograd kernel's folded epilogue), the rest of the trunk and
 // the heads on the train path, reading the prefix's last tensor.
-static int forward_ft_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const float* speed,
-                              const int64_t* command, int k, uint64_t prefix_key, float dropout_p,
-                              uint64_t seed, float* controls, float* pred_speed, hipStream_t s) {
-    net->ws_base = reinterpret_cast<float*>(bufs->workspace);
-    net->mc_src = 0; ++net->fwd_serial;
-    if (clear_status_once(net, bufs->workspace, s)) return 1;
-    net->bwd_done = 0;
-    // the trainable weights / BatchNorm buffers are about to change: the cached eval state goes stale
-    net->prep_key = 0; net->fold_key = 0;
-    if (ft_prep(net, bufs, k, prefix_key, s)) return 1;
+static int forward_ft_run(cilrs_net* net, const cilrs_buffers* bufs, const ImageSrc& src,
+                          const float* speed, const int64_t* command, float* controls,
+                          float* pred_speed, hipStream_t s, const FwdMode& m) {
+    const int k = m.ft_e;
+    if (fwd_begin(net, bufs, s)) return 1;
+    if (stage_input(net, bufs, src, s)) return 1;
+    drop_eval_state(net);      // the trainable weights / BatchNorm buffers are about to change
+    if (ft_prep(net, bufs, k, m.ft_key, s)) return 1;
     const float* mid = nullptr;
     net->ft_wino = 0;
     net->ft_route_wino = true;
@@ -1885,13 +1934,9 @@ static int forward_ft_from_x4(cilrs_net* net, const cilrs_buffers* bufs, const f
     if (rc0) return 1;
     const float* feat = mid;
     if (k < 5 && trunk_fwd_graph(net, bufs, 1, false, s, &feat, k, mid)) return 1;
-    if (heads_fwd(net, bufs, feat, speed, command, true, dropout_p, seed, controls, pred_speed, s))
+    if (heads_fwd(net, bufs, feat, speed, command, true, m.dropout_p, m.seed, controls, pred_speed, s))
         return 1;
-    net->trained_fwd = true;
-    net->frozen_fwd = false;
-    net->last_dropout = dropout_p;
-    net->mc_src = -1;
-    net->fwd_half = 0;
+    fwd_commit(net, cilrs_net::LastForward::Train, 0, m.dropout_p);
     return 0;
 }
 
@@ -1905,18 +1950,36 @@ static int check_bufs(const cilrs_net* net, const cilrs_buffers* bufs, bool need
     return 0;
 }
 
+// `who`: the entry's name in its messages
+static int forward_entry(cilrs_net* net, const cilrs_buffers* bufs, const char* who,
+                         const ImageSrc& src, const float* speed, const int64_t* command,
+                         float* controls, float* pred_speed, void* stream, const FwdMode& m) {
+    if (check_bufs(net, bufs, false)) return 1;
+    CILRS_CHECK(src.data && speed && command && controls && pred_speed, "%s: NULL tensor", who);
+    if (m.ft) {
+        CILRS_CHECK(0 <= m.ft_g && m.ft_g <= 5 && (m.ft_e == 0 || m.ft_e == m.ft_g),
+                    "forward_ft: supported cuts are bn_frozen_groups == grad_frozen_groups in 0..5, or "
+                    "bn_frozen_groups == 0 (got %d, %d)", m.ft_e, m.ft_g);
+        CILRS_CHECK(!(net->bf16_train && m.ft_g > 0),
+                    "forward_ft: a CILRS_PLAN_BF16_TRAIN plan cannot freeze");
+    }
+    if (m.frozen)
+        CILRS_CHECK(!net->bf16_train, "forward_frozen: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan "
+                    "rejects the frozen mode)");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (m.ft_e > 0 ? forward_ft_run(net, bufs, src, speed, command, controls, pred_speed, s, m)
+                   : forward_run(net, bufs, src, speed, command, controls, pred_speed, s, m))
+        return 1;
+    if (m.ft) { net->ft_bn = m.ft_e; net->ft_grad = m.ft_g; }
+    return 0;
+}
+
 int cilrs_net_forward(cilrs_net* net, const cilrs_buffers* bufs, const float* image, long sn,
                       long sc, long sh, long sw, const float* speed, const int64_t* command,
                       int train, float dropout_p, uint64_t seed, float* controls,
                       float* pred_speed, void* stream) {
-    if (check_bufs(net, bufs, false)) return 1;
-    CILRS_CHECK(image && speed && command && controls && pred_speed, "forward: NULL tensor");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* ws = reinterpret_cast<float*>(bufs->workspace);
-    RUN(net, "transform", 0.0, 0.0, s,
-        launch_nchw3_to_nhwc4(image, ws + net->x4, net->B, net->H, net->W, sn, sc, sh, sw, s));
-    return forward_from_x4(net, bufs, speed, command, train, dropout_p, seed, controls,
-                           pred_speed, s);
+    return forward_entry(net, bufs, "forward", {ImageSrc::FloatNCHW, image, sn, sc, sh, sw}, speed,
+                         command, controls, pred_speed, stream, {train, dropout_p, seed});
 }
 
 // The train-mode trunk of cilrs_net_forward(train = 1) -- the same convolution, BatchNorm and
@@ -1937,26 +2000,15 @@ int cilrs_net_forward_bn_stats(cilrs_net* net, const cilrs_buffers* bufs, const 
                     net->cg[ci].M);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float* ws = reinterpret_cast<float*>(bufs->workspace);
-    net->ws_base = ws;
-    net->mc_src = 0; ++net->fwd_serial;
-    if (clear_status_once(net, bufs->workspace, s)) return 1;
-    net->bwd_done = 0;
-    net->ft_bn = net->ft_grad = 0;
-    // no heads run: nothing here is a graph cilrs_net_backward could walk
-    net->trained_fwd = false;
-    net->frozen_fwd = false;
-    // the per-layer scale / shift tables are about to hold batch statistics: the cached eval state
-    // goes stale
-    net->prep_key = 0; net->fold_key = 0;
-    RUN(net, "transform", 0.0, 0.0, s,
-        launch_nchw3_to_nhwc4(image, ws + net->x4, net->B, net->H, net->W, sn, sc, sh, sw, s));
+    if (fwd_begin(net, bufs, s)) return 1;
+    drop_eval_state(net);      // the per-layer scale / shift tables are about to hold batch statistics
+    if (stage_input(net, bufs, {ImageSrc::FloatNCHW, image, sn, sc, sh, sw}, s)) return 1;
     RUN(net, "transform", 0.0, 0.0, s,
         launch_pad_cin3_to_4(bufs->params + net->A->convs[0].w, ws + net->w4, 64 * 49, s));
     const float* feat = nullptr;
     if (trunk_fwd_graph(net, bufs, 1, false, s, &feat, 0, nullptr, table)) return 1;
-    net->last_dropout = 0.f;
-    net->mc_src = -1;         // a train-mode forward: the tick-following entries refuse
-    net->fwd_half = 0;
+    // (no heads ran: nothing here is a graph cilrs_net_backward could walk)
+    fwd_commit(net, cilrs_net::LastForward::StatsOnly);
     return 0;
 }
 
@@ -1995,15 +2047,8 @@ int cilrs_bn_train_stats(const float* y, int M, int C, double* acc, float* parti
 int cilrs_net_forward_frozen(cilrs_net* net, const cilrs_buffers* bufs, const float* image, long sn,
                              long sc, long sh, long sw, const float* speed, const int64_t* command,
                              float* controls, float* pred_speed, void* stream) {
-    if (check_bufs(net, bufs, false)) return 1;
-    CILRS_CHECK(image && speed && command && controls && pred_speed, "forward_frozen: NULL tensor");
-    CILRS_CHECK(!net->bf16_train, "forward_frozen: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan "
-                "rejects the frozen mode)");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* ws = reinterpret_cast<float*>(bufs->workspace);
-    RUN(net, "transform", 0.0, 0.0, s,
-        launch_nchw3_to_nhwc4(image, ws + net->x4, net->B, net->H, net->W, sn, sc, sh, sw, s));
-    return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s, 0, true);
+    return forward_entry(net, bufs, "forward_frozen", {ImageSrc::FloatNCHW, image, sn, sc, sh, sw},
+                         speed, command, controls, pred_speed, stream, kFrozenMode);
 }
 
 // Fine-tuning on top of a pretrained trunk -- the reference's own first remedy for its failure on
@@ -2016,25 +2061,10 @@ int cilrs_net_forward_ft(cilrs_net* net, const cilrs_buffers* bufs, const float*
                          int bn_frozen_groups, int grad_frozen_groups, uint64_t prefix_key,
                          float dropout_p, uint64_t seed, float* controls, float* pred_speed,
                          void* stream) {
-    if (check_bufs(net, bufs, false)) return 1;
-    CILRS_CHECK(image && speed && command && controls && pred_speed, "forward_ft: NULL tensor");
-    const int e = bn_frozen_groups, g = grad_frozen_groups;
-    CILRS_CHECK(0 <= g && g <= 5 && (e == 0 || e == g),
-                "forward_ft: supported cuts are bn_frozen_groups == grad_frozen_groups in 0..5, or "
-                "bn_frozen_groups == 0 (got %d, %d)", e, g);
-    CILRS_CHECK(!(net->bf16_train && g > 0), "forward_ft: a CILRS_PLAN_BF16_TRAIN plan cannot freeze");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* ws = reinterpret_cast<float*>(bufs->workspace);
-    RUN(net, "transform", 0.0, 0.0, s,
-        launch_nchw3_to_nhwc4(image, ws + net->x4, net->B, net->H, net->W, sn, sc, sh, sw, s));
-    const int rc = e == 0 ? forward_from_x4(net, bufs, speed, command, 1, dropout_p, seed, controls,
-                                            pred_speed, s)
-                          : forward_ft_from_x4(net, bufs, speed, command, e, prefix_key, dropout_p,
-                                               seed, controls, pred_speed, s);
-    if (rc) return 1;
-    net->ft_bn = e;
-    net->ft_grad = g;
-    return 0;
+    return forward_entry(net, bufs, "forward_ft", {ImageSrc::FloatNCHW, image, sn, sc, sh, sw}, speed,
+                         command, controls, pred_speed, stream,
+                         {1, dropout_p, seed, 0, false, true, bn_frozen_groups, grad_frozen_groups,
+                          prefix_key});
 }
 int cilrs_net_ft_wino_convs(cilrs_net* net) { return net ? net->ft_wino : 0; }
 int cilrs_net_ft_cut(const cilrs_net* net, int* bn_frozen_groups, int* grad_frozen_groups) {
@@ -2048,15 +2078,9 @@ int cilrs_net_ft_cut(const cilrs_net* net, int* bn_frozen_groups, int* grad_froz
 static int forward_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
                       const float* speed, const int64_t* command, float* controls,
                       float* pred_speed, void* stream, int half) {
-    if (check_bufs(net, bufs, false)) return 1;
-    CILRS_CHECK(frames && speed && command && controls && pred_speed, "forward_u8%s: NULL tensor",
-                half == 2 ? "_bf16" : half ? "_f16" : "");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* ws = reinterpret_cast<float*>(bufs->workspace);
-    RUN(net, "transform", 0.0, 0.0, s,
-        launch_u8hwc_to_nhwc4(frames, ws + net->x4, (size_t)net->B * net->H * net->W, kImageMean,
-                              kImageStd, s));
-    return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s, half);
+    const char* who = half == 2 ? "forward_u8_bf16" : half ? "forward_u8_f16" : "forward_u8";
+    return forward_entry(net, bufs, who, {ImageSrc::U8HWC, frames}, speed, command, controls, pred_speed,
+                         stream, {0, 0.f, 0, half});
 }
 
 int cilrs_net_forward_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
@@ -2068,31 +2092,17 @@ int cilrs_net_forward_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_
 int cilrs_net_forward_frozen_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
                                 const float* speed, const int64_t* command, float* controls,
                                 float* pred_speed, void* stream) {
-    if (check_bufs(net, bufs, false)) return 1;
-    CILRS_CHECK(frames && speed && command && controls && pred_speed, "forward_frozen_u8: NULL tensor");
-    CILRS_CHECK(!net->bf16_train, "forward_frozen: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan "
-                "rejects the frozen mode)");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* ws = reinterpret_cast<float*>(bufs->workspace);
-    RUN(net, "transform", 0.0, 0.0, s,
-        launch_u8hwc_to_nhwc4(frames, ws + net->x4, (size_t)net->B * net->H * net->W, kImageMean,
-                              kImageStd, s));
-    return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s, 0, true);
+    return forward_entry(net, bufs, "forward_frozen_u8", {ImageSrc::U8HWC, frames}, speed, command,
+                         controls, pred_speed, stream, kFrozenMode);
 }
 
 int cilrs_net_forward_camera(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
                              int src_h, int src_w, int pixel_stride, long row_stride,
                              long frame_stride, const float* speed, const int64_t* command,
                              float* controls, float* pred_speed, void* stream) {
-    if (check_bufs(net, bufs, false)) return 1;
-    CILRS_CHECK(frames && speed && command && controls && pred_speed,
-                "forward_camera: NULL tensor");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* ws = reinterpret_cast<float*>(bufs->workspace);
-    RUN(net, "transform", 0.0, 0.0, s,
-        launch_camera_to_nhwc4(frames, ws + net->x4, net->B, src_h, src_w, pixel_stride,
-                               row_stride, frame_stride, net->H, net->W, kImageMean, kImageStd, s));
-    return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s);
+    return forward_entry(net, bufs, "forward_camera",
+                         camera_src(frames, src_h, src_w, pixel_stride, row_stride, frame_stride),
+                         speed, command, controls, pred_speed, stream, FwdMode());
 }
 
 int cilrs_net_forward_frozen_camera(cilrs_net* net, const cilrs_buffers* bufs,
@@ -2100,17 +2110,9 @@ int cilrs_net_forward_frozen_camera(cilrs_net* net, const cilrs_buffers* bufs,
                                     long row_stride, long frame_stride, const float* speed,
                                     const int64_t* command, float* controls, float* pred_speed,
                                     void* stream) {
-    if (check_bufs(net, bufs, false)) return 1;
-    CILRS_CHECK(frames && speed && command && controls && pred_speed,
-                "forward_frozen_camera: NULL tensor");
-    CILRS_CHECK(!net->bf16_train, "forward_frozen: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan "
-                "rejects the frozen mode)");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* ws = reinterpret_cast<float*>(bufs->workspace);
-    RUN(net, "transform", 0.0, 0.0, s,
-        launch_camera_to_nhwc4(frames, ws + net->x4, net->B, src_h, src_w, pixel_stride,
-                               row_stride, frame_stride, net->H, net->W, kImageMean, kImageStd, s));
-    return forward_from_x4(net, bufs, speed, command, 0, 0.f, 0, controls, pred_speed, s, 0, true);
+    return forward_entry(net, bufs, "forward_frozen_camera",
+                         camera_src(frames, src_h, src_w, pixel_stride, row_stride, frame_stride),
+                         speed, command, controls, pred_speed, stream, kFrozenMode);
 }
 
 int cilrs_net_forward_u8_f16(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
@@ -2326,18 +2328,21 @@ static int b1_build(cilrs_net* net, int nblk) {
     return 0;
 }
 
+// `frame`: a uint8 HWC frame that the kernel's first stage normalises; or `camera`: a raw camera
+// frame, staged into x4 by a launch of its own, and the kernel starts at its second stage
 static int b1_launch(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frame,
-                     int first_stage, const float* speed, const int64_t* command, float* controls,
-                     float* pred_speed, void* stream, int* done = nullptr, int seq = 0) {
+                     const ImageSrc* camera, const float* speed, const int64_t* command,
+                     float* controls, float* pred_speed, void* stream, int* done = nullptr,
+                     int seq = 0) {
     if (check_bufs(net, bufs, false)) return 1;
-    CILRS_CHECK((frame || first_stage == 1) && speed && command && controls && pred_speed,
+    CILRS_CHECK((frame || camera) && speed && command && controls && pred_speed,
                 "forward_u8_b1: NULL tensor");
     CILRS_CHECK(net->B == 1 && net->A->variant == 0 && net->b1_table != 0,
                 "forward_u8_b1: the persistent kernel serves the reference network at batch 1");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float* ws = reinterpret_cast<float*>(bufs->workspace);
-    net->ws_base = ws;
-    net->mc_src = 0; ++net->fwd_serial;
+    if (fwd_begin(net, bufs, s)) return 1;
+    if (camera && stage_input(net, bufs, *camera, s)) return 1;
     if (net->b1_blocks < 0) {
         int blocks = 0;
         if (infer_b1_grid(&blocks)) return 1;
@@ -2345,7 +2350,6 @@ static int b1_launch(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* f
         if (b1_build(net, blocks)) return 1;
         net->b1_blocks = blocks;
     }
-    if (clear_status_once(net, bufs->workspace, s)) return 1;
     if (eval_prep(net, bufs, s)) return 1;
     if (net->b1_ready_for != bufs->workspace) {
         CILRS_HIP(hipMemsetAsync(ws + net->b1_sync, 0, kB1SyncInts * sizeof(int), s));
@@ -2357,7 +2361,7 @@ static int b1_launch(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* f
     memset(&a, 0, sizeof(a));
     a.table = reinterpret_cast<const B1Stage*>(ws + net->b1_table);
     a.nstages = (int)net->b1_host.size();
-    a.first_stage = first_stage;
+    a.first_stage = camera ? 1 : 0;
     a.ws = ws; a.ws_bytes = net->ws_bytes;
     a.params = bufs->params; a.param_bytes = net->A->arena_floats * sizeof(float);
     a.done = done; a.seq = seq;
@@ -2370,17 +2374,14 @@ static int b1_launch(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* f
     a.stamps = stamps_on ? reinterpret_cast<long long*>(ws + net->b1_stamps) : nullptr;
     for (int i = 0; i < 3; ++i) { a.mean[i] = kImageMean[i]; a.stdv[i] = kImageStd[i]; }
     RUN(net, "infer_b1", 2.0 * 2.798e9 / 2.0, 0.0, s, launch_infer_b1(a, net->b1_blocks, s));
-    net->trained_fwd = false;
-    net->last_dropout = 0.f;
-    net->mc_src = 2;
-    net->fwd_half = 0;
+    fwd_commit(net, cilrs_net::LastForward::EvalB1);
     return 0;
 }
 
 int cilrs_net_forward_u8_b1(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frame,
                             const float* speed, const int64_t* command, float* controls,
                             float* pred_speed, void* stream) {
-    return b1_launch(net, bufs, frame, 0, speed, command, controls, pred_speed, stream);
+    return b1_launch(net, bufs, frame, nullptr, speed, command, controls, pred_speed, stream);
 }
 
 int cilrs_net_forward_camera_b1(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frame,
@@ -2389,13 +2390,9 @@ int cilrs_net_forward_camera_b1(cilrs_net* net, const cilrs_buffers* bufs, const
                                 float* pred_speed, int sync, void* stream) {
     if (check_bufs(net, bufs, false)) return 1;
     CILRS_CHECK(frame != nullptr, "forward_camera_b1: NULL frame");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* ws = reinterpret_cast<float*>(bufs->workspace);
-    RUN(net, "transform", 0.0, 0.0, s,
-        launch_camera_to_nhwc4(frame, ws + net->x4, 1, src_h, src_w, pixel_stride, row_stride,
-                               (long)src_h * row_stride, net->H, net->W, kImageMean, kImageStd, s));
-    if (b1_launch(net, bufs, nullptr, 1, speed, command, controls, pred_speed, stream)) return 1;
-    if (sync) CILRS_HIP(hipStreamSynchronize(s));
+    const ImageSrc cam = camera_src(frame, src_h, src_w, pixel_stride, row_stride, (long)src_h * row_stride);
+    if (b1_launch(net, bufs, nullptr, &cam, speed, command, controls, pred_speed, stream)) return 1;
+    if (sync) CILRS_HIP(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
     return 0;
 }
 
@@ -2403,7 +2400,8 @@ int cilrs_net_forward_u8_b1_post(cilrs_net* net, const cilrs_buffers* bufs, cons
                                  const float* speed, const int64_t* command, float* controls,
                                  float* pred_speed, int* done, int seq, void* stream) {
     CILRS_CHECK(done != nullptr, "forward_u8_b1_post: NULL completion word");
-    return b1_launch(net, bufs, frame, 0, speed, command, controls, pred_speed, stream, done, seq);
+    return b1_launch(net, bufs, frame, nullptr, speed, command, controls, pred_speed, stream, done,
+                     seq);
 }
 
 int cilrs_net_forward_u8_b1_sync(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frame,
@@ -2513,7 +2511,9 @@ static int forward_u8_graph(cilrs_net* net, const cilrs_buffers* bufs, const uin
     if (check_bufs(net, bufs, false)) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     CILRS_CHECK(s != nullptr, "forward_u8_graph: capture needs a non-default stream");
-    net->mc_src = 0; ++net->fwd_serial;
+    // (on the capture path forward_u8 runs underneath and keeps a record of its own; the replayed
+    //  graph overwrites every z and the head activations like the eval forward it was captured from)
+    if (fwd_begin(net, bufs, s)) return 1;
     const void* key[8] = {bufs->params, bufs->bn_running, bufs->workspace, frames, speed, command,
                           controls, pred_speed};
     bool same = net->graph_exec != nullptr && net->graph_half == half &&
@@ -2550,8 +2550,7 @@ static int forward_u8_graph(cilrs_net* net, const cilrs_buffers* bufs, const uin
         net->graph_wkey = net->weights_key;
     }
     CILRS_HIP(hipGraphLaunch(net->graph_exec, s));
-    net->mc_src = 1;
-    net->fwd_half = half;
+    fwd_commit(net, cilrs_net::LastForward::Eval, half);
     return 0;
 }
 
@@ -2573,6 +2572,30 @@ int cilrs_net_forward_u8_bf16_graph(cilrs_net* net, const cilrs_buffers* bufs,
                                     const int64_t* command, float* controls, float* pred_speed,
                                     void* stream) {
     return forward_u8_graph(net, bufs, frames, speed, command, controls, pred_speed, stream, 2);
+}
+
+// The features the plan's last eval-mode forward left for the tick-following entries (heads_mc,
+// gradcam, feature_moments, novelty): pooled in `combined`, or the last feature map alone.
+static void plan_features(const cilrs_net* net, const cilrs_buffers* bufs, const float** features,
+                          int* ld, const float** featmap, int* hw) {
+    const Arch& A = *net->A;
+    const float* ws = reinterpret_cast<const float*>(bufs->workspace);
+    *features = nullptr; *featmap = nullptr; *ld = 0; *hw = 0;
+    if (net->last.featmap_only()) {
+        *featmap = ws + net->cg[A.blocks.back().conv3 >= 0 ? A.blocks.back().conv3
+                                                           : A.blocks.back().conv2].z;
+        *hw = net->featHW;
+    } else {
+        *features = ws + net->combined; *ld = A.feat + 128;
+    }
+}
+static int plan_features_checked(const char* who, const cilrs_net* net, const cilrs_buffers* bufs,
+                                 const float** features, int* ld, const float** featmap, int* hw) {
+    CILRS_CHECK(!net->last.no_features(), "%s: no forward on this plan yet", who);
+    CILRS_CHECK(!net->last.train_features(), "%s: the plan's last forward ran in train mode (batch "
+                "statistics); run an eval-mode forward first", who);
+    plan_features(net, bufs, features, ld, featmap, hw);
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2633,20 +2656,10 @@ int cilrs_net_heads_mc(cilrs_net* net, const cilrs_buffers* bufs, const float* s
     if (check_bufs(net, bufs, false)) return 1;
     CILRS_CHECK(speed && command && mean && std, "net_heads_mc: NULL tensor");
     if (mc_check("net_heads_mc", net->B, samples, p, scratch, scratch_floats)) return 1;
-    CILRS_CHECK(net->mc_src != 0, "net_heads_mc: no forward on this plan yet");
-    CILRS_CHECK(net->mc_src > 0, "net_heads_mc: the plan's last forward ran in train mode (batch "
-                "statistics); run an eval-mode forward first");
-    const Arch& A = *net->A;
-    const float* ws = reinterpret_cast<const float*>(bufs->workspace);
     McHeadsArgs a;
-    mc_fill(a, A, bufs->params);
-    if (net->mc_src == 2) {
-        a.featmap = ws + net->cg[A.blocks.back().conv3 >= 0 ? A.blocks.back().conv3
-                                                            : A.blocks.back().conv2].z;
-        a.HW = net->featHW;
-    } else {
-        a.pooled = ws + net->combined; a.pooled_ld = A.feat + 128;
-    }
+    mc_fill(a, *net->A, bufs->params);
+    if (plan_features_checked("net_heads_mc", net, bufs, &a.pooled, &a.pooled_ld, &a.featmap, &a.HW))
+        return 1;
     a.speed = speed; a.cmd = reinterpret_cast<const long long*>(command);
     a.B = net->B; a.S = samples; a.p = p; a.seed = seed;
     a.mean = mean; a.stdv = std; a.samples_out = samples_out;
@@ -2754,13 +2767,13 @@ int cilrs_net_gradcam(cilrs_net* net, const cilrs_buffers* bufs, const float* sp
     if (gc_weights("net_gradcam", weights4, ha.w)) return 1;
     CILRS_CHECK(!net->bf16_train, "net_gradcam: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan keeps "
                 "16-bit feature maps)");
-    CILRS_CHECK(net->mc_src != 0, "net_gradcam: no forward on this plan yet");
-    CILRS_CHECK(!(net->mc_src < 0 && (net->ft_grad > 0 || net->ft_bn > 0)),
+    CILRS_CHECK(!net->last.no_features(), "net_gradcam: no forward on this plan yet");
+    CILRS_CHECK(!(net->last.train_features() && (net->ft_grad > 0 || net->ft_bn > 0)),
                 "net_gradcam: the plan's last forward was a fine-tuning step behind a frozen prefix; "
                 "run an eval-mode forward first");
-    CILRS_CHECK(net->mc_src > 0, "net_gradcam: the plan's last forward ran in train mode (batch "
+    CILRS_CHECK(!net->last.train_features(), "net_gradcam: the plan's last forward ran in train mode (batch "
                 "statistics); run an eval-mode forward first");
-    CILRS_CHECK(net->fwd_half == 0, "net_gradcam: the plan's last forward ran a 16-bit (fp16 / bf16) "
+    CILRS_CHECK(net->last.half == 0, "net_gradcam: the plan's last forward ran a 16-bit (fp16 / bf16) "
                 "trunk, whose feature maps are 16-bit; run an fp32 forward first");
     const int ci = gc_group_conv(A, layer);
     float* ws = reinterpret_cast<float*>(bufs->workspace);
@@ -2772,11 +2785,7 @@ int cilrs_net_gradcam(cilrs_net* net, const cilrs_buffers* bufs, const float* sp
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (layer == 4) {
         // the fast path: average pooling sits on layer4, so dA = (dy / d pooled) / (h * w)
-        if (net->mc_src == 2) {
-            ha.featmap = ma.A; ha.HW = net->featHW;
-        } else {
-            ha.pooled = ws + net->combined; ha.pooled_ld = A.feat + 128;
-        }
+        plan_features(net, bufs, &ha.pooled, &ha.pooled_ld, &ha.featmap, &ha.HW);
         ha.speed = speed; ha.cmd = reinterpret_cast<const long long*>(command);
         ha.B = net->B; ha.g = scratch; ha.out4 = scratch + (size_t)net->B * A.feat;
         ha.status = reinterpret_cast<int*>(reinterpret_cast<char*>(bufs->workspace) + net->status_b);
@@ -2784,8 +2793,7 @@ int cilrs_net_gradcam(cilrs_net* net, const cilrs_buffers* bufs, const float* sp
         RUN(net, "gradcam", 4.0 * net->B * 180480.0, 0.0, s, launch_heads_input_grad(ha, s));
     } else {
         // the graph path: the data-gradient chain stopped at this group's boundary, G[3] holds dA
-        CILRS_CHECK(net->trained_fwd && net->frozen_fwd && net->gc_bwd_fwd == net->fwd_serial &&
-                    net->gc_bwd_end == 5 - layer,
+        CILRS_CHECK(net->last.frozen() && net->last.gc_bwd_end == 5 - layer,
                     "net_gradcam: layer %d needs cilrs_net_forward_frozen* followed by "
                     "cilrs_net_backward[_data] over segments [0, %d) on this plan: no matching "
                     "backward", layer, 5 - layer);
@@ -2861,31 +2869,12 @@ int cilrs_feature_novelty(const float* features, int ld, const float* featmap, i
     return launch_novelty_score(a, scratch, reinterpret_cast<hipStream_t>(stream));
 }
 
-// the features the plan's last eval-mode forward left, resolved as cilrs_net_heads_mc does
-static int nov_plan_source(const char* who, const cilrs_net* net, const cilrs_buffers* bufs,
-                           const float** features, int* ld, const float** featmap, int* hw) {
-    CILRS_CHECK(net->mc_src != 0, "%s: no forward on this plan yet", who);
-    CILRS_CHECK(net->mc_src > 0, "%s: the plan's last forward ran in train mode (batch statistics); "
-                "run an eval-mode forward first", who);
-    const Arch& A = *net->A;
-    const float* ws = reinterpret_cast<const float*>(bufs->workspace);
-    *features = nullptr; *featmap = nullptr; *ld = 0; *hw = 0;
-    if (net->mc_src == 2) {
-        *featmap = ws + net->cg[A.blocks.back().conv3 >= 0 ? A.blocks.back().conv3
-                                                           : A.blocks.back().conv2].z;
-        *hw = net->featHW;
-    } else {
-        *features = ws + net->combined; *ld = A.feat + 128;
-    }
-    return 0;
-}
-
 int cilrs_net_feature_moments(cilrs_net* net, const cilrs_buffers* bufs, const int64_t* command,
                               const float* pivot, double* table, void* stream) {
     if (check_bufs(net, bufs, false)) return 1;
     CILRS_CHECK(command && pivot && table, "net_feature_moments: NULL tensor");
     NoveltyMomentsArgs a;
-    if (nov_plan_source("net_feature_moments", net, bufs, &a.features, &a.ld, &a.featmap, &a.HW))
+    if (plan_features_checked("net_feature_moments", net, bufs, &a.features, &a.ld, &a.featmap, &a.HW))
         return 1;
     const Arch& A = *net->A;
     CILRS_CHECK(net->B <= kNovMaxBatch, "net_feature_moments: batch %d above %d", net->B, kNovMaxBatch);
@@ -2907,7 +2896,7 @@ int cilrs_net_novelty(cilrs_net* net, const cilrs_buffers* bufs, const int64_t* 
     CILRS_CHECK(net->B <= kNovMaxBatch, "net_novelty: batch %d above %d", net->B, kNovMaxBatch);
     if (nov_score_check("net_novelty", mean, W, d2, scratch, scratch_floats, A.feat, net->B)) return 1;
     NoveltyScoreArgs a;
-    if (nov_plan_source("net_novelty", net, bufs, &a.features, &a.ld, &a.featmap, &a.HW)) return 1;
+    if (plan_features_checked("net_novelty", net, bufs, &a.features, &a.ld, &a.featmap, &a.HW)) return 1;
     a.cmd = reinterpret_cast<const long long*>(command);
     a.B = net->B; a.F = A.feat; a.NC = A.ncmd; a.mean = mean; a.W = W; a.d2 = d2;
     a.status = reinterpret_cast<int*>(reinterpret_cast<char*>(bufs->workspace) + net->status_b);
@@ -2930,7 +2919,7 @@ static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float*
                          const float* dpred_speed, int seg_begin, int seg_end, void* stream,
                          const bool data_only) {
     if (check_bufs(net, bufs, !data_only)) return 1;
-    CILRS_CHECK(net->trained_fwd, "backward needs a preceding train-mode forward on this plan");
+    CILRS_CHECK(net->last.keeps_graph(), "backward needs a preceding train-mode forward on this plan");
     CILRS_CHECK(0 <= seg_begin && seg_begin <= seg_end && seg_end <= 6, "bad segment range");
     // fine-tuning: the graph ends where the frozen prefix begins -- segments of frozen groups are
     // not run, and the first block of the last trainable group hands nothing further down
@@ -2946,7 +2935,7 @@ static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float*
     const int B = net->B;
     // data-only pass over a frozen graph: BatchNorm backward without reductions, data gradients
     // without the BatchNorm-partials epilogue
-    const bool lean_bn = data_only && net->frozen_fwd;
+    const bool lean_bn = data_only && net->last.frozen();
     // where a BatchNorm backward leaves dgamma / dbeta: the arena, or (data-only pass over a
     // train-mode graph, whose reductions still feed dx) a scratch nobody reads
     auto dgamma_of = [&](const BnT& b) { return data_only ? ws + net->bn_coef + 3 * 2048 : Gp + b.gamma; };
@@ -2973,13 +2962,12 @@ static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float*
 
     // (segment 0 rewrites d(speed encoder); segments 1..5 cycle the buffer G[1] that segment 5
     //  leaves d(stem conv output) in)
-    if (seg_begin == 0) net->bwd_done = 0;
-    if (seg_begin <= 5 && seg_end > 1) net->bwd_done &= ~(1u << 5);
+    if (seg_begin == 0) net->last.bwd_done = 0;
+    if (seg_begin <= 5 && seg_end > 1) net->last.bwd_done &= ~(1u << 5);
     // where G[3] stands once this call has gone through (cilrs_net_gradcam): a run from segment 0,
-    // or the continuation of one on the same forward; until then nothing
-    const bool gc_run = seg_begin == 0 || (net->gc_bwd_fwd == net->fwd_serial &&
-                                           net->gc_bwd_end == seg_begin);
-    net->gc_bwd_end = -1;
+    // or the continuation of one (every forward resets gc_bwd_end); until then nothing
+    const bool gc_run = seg_begin == 0 || net->last.gc_bwd_end == seg_begin;
+    net->last.gc_bwd_end = -1;
     for (int seg = seg_begin; seg < seg_end; ++seg) {
         if (seg == 0) {
             CILRS_CHECK(dcontrols && dpred_speed, "backward: output gradients missing");
@@ -2997,7 +2985,7 @@ static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float*
                     launch_avgpool_bwd(ws + net->dcombined, ws + net->G[3], B, net->featHW, A.feat,
                                        A.feat + 128, s));
             if (segment_done(seg)) return 1;
-            net->bwd_done |= 1u;
+            net->last.bwd_done |= 1u;
             continue;
         }
         if (seg >= 1 && seg <= 4) {
@@ -3086,7 +3074,7 @@ static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float*
                                           P + b.gamma, ws + g.stats, relu, dgamma_of(b),
                                           dbeta_of(b), 0, ws + net->bn_coef, ws + net->bn_partial,
                                           Gf(gdy), gg >= 0 ? Gf(gg) : nullptr, pre_nblk, s, nullptr,
-                                          net->frozen_fwd ? 1 : 0));
+                                          net->last.frozen() ? 1 : 0));
                     }
                     return 0;
                 };
@@ -3177,7 +3165,7 @@ static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float*
                     launch_bn_bwd_pool(ws + net->G[3], argmax, ws + g0.y, B, net->H0, net->W0, 64,
                                        P + b0.gamma, ws + g0.stats, dgamma_of(b0), dbeta_of(b0),
                                        ws + net->bn_coef, ws + net->bn_partial, ws + net->G[1], s,
-                                       net->frozen_fwd ? 1 : 0));
+                                       net->last.frozen() ? 1 : 0));
             // the stem's weight gradient runs on the main stream and uses the same slab scratch as
             // the weight gradients of the side stream: those must have finished (between the
             // segments of one call nothing else joins the two streams any more)
@@ -3196,7 +3184,7 @@ static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float*
                 return 1;
             }
             if (segment_done(seg)) return 1;
-            net->bwd_done |= 1u << 5;
+            net->last.bwd_done |= 1u << 5;
         }
     }
     // everything the side stream still runs (weight gradients, fused Adam launches) joins here
@@ -3209,7 +3197,7 @@ static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float*
         CILRS_HIP(hipEventRecord(net->fork_ev, net->side[0]));
         CILRS_HIP(hipStreamWaitEvent(s, net->fork_ev, 0));
     }
-    if (gc_run) { net->gc_bwd_end = seg_end; net->gc_bwd_fwd = net->fwd_serial; }
+    if (gc_run) net->last.gc_bwd_end = seg_end;
     return 0;
 }
 
@@ -3246,13 +3234,13 @@ int cilrs_net_backward_step(cilrs_net* net, const cilrs_buffers* bufs, const flo
 int cilrs_net_input_grads(cilrs_net* net, const cilrs_buffers* bufs, float* dimage, long sn, long sc,
                           long sh, long sw, float* dspeed, void* stream) {
     if (check_bufs(net, bufs, false)) return 1;
-    CILRS_CHECK(net->trained_fwd, "input_grads needs a preceding graph-keeping forward on this plan");
+    CILRS_CHECK(net->last.keeps_graph(), "input_grads needs a preceding graph-keeping forward on this plan");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const Arch& A = *net->A;
     float* ws = reinterpret_cast<float*>(bufs->workspace);
     const int B = net->B;
     if (dspeed) {
-        CILRS_CHECK(net->bwd_done & 1u, "input_grads: dspeed needs segment 0 (heads) of "
+        CILRS_CHECK(net->last.bwd_done & 1u, "input_grads: dspeed needs segment 0 (heads) of "
                     "cilrs_net_backward after the forward");
         // speed -> Linear(1, 128): d speed = d(pre-activation) . W_se0 (ds1 is masked by ReLU and
         // dropout and dropout-scaled in backward_heads)
@@ -3262,7 +3250,7 @@ int cilrs_net_input_grads(cilrs_net* net, const cilrs_buffers* bufs, float* dima
     if (dimage) {
         CILRS_CHECK(net->ft_grad == 0, "input_grads: the last forward froze %d trunk group(s); the "
                     "backward pass stops there, there is no image gradient", net->ft_grad);
-        CILRS_CHECK(net->bwd_done & (1u << 5), "input_grads: dimage needs segment 5 (stem) of "
+        CILRS_CHECK(net->last.bwd_done & (1u << 5), "input_grads: dimage needs segment 5 (stem) of "
                     "cilrs_net_backward after the forward");
         const ConvG& g0 = net->cg[0];
         RUN(net, "conv_dgrad.stem", 2.0 * g0.M * 64 * 147,
@@ -3281,7 +3269,7 @@ static int backward_heads(cilrs_net* net, const cilrs_buffers* bufs, const float
     const float* P = bufs->params;
     float* Gp = data_only ? nullptr : bufs->grads;
     const int B = net->B;
-    const float dscale = net->last_dropout > 0.f ? 1.0f / (1.0f - net->last_dropout) : 1.0f;
+    const float dscale = net->last.dropout > 0.f ? 1.0f / (1.0f - net->last.dropout) : 1.0f;
     const long long* cmd = reinterpret_cast<const long long*>(
         reinterpret_cast<const char*>(bufs->workspace) + net->cmd_b);
     float* dcomb = ws + net->dcombined;

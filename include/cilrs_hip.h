@@ -206,7 +206,8 @@ int cilrs_net_forward_ft(cilrs_net* net, const cilrs_buffers* bufs, const float*
 /* folded-epilogue Winograd launches of the last cilrs_net_forward_ft on this plan (= the eligible
  * convolutions of its eval-mode prefix; 0 for small batches, where the train plan has none) */
 int cilrs_net_ft_wino_convs(cilrs_net* net);
-/* the cut of the plan's last graph-keeping forward (0, 0 after cilrs_net_forward / _frozen) */
+/* the cut of the plan's last graph-keeping forward: (0, 0) after cilrs_net_forward with train != 0,
+ * cilrs_net_forward_frozen* and cilrs_net_forward_bn_stats; an eval-mode forward leaves it as it is */
 int cilrs_net_ft_cut(const cilrs_net* net, int* bn_frozen_groups, int* grad_frozen_groups);
 
 /* Byte offset, inside the workspace, of the plan's int32[4] status words.  The library zeroes them
