@@ -159,6 +159,11 @@ SIGNATURES = {
     "cilrs_net_profile_reset": (i32, [vp]),
     "cilrs_conv2d_fwd": (i32, [vp, vp, vp] + [i32] * 11 + [vp, sz, vp]),
     "cilrs_conv2d_dgrad": (i32, [vp, vp, vp, vp] + [i32] * 11 + [vp, sz, vp]),
+    "cilrs_conv2d_fwd_stats": (i32, [vp, vp, vp, vp, C.POINTER(i32)] + [i32] * 10 + [vp, sz, vp]),
+    "cilrs_conv2d_dgrad_bnbwd": (i32, [vp] * 7 + [i32, vp, C.POINTER(i32)] + [i32] * 10
+                                 + [vp, sz, vp]),
+    "cilrs_conv2d_takes_classes": (i32, [i32] * 9 + [sz, i32]),
+    "cilrs_net_conv_classes": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32)]),
     "cilrs_conv2d_wgrad_scratch_floats": (sz, [i32] * 9),
     "cilrs_conv2d_wgrad": (i32, [vp, vp, vp, vp] + [i32] * 10 + [vp]),
     "cilrs_conv2d_16_scratch_halfs": (sz, [i32] * 8),

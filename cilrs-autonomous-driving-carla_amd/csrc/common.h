@@ -61,7 +61,8 @@ constexpr float kImageStd[3] = {0.229f, 0.224f, 0.225f};
 // are COMPILED OUT of the product library: experiment_env() is the constant default unless the
 // library is built with -DCILRS_EXPERIMENTS (make CXXEXTRA=-DCILRS_EXPERIMENTS; tools/README.md).
 // Switches a test exercises (CILRS_WINO, CILRS_WINO_TAIL, CILRS_WINO_WGRAD, CILRS_OVERLAP,
-// CILRS_CONV16_TILE, CILRS_B1_STAMPS) stay run-time.
+// CILRS_CONV16_TILE, CILRS_B1_STAMPS) and the A/B switch of the position classes
+// (CILRS_IGEMM_CLASSES) stay run-time.
 #ifdef CILRS_EXPERIMENTS
 int experiment_env(const char* name, int dflt);
 #else
@@ -75,14 +76,23 @@ static inline size_t cdivz(size_t a, size_t b) { return (a + b - 1) / b; }
 //   * data gradient (dgrad)  dx[m][ci] = sum_{tap,co} dy[pix'(m,tap)][co] * W[co][flip(tap)][ci]
 //   * the 128..640-wide linear layers of the heads (1x1 "convs" over a [B,1,1,C] image)
 // Activations are NHWC, weights OHWI ([Cout][KH][KW][Cin], i.e. torch channels_last memory).
-// Up to four sub-problems run by ONE launch: the output-parity classes of a stride-2 data gradient.
-// They share x / w / y, the channel counts and the output tensor; each has its own enumerated
-// output grid, its own (at most four) filter taps and its own place in the output.
+// Up to nine sub-problems run by ONE launch: the output-parity classes of a stride-2 data gradient,
+// or the position classes of a small padded stride-1 map (corner / edge / interior rectangles of
+// output positions: every row of a class has the same valid filter taps, so the taps that only
+// meet padding are not in the class's K loop at all).  They share x / w / y, the channel counts
+// and the output tensor; each has its own enumerated output grid, its own (at most nine) filter
+// taps and its own place in the output.  Kernel-argument data, read in the block prologue only.
+constexpr int kConvMultiMax = 9;
 struct ConvMulti {
     int n;                 // 0 = a single problem (everything below unused)
-    int tile_begin[5];     // cumulative block count per class (class c owns [c], [c+1])
-    int Ho[4], Wo[4], out_h0[4], out_w0[4], ntaps[4];
-    int tap_dh[4][4], tap_dw[4][4], tap_w[4][4];
+    int spread;            // 1: blocks take their tiles in dispatch order (round-robin over the XCDs,
+                           // so every XCD gets the same share of every class) instead of one
+                           // contiguous chunk of tiles per XCD
+    int tile_begin[kConvMultiMax + 1];   // cumulative block count per class (class c owns [c], [c+1])
+    int Ho[kConvMultiMax], Wo[kConvMultiMax], out_h0[kConvMultiMax], out_w0[kConvMultiMax];
+    int ntaps[kConvMultiMax];
+    short tap_dh[kConvMultiMax][kConvMultiMax], tap_dw[kConvMultiMax][kConvMultiMax];
+    short tap_w[kConvMultiMax][kConvMultiMax];
 };
 
 struct ConvArgs {
@@ -122,13 +132,19 @@ struct ConvArgs {
     float* scratch;        // optional split-K scratch (>= 2*M*y_ld floats to be considered)
     size_t scratch_floats;
     int force_cfg;         // -1 auto; 0/1/2: 128x128, 128x64, 64x64 register-staged; 3/4/5: the
-                           // same tiles fed by LDS-DMA (tests/tuning)
+                           // same tiles fed by LDS-DMA (tests/tuning); -2: auto, but never the
+                           // position-class launch (the A/B of the class tests)
     int force_splitk;      // 0 auto
     int splitk;            // set by the launcher
     int prio_mode;         // set by the launcher: wave_priority() mode (CILRS_PRIO)
-    ConvMulti multi;       // set by launch_conv_dgrad (stride 2)
+    ConvMulti multi;       // set by the launchers (stride-2 parity classes / position classes)
 };
 int launch_conv_igemm(const ConvArgs& a, hipStream_t s);
+// Would launch_conv_igemm run this stride-1 problem as position classes?  Decided from the shape
+// (and whether split-K scratch of `scratch_floats` floats exists) alone; host only, no launch.
+// (N, H, W, Cin): the gathered tensor; Cout: columns written; dgrad: the data-gradient form.
+bool conv_igemm_takes_classes(int N, int H, int W, int Cin, int Cout, int K, int stride, int pad,
+                              bool dgrad, size_t scratch_floats, int force_splitk = 0);
 // fixed-order sum of dense [M][C] slabs (+ addend) with BatchNorm column partials [2][C][rows]
 int slab_reduce_rows(int M, int C, int* rows_per_block);
 int launch_slab_reduce_cols(int mode, const float* slabs, int splits, float* y, const float* addend,

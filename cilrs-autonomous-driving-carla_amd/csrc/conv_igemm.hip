@@ -74,9 +74,12 @@ constexpr bool igemm_swz() { return DMA || (BM == 64 && BN == 64 && TAP_UNIFORM)
 template <int BM, int BN, bool TAP_UNIFORM, bool DMA>
 constexpr int igemm_min_blocks() { return (!DMA && BM == 64 && BN == 64 && TAP_UNIFORM) ? 5 : 2; }
 
-// MULTI: the launch covers a.multi.n sub-problems (parity classes of a stride-2 data gradient);
-// a block finds its class from its logical id and takes the class's output grid, taps and K
-// length from a.multi -- four short launches of 0.4 rounds each become one launch of whole rounds.
+// MULTI: the launch covers a.multi.n sub-problems (parity classes of a stride-2 data gradient,
+// position classes of a small padded stride-1 map); a block finds its class from its logical id
+// and takes the class's output grid, taps and K length from a.multi -- four short launches of 0.4
+// rounds each become one launch of whole rounds.  M_ is then the pixel count of the whole output
+// (the pitch of a split-K slab, which is a dense image of the full output) and KT_ the K-tiles
+// per split of the dense tap table.
 template <int BM, int BN, int WM, int WN, bool TAP_UNIFORM, int W_MODE, bool DMA, bool MULTI = false>
 __global__ __launch_bounds__(256, (igemm_min_blocks<BM, BN, TAP_UNIFORM, DMA>()))
 void conv_igemm_kernel(const ConvArgs a, const int M_, const int Krow, const int KT_) {
@@ -104,13 +107,20 @@ void conv_igemm_kernel(const ConvArgs a, const int M_, const int Krow, const int
     wave_stagger(a.prio_mode);
     const int tilesN = a.Cout / BN;
     int logical = xcd_remap(blockIdx.x, gridDim.x);
+    if constexpr (MULTI) {
+        // classes sorted by K length: a contiguous chunk per XCD hands the long classes to the
+        // first XCDs and the short ones to the last
+        if (a.multi.spread) logical = blockIdx.x;
+    }
     // geometry of this block's (sub-)problem
     int cls = 0;
     int P_Ho = a.Ho, P_Wo = a.Wo, P_h0 = a.out_h0, P_w0 = a.out_w0, P_ntaps = a.ntaps;
     int M = M_, KT = KT_;
+    int mt_base = 0;       // M-tiles of the classes before this block's (fused column partials)
     if constexpr (MULTI) {
         while (cls + 1 < a.multi.n && logical >= a.multi.tile_begin[cls + 1]) ++cls;
         logical -= a.multi.tile_begin[cls];
+        mt_base = a.multi.tile_begin[cls] / tilesN;
         P_Ho = a.multi.Ho[cls]; P_Wo = a.multi.Wo[cls];
         P_h0 = a.multi.out_h0[cls]; P_w0 = a.multi.out_w0[cls];
         P_ntaps = a.multi.ntaps[cls];
@@ -126,9 +136,26 @@ void conv_igemm_kernel(const ConvArgs a, const int M_, const int Krow, const int
     // K-tile range of this split
     int kt_begin = 0, kt_end = KT;
     if (a.splitk > 1) {
-        const int per = (KT + a.splitk - 1) / a.splitk;
-        kt_begin = blockIdx.z * per;
-        kt_end = min(KT, kt_begin + per);
+        if constexpr (MULTI) {
+            // position classes: split z sums what split z of the SINGLE problem sums -- K-tiles
+            // [z * KT_, (z + 1) * KT_) of the dense tap table (KT_ = the single problem's K-tiles
+            // per split) -- less the tiles of taps the class does not have, which are products
+            // with zero padding there: every slab, and so the reduced result, is bit for bit the
+            // single launch's.  Tap t of the class sits at table position pos (the class keeps the
+            // table's order; the data gradient's tap_w is the flipped position).
+            const int ct = a.Cin / BK, lo = (int)blockIdx.z * KT_, hi = lo + KT_;
+            int b = 0, e = 0;
+            for (int t = 0; t < P_ntaps; ++t) {
+                const int pos = (W_MODE == 0) ? tap_w(t) : a.KH * a.KW - 1 - tap_w(t);
+                b += min(max(lo - pos * ct, 0), ct);
+                e += min(max(hi - pos * ct, 0), ct);
+            }
+            kt_begin = b; kt_end = e;
+        } else {
+            const int per = (KT + a.splitk - 1) / a.splitk;
+            kt_begin = blockIdx.z * per;
+            kt_end = min(KT, kt_begin + per);
+        }
     }
     const int nt = max(kt_end - kt_begin, 0);
 
@@ -494,7 +521,10 @@ void conv_igemm_kernel(const ConvArgs a, const int M_, const int Krow, const int
                 t2 += red[(w * BN + tid) * 2 + 1];
             }
             // channel-major partials [2][Cout][M-tiles]: the finalize reads each channel's row
-            const size_t mt = (size_t)(logical / tilesN), nmt = (size_t)((M + BM - 1) / BM);
+            // (classes: the tile index and the tile count run over all classes)
+            const size_t mt = (size_t)(mt_base + logical / tilesN);
+            const size_t nmt = MULTI ? (size_t)(a.multi.tile_begin[a.multi.n] / tilesN)
+                                     : (size_t)((M + BM - 1) / BM);
             a.bn_partial[(size_t)(n0 + tid) * nmt + mt] = t1;
             a.bn_partial[(size_t)(a.Cout + n0 + tid) * nmt + mt] = t2;
         }
@@ -506,7 +536,10 @@ void conv_igemm_kernel(const ConvArgs a, const int M_, const int Krow, const int
     const bool partial = a.splitk > 1;
     const bool dense = (a.out_sh == 1) && (a.out_sw == 1) && (a.out_H == P_Ho) &&
                        (a.out_W == P_Wo);
-    float* yout = partial ? a.y + (size_t)blockIdx.z * M * a.y_ld : a.y;
+    // a split-K slab of a single problem is [M][Cout] in enumeration order (the reduce maps it);
+    // a slab of a class launch is a dense image of the whole output, written at the global pixel
+    const bool slab_rows = partial && !MULTI;
+    float* yout = partial ? a.y + (size_t)blockIdx.z * (MULTI ? M_ : M) * a.y_ld : a.y;
     // fused BatchNorm-backward reductions of the layer this data gradient feeds: per channel
     // sum(g) and sum(g * xhat), g = dz * (z > 0), xhat = (y - mean) * rstd
     const bool bwd_red = a.bwd_partial != nullptr && !partial;
@@ -523,7 +556,7 @@ void conv_igemm_kernel(const ConvArgs a, const int M_, const int Krow, const int
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = min(mbase + (r & 3) + 8 * (r >> 2), M - 1);
-                if (dense || partial) {
+                if (dense || slab_rows) {
                     pix[r] = m;
                 } else {
                     const int n = m / HoWo, rem = m - n * HoWo;
@@ -612,7 +645,10 @@ void conv_igemm_kernel(const ConvArgs a, const int M_, const int Krow, const int
                 t1 += red[(w * BN + tid) * 2];
                 t2 += red[(w * BN + tid) * 2 + 1];
             }
-            const size_t mt = (size_t)(logical / tilesN), nmt = (size_t)((M + BM - 1) / BM);
+            // (classes: the tile index and the tile count run over all classes)
+            const size_t mt = (size_t)(mt_base + logical / tilesN);
+            const size_t nmt = MULTI ? (size_t)(a.multi.tile_begin[a.multi.n] / tilesN)
+                                     : (size_t)((M + BM - 1) / BM);
             a.bwd_partial[(size_t)(n0 + tid) * nmt + mt] = t1;
             a.bwd_partial[(size_t)(a.Cout + n0 + tid) * nmt + mt] = t2;
         }
@@ -881,11 +917,10 @@ const Cfg kCfg[6] = {
 };
 constexpr int kNumCfg = 6;
 
-double cfg_cost(int M, int Cout, int KT, const Cfg& c, int splitk) {
-    if (Cout % c.bn) return 1e30;
-    const double blocks = (double)cdiv(M, c.bm) * (Cout / c.bn) * splitk;
+// blocks: blocks of the launch (all splits); ktiles: K-tiles a block runs (the mean over the
+// blocks when they differ, as the classes of a multi-problem launch do)
+double cfg_cost_blocks(double blocks, double ktiles, int M, int Cout, const Cfg& c, int splitk) {
     const long per_cu = (long)((blocks + 255) / 256);
-    const double ktiles = (double)cdiv(KT, splitk);
     const double unit = 2.0 * c.bm * c.bn * BK * ktiles;               // flops per block
     const long full = per_cu / c.occ, rem = per_cu % c.occ;
     double t = 0.0;
@@ -894,6 +929,11 @@ double cfg_cost(int M, int Cout, int KT, const Cfg& c, int splitk) {
     t += (full + (rem ? 1 : 0)) * 2.5;                                   // fill / drain per group
     if (splitk > 1) t += 3.0 + 0.12 * splitk + (double)M * Cout * 4.0 * (splitk + 1) / 3.0e6;  // slabs + reduce
     return t;
+}
+double cfg_cost(int M, int Cout, int KT, const Cfg& c, int splitk) {
+    if (Cout % c.bn) return 1e30;
+    const double blocks = (double)cdiv(M, c.bm) * (Cout / c.bn) * splitk;
+    return cfg_cost_blocks(blocks, (double)cdiv(KT, splitk), M, Cout, c, splitk);
 }
 
 struct Choice { int cfg; int splitk; };
@@ -922,13 +962,211 @@ Choice choose(int M, int Cout, int KT, bool allow_split, int force_cfg, int forc
     return best;
 }
 
+// ---- position classes of a padded stride-1 map ------------------------------------------------
+// On a small map much of the K loop multiplies padding: 3x7 with a 3x3 filter and pad 1 has 133
+// valid (position, tap) pairs of 189.  A 64-row tile of consecutive rows spans several images, so
+// no tap is padding for a whole tile.  Grouped by output POSITION instead -- corner, edge and
+// interior rectangles, every image's rows of one rectangle together -- the valid taps are the same
+// for every row of a class, and the class's K loop simply has fewer taps (same kernel, same loop).
+// CILRS_IGEMM_CLASSES=0 in the environment of the process turns the class launch off (the A/B of
+// profiles/igemm_position_classes.log).
+bool classes_enabled() {
+    static const int env = getenv("CILRS_IGEMM_CLASSES") ? atoi(getenv("CILRS_IGEMM_CLASSES")) : 1;
+    return env != 0;
+}
+// The classes are sorted by K length, so xcd_remap's contiguous chunk of tiles per XCD hands the
+// nine-tap interior to the first XCDs and the four-tap corners to the last: the first XCD then runs
+// exactly the K-tiles it ran before and the launch is no shorter (measured with evenly cut class K
+// ranges: 116 vs 111 us at 3x7x512, B=128; 92 us in dispatch order, where every XCD gets the same
+// share of every class).
+// CILRS_IGEMM_CLASS_CHUNKS=1 of an experiments build puts the chunks back.
+bool classes_spread() {
+    static const int chunks = experiment_env("CILRS_IGEMM_CLASS_CHUNKS", 0);
+    return chunks == 0;
+}
+
+// Runs of consecutive output coordinates that see the same filter taps inside the image (stride
+// 1).  At most three (near border, interior, far border); 0 when there are more, or when some
+// coordinate sees no tap at all.
+struct TapRun { int begin, len; unsigned taps; };
+int position_runs(int out, int in, int K, int pad, TapRun (&r)[3]) {
+    int n = 0;
+    for (int o = 0; o < out; ++o) {
+        unsigned m = 0u;
+        for (int k = 0; k < K; ++k) {
+            const int i = o - pad + k;
+            if (i >= 0 && i < in) m |= 1u << k;
+        }
+        if (m == 0u) return 0;
+        if (n > 0 && r[n - 1].taps == m) { ++r[n - 1].len; continue; }
+        if (n == 3) return 0;
+        r[n++] = TapRun{o, 1, m};
+    }
+    return n;
+}
+
+// a: a single stride-1 problem with the dense KH x KW tap table and a dense output.  Fills mu with
+// the row-run x column-run rectangles, longest K first, and returns the launch's tile count (64x64
+// tiles); 0 when the problem has no classes or a class has less than one tile of rows.  A class's
+// enumerated grid is its rectangle, placed by out_h0 / out_w0; its tap offsets absorb the
+// rectangle's origin and the padding (the launch then runs with pad 0), so every tap of a class is
+// inside the image for every row of the class.
+int build_position_classes(const ConvArgs& a, ConvMulti& mu) {
+    if (a.stride != 1 || a.pad <= 0 || a.ntaps > kConvMultiMax || a.KH * a.KW != a.ntaps ||
+        a.Cout % 64 != 0 || a.H >= 32768 || a.W >= 32768)
+        return 0;
+    TapRun rr[3], rc[3];
+    const int nr = position_runs(a.Ho, a.H, a.KH, a.pad, rr);
+    const int nc = position_runs(a.Wo, a.W, a.KW, a.pad, rc);
+    if (nr == 0 || nc == 0 || nr * nc < 2) return 0;
+    struct Cls { int h0, w0, Ho, Wo, nt; short dh[kConvMultiMax], dw[kConvMultiMax], tw[kConvMultiMax]; };
+    Cls cl[kConvMultiMax];
+    int ncl = 0;
+    for (int i = 0; i < nr; ++i)
+        for (int j = 0; j < nc; ++j) {
+            Cls k;
+            k.h0 = rr[i].begin; k.w0 = rc[j].begin; k.Ho = rr[i].len; k.Wo = rc[j].len; k.nt = 0;
+            if ((long)a.N * k.Ho * k.Wo < 64) return 0;
+            for (int t = 0; t < a.ntaps; ++t) {         // table order kept: the order of the sum
+                if (!((rr[i].taps >> a.tap_dh[t]) & 1u) || !((rc[j].taps >> a.tap_dw[t]) & 1u))
+                    continue;
+                k.dh[k.nt] = (short)(k.h0 - a.pad + a.tap_dh[t]);
+                k.dw[k.nt] = (short)(k.w0 - a.pad + a.tap_dw[t]);
+                k.tw[k.nt] = (short)a.tap_w[t];
+                ++k.nt;
+            }
+            cl[ncl++] = k;
+        }
+    for (int i = 1; i < ncl; ++i)                        // longest K first (stable)
+        for (int j = i; j > 0 && cl[j].nt > cl[j - 1].nt; --j) {
+            const Cls t = cl[j]; cl[j] = cl[j - 1]; cl[j - 1] = t;
+        }
+    memset(&mu, 0, sizeof(mu));
+    mu.n = ncl;
+    mu.spread = classes_spread() ? 1 : 0;
+    const int tilesN = a.Cout / 64;
+    int total = 0;
+    for (int i = 0; i < ncl; ++i) {
+        mu.tile_begin[i] = total;
+        total += cdiv(a.N * cl[i].Ho * cl[i].Wo, 64) * tilesN;
+        mu.Ho[i] = cl[i].Ho; mu.Wo[i] = cl[i].Wo;
+        mu.out_h0[i] = cl[i].h0; mu.out_w0[i] = cl[i].w0; mu.ntaps[i] = cl[i].nt;
+        for (int t = 0; t < cl[i].nt; ++t) {
+            mu.tap_dh[i][t] = cl[i].dh[t]; mu.tap_dw[i][t] = cl[i].dw[t];
+            mu.tap_w[i][t] = cl[i].tw[t];
+        }
+    }
+    for (int i = ncl; i <= kConvMultiMax; ++i) mu.tile_begin[i] = total;
+    return total;
+}
+
+// The class launch keeps the single problem's tile (64x64 register-staged) and its split count, and
+// split z of a class covers the K range split z of the single problem covers (see the kernel):
+// the classes only drop products with padding, so the result is the single launch's bit for bit
+// and a model trained with classes on is the model trained with them off.  Priced by the same
+// model as the single problem, with the classes' block count and mean K-tiles per block; taken
+// when that is below `single_cost`.  Returns the tile count (0: not taken).
+int choose_classes(const ConvArgs& a, int M, int sk, double single_cost, ConvMulti& mu) {
+    const int tiles = build_position_classes(a, mu);
+    if (tiles == 0) return 0;
+    // one round only: pricing a block by the MEAN K length -- and the balance of long and short
+    // classes over the XCDs -- holds while every block of the launch is resident at once; in
+    // later rounds blocks go wherever a slot frees up (layer1 at B=128, 2,200 tiles on 1,280
+    // slots, measured 9 % slower as classes: tools/conv_bench.py)
+    if ((long)tiles * sk > 256L * kCfg[2].occ) return 0;
+    double sum = 0.0;              // K-tiles of all blocks of all splits
+    for (int c = 0; c < mu.n; ++c)
+        sum += (double)(mu.tile_begin[c + 1] - mu.tile_begin[c]) * mu.ntaps[c] * (a.Cin / BK);
+    const double cost =
+        cfg_cost_blocks((double)tiles * sk, sum / ((double)tiles * sk), M, a.Cout, kCfg[2], sk);
+    return cost < single_cost ? tiles : 0;
+}
+
+// What launch_conv_igemm runs for a normalised problem (dense tap table filled, dense output
+// fields set): tile config, split count and, if class_tiles > 0, the position classes in mu.
+struct IgemmPlan { Choice ch; int class_tiles; };
+IgemmPlan plan_igemm(const ConvArgs& a, bool class_candidate, ConvMulti& mu) {
+    const int M = a.N * a.Ho * a.Wo;
+    const bool uniform = (a.Cin % BK) == 0;
+    const int KT = uniform ? a.ntaps * (a.Cin / BK) : cdiv(a.KH * a.KW * a.Cin, BK);
+    const size_t slab = (size_t)M * a.y_ld;
+    const bool can_split = a.scratch != nullptr && a.scratch_floats >= 2 * slab && uniform;
+    IgemmPlan p;
+    p.ch = choose(M, a.Cout, KT, can_split, a.force_cfg, a.force_splitk);
+    while (p.ch.splitk > 1 && (size_t)p.ch.splitk * slab > a.scratch_floats) --p.ch.splitk;
+    p.class_tiles = 0;
+    // classes follow from the shape alone: never from the epilogue hooks, the stream or profiling
+    if (class_candidate && uniform && (a.force_cfg == -1 || a.force_cfg == 2) && classes_enabled() &&
+        p.ch.cfg == 2) {
+        const double single = cfg_cost(M, a.Cout, KT, kCfg[2], p.ch.splitk);
+        p.class_tiles = choose_classes(a, M, p.ch.splitk, single, mu);
+    }
+    return p;
+}
+
+// fills the dense KH x KW tap table (forward order) of the uniform path
+void dense_taps(ConvArgs& a) {
+    a.ntaps = a.KH * a.KW;
+    for (int t = 0; t < a.ntaps; ++t) {
+        a.tap_dh[t] = t / a.KW;
+        a.tap_dw[t] = t % a.KW;
+        a.tap_w[t] = (a.w_mode == 0) ? t : a.ntaps - 1 - t;      // dgrad: flipped filter
+    }
+}
+
+// one launch over the sub-problems of a.multi (64x64 register-staged tile); M_all: pixels of the
+// whole output = pitch of a split-K slab
+static_assert(sizeof(ConvArgs) + 3 * sizeof(int) <= 4096, "kernel arguments exceed the launch limit");
+template <int W_MODE>
+int launch_multi(const ConvArgs& a, int tiles, int M_all, int kt_per_split, hipStream_t s) {
+    constexpr size_t lds = (size_t)(2 * 64 * BK + 2 * BK * 64) * sizeof(float);
+    if (set_max_dynamic_lds(
+            reinterpret_cast<const void*>(&conv_igemm_kernel<64, 64, 2, 2, true, W_MODE, false, true>),
+            (int)lds))
+        return 1;
+    conv_igemm_kernel<64, 64, 2, 2, true, W_MODE, false, true>
+        <<<dim3(tiles, 1, a.splitk > 1 ? a.splitk : 1), 256, lds, s>>>(a, M_all,
+                                                                      a.KH * a.KW * a.Cin,
+                                                                      kt_per_split);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace
+
+bool conv_igemm_takes_classes(int N, int H, int W, int Cin, int Cout, int K, int stride, int pad,
+                              bool dgrad, size_t scratch_floats, int force_splitk) {
+    if (stride != 1 || K * K > 16 || Cin <= 0 || Cout <= 0) return false;
+    const int Ho = H + 2 * pad - K + 1, Wo = W + 2 * pad - K + 1;
+    if (Ho <= 0 || Wo <= 0) return false;
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = N; a.KH = a.KW = K; a.stride = 1;
+    if (!dgrad) {
+        a.H = H; a.W = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.pad = pad;
+        a.w_mode = 0; a.w_cin = Cin;
+    } else {                 // as launch_conv_dgrad: gathers dy, writes forward Cin columns
+        a.H = Ho; a.W = Wo; a.Cin = Cout; a.Ho = H; a.Wo = W; a.Cout = Cin; a.pad = K - 1 - pad;
+        a.w_mode = 1; a.w_cin = Cin;
+    }
+    if (a.Cin % BK != 0 || a.Cout % 64 != 0) return false;
+    a.x_ld = a.Cin; a.y_ld = a.Cout;
+    a.force_cfg = -1; a.force_splitk = force_splitk;
+    a.scratch_floats = scratch_floats;
+    a.scratch = scratch_floats ? reinterpret_cast<float*>(sizeof(float) * 4) : nullptr;   // (never read)
+    a.out_H = a.Ho; a.out_W = a.Wo; a.out_sh = a.out_sw = 1;
+    dense_taps(a);
+    ConvMulti mu;
+    return plan_igemm(a, true, mu).class_tiles > 0;
+}
 
 int launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     ConvArgs a = a_in;
     a.prio_mode = wave_priority_mode();
     const int M = a.N * a.Ho * a.Wo;
     const bool uniform = (a.Cin % BK) == 0;
+    // position classes: only for the dense problem the caller left to the launcher
+    const bool class_candidate = a_in.out_H == 0 && a_in.ntaps == 0 && a_in.multi.n == 0;
     // the uniform path addresses both operands with 32-bit byte offsets (buffer loads)
     CILRS_CHECK(!uniform || ((size_t)a.N * a.H * a.W * a.x_ld * sizeof(float) < (1ull << 32) &&
                              (size_t)(a.w_mode == 0 ? a.Cout : a.Cin) * a.KH * a.KW *
@@ -939,12 +1177,7 @@ int launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     }
     if (uniform && a.ntaps == 0) {   // dense KH x KW table, forward order
         CILRS_CHECK(a.KH * a.KW <= 16, "conv_igemm: more than 16 taps on the uniform path");
-        a.ntaps = a.KH * a.KW;
-        for (int t = 0; t < a.ntaps; ++t) {
-            a.tap_dh[t] = t / a.KW;
-            a.tap_dw[t] = t % a.KW;
-            a.tap_w[t] = (a.w_mode == 0) ? t : a.ntaps - 1 - t;      // dgrad: flipped filter
-        }
+        dense_taps(a);
     }
     const int KT = uniform ? a.ntaps * (a.Cin / BK) : cdiv(a.KH * a.KW * a.Cin, BK);
     // W_MODE 0 weight rows are addressed with the forward row pitch KH*KW*Cin
@@ -962,10 +1195,10 @@ int launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     CILRS_CHECK(a.ntaps <= 16, "conv_igemm: too many taps");
 
     // ---- tile / split-K choice ----
-    const size_t slab = (size_t)M * a.y_ld;
-    const bool can_split = a.scratch != nullptr && a.scratch_floats >= 2 * slab && uniform;
-    Choice ch = choose(M, a.Cout, KT, can_split, a.force_cfg, a.force_splitk);
-    while (ch.splitk > 1 && (size_t)ch.splitk * slab > a.scratch_floats) --ch.splitk;
+    const IgemmPlan plan = plan_igemm(a, class_candidate, a.multi);
+    const Choice ch = plan.ch;
+    const int class_tiles = plan.class_tiles;
+    if (class_tiles == 0) a.multi.n = 0;
     CILRS_CHECK(ch.splitk == 1 || (a.scratch && uniform), "conv_igemm: split-K needs scratch");
     CILRS_CHECK(ch.cfg >= 0 && ch.cfg < kNumCfg && a.Cout % kCfg[ch.cfg].bn == 0,
                 "conv_igemm: tile config %d does not fit Cout=%d", ch.cfg, a.Cout);
@@ -984,16 +1217,26 @@ int launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     }
     float* const fwd_partial = a.bn_partial;
     float* const bwd_partial = a.bwd_partial;
+    // M-tiles that write fused column partials (classes: the tiles of all classes)
+    const int mtiles = class_tiles > 0 ? class_tiles / (a.Cout / 64) : cdiv(M, kCfg[ch.cfg].bm);
     if (a_in.bn_nblk)
-        *a_in.bn_nblk = !a.bn_partial ? 0
-                        : a.splitk == 1 ? cdiv(M, kCfg[ch.cfg].bm) : cols_nblk;
+        *a_in.bn_nblk = !a.bn_partial ? 0 : a.splitk == 1 ? mtiles : cols_nblk;
     if (!(a.splitk == 1 && dense_out)) a.bwd_partial = nullptr;
     if (a_in.bwd_nblk)
-        *a_in.bwd_nblk = a.bwd_partial ? cdiv(M, kCfg[ch.cfg].bm) : (bwd_partial ? cols_nblk : 0);
+        *a_in.bwd_nblk = a.bwd_partial ? mtiles : (bwd_partial ? cols_nblk : 0);
     float* final_y = a.y;
     if (a.splitk > 1) a.y = a.scratch;      // partials, summed by the reduce launch below
 
     int rc = 1;
+    if (class_tiles > 0) {
+        // a class's tap offsets hold the padding; the output stays the dense [N][Ho][Wo] image
+        const int pad = a.pad;
+        a.pad = 0;
+        const int per = cdiv(KT, a.splitk > 1 ? a.splitk : 1);     // the single problem's K-tiles per split
+        rc = a.w_mode == 1 ? launch_multi<1>(a, class_tiles, M, per, s)
+                           : launch_multi<0>(a, class_tiles, M, per, s);
+        a.pad = pad;
+    } else
 #define CILRS_DISPATCH(BM_, BN_, DMA_)                                                          \
     do {                                                                                        \
         if (a.w_mode == 1) rc = launch_cfg<BM_, BN_, 2, 2, true, 1, DMA_>(a, M, Krow, KT, s);   \
@@ -1146,7 +1389,7 @@ int launch_conv_dgrad(const DgradArgs& d, hipStream_t s) {
                 mu.tap_w[i][t] = cl[i].tw[t];
             }
         }
-        for (int i = ncl; i < 5; ++i) mu.tile_begin[i] = total;
+        for (int i = ncl; i <= kConvMultiMax; ++i) mu.tile_begin[i] = total;
         CILRS_CHECK((size_t)c.N * c.H * c.W * c.x_ld * sizeof(float) < (1ull << 32) &&
                         (size_t)c.Cin * c.KH * c.KW * c.w_cin * sizeof(float) < (1ull << 32),
                     "conv_dgrad: tensor larger than 4 GB");
@@ -1154,15 +1397,7 @@ int launch_conv_dgrad(const DgradArgs& d, hipStream_t s) {
                         ((uintptr_t)c.y & 15) == 0 && c.x_ld % 4 == 0 && c.y_ld % 4 == 0 &&
                         c.w_cin % 4 == 0,
                     "conv_dgrad: operands must be 16-byte aligned");
-        constexpr size_t lds = (size_t)(2 * 64 * BK + 2 * BK * 64) * sizeof(float);
-        if (set_max_dynamic_lds(
-                reinterpret_cast<const void*>(&conv_igemm_kernel<64, 64, 2, 2, true, 1, false, true>),
-                (int)lds))
-            return 1;
-        conv_igemm_kernel<64, 64, 2, 2, true, 1, false, true>
-            <<<dim3(total, 1, 1), 256, lds, s>>>(c, 0, c.KH * c.KW * c.Cin, 0);
-        CILRS_LAUNCH_CHECK();
-        return 0;
+        return launch_multi<1>(c, total, c.N * d.H * d.W, 0, s);
     }
     for (int ph = 0; ph < 2; ++ph)
         for (int pw = 0; pw < 2; ++pw) {

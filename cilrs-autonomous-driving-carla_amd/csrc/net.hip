@@ -1049,9 +1049,10 @@ int cilrs_net_create_ex(int variant, int batch, int height, int width, unsigned 
             for (size_t ci = 0; ci < A.convs.size(); ++ci) {
                 // per-tile column partials: forward (conv output) and backward (the data
                 // gradient's output = this conv's input) reductions ride on the GEMM epilogues
-                const size_t t = (size_t)cdiv(n->cg[ci].M, 64) * 2 * A.convs[ci].cout;
+                // (+ kConvMultiMax: a position-class launch rounds every class up to whole tiles)
+                const size_t t = (size_t)(cdiv(n->cg[ci].M, 64) + kConvMultiMax) * 2 * A.convs[ci].cout;
                 if (t > need) need = t;
-                const size_t tb = (size_t)cdiv(B * n->cg[ci].H * n->cg[ci].W, 64) * 2 *
+                const size_t tb = (size_t)(cdiv(B * n->cg[ci].H * n->cg[ci].W, 64) + kConvMultiMax) * 2 *
                                   A.convs[ci].cin;
                 if (ci > 0 && tb > need) need = tb;
                 if (bn_partial_floats(A.convs[ci].cout) > need)
@@ -3623,6 +3624,74 @@ int cilrs_conv2d_dgrad(const float* dy, const float* w, float* dx, const float* 
     a.scratch = scratch; a.scratch_floats = scratch_floats;
     a.force_cfg = force_cfg; a.force_splitk = force_splitk;
     return launch_conv_dgrad(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cilrs_conv2d_fwd_stats(const float* x, const float* w, float* y, float* partial, int* nblk,
+                           int N, int H, int W, int Cin, int Cout, int K, int stride, int pad,
+                           int force_cfg, int force_splitk, float* scratch, size_t scratch_floats,
+                           void* stream) {
+    CILRS_CHECK(x && w && y && partial && nblk, "conv2d_fwd_stats: NULL argument");
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.w = w; a.y = y;
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin;
+    a.Ho = (H + 2 * pad - K) / stride + 1; a.Wo = (W + 2 * pad - K) / stride + 1; a.Cout = Cout;
+    a.KH = a.KW = K; a.stride = stride; a.pad = pad;
+    a.x_ld = Cin; a.y_ld = Cout; a.w_mode = 0; a.w_cin = Cin;
+    a.scratch = scratch; a.scratch_floats = scratch_floats;
+    a.force_cfg = force_cfg; a.force_splitk = force_splitk;
+    a.bn_partial = partial; a.bn_nblk = nblk; *nblk = 0;
+    // the caller's buffer holds cilrs_bn_partial_floats(Cout): as many row groups as the BatchNorm kernels use
+    CILRS_CHECK((size_t)(cdiv(N * a.Ho * a.Wo, 64) + kConvMultiMax) * 2 * Cout <= bn_partial_floats(Cout),
+                "conv2d_fwd_stats: more than %zu rows", bn_partial_floats(Cout) / 2 / Cout * 64);
+    return launch_conv_igemm(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cilrs_conv2d_dgrad_bnbwd(const float* dy, const float* w, float* dx, const float* addend,
+                             const float* bwd_z, const float* bwd_y, const float* bwd_stats,
+                             int bwd_relu, float* partial, int* nblk, int N, int H, int W, int Cin,
+                             int Cout, int K, int stride, int pad, int force_cfg, int force_splitk,
+                             float* scratch, size_t scratch_floats, void* stream) {
+    CILRS_CHECK(dy && w && dx && bwd_y && bwd_stats && partial && nblk && (bwd_z || !bwd_relu),
+                "conv2d_dgrad_bnbwd: NULL argument");
+    CILRS_CHECK(stride == 1, "conv2d_dgrad_bnbwd: stride 1 only");
+    DgradArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dy = dy; a.w = w; a.dx = dx; a.addend = addend;
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin;
+    a.Ho = H + 2 * pad - K + 1; a.Wo = W + 2 * pad - K + 1;
+    a.Cout = Cout; a.K = K; a.stride = stride; a.pad = pad;
+    a.dy_ld = Cout; a.dx_ld = Cin;
+    a.scratch = scratch; a.scratch_floats = scratch_floats;
+    a.force_cfg = force_cfg; a.force_splitk = force_splitk;
+    a.bwd_z = bwd_z; a.bwd_y = bwd_y; a.bwd_stats = bwd_stats; a.bwd_relu = bwd_relu;
+    a.bwd_partial = partial; a.bwd_nblk = nblk; *nblk = 0;
+    CILRS_CHECK((size_t)(cdiv(N * H * W, 64) + kConvMultiMax) * 2 * Cin <= bn_partial_floats(Cin),
+                "conv2d_dgrad_bnbwd: more than %zu rows", bn_partial_floats(Cin) / 2 / Cin * 64);
+    return launch_conv_dgrad(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cilrs_conv2d_takes_classes(int N, int H, int W, int Cin, int Cout, int K, int stride, int pad,
+                               int dgrad, size_t scratch_floats, int force_splitk) {
+    return conv_igemm_takes_classes(N, H, W, Cin, Cout, K, stride, pad, dgrad != 0, scratch_floats,
+                                    force_splitk) ? 1 : 0;
+}
+
+int cilrs_net_conv_classes(const cilrs_net* net, int conv, int* fwd, int* dgrad) {
+    CILRS_CHECK(net != nullptr, "conv_classes: net is NULL");
+    CILRS_CHECK(conv >= 0 && conv < (int)net->cg.size(), "conv_classes: conv %d out of range", conv);
+    const ConvT& c = net->A->convs[conv];
+    const ConvG& g = net->cg[conv];
+    // the stem has kernels of its own; a Winograd layer never reaches the implicit GEMM; the
+    // 16-bit train mode runs other kernels
+    const bool igemm = conv > 0 && !net->wino_on[conv] && !net->bf16_train;
+    const bool yes_f = igemm && conv_igemm_takes_classes(net->B, g.H, g.W, c.cin, c.cout, c.k, c.stride,
+                                                         c.pad, false, net->ksplit_floats);
+    const bool yes_d = igemm && conv_igemm_takes_classes(net->B, g.H, g.W, c.cin, c.cout, c.k, c.stride,
+                                                         c.pad, true, net->ksplit_floats);
+    if (fwd) *fwd = yes_f ? 1 : 0;
+    if (dgrad) *dgrad = yes_d ? 1 : 0;
+    return 0;
 }
 
 static WgradArgs make_wgrad(const float* x, const float* dy, float* dw, float* scratch, int N,

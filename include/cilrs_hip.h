@@ -834,6 +834,34 @@ int cilrs_conv2d_dgrad(const float* dy, const float* w, float* dx, const float* 
                        int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                        int force_cfg, int force_splitk, float* scratch, size_t scratch_floats,
                        void* stream);
+/* The same two calls with the BatchNorm reductions the plan fuses into them (test aids: the plan's
+ * own hooks, reachable without a plan).  force_cfg -2: auto, but never the position-class launch.
+ * cilrs_conv2d_fwd_stats: partial (>= cilrs_bn_partial_floats(Cout) floats) receives the column
+ * partials of y, channel-major [2][Cout][*nblk]: sums and sums of squares over *nblk row groups.
+ * cilrs_conv2d_dgrad_bnbwd (stride 1): dx is the output gradient of a BatchNorm layer with raw
+ * input bwd_y, output bwd_z (read when bwd_relu) and statistics bwd_stats (mean | rstd), all
+ * [N*H*W][Cin]; partial receives [2][Cin][*nblk] partial sums of g and g * xhat, g = dx * (z > 0),
+ * xhat = (y - mean) * rstd.  *nblk == 0: the launch chosen does not fuse them. */
+int cilrs_conv2d_fwd_stats(const float* x, const float* w, float* y, float* partial, int* nblk,
+                           int N, int H, int W, int Cin, int Cout, int K, int stride, int pad,
+                           int force_cfg, int force_splitk, float* scratch, size_t scratch_floats,
+                           void* stream);
+int cilrs_conv2d_dgrad_bnbwd(const float* dy, const float* w, float* dx, const float* addend,
+                             const float* bwd_z, const float* bwd_y, const float* bwd_stats,
+                             int bwd_relu, float* partial, int* nblk, int N, int H, int W, int Cin,
+                             int Cout, int K, int stride, int pad, int force_cfg, int force_splitk,
+                             float* scratch, size_t scratch_floats, void* stream);
+/* Does the implicit GEMM run this stride-1 convolution (forward, or dgrad != 0: its data gradient)
+ * as position classes -- corner / edge / interior rectangles of output positions in one launch,
+ * each with only the filter taps that meet the image (csrc/conv_igemm.hip)?  Decided from the
+ * shape and the split-K scratch available (force_splitk as in cilrs_conv2d_fwd) alone: padded stride-1 maps whose every class has at
+ * least 64 rows, whose blocks fit one round on the chip and whose class launch the kernel cost model prices below the single problem.
+ * CILRS_IGEMM_CLASSES=0 in the environment of the process turns the path off (0 here).
+ * cilrs_net_conv_classes: the same for convolution `conv` of the plan's train step (numbered as in
+ * cilrs_net_activation_info); 0 / 0 for a convolution that does not run on the implicit GEMM. */
+int cilrs_conv2d_takes_classes(int N, int H, int W, int Cin, int Cout, int K, int stride, int pad,
+                               int dgrad, size_t scratch_floats, int force_splitk);
+int cilrs_net_conv_classes(const cilrs_net* net, int conv, int* fwd, int* dgrad);
 /* d(loss)/dw (OHWI, Cin_dst channels kept); scratch from cilrs_conv2d_wgrad_scratch_floats */
 size_t cilrs_conv2d_wgrad_scratch_floats(int N, int H, int W, int Cin, int Cout, int KH, int KW,
                                          int stride, int pad);
