@@ -88,6 +88,9 @@ SIGNATURES = {
     "cilrs_feature_novelty": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp, vp]),
     "cilrs_net_feature_moments": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp]),
     "cilrs_net_novelty": (i32, [vp, C.POINTER(Buffers), vp, vp, vp, vp, vp, sz, vp]),
+    "cilrs_kcenter_scratch_bytes": (sz, [i32]),
+    "cilrs_kcenter_cover": (i32, [vp, C.c_long, i32, i32, vp, C.c_long, i32, vp, vp]),
+    "cilrs_kcenter_greedy": (i32, [vp, C.c_long, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
     "cilrs_net_infer16_conv_info": (i32, [vp, i32, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),
                                           C.POINTER(i32), C.POINTER(i32)]),
     "cilrs_net_infer16_io_info": (i32, [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),

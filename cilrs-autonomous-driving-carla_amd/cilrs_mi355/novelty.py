@@ -225,6 +225,27 @@ class FeatureDensity:
             self._score_op(features, commands.contiguous(), d2)
         return d2
 
+    # ---- whitened coordinates (cilrs_mi355.select) ---------------------------------------------
+    def _origin(self):
+        """the mean of the first command the fit saw: any fixed origin gives the same distances"""
+        return self.mean[int(np.flatnonzero(self.present)[0])]
+
+    def whiten(self, features):
+        """(features[:, :F] - mean[k0]) @ tril(W).T as float32 [B, F] on the features' device, k0
+        the first command present in the fit: squared Euclidean distances between whitened rows
+        are the Mahalanobis distances of the score.  One library GEMM, run once per pool."""
+        self._need_finalized("whiten")
+        if features.dim() != 2 or features.dtype != torch.float32 or features.size(1) < self.F:
+            raise RuntimeError(f"FeatureDensity.whiten: features must be float32 [B, >= {self.F}], "
+                               f"got {features.dtype} {tuple(features.shape)}")
+        return (features[:, :self.F] - self._origin()) @ torch.tril(self.W).T
+
+    def whitened_means(self):
+        """The means of the commands the fit saw, in the coordinates of ``whiten``: [K', F]."""
+        self._need_finalized("whitened_means")
+        rows = torch.from_numpy(np.flatnonzero(self.present)).to(self.mean.device)
+        return self.whiten(self.mean.index_select(0, rows))
+
     # ---- calibration --------------------------------------------------------------------------
     def _log_room(self, b, device):
         if self.log is None:

@@ -1,0 +1,214 @@
+"""Which K frames of a recorded drive to label: greedy k-center selection in feature space.
+
+The reference's README ends its campus-map section with two remedies, domain adaptation or targeted
+data collection.  ``FeatureDensity`` / ``Predictor.predict_novelty`` say how far ONE frame is from
+what the trunk saw in training; the top-K novel frames of a 20 Hz log are a few hundred near-copies
+of the same junction.  The core-set rule (Sener & Savarese, 2018) starts from what is already
+covered and repeatedly takes the frame farthest from everything chosen so far; it is defined in
+include/cilrs_hip.h ("Greedy k-center") and runs as one streaming pass over the pool per pick
+(csrc/kcenter.hip).  The same call thins a redundant training set.
+
+    pool = FramePool(model, capacity=200_000)
+    for images, speeds, commands in log_batches:        # eval-mode forwards, nothing copied to the host
+        pool.add(images, speeds, commands)
+    s = pool.select(500, density=fd)                    # Mahalanobis metric, the fit's command means covered
+    s.indices, s.coverage()                             # frames to label; covering radius after each pick
+    more = pool.select(500, density=fd, covered=pool.features()[torch.from_numpy(s.indices).cuda()])
+
+fp32 only: the pool goes through the module's fp32 eval-mode forward.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+
+@dataclass
+class Selection:
+    """indices int64 [k'] and radius float32 [k'] on the host: radius[t] is the squared distance of
+    pick t to everything covered before it, non-increasing; the picks are cut at the first
+    radius == 0 (every remaining row coincides with a chosen one), so k' <= k.  min_dist float32
+    [N] (device): each pool row's squared distance to the nearest centre after the last pick.  rows:
+    the device rows the selection ran on (the whitened pool, or the pool itself)."""
+    indices: np.ndarray
+    radius: np.ndarray
+    min_dist: torch.Tensor
+    metric: str
+    rows: torch.Tensor = None
+
+    def coverage(self):
+        """The covering radius after each pick, in the metric's own unit: the curve to read "how
+        many frames are enough" from."""
+        return np.sqrt(self.radius)
+
+
+class FramePool:
+    """Pooled trunk features of up to ``capacity`` frames, float32 [capacity, F] on the model's
+    device."""
+
+    def __init__(self, model, capacity: int, half=False):
+        if half:
+            raise RuntimeError("FramePool: fp32 only (a 16-bit trunk's features are not the ones a "
+                               "density was fitted on)")
+        capacity = int(capacity)
+        if not 1 <= capacity <= 1 << 24:
+            raise ValueError("capacity must be in 1..2^24")
+        self.model = model
+        self.F = int(model.FEATURES)
+        self.device = next(model.parameters()).device
+        self.capacity = capacity
+        self.pool = torch.empty(capacity, self.F, dtype=torch.float32, device=self.device)
+        self.count = 0
+        self.weights_key = 0
+
+    def __len__(self):
+        return self.count
+
+    def features(self):
+        """View [count, F] of the rows added so far."""
+        return self.pool[:self.count]
+
+    def clear(self):
+        self.count, self.weights_key = 0, 0
+
+    # ---- filling ---------------------------------------------------------------------------------
+    def _room(self, b, who):
+        if self.count + b > self.capacity:
+            raise RuntimeError(f"FramePool.{who}: the pool is full ({self.count} + {b} rows, "
+                               f"capacity {self.capacity})")
+        return self.pool[self.count:self.count + b]
+
+    def add_features(self, features):
+        """The op-level form: append rows of already pooled features (float32 [B, ld >= F], features
+        first).  A device copy; no synchronise."""
+        if features.dim() != 2 or features.dtype != torch.float32 or features.size(1) < self.F:
+            raise RuntimeError(f"FramePool.add_features: features must be float32 [B, >= {self.F}], "
+                               f"got {features.dtype} {tuple(features.shape)}")
+        b = features.size(0)
+        self._room(b, "add_features").copy_(features[:, :self.F])
+        self.count += b
+        return self
+
+    def add(self, images, speeds, commands):
+        """One batch of the log: the module's fp32 eval-mode forward (as FeatureDensity.update runs
+        it), then a device copy of the pooled features it left into the next rows of the pool.
+        Nothing is copied to the host.  Keep the model in eval mode between two adds: anything that
+        may have changed the weights (a train() / eval() switch included) raises."""
+        if self.device.type != "cuda":
+            raise RuntimeError("FramePool.add needs the model on an MI355X (no CPU fallback)")
+        self._room(images.size(0), "add")
+        eng = self.model.engine()
+        if eng.train_precision != "fp32":
+            raise RuntimeError("FramePool.add: fp32 only (the engine is set to 16-bit plans)")
+        was_training = self.model.training
+        self.model.eval()
+        with torch.no_grad():
+            self.model(images, speeds, commands)
+        key = int(eng.weights_key())
+        if was_training:
+            self.model.train()
+        if self.weights_key and key != self.weights_key:
+            raise RuntimeError("FramePool.add: the weights changed since the first add; clear() "
+                               "starts a new pool")
+        self.weights_key = key
+        return self.add_features(eng.plan_features(eng.last_plan))
+
+    # ---- the launches (host tests replace them) ------------------------------------------------------
+    def _need_device(self, who):
+        if self.device.type != "cuda":
+            raise RuntimeError(f"FramePool.{who} needs the pool on an MI355X (no CPU fallback)")
+
+    def _cover_op(self, rows, centres, mind):
+        """cilrs_kcenter_cover: mind = min(mind, distance to every centre)"""
+        self._need_device("select")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        L.check(L.lib().cilrs_kcenter_cover(
+            L.ptr(rows), rows.stride(0), rows.size(0), rows.size(1), L.ptr(centres),
+            centres.stride(0), centres.size(0), L.ptr(mind), L.C.c_void_p(stream)))
+
+    def _greedy_op(self, rows, mind, k):
+        """cilrs_kcenter_greedy: k picks; returns (sel int64 [k], radius float32 [k]) on the device"""
+        self._need_device("select")
+        n = rows.size(0)
+        sel = torch.empty(k, dtype=torch.int64, device=rows.device)
+        radius = torch.empty(k, dtype=torch.float32, device=rows.device)
+        nbytes = L.lib().cilrs_kcenter_scratch_bytes(n)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=rows.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        L.check(L.lib().cilrs_kcenter_greedy(
+            L.ptr(rows), rows.stride(0), n, rows.size(1), L.ptr(mind), k, L.ptr(sel), L.ptr(radius),
+            L.ptr(scratch), nbytes, L.C.c_void_p(stream)))
+        return sel, radius
+
+    # ---- selection -------------------------------------------------------------------------------
+    @staticmethod
+    def _kernel_rows(t):
+        """float32 rows as the kernels take them: unit column stride, 16-byte aligned rows"""
+        if t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
+            t = t.contiguous()
+        return t
+
+    def select(self, k, density=None, covered=None, first=None) -> Selection:
+        """Greedy k-center over the rows added so far: up to ``k`` picks, each the row farthest from
+        everything covered before it.
+
+        density   a finalised FeatureDensity: the rows are ``density.whiten(pool)`` (Mahalanobis
+                  metric) and the fit's command means count as covered.  None: the raw features,
+                  Euclidean.
+        covered   float32 [M, >= F] of frames already labelled or chosen earlier; covered as well.
+        first     with nothing to cover, the row that is the first centre (default row 0)."""
+        n, k = self.count, int(k)
+        if n == 0:
+            raise RuntimeError("FramePool.select: the pool is empty")
+        if not 1 <= k <= n:
+            raise ValueError(f"k must be in 1..{n} (the rows in the pool)")
+        if self.F % 4 or not 4 <= self.F <= 2048:
+            raise RuntimeError(f"FramePool.select: feature width {self.F}")
+        rows, centres, metric = self.features(), [], "euclidean"
+        if density is not None:
+            density._need_finalized("whiten")
+            if density.F != self.F:
+                raise RuntimeError(f"FramePool.select: the density was fitted on {density.F} "
+                                   f"features, the pool holds {self.F}")
+            rows, metric = density.whiten(rows), "mahalanobis"
+            centres.append(density.whitened_means())
+        if covered is not None:
+            if covered.dim() != 2 or covered.dtype != torch.float32 or covered.size(1) < self.F or \
+                    covered.size(0) > 65536:
+                raise RuntimeError(f"FramePool.select: covered must be float32 [M <= 65536, >= "
+                                   f"{self.F}], got {covered.dtype} {tuple(covered.shape)}")
+            covered = covered.to(rows.device)
+            if covered.size(0):
+                centres.append(density.whiten(covered) if density is not None
+                               else covered[:, :self.F])
+        if first is not None:
+            if centres:
+                raise ValueError("first: only with nothing to cover (no density, no covered rows)")
+            first = int(first)
+            if not 0 <= first < n:
+                raise ValueError(f"first must be in 0..{n - 1}")
+            centres.append(rows[first:first + 1])
+        rows = self._kernel_rows(rows)
+        mind = torch.full((n,), float("inf"), dtype=torch.float32, device=rows.device)
+        for c in centres:
+            self._cover_op(rows, self._kernel_rows(c), mind)
+        picks = k if first is None else k - 1
+        if picks:
+            sel, radius = self._greedy_op(rows, mind, picks)
+        else:
+            sel = torch.empty(0, dtype=torch.int64, device=rows.device)
+            radius = torch.empty(0, dtype=torch.float32, device=rows.device)
+        if rows.device.type == "cuda":
+            torch.cuda.current_stream(rows.device).synchronize()
+        sel, radius = sel.cpu().numpy(), radius.cpu().numpy()
+        if first is not None:
+            sel = np.concatenate([np.array([first], dtype=np.int64), sel])
+            radius = np.concatenate([np.array([np.inf], dtype=np.float32), radius])
+        zero = np.flatnonzero(radius == 0.0)
+        if zero.size:
+            sel, radius = sel[:zero[0]], radius[:zero[0]]
+        return Selection(sel, radius, mind, metric, rows)

@@ -478,6 +478,46 @@ int cilrs_net_novelty(cilrs_net* net, const cilrs_buffers* bufs, const int64_t* 
                       const float* mean, const float* W, float* d2, float* scratch,
                       size_t scratch_floats, void* stream);
 
+/* ---- Greedy k-center: which K frames of a pool to label (csrc/kcenter.hip) -----------------------
+ * The novelty score says how far ONE frame is from the fit; the top-K novel frames of a 20 Hz log
+ * are near-copies of each other.  The core-set rule (Sener & Savarese, 2018) is greedy k-center
+ * (farthest-point selection): start from what is covered, then repeatedly take the row farthest from
+ * everything chosen so far.  On rows whitened by the novelty score's W the squared Euclidean
+ * distance below is that score's Mahalanobis distance.  The reference has no such path; parity is
+ * pinned by this definition (restated in float64 by tests/_kcenter.py).
+ *   Inputs   rows X fp32 [N][ld], the first D columns used (columns D.. are never read); mind, a
+ *            running minimum-distance vector fp32 [N] that the caller owns and initialises (+inf:
+ *            nothing covered yet).
+ *   Distance d(x, c) = sum_j t_j^2, t_j = x_j - c_j, all in fp32: lane l of a wave runs
+ *            a = fmaf(t_j, t_j, a) from a = 0 over its columns j = 256 q + 4 l + e < D (q ascending,
+ *            then e = 0..3); the 64 lane sums are combined by a += shfl_xor(a, o), o = 32, 16, .., 1
+ *            (the order of cilrs_feature_novelty).  Nothing else is fused.
+ *   Cover    for m = 0..M-1 in order: mind[i] = min(mind[i], d(X_i, C_m)) for centres C fp32
+ *            [M][ldc]; min(a, b) is b < a ? b : a, so a NaN distance never replaces a value.
+ *   Greedy   for t = 0..K-1: i_t = the index of the largest mind[i], the lowest index among equal
+ *            values -- an entry wins by v > best || (v == best && i < besti) starting from
+ *            (mind[0], 0), so NaN entries never win; sel[t] = i_t, radius[t] = mind[i_t]; then
+ *            mind[i] = min(mind[i], d(X_i, X_{i_t})) for every i, which makes mind[i_t] exactly 0.
+ *            Max, min and the tie rule are exact: the result does not depend on how the rows are
+ *            spread over workgroups, only the distance order fixes bits, and K1 picks followed by K2
+ *            more on the same mind are bit for bit K1 + K2 picks.  Once radius[t] == 0 every row
+ *            coincides with a chosen one; later picks are index 0 by the tie rule and carry no
+ *            meaning.
+ * cilrs_kcenter_cover: one launch (eight centres at a time in LDS: X is read once per eight).
+ * cilrs_kcenter_greedy: K + 1 launches on `stream` -- one pass over mind, then one streaming pass
+ * over X per pick; no atomics, no fences, no grid barrier, no host synchronisation.  sel int64 [K],
+ * radius fp32 [K] and mind are device memory; scratch: cilrs_kcenter_scratch_bytes(N) bytes (0 for
+ * an N outside its range), 16-byte aligned, contents irrelevant before and after.
+ * Refused (non-zero, text in cilrs_last_error, nothing launched): NULL tensors; N outside 1..2^24;
+ * D outside 4..2048 or not a multiple of 4; ld or ldc below D or not a multiple of 4; X, C or the
+ * scratch not 16-byte aligned; M outside 0..65536 (M == 0 is a successful no-op); K outside 1..N;
+ * a scratch smaller than asked. */
+size_t cilrs_kcenter_scratch_bytes(int N);
+int cilrs_kcenter_cover(const float* X, long ld, int N, int D, const float* C, long ldc, int M,
+                        float* mind, void* stream);
+int cilrs_kcenter_greedy(const float* X, long ld, int N, int D, float* mind, int K, int64_t* sel,
+                         float* radius, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Same, fed with uint8 RGB HWC frames [B,H,W,3]: fuses preprocess_image's /255, HWC->CHW and
  * Normalize(mean,std) (autonomous_drive.py:897-902; the cv2.resize is the caller's). */
 int cilrs_net_forward_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
