@@ -3,5 +3,6 @@
 from .bn_estimate import BatchNormEstimator, update_bn  # noqa: F401
 from .data import BatchLoader, CachedBatchLoader, DeviceDataset  # noqa: F401
 from .model import CILRS, CILRSResNet50  # noqa: F401
+from .neighbours import NeighbourIndex  # noqa: F401
 from .select import FramePool, Selection  # noqa: F401
 from .train import CONFIG_A, CONFIG_B, LOSS_KEYS, TrainConfig, Trainer  # noqa: F401

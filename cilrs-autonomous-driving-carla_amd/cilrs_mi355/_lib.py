@@ -91,6 +91,12 @@ SIGNATURES = {
     "cilrs_kcenter_scratch_bytes": (sz, [i32]),
     "cilrs_kcenter_cover": (i32, [vp, C.c_long, i32, i32, vp, C.c_long, i32, vp, vp]),
     "cilrs_kcenter_greedy": (i32, [vp, C.c_long, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
+    "cilrs_knn_scratch_bytes": (sz, [i32, i32, i32]),
+    "cilrs_knn": (i32, [vp, C.c_long, i32, i32, vp, C.c_long, i32, vp, i32, vp, vp, vp, sz, vp]),
+    "cilrs_feature_whiten_scratch_floats": (sz, [i32, i32]),
+    "cilrs_feature_whiten": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "cilrs_net_knn_scratch_bytes": (sz, [i32, i32, i32, i32]),
+    "cilrs_net_knn": (i32, [vp, C.POINTER(Buffers), vp, C.c_long, i32, vp, vp, i32, vp, vp, vp, sz, vp]),
     "cilrs_net_infer16_conv_info": (i32, [vp, i32, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),
                                           C.POINTER(i32), C.POINTER(i32)]),
     "cilrs_net_infer16_io_info": (i32, [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),

@@ -230,6 +230,7 @@ class Engine:
         self._mc_bufs = {}                # run_heads_mc: (owner, B, S) -> scratch + pinned outputs
         self._gc_bufs = {}                # run_gradcam: (owner, B, H, W, layer) -> the same
         self._nov_bufs = {}               # run_novelty: (owner, B) -> scratch + pinned d2
+        self._knn_bufs = {}               # run_knn: (owner, B, k) -> scratch + pinned idx, dist
         # "fp32" (the reference's arithmetic) or "bf16": train-mode trunk convolutions on the bf16
         # matrix pipe (include/cilrs_hip.h CILRS_PLAN_BF16_TRAIN); set through
         # Trainer(..., precision=) or directly before the first train-mode forward
@@ -804,6 +805,32 @@ class Engine:
             pl.handle, C.byref(pl.bufs), L.ptr(command), L.ptr(mean), L.ptr(W), L.ptr(out),
             L.ptr(scratch), scratch.numel(), self._stream()))
         return out
+
+    def run_knn(self, rows, origin, W, k, owner=None):
+        """cilrs_net_knn: the k rows of ``rows`` [N, F] (a NeighbourIndex's) nearest to the features
+        the last eval-mode forward left in its plan, whitened by (origin, W) when given.  Enqueues
+        the launches on the current stream and returns (idx int64 [B, k], dist float32 [B, k]) in
+        PINNED host buffers, valid after the stream is synchronised and until the next call with
+        the same (owner, B, k); the scratch is cached the same way (see run_novelty)."""
+        pl = self.last_plan
+        if pl is None:
+            raise RuntimeError("run_knn: no forward yet")
+        b, n, k = pl.batch, rows.size(0), int(k)
+        need = L.lib().cilrs_net_knn_scratch_bytes(self.feature_width(), b, n, k)
+        cache, key = self._knn_bufs, (id(owner) if owner is not None else None, b, k)
+        bufs = cache.pop(key, None)
+        if bufs is None or bufs[0].numel() < need:
+            while len(cache) >= self.MC_CACHE_ENTRIES:
+                cache.pop(next(iter(cache)))             # the least recently used
+            bufs = (torch.empty(max(need, 16), dtype=torch.uint8, device=self.device),
+                    torch.full((b, k), -1, dtype=torch.int64).pin_memory(),
+                    torch.zeros(b, k, dtype=torch.float32).pin_memory())
+        cache[key] = bufs
+        scratch, idx, dist = bufs
+        L.check(L.lib().cilrs_net_knn(
+            pl.handle, C.byref(pl.bufs), L.ptr(rows), rows.stride(0), n, L.ptr(origin), L.ptr(W), k,
+            L.ptr(idx), L.ptr(dist), L.ptr(scratch), scratch.numel(), self._stream()))
+        return idx, dist
 
     def run_forward_camera(self, frames_u8, speed, command, height=88, width=200, out=None):
         """Raw camera frames uint8 [B,Hs,Ws,3|4] (device) -> eval forward with the whole of

@@ -809,6 +809,56 @@ class Predictor:
         _speed, cmd = self._mc_inputs(camera)
         return point, float(self._novelty_run(cmd, density)[0])
 
+    # ---- nearest recorded frames --------------------------------------------------------------------
+    def _neighbours_check(self, index, k, who):
+        """What the neighbour calls refuse before anything is launched."""
+        if self.half:
+            raise RuntimeError(f"{who}: fp32 predictors only (an index of fp32 features does not "
+                               "describe a 16-bit trunk's)")
+        index.check_model(self.model, who)
+        if index.device != self.eng.device:
+            raise RuntimeError(f"{who}: the index is on {index.device}, the predictor on "
+                               f"{self.eng.device}")
+        return index._check_k(k)
+
+    def _neighbours_run(self, index, k):
+        """The k-NN launches on this predictor's stream, on the plan the tick just used, into pinned
+        buffers; one synchronise."""
+        eng = self.eng
+        eng.last_plan = eng.plan(self.batch, self.frames_host.size(1), self.frames_host.size(2))
+        with torch.cuda.stream(self.stream):
+            idx, dist = eng.run_knn(index.rows, index.origin, index.W, k, owner=self)
+            self.stream.synchronize()
+        return idx.numpy().copy(), dist.numpy().copy()
+
+    @torch.no_grad()
+    def predict_neighbours(self, frames_u8, speeds_kmh, commands, index, k=8):
+        """predict_batch plus the recorded frames the trunk finds nearest: returns (controls [B,3],
+        pred_speed [B] in km/h, idx int64 [B,k], dist float32 [B,k]); the first two are exactly
+        predict_batch's columns.  idx / dist are the k rows of ``index`` (a
+        cilrs_mi355.neighbours.NeighbourIndex, from FramePool.index) nearest to the pooled features,
+        ascending, squared distances in the index's metric (include/cilrs_hip.h, cilrs_net_knn): an
+        unchanged predict_batch -- persistent launch, degraded mode and all -- then the k-NN
+        launches on this predictor's stream and one more synchronise.  dist[:, -1] is the
+        non-parametric novelty score; ``index.percentile`` turns it into a threshold with a meaning.
+        fp32 predictors only; an index of another feature width or of a density fitted for another
+        command count raises RuntimeError before anything is launched."""
+        k = self._neighbours_check(index, k, "predict_neighbours")
+        out = self.predict_batch(frames_u8, speeds_kmh, commands)
+        idx, dist = self._neighbours_run(index, k)
+        return out[:, :3].copy(), out[:, 3].copy(), idx, dist
+
+    @torch.no_grad()
+    def predict_controls_neighbours(self, image_rgb_u8, speed_kmh, command_idx, index, k=8):
+        """predict_controls with the nearest recorded frames: ((steer, throttle, brake, speed_kmh),
+        idx [k], dist [k]).  Frames that are not 88x200x3 go through predict_camera's path first."""
+        if self.batch != 1:
+            raise RuntimeError("predict_controls_neighbours is the single-frame control-loop path")
+        k = self._neighbours_check(index, k, "predict_controls_neighbours")
+        point = self.predict_controls(np.asarray(image_rgb_u8), speed_kmh, command_idx)
+        idx, dist = self._neighbours_run(index, k)
+        return point, idx[0], dist[0]
+
     # ---- Grad-CAM --------------------------------------------------------------------------------
     GRADCAM_LAYERS ={"layer1": 1, "layer2": 2, "layer3": 3, "layer4": 4}
 

@@ -14,6 +14,7 @@ include/cilrs_hip.h ("Greedy k-center") and runs as one streaming pass over the 
     s = pool.select(500, density=fd)                    # Mahalanobis metric, the fit's command means covered
     s.indices, s.coverage()                             # frames to label; covering radius after each pick
     more = pool.select(500, density=fd, covered=pool.features()[torch.from_numpy(s.indices).cuda()])
+    idx, dist = pool.index(density=fd).query(features, k=8)     # the nearest recorded frames
 
 fp32 only: the pool goes through the module's fp32 eval-mode forward.  There is no CPU fallback.
 """
@@ -143,6 +144,27 @@ class FramePool:
             L.ptr(rows), rows.stride(0), n, rows.size(1), L.ptr(mind), k, L.ptr(sel), L.ptr(radius),
             L.ptr(scratch), nbytes, L.C.c_void_p(stream)))
         return sel, radius
+
+    # ---- nearest neighbours (cilrs_mi355.neighbours) -----------------------------------------------
+    index_class = None                    # host tests put a NeighbourIndex with replaced launches here
+
+    def index(self, density=None):
+        """A NeighbourIndex over a copy of the rows added so far.  density: a finalised
+        FeatureDensity -- the rows are whitened through cilrs_feature_whiten (Mahalanobis metric)
+        and the index keeps the tables that whiten a query the same way.  None: Euclidean."""
+        from .neighbours import NeighbourIndex
+        cls = self.index_class or NeighbourIndex
+        if self.count == 0:
+            raise RuntimeError("FramePool.index: the pool is empty")
+        if density is None:
+            return cls(self.features().clone(), weights_key=self.weights_key)
+        density._need_finalized("index")
+        if density.F != self.F:
+            raise RuntimeError(f"FramePool.index: the density was fitted on {density.F} features, "
+                               f"the pool holds {self.F}")
+        return cls(self.features(), "mahalanobis", density._origin().clone(), density.W.clone(),
+                   weights_key=density.fit_weights_key or self.weights_key, commands=density.NC,
+                   whitened=False)
 
     # ---- selection -------------------------------------------------------------------------------
     @staticmethod

@@ -796,5 +796,29 @@ struct NoveltyScoreArgs {
 };
 size_t novelty_scratch_floats(int F, int batch);
 int launch_novelty_score(NoveltyScoreArgs& a, float* scratch, hipStream_t s);
+// y = tril(W) (v - origin), fp32 [B][F]: the score's first two launches with one fixed origin, y stored
+struct NoveltyWhitenArgs {
+    const float* features; int ld;        // as above
+    const float* featmap; int HW;
+    int B, F;
+    const float* origin;                  // [F], or NULL: nothing subtracted
+    const float* W;                       // [F][F], lower triangle read; NULL: y is not written
+    float* u;                             // [B][F] v - origin
+    float* y;                             // [B][F]
+};
+int launch_novelty_whiten(const NoveltyWhitenArgs& a, hipStream_t s);
+
+// ---- nearest neighbours (knn.hip; cilrs_knn) ------------------------------------------------------
+struct KnnArgs {
+    const float* X; long ld; int N, D;    // the pool's rows
+    const float* Y; long ldq; int Q;      // the queries
+    const long long* skip;                // [Q] or NULL
+    int K;
+    int64_t* idx; float* dist;            // [Q][K]; either may be pinned host memory
+    void* scratch;
+};
+size_t knn_scratch_bytes(int N, int Q, int K);       // 0 outside the ranges
+int knn_check(const char* who, const KnnArgs& a, size_t scratch_bytes);
+int launch_knn(const KnnArgs& a, hipStream_t s);
 
 }  // namespace cilrs

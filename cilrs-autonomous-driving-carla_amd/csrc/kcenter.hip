@@ -27,12 +27,10 @@
 
 #pragma clang fp contract(off)      // the chains are written with fmaf(); nothing else fuses
 
+#include "kc_dist.h"                // the distance, shared with knn.hip
+
 namespace cilrs {
 namespace {
-
-constexpr int kKcMaxGrid = 1024;        // workgroups of 4 waves: 16 waves on each of 256 CUs
-constexpr int kKcCentres = 8;           // centres per LDS chunk of the cover kernel
-constexpr int kKcMaxN = 1 << 24, kKcMaxD = 2048, kKcMaxM = 65536;
 
 struct __attribute__((aligned(8))) KcPair { float v; int i; };
 
@@ -41,13 +39,6 @@ __device__ __forceinline__ bool kc_wins(const KcPair a, const KcPair b) {
     return a.v > b.v || (a.v == b.v && a.i < b.i);
 }
 __device__ __forceinline__ KcPair kc_none() { return KcPair{-__builtin_inff(), INT_MAX}; }
-
-// fixed-order butterfly sum over the 64 lanes of a wave (the order of cilrs_feature_novelty)
-__device__ __forceinline__ float kc_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // the largest pair of a workgroup of 256 threads; valid in every thread.  No pair holds a NaN.
 __device__ __forceinline__ KcPair kc_block_max(KcPair b, KcPair* red) {
@@ -64,31 +55,6 @@ __device__ __forceinline__ KcPair kc_block_max(KcPair b, KcPair* red) {
     for (int w = 1; w < 4; ++w)
         if (kc_wins(red[w], b)) b = red[w];
     return b;
-}
-
-// a lane's quads of one row: columns 256 q + 4 lane .. + 3 where they are below D, else zeros
-// (a zero difference leaves the chain as it is)
-template <int NQ>
-__device__ __forceinline__ void kc_load_row(const float* __restrict__ row, const int D, const int lane,
-                                            f32x4 (&x)[NQ]) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const int j = q * 256 + lane * 4;
-        x[q] = j < D ? *reinterpret_cast<const f32x4*>(row + j) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-}
-
-template <int NQ>
-__device__ __forceinline__ float kc_dist(const f32x4 (&x)[NQ], const f32x4 (&c)[NQ]) {
-    float a = 0.f;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float t = x[q][e] - c[q][e];
-            a = fmaf(t, t, a);
-        }
-    return kc_wave_sum(a);
 }
 
 // Pair 0 of a launch starts from (mind[0], 0) as the definition does, so a NaN in mind[0] stays the
@@ -204,12 +170,7 @@ __global__ __launch_bounds__(256) void kc_cover_kernel(const KcCoverArgs a) {
     for (int m0 = 0; m0 < a.M; m0 += kKcCentres) {
         const int nm = min(kKcCentres, a.M - m0);
         __syncthreads();
-        for (int e = tid; e < nm * NQ * 64; e += 256) {
-            const int m = e / (NQ * 64), j = (e - m * (NQ * 64)) * 4;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (j < D) v = *reinterpret_cast<const f32x4*>(a.C + (size_t)(m0 + m) * a.ldc + j);
-            *reinterpret_cast<f32x4*>(&cs[m][j]) = v;
-        }
+        kc_stage_rows<NQ>(&cs[0][0], a.C + (size_t)m0 * a.ldc, a.ldc, nm, D, tid);
         __syncthreads();
         for (int r0 = (blockIdx.x * 4 + wave) * R; r0 < N; r0 += step) {
             f32x4 x[R][NQ];
@@ -241,7 +202,6 @@ __global__ __launch_bounds__(256) void kc_cover_kernel(const KcCoverArgs a) {
     }
 }
 
-int kc_grid(const int N) { return min(kKcMaxGrid, cdiv(N, 4)); }
 size_t kc_pairs(const int N) { return ((size_t)kc_grid(N) + 1) & ~(size_t)1; }   // per buffer, 16 bytes apart
 
 int kc_check_rows(const char* who, const float* X, long ld, int N, int D, const float* mind) {

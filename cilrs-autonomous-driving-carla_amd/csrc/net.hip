@@ -2907,6 +2907,63 @@ int cilrs_net_novelty(cilrs_net* net, const cilrs_buffers* bufs, const int64_t* 
     return 0;
 }
 
+size_t cilrs_feature_whiten_scratch_floats(int F, int batch) {
+    if ((F != 512 && F != 2048) || batch < 1 || batch > kNovMaxBatch) return 0;
+    return (size_t)batch * F;
+}
+
+int cilrs_feature_whiten(const float* features, int ld, int batch, int F, const float* origin,
+                         const float* W, float* y, float* scratch, size_t scratch_floats,
+                         void* stream) {
+    CILRS_CHECK(features && origin && W && y, "feature_whiten: NULL tensor");
+    CILRS_CHECK(batch >= 1 && batch <= kNovMaxBatch, "feature_whiten: batch %d outside 1..%d", batch,
+                kNovMaxBatch);
+    CILRS_CHECK(F == 512 || F == 2048, "feature_whiten: feature width %d (512 or 2048)", F);
+    CILRS_CHECK(ld >= F, "feature_whiten: ld %d below the %d features", ld, F);
+    CILRS_CHECK(scratch != nullptr && scratch_floats >= (size_t)batch * F,
+                "feature_whiten: scratch of %zu floats, %zu needed", scratch ? scratch_floats : (size_t)0,
+                (size_t)batch * F);
+    CILRS_CHECK(((uintptr_t)W & 15) == 0 && ((uintptr_t)scratch & 15) == 0,
+                "feature_whiten: W and scratch must be 16-byte aligned");
+    const NoveltyWhitenArgs a{features, ld, nullptr, 0, batch, F, origin, W, scratch, y};
+    return launch_novelty_whiten(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ------------------------------------------------------------------------------------------------
+// Nearest neighbours of the tick's features (knn.hip)
+// ------------------------------------------------------------------------------------------------
+// scratch: u [B][F] | y [B][F] | the lists of cilrs_knn
+size_t cilrs_net_knn_scratch_bytes(int F, int batch, int N, int K) {
+    const size_t lists = knn_scratch_bytes(N, batch, K);
+    if ((F != 512 && F != 2048) || lists == 0) return 0;
+    return 2 * (size_t)batch * F * sizeof(float) + lists;
+}
+
+int cilrs_net_knn(cilrs_net* net, const cilrs_buffers* bufs, const float* X, long ld, int N,
+                  const float* origin, const float* W, int K, int64_t* idx, float* dist,
+                  void* scratch, size_t scratch_bytes, void* stream) {
+    if (check_bufs(net, bufs, false)) return 1;
+    const Arch& A = *net->A;
+    const int F = A.feat, B = net->B;
+    CILRS_CHECK((origin != nullptr) == (W != nullptr), "net_knn: origin and W go together");
+    CILRS_CHECK(W == nullptr || ((uintptr_t)W & 15) == 0, "net_knn: W must be 16-byte aligned");
+    const size_t rows = (size_t)B * F * sizeof(float);
+    CILRS_CHECK(scratch != nullptr && scratch_bytes >= 2 * rows,
+                "net_knn: scratch of %zu bytes, needs %zu", scratch ? scratch_bytes : (size_t)0,
+                cilrs_net_knn_scratch_bytes(F, B, N, K));
+    float* u = reinterpret_cast<float*>(scratch);
+    KnnArgs k{X, ld, N, F, W ? u + (size_t)B * F : u, F, B, nullptr, K, idx, dist,
+              reinterpret_cast<char*>(scratch) + 2 * rows};
+    if (knn_check("net_knn", k, scratch_bytes - 2 * rows)) return 1;
+    NoveltyWhitenArgs a;
+    if (plan_features_checked("net_knn", net, bufs, &a.features, &a.ld, &a.featmap, &a.HW)) return 1;
+    a.B = B; a.F = F; a.origin = origin; a.W = W; a.u = u; a.y = u + (size_t)B * F;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    RUN(net, "knn_features", W ? (double)B * F * (F + 1) : 0.0, 0.0, s, launch_novelty_whiten(a, s));
+    RUN(net, "knn", 3.0 * B * (double)N * F, (double)N * F * 4.0 * ((B + 7) / 8), s, launch_knn(k, s));
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------

@@ -22,6 +22,8 @@
 //                    frames walking through LDS four at a time.  Writes the per-frame sum of
 //                    squares of its eight rows.
 //   nov_sum_kernel   d2[b] = the partial sums added in workgroup order.
+// Whitening (cilrs_feature_whiten): the first two of those launches with one fixed origin instead
+// of the per-frame command mean, y stored instead of summed (nov_u0_kernel, nov_whiten_kernel).
 // Every sum runs in a fixed order (include/cilrs_hip.h states it); a frame's arithmetic never
 // depends on which frames share its chunk.
 #include "common.h"
@@ -155,6 +157,55 @@ __device__ __forceinline__ float nov_wave_sum(float v) {
     return v;
 }
 
+// row i of W as a wave holds it: columns 256 q + 4 lane + e; zero where j > i (never loaded)
+__device__ __forceinline__ void nov_load_w(const float* __restrict__ W, const int F, const int i,
+                                           const int lane, f32x4 (&w)[kNovQuads]) {
+    const int nq = F >> 8;
+    const float* wr = W + (size_t)i * F;
+#pragma unroll
+    for (int q = 0; q < kNovQuads; ++q) {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        const int j = q * 256 + lane * 4;
+        if (q < nq) {
+            if (j + 3 <= i) {
+                v = *reinterpret_cast<const f32x4*>(wr + j);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (j + e <= i) v[e] = wr[j + e];
+            }
+        }
+        w[q] = v;
+    }
+}
+
+// y_i = sum_j W_ij u_j of one frame staged in LDS: the lane chain, then the butterfly
+__device__ __forceinline__ float nov_row_dot(const f32x4 (&w)[kNovQuads], const float* __restrict__ us,
+                                             const int nq, const int lane) {
+    float acc = 0.f;
+#pragma unroll
+    for (int q = 0; q < kNovQuads; ++q) {
+        if (q < nq) {
+            const f32x4 uv = *reinterpret_cast<const f32x4*>(&us[q * 256 + lane * 4]);
+            acc = fmaf(w[q][0], uv[0], acc);
+            acc = fmaf(w[q][1], uv[1], acc);
+            acc = fmaf(w[q][2], uv[2], acc);
+            acc = fmaf(w[q][3], uv[3], acc);
+        }
+    }
+    return nov_wave_sum(acc);
+}
+
+// stage frames b0 .. b0 + nb - 1 of u [B][F] in LDS
+__device__ __forceinline__ void nov_stage_u(float (*us)[kMcMaxFeat], const float* __restrict__ u,
+                                            const int F, const int b0, const int nb, const int tid) {
+    for (int e = tid; e < nb * (F >> 2); e += 256) {
+        const int b = e / (F >> 2), q = e - b * (F >> 2);
+        *reinterpret_cast<f32x4*>(&us[b][q * 4]) =
+            *reinterpret_cast<const f32x4*>(u + (size_t)(b0 + b) * F + q * 4);
+    }
+}
+
 __global__ __launch_bounds__(256) void nov_u_kernel(const NoveltyScoreArgs a) {
     const int parts = a.F >> 8;
     const int b = blockIdx.x / parts, c = (blockIdx.x - b * parts) * 256 + threadIdx.x;
@@ -170,59 +221,60 @@ __global__ __launch_bounds__(256) void nov_gemv_kernel(const NoveltyScoreArgs a)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int F = a.F, nwg = F / kNovWgRows, g = blockIdx.x;
     const int nq = F >> 8;
-    // the wave's two rows of W, columns 256 q + 4 lane + e; zero where j > i (never loaded)
     f32x4 w[2][kNovQuads];
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int i = g + nwg * (2 * wave + r);
-        const float* wr = a.W + (size_t)i * F;
-#pragma unroll
-        for (int q = 0; q < kNovQuads; ++q) {
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            const int j = q * 256 + lane * 4;
-            if (q < nq) {
-                if (j + 3 <= i) {
-                    v = *reinterpret_cast<const f32x4*>(wr + j);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (j + e <= i) v[e] = wr[j + e];
-                }
-            }
-            w[r][q] = v;
-        }
-    }
+    for (int r = 0; r < 2; ++r) nov_load_w(a.W, F, g + nwg * (2 * wave + r), lane, w[r]);
     for (int b0 = 0; b0 < a.B; b0 += kNovFrames) {
         const int nb = min(kNovFrames, a.B - b0);
         __syncthreads();
-        for (int e = tid; e < nb * (F >> 2); e += 256) {
-            const int b = e / (F >> 2), q = e - b * (F >> 2);
-            *reinterpret_cast<f32x4*>(&us[b][q * 4]) =
-                *reinterpret_cast<const f32x4*>(a.u + (size_t)(b0 + b) * F + q * 4);
-        }
+        nov_stage_u(us, a.u, F, b0, nb, tid);
         __syncthreads();
         for (int b = 0; b < nb; ++b) {
             float y[2];
 #pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                float acc = 0.f;
-#pragma unroll
-                for (int q = 0; q < kNovQuads; ++q) {
-                    if (q < nq) {
-                        const f32x4 uv = *reinterpret_cast<const f32x4*>(&us[b][q * 256 + lane * 4]);
-                        acc = fmaf(w[r][q][0], uv[0], acc);
-                        acc = fmaf(w[r][q][1], uv[1], acc);
-                        acc = fmaf(w[r][q][2], uv[2], acc);
-                        acc = fmaf(w[r][q][3], uv[3], acc);
-                    }
-                }
-                y[r] = nov_wave_sum(acc);
-            }
+            for (int r = 0; r < 2; ++r) y[r] = nov_row_dot(w[r], us[b], nq, lane);
             if (lane == 0) red[wave][b] = fmaf(y[1], y[1], y[0] * y[0]);
         }
         __syncthreads();
         if (tid < nb)
             a.part[(size_t)g * a.B + b0 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    }
+}
+
+// u = v - origin (pooling a feature map first); origin NULL: u = v
+__global__ __launch_bounds__(256) void nov_u0_kernel(const NoveltyWhitenArgs a) {
+    const int parts = a.F >> 8;
+    const int b = blockIdx.x / parts, c = (blockIdx.x - b * parts) * 256 + threadIdx.x;
+    const float v = nov_feature(a.features, a.ld, a.featmap, a.HW, a.F, b, c);
+    a.u[(size_t)b * a.F + c] = a.origin ? v - a.origin[c] : v;
+}
+
+// nov_gemv_kernel's product with y stored: workgroup (g, s) writes y[b][g + (F / 8) r], r = 0..7, for
+// the frames b of slice s
+__global__ __launch_bounds__(256) void nov_whiten_kernel(const NoveltyWhitenArgs a) {
+    __shared__ __align__(16) float us[kNovFrames][kMcMaxFeat];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int F = a.F, nwg = F / kNovWgRows, g = blockIdx.x;
+    const int nq = F >> 8;
+    f32x4 w[2][kNovQuads];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) nov_load_w(a.W, F, g + nwg * (2 * wave + r), lane, w[r]);
+    // the frames split over gridDim.y in whole LDS chunks: a frame's y does not depend on the split
+    const int ny = gridDim.y;
+    const int per = ((a.B + ny - 1) / ny + kNovFrames - 1) / kNovFrames * kNovFrames;
+    const int bend = min(a.B, ((int)blockIdx.y + 1) * per);
+    for (int b0 = blockIdx.y * per; b0 < bend; b0 += kNovFrames) {
+        const int nb = min(kNovFrames, bend - b0);
+        __syncthreads();
+        nov_stage_u(us, a.u, F, b0, nb, tid);
+        __syncthreads();
+        for (int b = 0; b < nb; ++b) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const float y = nov_row_dot(w[r], us[b], nq, lane);
+                if (lane == 0) a.y[(size_t)(b0 + b) * F + g + nwg * (2 * wave + r)] = y;
+            }
+        }
     }
 }
 
@@ -265,6 +317,19 @@ int launch_novelty_score(NoveltyScoreArgs& a, float* scratch, hipStream_t s) {
     nov_gemv_kernel<<<a.F / kNovWgRows, 256, 0, s>>>(a);
     CILRS_LAUNCH_CHECK();
     nov_sum_kernel<<<cdiv(a.B, 64), 64, 0, s>>>(a);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_novelty_whiten(const NoveltyWhitenArgs& a, hipStream_t s) {
+    CILRS_CHECK(a.F % 256 == 0 && a.F >= 256 && a.F <= kMcMaxFeat, "feature_whiten: feature width %d",
+                a.F);
+    nov_u0_kernel<<<a.B * (a.F >> 8), 256, 0, s>>>(a);
+    CILRS_LAUNCH_CHECK();
+    if (a.W == nullptr) return 0;
+    // a pool's worth of frames: enough workgroups for the chip (about eight per CU)
+    const int wgs = a.F / kNovWgRows, split = max(1, min(cdiv(a.B, 64), 2048 / wgs));
+    nov_whiten_kernel<<<dim3(wgs, split), 256, 0, s>>>(a);
     CILRS_LAUNCH_CHECK();
     return 0;
 }

@@ -518,6 +518,66 @@ int cilrs_kcenter_cover(const float* X, long ld, int N, int D, const float* C, l
 int cilrs_kcenter_greedy(const float* X, long ld, int N, int D, float* mind, int K, int64_t* sel,
                          float* radius, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Nearest neighbours: which rows of a pool a query looks like (csrc/knn.hip) -------------------
+ * The novelty score gives one number and assumes Gaussians; the k nearest recorded frames answer
+ * with examples, and the distance to the K-th of them is the non-parametric score of Sun et al.
+ * (2022).  The reference has no such path; parity is pinned by this definition (restated in float64
+ * by tests/_knn.py).
+ *   Inputs   rows X fp32 [N][ld] and queries Y fp32 [Q][ldq], the first D columns used (columns D..
+ *            are never read); skip int64 [Q] or NULL.
+ *   Distance d(x, y) is exactly the distance of "Greedy k-center" above: the same lane chains and
+ *            butterfly, the same bits (the device code is shared, csrc/kc_dist.h).
+ *   Result   row i is a candidate for query q unless skip[q] == i or d(X_i, Y_q) is NaN; a skip
+ *            value outside 0..N-1 excludes nothing (skip is the leave-one-out switch for queries
+ *            that are pool rows themselves).  idx[q][0..K-1], dist[q][0..K-1] are the K candidates
+ *            smallest in the total order (d, i), ascending: an entry precedes another by
+ *            d < d' || (d == d' && i < i'); +inf is an ordinary value.  With fewer than K
+ *            candidates the remaining slots hold idx = -1 and dist = +inf.
+ *            Min, comparison and the tie rule are exact and every distance has fixed bits: the
+ *            result does not depend on how the rows are spread over waves, workgroups or launches,
+ *            a query's result does not depend on the queries it shares a call with, and the result
+ *            for K is the first K columns of the result for any K' > K.
+ * cilrs_knn: per chunk of at most eight queries two or three launches on `stream` -- one streaming
+ * pass over X with the queries staged in LDS (X is read once per eight queries), then the fold of
+ * the workgroups' lists (in two levels where a query's lists hold more than 2,048 pairs); no
+ * atomics, no fences, no grid barrier, no host synchronisation.  idx int64
+ * [Q][K] and dist fp32 [Q][K] may be pinned host memory; scratch: cilrs_knn_scratch_bytes(N, Q, K)
+ * bytes of device memory (0 for arguments outside the ranges), 16-byte aligned, contents irrelevant
+ * before and after.
+ * Refused (non-zero, text in cilrs_last_error, nothing launched): NULL tensors (skip is exempt); N
+ * outside 1..2^24; D outside 4..2048 or not a multiple of 4; ld or ldq below D or not a multiple of
+ * 4; X, Y or the scratch not 16-byte aligned; Q outside 1..65536; K outside 1..64; a scratch
+ * smaller than asked.
+ *
+ * cilrs_feature_whiten: y = tril(W) (v - origin) as fp32 [batch][F] for rows v [batch][ld] -- the
+ * first two launches of cilrs_feature_novelty (u = v - origin in fp32; y_i = sum_{j <= i} W_ij u_j
+ * in the order of "Score" above) with one fixed origin [F] instead of a per-row command mean, y
+ * stored instead of summed.  A row's y does not depend on the batch or its place in it, so a query
+ * whitened by this entry is at distance exactly 0 from its own row of a pool whitened by it.
+ * scratch: cilrs_feature_whiten_scratch_floats(F, batch) floats (0 for a width other than 512 / 2048
+ * or a batch outside 1..65536), 16-byte aligned like W.  Refused: NULL tensors; those widths and
+ * batches; ld < F; a scratch smaller than asked; a W or scratch that is not 16-byte aligned.
+ *
+ * cilrs_net_knn: cilrs_knn of the features the plan's last eval-mode forward left (resolved exactly
+ * as cilrs_net_novelty resolves them) against the rows X [N][ld] of an index, D = F and Q = the
+ * plan's batch.  With origin and W (both or neither) the features are whitened first; X then holds
+ * rows whitened by cilrs_feature_whiten with the same tables.  scratch:
+ * cilrs_net_knn_scratch_bytes(F, batch, N, K) bytes.  Refuses what cilrs_knn and cilrs_net_novelty
+ * refuse (no forward yet, a train-mode forward last).  No launch of any other entry changes, nor
+ * does the workspace layout. */
+size_t cilrs_knn_scratch_bytes(int N, int Q, int K);
+int cilrs_knn(const float* X, long ld, int N, int D, const float* Y, long ldq, int Q,
+              const int64_t* skip, int K, int64_t* idx, float* dist, void* scratch,
+              size_t scratch_bytes, void* stream);
+size_t cilrs_feature_whiten_scratch_floats(int F, int batch);
+int cilrs_feature_whiten(const float* features, int ld, int batch, int F, const float* origin,
+                         const float* W, float* y, float* scratch, size_t scratch_floats,
+                         void* stream);
+size_t cilrs_net_knn_scratch_bytes(int F, int batch, int N, int K);
+int cilrs_net_knn(cilrs_net* net, const cilrs_buffers* bufs, const float* X, long ld, int N,
+                  const float* origin, const float* W, int K, int64_t* idx, float* dist,
+                  void* scratch, size_t scratch_bytes, void* stream);
+
 /* Same, fed with uint8 RGB HWC frames [B,H,W,3]: fuses preprocess_image's /255, HWC->CHW and
  * Normalize(mean,std) (autonomous_drive.py:897-902; the cv2.resize is the caller's). */
 int cilrs_net_forward_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
