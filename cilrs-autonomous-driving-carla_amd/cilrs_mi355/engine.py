@@ -227,10 +227,7 @@ class Engine:
         self.plans = {}
         self.bufs = {}
         self.last_plan = None
-        self._mc_bufs = {}                # run_heads_mc: (owner, B, S) -> scratch + pinned outputs
-        self._gc_bufs = {}                # run_gradcam: (owner, B, H, W, layer) -> the same
-        self._nov_bufs = {}               # run_novelty: (owner, B) -> scratch + pinned d2
-        self._knn_bufs = {}               # run_knn: (owner, B, k) -> scratch + pinned idx, dist
+        self._followup_bufs = {}          # (follow-up, owner, shape...) -> scratch + pinned outputs
         # "fp32" (the reference's arithmetic) or "bf16": train-mode trunk convolutions on the bf16
         # matrix pipe (include/cilrs_hip.h CILRS_PLAN_BF16_TRAIN); set through
         # Trainer(..., precision=) or directly before the first train-mode forward
@@ -621,18 +618,37 @@ class Engine:
 
     MC_CACHE_ENTRIES = 8
 
+    def _followup_plan(self, who):
+        """The plan a tick follow-up runs on: the last forward's."""
+        if self.last_plan is None:
+            raise RuntimeError(f"{who}: no forward yet")
+        return self.last_plan
+
+    def _followup_buffers(self, name, owner, shape, make, usable=None):
+        """The device scratch and pinned host outputs of follow-up `name` for (owner, shape...),
+        built by make() on a miss or where usable(bufs) says the cached ones no longer do.  Each
+        follow-up keeps its MC_CACHE_ENTRIES most recently used entries: callers that may run at
+        the same time on different streams (two Predictors on one model) pass themselves as
+        `owner` and so never share a buffer."""
+        cache, key = self._followup_bufs, (name, id(owner) if owner is not None else None) + shape
+        bufs = cache.pop(key, None)
+        if bufs is None or (usable is not None and not usable(bufs)):
+            mine = [k for k in cache if k[0] == name]        # least recently used first
+            for k in mine[:-(self.MC_CACHE_ENTRIES - 1)]:    # room for the new one
+                del cache[k]
+            bufs = make()
+        cache[key] = bufs                                # (re-inserted: most recently used last)
+        return bufs
+
     def run_heads_mc(self, speed, command, samples, p, seed=0, return_samples=False, owner=None):
         """Monte-Carlo dropout through the heads (include/cilrs_hip.h, cilrs_net_heads_mc) on the
         features the last eval-mode forward left in its plan: enqueues the launches on the current
         stream and returns (mean [B,4], std [B,4], samples [B,S,4] or None) as views of a PINNED
         host buffer that the kernels write -- valid after the stream is synchronised and until the
         next call with the same (B, S).  speed / command: the tensors the forward was given
-        (device or pinned host).  Scratch and outputs are cached per (owner, B, S), the
-        MC_CACHE_ENTRIES most recent: callers that may run at the same time on different streams
-        (two Predictors on one model) pass themselves as `owner` and so never share a buffer."""
-        pl = self.last_plan
-        if pl is None:
-            raise RuntimeError("run_heads_mc: no forward yet")
+        (device or pinned host).  Scratch and outputs are cached per (owner, B, S)
+        (_followup_buffers)."""
+        pl = self._followup_plan("run_heads_mc")
         samples, p, b = int(samples), float(p), pl.batch
         if not 1 <= samples <= self.MC_MAX_SAMPLES:
             raise ValueError(f"samples must be in 1..{self.MC_MAX_SAMPLES}")
@@ -640,18 +656,14 @@ class Engine:
             raise ValueError(f"batch * samples must not exceed {self.MC_MAX_ROWS}")
         if not 0.0 <= p < 1.0:                       # (NaN fails both comparisons)
             raise ValueError("dropout probability must be in [0, 1)")
-        cache, key = self._mc_bufs, (id(owner) if owner is not None else None, b, samples)
-        bufs = cache.pop(key, None)
-        if bufs is None:
-            while len(cache) >= self.MC_CACHE_ENTRIES:
-                cache.pop(next(iter(cache)))             # the least recently used
+
+        def make():
             n = L.lib().cilrs_heads_mc_scratch_floats(self.variant, b, samples)
             scratch = torch.empty(n, dtype=torch.float32, device=self.device)
             host = torch.zeros(b * 8 + b * samples * 4, dtype=torch.float32).pin_memory()
-            bufs = (scratch, host, host[:b * 4].view(b, 4), host[b * 4:b * 8].view(b, 4),
+            return (scratch, host, host[:b * 4].view(b, 4), host[b * 4:b * 8].view(b, 4),
                     host[b * 8:].view(b, samples, 4))
-        cache[key] = bufs                                # (re-inserted: most recently used last)
-        scratch, _host, mean, std, smp = bufs
+        scratch, _host, mean, std, smp = self._followup_buffers("mc", owner, (b, samples), make)
         L.check(L.lib().cilrs_net_heads_mc(
             pl.handle, C.byref(pl.bufs), L.ptr(speed), L.ptr(command), samples, p,
             int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(mean), L.ptr(std),
@@ -727,19 +739,13 @@ class Engine:
         heat [B,H,W], peak [B], heat_u8 [B,H,W] or None) as views of PINNED host buffers that the
         kernels write -- valid after the stream is synchronised and until the next call with the
         same (owner, plan shape, layer).  speed / command: the tensors the forward was given."""
-        pl = self.last_plan
-        if pl is None:
-            raise RuntimeError("run_gradcam: no forward yet")
+        pl = self._followup_plan("run_gradcam")
         layer = int(layer)
         if not 1 <= layer <= 4:
             raise ValueError("layer must be in 1..4")
         w = self._gradcam_weights(weights4)
-        cache = self._gc_bufs
-        key = (id(owner) if owner is not None else None, pl.batch, pl.h, pl.w, layer)
-        bufs = cache.pop(key, None)
-        if bufs is None:
-            while len(cache) >= self.MC_CACHE_ENTRIES:
-                cache.pop(next(iter(cache)))             # the least recently used
+
+        def make():
             h, wd, ch = L.i32(), L.i32(), L.i32()
             L.check(L.lib().cilrs_net_gradcam_info(pl.handle, layer, None, None, C.byref(h),
                                                    C.byref(wd), C.byref(ch)))
@@ -748,10 +754,10 @@ class Engine:
             scratch = torch.empty(n, dtype=torch.float32, device=self.device)
             host = torch.zeros(ncam + b + nheat, dtype=torch.float32).pin_memory()
             u8 = torch.zeros(nheat, dtype=torch.uint8).pin_memory().view(b, pl.h, pl.w)
-            bufs = (scratch, host, host[:ncam].view(b, h.value, wd.value), host[ncam:ncam + b],
+            return (scratch, host, host[:ncam].view(b, h.value, wd.value), host[ncam:ncam + b],
                     host[ncam + b:].view(b, pl.h, pl.w), u8)
-        cache[key] = bufs                                # (re-inserted: most recently used last)
-        scratch, _host, cam, peak, heat, u8 = bufs
+        scratch, _host, cam, peak, heat, u8 = self._followup_buffers(
+            "gradcam", owner, (pl.batch, pl.h, pl.w, layer), make)
         L.check(L.lib().cilrs_net_gradcam(
             pl.handle, C.byref(pl.bufs), L.ptr(speed), L.ptr(command), w, layer, L.ptr(cam),
             L.ptr(heat), L.ptr(u8) if want_u8 else None, L.ptr(peak), L.ptr(scratch),
@@ -775,9 +781,7 @@ class Engine:
         """cilrs_net_feature_moments: add the pooled features the last eval-mode forward left in
         its plan, one row per frame, to the float64 moment table (include/cilrs_hip.h).  One
         launch on the current stream; nothing is copied to the host."""
-        pl = self.last_plan
-        if pl is None:
-            raise RuntimeError("run_feature_moments: no forward yet")
+        pl = self._followup_plan("run_feature_moments")
         L.check(L.lib().cilrs_net_feature_moments(
             pl.handle, C.byref(pl.bufs), L.ptr(command), L.ptr(pivot), L.ptr(table), self._stream()))
 
@@ -786,20 +790,14 @@ class Engine:
         the three launches on the current stream and returns d2 [B].  Without `d2` the kernels
         write a PINNED host buffer, valid after the stream is synchronised and until the next call
         with the same (owner, B); the scratch is cached the same way (see run_heads_mc)."""
-        pl = self.last_plan
-        if pl is None:
-            raise RuntimeError("run_novelty: no forward yet")
+        pl = self._followup_plan("run_novelty")
         b = pl.batch
-        cache, key = self._nov_bufs, (id(owner) if owner is not None else None, b)
-        bufs = cache.pop(key, None)
-        if bufs is None:
-            while len(cache) >= self.MC_CACHE_ENTRIES:
-                cache.pop(next(iter(cache)))             # the least recently used
+
+        def make():
             n = L.lib().cilrs_feature_novelty_scratch_floats(self.feature_width(), b)
-            bufs = (torch.empty(n, dtype=torch.float32, device=self.device),
+            return (torch.empty(n, dtype=torch.float32, device=self.device),
                     torch.zeros(b, dtype=torch.float32).pin_memory())
-        cache[key] = bufs
-        scratch, host = bufs
+        scratch, host = self._followup_buffers("novelty", owner, (b,), make)
         out = host if d2 is None else d2
         L.check(L.lib().cilrs_net_novelty(
             pl.handle, C.byref(pl.bufs), L.ptr(command), L.ptr(mean), L.ptr(W), L.ptr(out),
@@ -812,21 +810,17 @@ class Engine:
         the launches on the current stream and returns (idx int64 [B, k], dist float32 [B, k]) in
         PINNED host buffers, valid after the stream is synchronised and until the next call with
         the same (owner, B, k); the scratch is cached the same way (see run_novelty)."""
-        pl = self.last_plan
-        if pl is None:
-            raise RuntimeError("run_knn: no forward yet")
+        pl = self._followup_plan("run_knn")
         b, n, k = pl.batch, rows.size(0), int(k)
         need = L.lib().cilrs_net_knn_scratch_bytes(self.feature_width(), b, n, k)
-        cache, key = self._knn_bufs, (id(owner) if owner is not None else None, b, k)
-        bufs = cache.pop(key, None)
-        if bufs is None or bufs[0].numel() < need:
-            while len(cache) >= self.MC_CACHE_ENTRIES:
-                cache.pop(next(iter(cache)))             # the least recently used
-            bufs = (torch.empty(max(need, 16), dtype=torch.uint8, device=self.device),
+
+        def make():
+            return (torch.empty(max(need, 16), dtype=torch.uint8, device=self.device),
                     torch.full((b, k), -1, dtype=torch.int64).pin_memory(),
                     torch.zeros(b, k, dtype=torch.float32).pin_memory())
-        cache[key] = bufs
-        scratch, idx, dist = bufs
+        # (a pool that has grown since the entry was made needs longer lists: rebuilt)
+        scratch, idx, dist = self._followup_buffers("knn", owner, (b, k), make,
+                                                    lambda bufs: bufs[0].numel() >= need)
         L.check(L.lib().cilrs_net_knn(
             pl.handle, C.byref(pl.bufs), L.ptr(rows), rows.stride(0), n, L.ptr(origin), L.ptr(W), k,
             L.ptr(idx), L.ptr(dist), L.ptr(scratch), scratch.numel(), self._stream()))

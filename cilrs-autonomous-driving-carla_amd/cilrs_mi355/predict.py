@@ -120,6 +120,15 @@ class Predictor:
             raise RuntimeError(f"predict_controls: command index out of range (expected 0..{nc - 1})")
         return c
 
+    @staticmethod
+    def _result4(controls, pred_speed):
+        """np.float32 [B,4] = (steer, throttle, brake, speed_kmh) from the pinned outputs of a
+        forward: controls [B,3] (or flat) and the normalised pred_speed [B]."""
+        out = np.empty((pred_speed.shape[0], 4), dtype=np.float32)
+        out[:, :3] = controls.reshape(-1, 3)
+        out[:, 3] = pred_speed * np.float32(SPEED_NORM_FACTOR)                  # :920
+        return out
+
     @torch.no_grad()
     def predict_batch(self, frames_u8, speeds_kmh, commands):
         """frames uint8 [B,88,200,3] RGB, km/h, command idx -> np.float32 [B,4] =
@@ -165,10 +174,7 @@ class Predictor:
                 self.stream.synchronize()
         if self.persistent and not np.isfinite(self._ctrl_np).all():
             self.eng.check_status()       # a grid barrier that gave up leaves NaN outputs
-        out = np.empty((self.batch, 4), dtype=np.float32)
-        out[:, :3] = self._ctrl_np
-        out[:, 3] = self._spd_np * np.float32(SPEED_NORM_FACTOR)                # :920
-        return out
+        return self._result4(self._ctrl_np, self._spd_np)
 
     def _tick_persistent(self, frames_u8, speeds_kmh, commands):
         """One control-loop tick on the persistent launch: stage the inputs in the pinned buffer
@@ -226,10 +232,7 @@ class Predictor:
             self._spd_np[...] = np.nan
         if not np.isfinite(self._ctrl_np).all() and self._barrier_gave_up(fast.plan):
             return self._tick_per_layer()
-        out = np.empty((self.batch, 4), dtype=np.float32)
-        out[:, :3] = self._ctrl_np
-        out[:, 3] = self._spd_np * np.float32(SPEED_NORM_FACTOR)                # :920
-        return out
+        return self._result4(self._ctrl_np, self._spd_np)
 
     def _planner_refused(self):
         """A persistent call just failed.  If the library's planner said that it has no tiling
@@ -283,10 +286,7 @@ class Predictor:
                                     half=self.half, persistent=False)
             self.out_host[:self.batch * 4].copy_(self.out_dev, non_blocking=True)
             self.stream.synchronize()
-        out = np.empty((self.batch, 4), dtype=np.float32)
-        out[:, :3] = self._ctrl_np
-        out[:, 3] = self._spd_np * np.float32(SPEED_NORM_FACTOR)                # :920
-        return out
+        return self._result4(self._ctrl_np, self._spd_np)
 
     @torch.no_grad()
     def predict_camera(self, frame_u8, speed_kmh, command_idx):
@@ -425,25 +425,49 @@ class Predictor:
         kernel run on this predictor's stream through the per-layer plan of the same shape; the
         single-frame persistent state and later predict_batch calls are not disturbed."""
         wts = self._saliency_weights(output)                       # ValueError before any launch
+        frames, speeds, cmds, camera = self._checked_frames("saliency", frames_u8, speeds_kmh,
+                                                            commands)
+        b, h, w = self.batch, self.frames_host.size(1), self.frames_host.size(2)
+
+        def launch(eng, sal, pl, dc_dev, ds_dev):
+            eng.run_backward(pl, dc_dev, ds_dev, data_only=True, segments=(0, 6))
+            eng.run_input_grads(pl, sal["dimage"], None)
+            eng.run_saliency_map(sal["dimage"], [1.0 / (255.0 * sd) for sd in IMG_STD],
+                                 heat=sal["heat"], peak=sal["peak"])
+        out, o, _ = self._frozen_graph_run(frames, speeds, cmds, camera, wts, launch, 5 * b + b * h * w)
+        return out, o[5 * b:].reshape(b, h, w).copy(), o[4 * b:5 * b].copy()
+
+    def _checked_frames(self, who, frames_u8, speeds_kmh, commands):
+        """What `who` (saliency, gradcam) refuses of its frames, speeds and commands before
+        anything is launched: returns (frames, speeds in km/h as float64, commands, whether the
+        frames are camera-sized, i.e. to be resized on the device)."""
         frames = np.asarray(frames_u8)
-        h, w = self.frames_host.size(1), self.frames_host.size(2)
-        if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[0] != self.batch or \
+        b = self.batch
+        if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[0] != b or \
                 frames.shape[3] not in (3, 4):
-            raise RuntimeError(f"saliency: frames must be uint8 [{self.batch},H,W,3] (camera "
-                               "frames: 3 or 4 bytes per pixel)")
-        camera = frames.shape[1:] != (h, w, 3)
+            raise RuntimeError(f"{who}: frames must be uint8 [{b},H,W,3] (camera frames: 3 or 4 "
+                               "bytes per pixel)")
+        camera = frames.shape[1:] != (self.frames_host.size(1), self.frames_host.size(2), 3)
         cmds = self._check_commands(commands)
-        speeds = np.minimum(np.asarray(speeds_kmh, dtype=np.float64) / SPEED_NORM_FACTOR, 1.0)
-        if cmds.shape != (self.batch,) or speeds.shape != (self.batch,):
-            raise RuntimeError(f"saliency: {self.batch} speeds and commands expected")
+        speeds = np.asarray(speeds_kmh, dtype=np.float64)
+        if cmds.shape != (b,) or speeds.shape != (b,):
+            raise RuntimeError(f"{who}: {b} speeds and commands expected")
+        return frames, speeds, cmds, camera
+
+    def _frozen_graph_run(self, frames, speeds, cmds, camera, wts, launch, n_out):
+        """What saliency and the deeper Grad-CAM layers share: checked inputs through the pinned
+        staging buffer, the eval-mode forward that keeps its graph, then launch(eng, sal, pl,
+        d controls, d pred_speed) on this predictor's stream, the first n_out output floats back
+        to the host, one synchronise.  Returns (out [B,4], the host outputs, launch's result)."""
+        b, h, w = self.batch, self.frames_host.size(1), self.frames_host.size(2)
         if self.model.engine() is not self.eng:
-            self.__init__(self.model, self.batch, h, w, self.use_graph, self.half, self.persistent)
+            self.__init__(self.model, b, h, w, self.use_graph, self.half, self.persistent)
         if self.model.training:
             self.model.eval()
         sal = self._saliency_buffers(tuple(frames.shape))
         f_np, s_np, dc_np, ds_np, c_np = sal["host_np"]
         np.copyto(f_np, frames)
-        s_np[...] = speeds
+        s_np[...] = np.minimum(speeds / SPEED_NORM_FACTOR, 1.0)
         dc_np[...] = wts[:3]
         ds_np[...] = wts[3]
         c_np[...] = cmds
@@ -454,18 +478,11 @@ class Predictor:
             sal["dev"].copy_(sal["host"], non_blocking=True)
             _, _, pl = eng.run_forward_frozen_u8(f_dev, s_dev, c_dev, h if camera else None,
                                                  w if camera else None, out=(sal["ctrl"], sal["spd"]))
-            eng.run_backward(pl, dc_dev, ds_dev, data_only=True, segments=(0, 6))
-            eng.run_input_grads(pl, sal["dimage"], None)
-            eng.run_saliency_map(sal["dimage"], [1.0 / (255.0 * sd) for sd in IMG_STD],
-                                 heat=sal["heat"], peak=sal["peak"])
-            sal["out_host"].copy_(sal["out_dev"], non_blocking=True)
+            res = launch(eng, sal, pl, dc_dev, ds_dev)
+            sal["out_host"][:n_out].copy_(sal["out_dev"][:n_out], non_blocking=True)
             self.stream.synchronize()
-        b = self.batch
         o = sal["out_np"]
-        out = np.empty((b, 4), dtype=np.float32)
-        out[:, :3] = o[:3 * b].reshape(b, 3)
-        out[:, 3] = o[3 * b:4 * b] * np.float32(SPEED_NORM_FACTOR)
-        return out, o[5 * b:].reshape(b, h, w).copy(), o[4 * b:5 * b].copy()
+        return self._result4(o[:3 * b], o[3 * b:4 * b]), o, res
 
     # ---- SmoothGrad / integrated gradients --------------------------------------------------------
     ATTRIBUTION_METHODS = {"smoothgrad": 0, "integrated": 1}      # CILRS_ATTR_* of the library
@@ -647,9 +664,7 @@ class Predictor:
             att["out_host"].copy_(att["out_dev"], non_blocking=True)
             self.stream.synchronize()
         o = att["out_np"]
-        out = np.empty((b, 4), dtype=np.float32)
-        out[:, :3] = o[:3 * b].reshape(b, 3)
-        out[:, 3] = o[3 * b:4 * b] * np.float32(SPEED_NORM_FACTOR)
+        out = self._result4(o[:3 * b], o[3 * b:4 * b])
         info = dict(method=method, samples=samples, chunk=chunk)
         hw = b * h * w
         if integrated:
@@ -696,8 +711,8 @@ class Predictor:
             raise ValueError("seed must be an integer in 0..2**64-1")
         return samples, p, int(seed)
 
-    def _mc_inputs(self, camera=False):
-        """(speed, command) tensors of the tick that just ran, as the MC launches read them.  Every
+    def _tick_inputs(self, camera=False):
+        """(speed, command) tensors of the tick that just ran, as its follow-ups read them.  Every
         tick stages them in pinned host memory first, and a persistent zero-copy predictor keeps
         reading them there (as its forward does, also on a degraded tick, which copies them to the
         device besides); every other predictor passes the device copies its forward read."""
@@ -707,15 +722,30 @@ class Predictor:
             return cam[4] if host else (cam[2][2], cam[2][3])
         return (self.speed_host, self.cmd_host) if host else (self.speed_dev, self.cmd_dev)
 
-    def _mc_run(self, speed, command, samples, p, seed, return_samples):
-        """The MC launches on this predictor's stream, on the plan the tick just used, into a
-        pinned buffer; one synchronise.  Returns km/h-scaled copies (mean, std, samples)."""
+    def _after_tick(self, launch):
+        """What follows a tick: launch(eng) on this predictor's stream, on the plan the tick just
+        used (the engine's last_plan from here on), into the engine's pinned buffers; one
+        synchronise.  Returns what launch returned."""
         eng = self.eng
         eng.last_plan = eng.plan(self.batch, self.frames_host.size(1), self.frames_host.size(2))
         with torch.cuda.stream(self.stream):
-            mean, std, smp = eng.run_heads_mc(speed, command, samples, p, seed, return_samples,
-                                              owner=self)
+            res = launch(eng)
             self.stream.synchronize()
+        return res
+
+    def _controls_tick(self, image_rgb_u8, speed_kmh, command_idx):
+        """predict_controls (predict_camera for a frame that is not 88x200x3, else predict_batch)
+        plus what its follow-ups read: (point tuple, speed, command) -- see _tick_inputs."""
+        image_rgb_u8 = np.asarray(image_rgb_u8)
+        camera = image_rgb_u8.shape != tuple(self.frames_host.shape[1:])
+        point = self.predict_controls(image_rgb_u8, speed_kmh, command_idx)
+        return (point,) + tuple(self._tick_inputs(camera))
+
+    def _mc_run(self, speed, command, samples, p, seed, return_samples):
+        """The MC launches after the tick (_after_tick).  Returns km/h-scaled copies (mean, std,
+        samples)."""
+        mean, std, smp = self._after_tick(lambda eng: eng.run_heads_mc(
+            speed, command, samples, p, seed, return_samples, owner=self))
         scale = np.array([1.0, 1.0, 1.0, SPEED_NORM_FACTOR], dtype=np.float32)
         return (mean.numpy() * scale, std.numpy() * scale,
                 smp.numpy() * scale if return_samples else None)
@@ -734,7 +764,7 @@ class Predictor:
         masks.  Bad arguments raise ValueError before anything is launched."""
         samples, p, seed = self._mc_args(samples, p, seed)
         point = self.predict_batch(frames_u8, speeds_kmh, commands)
-        speed, cmd = self._mc_inputs()
+        speed, cmd = self._tick_inputs()
         mean, std, smp = self._mc_run(speed, cmd, samples, p, seed, return_samples)
         out = {"point": point, "mean": mean, "std": std}
         if return_samples:
@@ -750,13 +780,7 @@ class Predictor:
         if self.batch != 1:
             raise RuntimeError("predict_controls_uncertain is the single-frame control-loop path")
         samples, p, seed = self._mc_args(samples, p, seed)
-        image_rgb_u8 = np.asarray(image_rgb_u8)
-        if image_rgb_u8.shape != tuple(self.frames_host.shape[1:]):
-            self.predict_camera(image_rgb_u8, speed_kmh, command_idx)
-            speed, cmd = self._mc_inputs(camera=True)
-        else:
-            self.predict_batch(image_rgb_u8[None], [speed_kmh], [command_idx])
-            speed, cmd = self._mc_inputs()
+        _point, speed, cmd = self._controls_tick(image_rgb_u8, speed_kmh, command_idx)
         mean, std, _ = self._mc_run(speed, cmd, samples, p, seed, False)
         return tuple(float(x) for x in mean[0]), tuple(float(x) for x in std[0])
 
@@ -770,13 +794,8 @@ class Predictor:
         density.check_commands(self._check_commands(commands), who)
 
     def _novelty_run(self, command, density):
-        """The score launches on this predictor's stream, on the plan the tick just used, into a
-        pinned buffer; one synchronise."""
-        eng = self.eng
-        eng.last_plan = eng.plan(self.batch, self.frames_host.size(1), self.frames_host.size(2))
-        with torch.cuda.stream(self.stream):
-            d2 = eng.run_novelty(command, density.mean, density.W, owner=self)
-            self.stream.synchronize()
+        """The score launches after the tick (_after_tick)."""
+        d2 = self._after_tick(lambda eng: eng.run_novelty(command, density.mean, density.W, owner=self))
         return d2.numpy().copy()
 
     @torch.no_grad()
@@ -792,7 +811,7 @@ class Predictor:
         raise RuntimeError before anything is launched."""
         self._novelty_check(density, commands, "predict_novelty")
         out = self.predict_batch(frames_u8, speeds_kmh, commands)
-        _speed, cmd = self._mc_inputs()
+        _speed, cmd = self._tick_inputs()
         d2 = self._novelty_run(cmd, density)
         return out[:, :3].copy(), out[:, 3].copy(), d2
 
@@ -803,10 +822,7 @@ class Predictor:
         if self.batch != 1:
             raise RuntimeError("predict_controls_novelty is the single-frame control-loop path")
         self._novelty_check(density, [int(command_idx)], "predict_controls_novelty")
-        image_rgb_u8 = np.asarray(image_rgb_u8)
-        camera = image_rgb_u8.shape != tuple(self.frames_host.shape[1:])
-        point = self.predict_controls(image_rgb_u8, speed_kmh, command_idx)
-        _speed, cmd = self._mc_inputs(camera)
+        point, _speed, cmd = self._controls_tick(image_rgb_u8, speed_kmh, command_idx)
         return point, float(self._novelty_run(cmd, density)[0])
 
     # ---- nearest recorded frames --------------------------------------------------------------------
@@ -822,13 +838,9 @@ class Predictor:
         return index._check_k(k)
 
     def _neighbours_run(self, index, k):
-        """The k-NN launches on this predictor's stream, on the plan the tick just used, into pinned
-        buffers; one synchronise."""
-        eng = self.eng
-        eng.last_plan = eng.plan(self.batch, self.frames_host.size(1), self.frames_host.size(2))
-        with torch.cuda.stream(self.stream):
-            idx, dist = eng.run_knn(index.rows, index.origin, index.W, k, owner=self)
-            self.stream.synchronize()
+        """The k-NN launches after the tick (_after_tick)."""
+        idx, dist = self._after_tick(
+            lambda eng: eng.run_knn(index.rows, index.origin, index.W, k, owner=self))
         return idx.numpy().copy(), dist.numpy().copy()
 
     @torch.no_grad()
@@ -855,7 +867,7 @@ class Predictor:
         if self.batch != 1:
             raise RuntimeError("predict_controls_neighbours is the single-frame control-loop path")
         k = self._neighbours_check(index, k, "predict_controls_neighbours")
-        point = self.predict_controls(np.asarray(image_rgb_u8), speed_kmh, command_idx)
+        point, _speed, _cmd = self._controls_tick(image_rgb_u8, speed_kmh, command_idx)
         idx, dist = self._neighbours_run(index, k)
         return point, idx[0], dist[0]
 
@@ -885,61 +897,27 @@ class Predictor:
         if self.half:
             raise RuntimeError("gradcam: fp32 predictors only (a 16-bit trunk keeps 16-bit feature "
                                "maps)")
-        frames = np.asarray(frames_u8)
-        h, w = self.frames_host.size(1), self.frames_host.size(2)
+        frames, speeds, cmds, camera = self._checked_frames("gradcam", frames_u8, speeds_kmh,
+                                                            commands)
         b = self.batch
-        if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[0] != b or \
-                frames.shape[3] not in (3, 4):
-            raise RuntimeError(f"gradcam: frames must be uint8 [{b},H,W,3] (camera frames: 3 or 4 "
-                               "bytes per pixel)")
-        camera = frames.shape[1:] != (h, w, 3)
-        cmds = self._check_commands(commands)
-        speeds = np.asarray(speeds_kmh, dtype=np.float64)
-        if cmds.shape != (b,) or speeds.shape != (b,):
-            raise RuntimeError(f"gradcam: {b} speeds and commands expected")
         if camera and lnum == 4 and b != 1:
             raise RuntimeError("gradcam: camera-sized frames at layer4 take predict_camera's path, "
                                "which is the single-frame one")
-        eng = self.eng
         if lnum == 4:
             if camera:
                 r = self.predict_camera(frames[0], float(speeds[0]), int(cmds[0]))
                 out = np.asarray([r], dtype=np.float32)
             else:
                 out = self.predict_batch(frames, speeds, cmds)
-            eng = self.eng                                   # (a re-attached model re-initialises)
-            speed, cmd = self._mc_inputs(camera)
-            eng.last_plan = eng.plan(b, h, w)
-            with torch.cuda.stream(self.stream):
-                cam, heat, peak, u8 = eng.run_gradcam(speed, cmd, wts, 4, want_u8, owner=self)
-                self.stream.synchronize()
+            speed, cmd = self._tick_inputs(camera)
+            cam, heat, peak, u8 = self._after_tick(
+                lambda eng: eng.run_gradcam(speed, cmd, wts, 4, want_u8, owner=self))
         else:
-            if self.model.engine() is not self.eng:
-                self.__init__(self.model, b, h, w, self.use_graph, self.half, self.persistent)
-                eng = self.eng
-            if self.model.training:
-                self.model.eval()
-            sal = self._saliency_buffers(tuple(frames.shape))
-            f_np, s_np, dc_np, ds_np, c_np = sal["host_np"]
-            np.copyto(f_np, frames)
-            s_np[...] = np.minimum(speeds / SPEED_NORM_FACTOR, 1.0)
-            dc_np[...] = wts[:3]
-            ds_np[...] = wts[3]
-            c_np[...] = cmds
-            f_dev, s_dev, dc_dev, ds_dev, c_dev = sal["dev_views"]
-            self._order_after_weight_updates()
-            with torch.cuda.stream(self.stream):
-                sal["dev"].copy_(sal["host"], non_blocking=True)
-                _, _, pl = eng.run_forward_frozen_u8(f_dev, s_dev, c_dev, h if camera else None,
-                                                     w if camera else None,
-                                                     out=(sal["ctrl"], sal["spd"]))
+            def launch(eng, sal, pl, dc_dev, ds_dev):
+                _f, s_dev, _dc, _ds, c_dev = sal["dev_views"]
                 eng.run_backward(pl, dc_dev, ds_dev, data_only=True, segments=(0, 5 - lnum))
-                cam, heat, peak, u8 = eng.run_gradcam(s_dev, c_dev, wts, lnum, want_u8, owner=self)
-                sal["out_host"][:4 * b].copy_(sal["out_dev"][:4 * b], non_blocking=True)
-                self.stream.synchronize()
-            o = sal["out_np"]
-            out = np.empty((b, 4), dtype=np.float32)
-            out[:, :3] = o[:3 * b].reshape(b, 3)
-            out[:, 3] = o[3 * b:4 * b] * np.float32(SPEED_NORM_FACTOR)
+                return eng.run_gradcam(s_dev, c_dev, wts, lnum, want_u8, owner=self)
+            out, _o, (cam, heat, peak, u8) = self._frozen_graph_run(frames, speeds, cmds, camera, wts,
+                                                                    launch, 4 * b)
         return (out, (u8 if want_u8 else heat).numpy().copy(), cam.numpy().copy(),
                 peak.numpy().copy())

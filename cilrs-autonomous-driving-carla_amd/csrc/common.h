@@ -723,14 +723,52 @@ __device__ __forceinline__ float dropout_u(const unsigned long long seed, const 
 constexpr int kMcMaxFeat = 2048;          // widest trunk feature vector (ResNet-50 variant)
 constexpr int kMcSharedFloats = 640;      // per frame: a0[128] | hv[256] | pp[256] (mc_pre_kernel)
 constexpr int kMcMaxSamples = 4096, kMcMaxRows = 65536;
-struct McHeadsArgs {
+
+// ---- what follows a tick: the seam of heads_mc, gradcam, feature_moments, novelty, whiten / knn ----
+// Where a batch's pooled features live: stored rows, or (after the persistent launch) the last
+// feature map alone, which the consumer pools in cell order.
+struct FeatureSrc {
+    const float* features; int ld;        // [B][ld] features, or NULL:
+    const float* featmap; int HW;         //   [B][HW][F] last feature map, pooled by the consumer
+};
+// The heads' weights inside a parameter vector (filled by head_weights() in net.hip).
+struct HeadWeights {
     const float* se0_w; const float* se0_b; const float* se3_w; const float* se3_b;
     const float* br_w[kMaxCmd][3]; const float* br_b[kMaxCmd][3];
     const float* sp0_w; const float* sp0_b; const float* sp3_w; const float* sp3_b;
     const float* sp5_w; const float* sp5_b;
     int ncmd, F;
-    const float* pooled; int pooled_ld;   // [B][pooled_ld] features, or NULL:
-    const float* featmap; int HW;         //   [B][HW][F] last feature map, pooled by the pre launch
+};
+#if defined(__HIPCC__)
+// Pooled fp32 feature c of frame b: the stored one, or AdaptiveAvgPool2d(1,1) + Flatten in cell
+// order.  Additions and one division only, and it has to stay so: novelty.hip, knn.hip and
+// kcenter.hip include this header with `#pragma clang fp contract(off)`, mc_heads.hip and
+// gradcam.hip without, so a multiply-add written here would round differently per file.
+__device__ __forceinline__ float pooled_feature(const FeatureSrc& f, const int F, const int b,
+                                                const int c) {
+    if (f.featmap == nullptr) return f.features[(size_t)b * f.ld + c];
+    const float* p = f.featmap + (size_t)b * f.HW * F + c;
+    float s = 0.f;
+    for (int q = 0; q < f.HW; ++q) s += p[(size_t)q * F];
+    return s / (float)f.HW;
+}
+// fixed-order butterfly sum over the 64 lanes of a wave
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+// a command outside 0..ncmd-1 takes branch 0 (torch.gather would raise); which thread raises the
+// sticky status word for it is each kernel's own
+__device__ __forceinline__ int command_branch(const long long* cmd, const int b, const int ncmd) {
+    const long long c = cmd[b];
+    return (c < 0 || c >= ncmd) ? 0 : (int)c;
+}
+#endif
+
+struct McHeadsArgs {
+    HeadWeights hw;
+    FeatureSrc src;
     const float* speed; const long long* cmd;
     int B, S;
     float p; unsigned long long seed;
@@ -747,13 +785,8 @@ int launch_mc_heads(McHeadsArgs& a, float* scratch, hipStream_t s);
 constexpr int kGcMaxC = 2048;             // widest trunk group (layer4 of the ResNet-50 variant)
 constexpr int kGcMaxHW = 4096;            // cells of the coarse map kept in LDS
 struct HeadsGradArgs {
-    const float* se0_w; const float* se0_b; const float* se3_w; const float* se3_b;
-    const float* br_w[kMaxCmd][3]; const float* br_b[kMaxCmd][3];
-    const float* sp0_w; const float* sp0_b; const float* sp3_w; const float* sp3_b;
-    const float* sp5_w; const float* sp5_b;
-    int ncmd, F;
-    const float* pooled; int pooled_ld;   // [B][pooled_ld] features, or NULL:
-    const float* featmap; int HW;         //   [B][HW][F] last feature map, pooled by the kernel
+    HeadWeights hw;
+    FeatureSrc src;
     const float* speed; const long long* cmd;
     float w[4];                           // y = w . (steer, throttle, brake, pred_speed)
     int B;
@@ -773,8 +806,7 @@ int launch_gradcam_map(const GradcamMapArgs& a, hipStream_t s);
 
 // ---- feature-space novelty (novelty.hip; cilrs_feature_moments, cilrs_feature_novelty) ----------
 struct NoveltyMomentsArgs {
-    const float* features; int ld;        // [B][ld] features, or NULL:
-    const float* featmap; int HW;         //   [B][HW][F] last feature map, pooled by the kernel
+    FeatureSrc src;
     const long long* cmd;
     int B, F, NC;
     const float* pivot;                   // [F]
@@ -784,8 +816,7 @@ struct NoveltyMomentsArgs {
 size_t novelty_moments_doubles(int F, int NC);
 int launch_novelty_moments(const NoveltyMomentsArgs& a, hipStream_t s);
 struct NoveltyScoreArgs {
-    const float* features; int ld;        // as above
-    const float* featmap; int HW;
+    FeatureSrc src;
     const long long* cmd;
     int B, F, NC;
     const float* mean;                    // [NC][F]
@@ -798,8 +829,7 @@ size_t novelty_scratch_floats(int F, int batch);
 int launch_novelty_score(NoveltyScoreArgs& a, float* scratch, hipStream_t s);
 // y = tril(W) (v - origin), fp32 [B][F]: the score's first two launches with one fixed origin, y stored
 struct NoveltyWhitenArgs {
-    const float* features; int ld;        // as above
-    const float* featmap; int HW;
+    FeatureSrc src;
     int B, F;
     const float* origin;                  // [F], or NULL: nothing subtracted
     const float* W;                       // [F][F], lower triangle read; NULL: y is not written

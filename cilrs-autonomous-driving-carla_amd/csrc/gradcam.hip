@@ -29,12 +29,6 @@ namespace {
 constexpr int kGcThreads = 1024;
 constexpr int kGcWaves = kGcThreads / 64;
 
-__device__ __forceinline__ float gc_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // y[o] = act(W[o][0..K) . x + b[o]) for o in [0, n): a wave takes four rows at a time so that their
 // loads are in flight together; lanes stride each row in 16-byte pieces, butterfly sum.  K % 4 == 0,
 // n % 4 == 0, x in LDS
@@ -62,7 +56,7 @@ __device__ __forceinline__ void gc_rows(const float* __restrict__ W, const int l
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float v = gc_wave_sum(acc[r]) + bias[o0 + r];
+            const float v = wave_sum(acc[r]) + bias[o0 + r];
             if (lane == 0) y[o0 + r] = relu ? fmaxf(v, 0.f) : v;
         }
     }
@@ -77,7 +71,7 @@ __device__ __forceinline__ void gc_row_256(const float* __restrict__ w, const fl
     acc = fmaf(xv[1], wv[1], acc);
     acc = fmaf(xv[2], wv[2], acc);
     acc = fmaf(xv[3], wv[3], acc);
-    acc = gc_wave_sum(acc) + bias[0];
+    acc = wave_sum(acc) + bias[0];
     if (lane == 0) y[0] = acc;
 }
 
@@ -129,65 +123,54 @@ __global__ __launch_bounds__(kGcThreads) void heads_input_grad_kernel(const Head
     __shared__ __align__(16) float part[4096];                // partial column sums [groups][ncols]
     __shared__ float outv[4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int F = a.F;
-    const long long cmd = a.cmd[b];
-    const bool bad = cmd < 0 || cmd >= a.ncmd;
-    const int k = bad ? 0 : (int)cmd;
-    if (tid == 0 && bad && a.status) a.status[0] = 1;
-    if (a.featmap) {                       // AdaptiveAvgPool2d(1,1) + Flatten, pixel order
-        const float* fm = a.featmap + (size_t)b * a.HW * F;
-        for (int c = tid; c < F; c += kGcThreads) {
-            float s = 0.f;
-            for (int p = 0; p < a.HW; ++p) s += fm[(size_t)p * F + c];
-            comb[c] = s / (float)a.HW;
-        }
-    } else {
-        const float* pv = a.pooled + (size_t)b * a.pooled_ld;
-        for (int c = tid; c < F; c += kGcThreads) comb[c] = pv[c];
-    }
-    if (tid < 128) a0[tid] = fmaxf(fmaf(a.se0_w[tid], a.speed[b], a.se0_b[tid]), 0.f);
+    const HeadWeights& hw = a.hw;
+    const int F = hw.F;
+    const int k = command_branch(a.cmd, b, hw.ncmd);
+    if (tid == 0 && a.status && (a.cmd[b] < 0 || a.cmd[b] >= hw.ncmd)) a.status[0] = 1;
+    for (int c = tid; c < F; c += kGcThreads) comb[c] = pooled_feature(a.src, F, b, c);
+    if (tid < 128) a0[tid] = fmaxf(fmaf(hw.se0_w[tid], a.speed[b], hw.se0_b[tid]), 0.f);
     __syncthreads();
     // forward: f, then h1 and p1 (both read comb), h2 and p2, the four outputs
-    gc_rows(a.se3_w, 128, 128, 128, a.se3_b, a0, comb + F, true, wave, lane);
+    gc_rows(hw.se3_w, 128, 128, 128, hw.se3_b, a0, comb + F, true, wave, lane);
     __syncthreads();
-    gc_rows(a.br_w[k][0], F + 128, F + 128, 256, a.br_b[k][0], comb, act[0], true, wave, lane);
-    gc_rows(a.sp0_w, F, F, 256, a.sp0_b, comb, act[2], true, wave, lane);
+    gc_rows(hw.br_w[k][0], F + 128, F + 128, 256, hw.br_b[k][0], comb, act[0], true, wave, lane);
+    gc_rows(hw.sp0_w, F, F, 256, hw.sp0_b, comb, act[2], true, wave, lane);
     __syncthreads();
-    gc_rows(a.br_w[k][1], 256, 256, 256, a.br_b[k][1], act[0], act[1], true, wave, lane);
-    gc_rows(a.sp3_w, 256, 256, 256, a.sp3_b, act[2], act[3], true, wave, lane);
+    gc_rows(hw.br_w[k][1], 256, 256, 256, hw.br_b[k][1], act[0], act[1], true, wave, lane);
+    gc_rows(hw.sp3_w, 256, 256, 256, hw.sp3_b, act[2], act[3], true, wave, lane);
     __syncthreads();
-    if (wave < 3) gc_row_256(a.br_w[k][2] + wave * 256, a.br_b[k][2] + wave, act[1], outv + wave, lane);
-    else if (wave == 3) gc_row_256(a.sp5_w, a.sp5_b, act[3], outv + 3, lane);
+    if (wave < 3) gc_row_256(hw.br_w[k][2] + wave * 256, hw.br_b[k][2] + wave, act[1], outv + wave, lane);
+    else if (wave == 3) gc_row_256(hw.sp5_w, hw.sp5_b, act[3], outv + 3, lane);
     // backward of y = w . outputs: dh2 = relu'(h2) W_k5^T w[0..2], dp2 = relu'(p2) W_p5^T w[3]
     if (tid >= 256 && tid < 512) {
         const int j = tid - 256;
-        const float* w5 = a.br_w[k][2];
+        const float* w5 = hw.br_w[k][2];
         float s = __fmul_rn(w5[j], a.w[0]);
         s = fmaf(w5[256 + j], a.w[1], s);
         s = fmaf(w5[512 + j], a.w[2], s);
         dv[0][j] = act[1][j] > 0.f ? s : 0.f;
     } else if (tid >= 512 && tid < 768) {
         const int j = tid - 512;
-        dv[2][j] = act[3][j] > 0.f ? __fmul_rn(a.sp5_w[j], a.w[3]) : 0.f;
+        dv[2][j] = act[3][j] > 0.f ? __fmul_rn(hw.sp5_w[j], a.w[3]) : 0.f;
     }
     __syncthreads();
     if (a.out4 && tid < 4) a.out4[(size_t)b * 4 + tid] = outv[tid];
     // dh1 = relu'(h1) W_k3^T dh2
-    int groups = gc_cols_partial(a.br_w[k][1], 256, 256, 256, dv[0], part, tid);
+    int groups = gc_cols_partial(hw.br_w[k][1], 256, 256, 256, dv[0], part, tid);
     __syncthreads();
     if (tid < 256) dv[1][tid] = act[0][tid] > 0.f ? gc_join(part, groups, 256, tid) : 0.f;
     __syncthreads();
     // dp1 = relu'(p1) W_p3^T dp2
-    groups = gc_cols_partial(a.sp3_w, 256, 256, 256, dv[2], part, tid);
+    groups = gc_cols_partial(hw.sp3_w, 256, 256, 256, dv[2], part, tid);
     __syncthreads();
     if (tid < 256) dv[3][tid] = act[2][tid] > 0.f ? gc_join(part, groups, 256, tid) : 0.f;
     __syncthreads();
     // g = W_k0[:, :F]^T dh1 + W_p0^T dp1, the branch first (comb is free now: it holds the first)
-    groups = gc_cols_partial(a.br_w[k][0], F + 128, F, 256, dv[1], part, tid);
+    groups = gc_cols_partial(hw.br_w[k][0], F + 128, F, 256, dv[1], part, tid);
     __syncthreads();
     for (int c = tid; c < F; c += kGcThreads) comb[c] = gc_join(part, groups, F, c);
     __syncthreads();
-    groups = gc_cols_partial(a.sp0_w, F, F, 256, dv[3], part, tid);
+    groups = gc_cols_partial(hw.sp0_w, F, F, 256, dv[3], part, tid);
     __syncthreads();
     float* g = a.g + (size_t)b * F;
     for (int c = tid; c < F; c += kGcThreads) g[c] = __fadd_rn(comb[c], gc_join(part, groups, F, c));
@@ -235,7 +218,7 @@ __global__ __launch_bounds__(kGcThreads) void gradcam_map_kernel(const GradcamMa
         const float* ap = A + (size_t)p * C;
         float acc = 0.f;
         for (int c = lane; c < C; c += 64) acc = fmaf(alpha[c], ap[c], acc);
-        acc = gc_wave_sum(acc);
+        acc = wave_sum(acc);
         if (lane == 0) { cam[p] = acc; coarse[p] = fmaxf(acc, 0.f); }
         m = fmaxf(m, acc);
     }
@@ -271,8 +254,9 @@ __global__ __launch_bounds__(kGcThreads) void gradcam_map_kernel(const GradcamMa
 }  // namespace
 
 int launch_heads_input_grad(const HeadsGradArgs& a, hipStream_t s) {
-    CILRS_CHECK((a.F == 256 || a.F == 512 || a.F == 1024 || a.F == 2048) && a.F <= kMcMaxFeat,
-                "heads_input_grad: feature width %d", a.F);
+    const int F = a.hw.F;
+    CILRS_CHECK((F == 256 || F == 512 || F == 1024 || F == 2048) && F <= kMcMaxFeat,
+                "heads_input_grad: feature width %d", F);
     heads_input_grad_kernel<<<a.B, kGcThreads, 0, s>>>(a);
     CILRS_LAUNCH_CHECK();
     return 0;

@@ -13,13 +13,6 @@ constexpr int kKcMaxGrid = 1024;        // workgroups of 4 waves: 16 waves on ea
 constexpr int kKcCentres = 8;           // centres (queries) per LDS chunk
 constexpr int kKcMaxN = 1 << 24, kKcMaxD = 2048, kKcMaxM = 65536;
 
-// fixed-order butterfly sum over the 64 lanes of a wave (the order of cilrs_feature_novelty)
-__device__ __forceinline__ float kc_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // a lane's quads of one row: columns 256 q + 4 lane .. + 3 where they are below D, else zeros
 // (a zero difference leaves the chain as it is)
 template <int NQ>
@@ -42,7 +35,7 @@ __device__ __forceinline__ float kc_dist(const f32x4 (&x)[NQ], const f32x4 (&c)[
             const float t = x[q][e] - c[q][e];
             a = fmaf(t, t, a);
         }
-    return kc_wave_sum(a);
+    return wave_sum(a);          // the order of cilrs_feature_novelty
 }
 
 // stage up to kKcCentres rows of C (columns below D, zeros above) in LDS as cs[m][NQ * 256]

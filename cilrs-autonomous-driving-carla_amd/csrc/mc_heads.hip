@@ -36,46 +36,25 @@ constexpr int kMcLd = 260;             // LDS row pitch in floats (256 + 4: rows
 constexpr int kMcOutOff = 2 * kMcRows * kMcLd;
 constexpr int kMcLdsBytes = (kMcOutOff + kMcRows * 4) * (int)sizeof(float);
 
-__device__ __forceinline__ int mc_branch(const McHeadsArgs& a, const int b) {
-    const long long c = a.cmd[b];
-    return (c < 0 || c >= a.ncmd) ? 0 : (int)c;
-}
-
-// fixed-order butterfly sum over the 64 lanes of a wave
-__device__ __forceinline__ float mc_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 __global__ __launch_bounds__(512) void mc_pre_kernel(const McHeadsArgs a) {
     __shared__ float v[kMcMaxFeat];
     const int b = blockIdx.x >> 6, part = blockIdx.x & 63;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int F = a.F;
-    const int k = mc_branch(a, b);
-    if (a.featmap) {                   // AdaptiveAvgPool2d(1,1) + Flatten, pixel order
-        const float* fm = a.featmap + (size_t)b * a.HW * F;
-        for (int c = tid; c < F; c += 512) {
-            float s = 0.f;
-            for (int p = 0; p < a.HW; ++p) s += fm[(size_t)p * F + c];
-            v[c] = s / (float)a.HW;
-        }
-    } else {
-        const float* pv = a.pooled + (size_t)b * a.pooled_ld;
-        for (int c = tid; c < F; c += 512) v[c] = pv[c];
-    }
+    const HeadWeights& hw = a.hw;
+    const int F = hw.F;
+    const int k = command_branch(a.cmd, b, hw.ncmd);
+    for (int c = tid; c < F; c += 512) v[c] = pooled_feature(a.src, F, b, c);
     float* sh = a.shared + (size_t)b * kMcSharedFloats;
     if (part == 0) {
-        if (tid < 128) sh[tid] = fmaxf(fmaf(a.se0_w[tid], a.speed[b], a.se0_b[tid]), 0.f);
+        if (tid < 128) sh[tid] = fmaxf(fmaf(hw.se0_w[tid], a.speed[b], hw.se0_b[tid]), 0.f);
         // a command outside 0..ncmd-1: torch.gather would raise; branch 0 is used (sticky word)
-        if (tid == 0 && a.status && (a.cmd[b] < 0 || a.cmd[b] >= a.ncmd)) a.status[0] = 1;
+        if (tid == 0 && a.status && (a.cmd[b] < 0 || a.cmd[b] >= hw.ncmd)) a.status[0] = 1;
     }
     __syncthreads();
     const int slot = part * 8 + wave;            // 0..255 hv, 256..511 pp
     const int o = slot & 255;
     const bool sp = slot >= 256;
-    const float* w = sp ? a.sp0_w + (size_t)o * F : a.br_w[k][0] + (size_t)o * (F + 128);
+    const float* w = sp ? hw.sp0_w + (size_t)o * F : hw.br_w[k][0] + (size_t)o * (F + 128);
     float acc = 0.f;
     for (int q = lane; q < (F >> 2); q += 64) {
         const f32x4 wv = *reinterpret_cast<const f32x4*>(w + q * 4);
@@ -85,10 +64,10 @@ __global__ __launch_bounds__(512) void mc_pre_kernel(const McHeadsArgs a) {
         acc = fmaf(xv[2], wv[2], acc);
         acc = fmaf(xv[3], wv[3], acc);
     }
-    acc = mc_wave_sum(acc);
+    acc = wave_sum(acc);
     if (lane == 0) {
-        if (sp) sh[384 + o] = fmaxf(acc + a.sp0_b[o], 0.f);
-        else sh[128 + o] = acc + a.br_b[k][0][o];
+        if (sp) sh[384 + o] = fmaxf(acc + hw.sp0_b[o], 0.f);
+        else sh[128 + o] = acc + hw.br_b[k][0][o];
     }
 }
 
@@ -174,12 +153,13 @@ __global__ __launch_bounds__(512) void mc_sample_kernel(const McHeadsArgs a) {
     const int b = blockIdx.x / a.nchunks, chain = blockIdx.z;
     const int s0 = (blockIdx.x - b * a.nchunks) * kMcRows;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int S = a.S, F = a.F, NC = a.ncmd;
+    const HeadWeights& hw = a.hw;
+    const int S = a.S, F = hw.F, NC = hw.ncmd;
     const unsigned row0 = (unsigned)(b * S + s0);
     const float p = a.p;
     const unsigned long long seed = a.seed;
     const float* sh = a.shared + (size_t)b * kMcSharedFloats;
-    const int k = mc_branch(a, b);
+    const int k = command_branch(a.cmd, b, hw.ncmd);
     const float* wl;                           // the chain's last Linear
     const float* bl;
     int nout;
@@ -188,25 +168,25 @@ __global__ __launch_bounds__(512) void mc_sample_kernel(const McHeadsArgs a) {
         mc_mask_rows(sh, X, 128, 0, row0, p, seed, tid);
         __syncthreads();
         if (wave < 4) {
-            const f32x16 acc = mc_tile(X, a.se3_w, 128, 128, wave * 32, lane);
-            mc_store_tile(acc, Y, a.se3_b, wave * 32, lane, 128, -1, row0, p, seed);
+            const f32x16 acc = mc_tile(X, hw.se3_w, 128, 128, wave * 32, lane);
+            mc_store_tile(acc, Y, hw.se3_b, wave * 32, lane, 128, -1, row0, p, seed);
         }
         __syncthreads();
         // h1 = drop_{1+2k}(relu(W_k0 [v | f] + b)): the visual half and the bias come from hv
-        const f32x16 acc1 = mc_tile(Y, a.br_w[k][0] + F, F + 128, 128, wave * 32, lane);
+        const f32x16 acc1 = mc_tile(Y, hw.br_w[k][0] + F, F + 128, 128, wave * 32, lane);
         mc_store_tile(acc1, X, sh + 128, wave * 32, lane, 256, 1 + 2 * k, row0, p, seed);
         __syncthreads();
         // h2 = drop_{2+2k}(relu(W_k3 h1 + b))
-        const f32x16 acc2 = mc_tile(X, a.br_w[k][1], 256, 256, wave * 32, lane);
-        mc_store_tile(acc2, Y, a.br_b[k][1], wave * 32, lane, 256, 2 + 2 * k, row0, p, seed);
-        wl = a.br_w[k][2]; bl = a.br_b[k][2]; nout = 3;
+        const f32x16 acc2 = mc_tile(X, hw.br_w[k][1], 256, 256, wave * 32, lane);
+        mc_store_tile(acc2, Y, hw.br_b[k][1], wave * 32, lane, 256, 2 + 2 * k, row0, p, seed);
+        wl = hw.br_w[k][2]; bl = hw.br_b[k][2]; nout = 3;
     } else {
         // p1 = drop_{2NC+1}(relu(W_p0 v + b)); p2 = relu(W_p3 p1 + b)
         mc_mask_rows(sh + 384, X, 256, 2 * NC + 1, row0, p, seed, tid);
         __syncthreads();
-        const f32x16 acc = mc_tile(X, a.sp3_w, 256, 256, wave * 32, lane);
-        mc_store_tile(acc, Y, a.sp3_b, wave * 32, lane, 256, -1, row0, p, seed);
-        wl = a.sp5_w; bl = a.sp5_b; nout = 1;
+        const f32x16 acc = mc_tile(X, hw.sp3_w, 256, 256, wave * 32, lane);
+        mc_store_tile(acc, Y, hw.sp3_b, wave * 32, lane, 256, -1, row0, p, seed);
+        wl = hw.sp5_w; bl = hw.sp5_b; nout = 1;
     }
     __syncthreads();
     // last Linear (3 or 1 outputs over 256 inputs): a wave per row, a lane per input quad
@@ -219,7 +199,7 @@ __global__ __launch_bounds__(512) void mc_sample_kernel(const McHeadsArgs a) {
             acc = fmaf(xv[1], wv[1], acc);
             acc = fmaf(xv[2], wv[2], acc);
             acc = fmaf(xv[3], wv[3], acc);
-            acc = mc_wave_sum(acc) + bl[o];
+            acc = wave_sum(acc) + bl[o];
             if (lane == 0) {
                 outv[row * 4 + col0 + o] = acc;
                 if (s0 + row < S) {
@@ -251,7 +231,8 @@ size_t mc_heads_scratch_floats(int batch, int samples) {
 }
 
 int launch_mc_heads(McHeadsArgs& a, float* scratch, hipStream_t s) {
-    CILRS_CHECK(a.F % 4 == 0 && a.F >= 4 && a.F <= kMcMaxFeat, "heads_mc: feature width %d", a.F);
+    CILRS_CHECK(a.hw.F % 4 == 0 && a.hw.F >= 4 && a.hw.F <= kMcMaxFeat, "heads_mc: feature width %d",
+                a.hw.F);
     a.shared = scratch;
     a.samples = scratch + (size_t)a.B * kMcSharedFloats;
     if (set_max_dynamic_lds(reinterpret_cast<const void*>(mc_sample_kernel), kMcLdsBytes)) return 1;

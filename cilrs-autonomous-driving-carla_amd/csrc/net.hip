@@ -452,6 +452,9 @@ int clear_status_once(cilrs_net* net, void* workspace, hipStream_t s) {
     net->status_cleared_for = workspace;
     return 0;
 }
+static int* status_words(const cilrs_net* net, const cilrs_buffers* bufs) {
+    return reinterpret_cast<int*>(reinterpret_cast<char*>(bufs->workspace) + net->status_b);
+}
 
 // The two writers of cilrs_net::last: every forward calls fwd_begin before its first launch (from
 // there on the workspace no longer holds the previous forward) and fwd_commit at its successful end.
@@ -1717,7 +1720,7 @@ static int heads_fwd(cilrs_net* net, const cilrs_buffers* bufs, const float* fea
     float* ws = reinterpret_cast<float*>(bufs->workspace);
     const float* P = bufs->params;
     const int B = net->B;
-    int* status = reinterpret_cast<int*>(reinterpret_cast<char*>(bufs->workspace) + net->status_b);
+    int* status = status_words(net, bufs);
     const int featw = A.feat, comb = A.feat + 128;
     if (!graph && B <= kHeadsSmallMaxB && A.variant == 0) {
         // ---- inference at control-loop batch sizes: 4 launches, commanded branch only ----
@@ -2369,7 +2372,7 @@ static int b1_launch(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* f
     a.frame = frame; a.speed = speed; a.cmd = reinterpret_cast<const long long*>(command);
     a.controls = controls; a.pred_speed = pred_speed;
     a.sync = reinterpret_cast<int*>(ws + net->b1_sync);
-    a.status = reinterpret_cast<int*>(reinterpret_cast<char*>(bufs->workspace) + net->status_b);
+    a.status = status_words(net, bufs);
     // CILRS_B1_STAMPS=1: block 0 records its clock at every stage (cilrs_net_b1_stage_us)
     static const int stamps_on = getenv("CILRS_B1_STAMPS") ? atoi(getenv("CILRS_B1_STAMPS")) : 0;
     a.stamps = stamps_on ? reinterpret_cast<long long*>(ws + net->b1_stamps) : nullptr;
@@ -2577,26 +2580,34 @@ int cilrs_net_forward_u8_bf16_graph(cilrs_net* net, const cilrs_buffers* bufs,
 
 // The features the plan's last eval-mode forward left for the tick-following entries (heads_mc,
 // gradcam, feature_moments, novelty): pooled in `combined`, or the last feature map alone.
-static void plan_features(const cilrs_net* net, const cilrs_buffers* bufs, const float** features,
-                          int* ld, const float** featmap, int* hw) {
+static FeatureSrc plan_features(const cilrs_net* net, const cilrs_buffers* bufs) {
     const Arch& A = *net->A;
     const float* ws = reinterpret_cast<const float*>(bufs->workspace);
-    *features = nullptr; *featmap = nullptr; *ld = 0; *hw = 0;
     if (net->last.featmap_only()) {
-        *featmap = ws + net->cg[A.blocks.back().conv3 >= 0 ? A.blocks.back().conv3
-                                                           : A.blocks.back().conv2].z;
-        *hw = net->featHW;
-    } else {
-        *features = ws + net->combined; *ld = A.feat + 128;
+        const BlockT& blk = A.blocks.back();
+        return {nullptr, 0, ws + net->cg[blk.conv3 >= 0 ? blk.conv3 : blk.conv2].z, net->featHW};
     }
+    return {ws + net->combined, A.feat + 128, nullptr, 0};
 }
 static int plan_features_checked(const char* who, const cilrs_net* net, const cilrs_buffers* bufs,
-                                 const float** features, int* ld, const float** featmap, int* hw) {
+                                 FeatureSrc* src) {
     CILRS_CHECK(!net->last.no_features(), "%s: no forward on this plan yet", who);
     CILRS_CHECK(!net->last.train_features(), "%s: the plan's last forward ran in train mode (batch "
                 "statistics); run an eval-mode forward first", who);
-    plan_features(net, bufs, features, ld, featmap, hw);
+    *src = plan_features(net, bufs);
     return 0;
+}
+
+// the heads' weights inside the parameter vector P (mc_heads.hip, gradcam.hip)
+static HeadWeights head_weights(const Arch& A, const float* P) {
+    HeadWeights h{};
+    h.se0_w = P + A.se0.w; h.se0_b = P + A.se0.b; h.se3_w = P + A.se3.w; h.se3_b = P + A.se3.b;
+    for (int k = 0; k < A.ncmd; ++k)
+        for (int l = 0; l < 3; ++l) { h.br_w[k][l] = P + A.br[k][l].w; h.br_b[k][l] = P + A.br[k][l].b; }
+    h.sp0_w = P + A.sp0.w; h.sp0_b = P + A.sp0.b; h.sp3_w = P + A.sp3.w; h.sp3_b = P + A.sp3.b;
+    h.sp5_w = P + A.sp5.w; h.sp5_b = P + A.sp5.b;
+    h.ncmd = A.ncmd; h.F = A.feat;
+    return h;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2616,16 +2627,6 @@ static int mc_check(const char* who, int batch, int samples, float p, const floa
     return 0;
 }
 
-static void mc_fill(McHeadsArgs& a, const Arch& A, const float* P) {
-    memset(&a, 0, sizeof(a));
-    a.se0_w = P + A.se0.w; a.se0_b = P + A.se0.b; a.se3_w = P + A.se3.w; a.se3_b = P + A.se3.b;
-    for (int k = 0; k < A.ncmd; ++k)
-        for (int l = 0; l < 3; ++l) { a.br_w[k][l] = P + A.br[k][l].w; a.br_b[k][l] = P + A.br[k][l].b; }
-    a.sp0_w = P + A.sp0.w; a.sp0_b = P + A.sp0.b; a.sp3_w = P + A.sp3.w; a.sp3_b = P + A.sp3.b;
-    a.sp5_w = P + A.sp5.w; a.sp5_b = P + A.sp5.b;
-    a.ncmd = A.ncmd; a.F = A.feat;
-}
-
 size_t cilrs_heads_mc_scratch_floats(int variant, int batch, int samples) {
     if (!variant_ok(variant) || batch < 1 || samples < 1) return 0;
     return mc_heads_scratch_floats(batch, samples);
@@ -2641,9 +2642,9 @@ int cilrs_heads_mc(int variant, const float* params, const float* pooled, int po
     const Arch& A = arch(variant);
     CILRS_CHECK(pooled_ld >= A.feat, "heads_mc: pooled_ld %d below the %d features", pooled_ld, A.feat);
     CILRS_CHECK(((uintptr_t)params & 15) == 0, "heads_mc: params must be 16-byte aligned");
-    McHeadsArgs a;
-    mc_fill(a, A, params);
-    a.pooled = pooled; a.pooled_ld = pooled_ld;
+    McHeadsArgs a{};
+    a.hw = head_weights(A, params);
+    a.src = {pooled, pooled_ld, nullptr, 0};
     a.speed = speed; a.cmd = reinterpret_cast<const long long*>(command);
     a.B = batch; a.S = samples; a.p = p; a.seed = seed;
     a.mean = mean; a.stdv = std; a.samples_out = samples_out; a.status = status;
@@ -2657,14 +2658,13 @@ int cilrs_net_heads_mc(cilrs_net* net, const cilrs_buffers* bufs, const float* s
     if (check_bufs(net, bufs, false)) return 1;
     CILRS_CHECK(speed && command && mean && std, "net_heads_mc: NULL tensor");
     if (mc_check("net_heads_mc", net->B, samples, p, scratch, scratch_floats)) return 1;
-    McHeadsArgs a;
-    mc_fill(a, *net->A, bufs->params);
-    if (plan_features_checked("net_heads_mc", net, bufs, &a.pooled, &a.pooled_ld, &a.featmap, &a.HW))
-        return 1;
+    McHeadsArgs a{};
+    a.hw = head_weights(*net->A, bufs->params);
+    if (plan_features_checked("net_heads_mc", net, bufs, &a.src)) return 1;
     a.speed = speed; a.cmd = reinterpret_cast<const long long*>(command);
     a.B = net->B; a.S = samples; a.p = p; a.seed = seed;
     a.mean = mean; a.stdv = std; a.samples_out = samples_out;
-    a.status = reinterpret_cast<int*>(reinterpret_cast<char*>(bufs->workspace) + net->status_b);
+    a.status = status_words(net, bufs);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     RUN(net, "heads_mc", 2.0 * net->B * samples * 180480.0, 0.0, s, launch_mc_heads(a, scratch, s));
     return 0;
@@ -2673,16 +2673,6 @@ int cilrs_net_heads_mc(cilrs_net* net, const cilrs_buffers* bufs, const float* s
 // ------------------------------------------------------------------------------------------------
 // Grad-CAM (gradcam.hip)
 // ------------------------------------------------------------------------------------------------
-static void hg_fill(HeadsGradArgs& a, const Arch& A, const float* P) {
-    memset(&a, 0, sizeof(a));
-    a.se0_w = P + A.se0.w; a.se0_b = P + A.se0.b; a.se3_w = P + A.se3.w; a.se3_b = P + A.se3.b;
-    for (int k = 0; k < A.ncmd; ++k)
-        for (int l = 0; l < 3; ++l) { a.br_w[k][l] = P + A.br[k][l].w; a.br_b[k][l] = P + A.br[k][l].b; }
-    a.sp0_w = P + A.sp0.w; a.sp0_b = P + A.sp0.b; a.sp3_w = P + A.sp3.w; a.sp3_b = P + A.sp3.b;
-    a.sp5_w = P + A.sp5.w; a.sp5_b = P + A.sp5.b;
-    a.ncmd = A.ncmd; a.F = A.feat;
-}
-
 static int gc_weights(const char* who, const float* weights4, float* w) {
     CILRS_CHECK(weights4 != nullptr, "%s: NULL tensor (weights4)", who);
     for (int i = 0; i < 4; ++i) {
@@ -2706,10 +2696,10 @@ int cilrs_heads_input_grad(int variant, const float* params, const float* pooled
                             pooled_ld, A.feat);
     else CILRS_CHECK(hw >= 1, "heads_input_grad: feature map of %d cells", hw);
     CILRS_CHECK(((uintptr_t)params & 15) == 0, "heads_input_grad: params must be 16-byte aligned");
-    HeadsGradArgs a;
-    hg_fill(a, A, params);
+    HeadsGradArgs a{};
+    a.hw = head_weights(A, params);
     if (gc_weights("heads_input_grad", weights4, a.w)) return 1;
-    a.pooled = pooled; a.pooled_ld = pooled_ld; a.featmap = featmap; a.HW = hw;
+    a.src = {pooled, pooled_ld, featmap, hw};
     a.speed = speed; a.cmd = reinterpret_cast<const long long*>(command);
     a.B = batch; a.g = g; a.out4 = out4; a.status = status;
     return launch_heads_input_grad(a, reinterpret_cast<hipStream_t>(stream));
@@ -2763,8 +2753,8 @@ int cilrs_net_gradcam(cilrs_net* net, const cilrs_buffers* bufs, const float* sp
     const size_t need = (size_t)net->B * (A.feat + 4);
     CILRS_CHECK(scratch != nullptr && scratch_floats >= need,
                 "net_gradcam: scratch of %zu floats, %zu needed", scratch_floats, need);
-    HeadsGradArgs ha;
-    hg_fill(ha, A, bufs->params);
+    HeadsGradArgs ha{};
+    ha.hw = head_weights(A, bufs->params);
     if (gc_weights("net_gradcam", weights4, ha.w)) return 1;
     CILRS_CHECK(!net->bf16_train, "net_gradcam: fp32 plans only (a CILRS_PLAN_BF16_TRAIN plan keeps "
                 "16-bit feature maps)");
@@ -2786,10 +2776,10 @@ int cilrs_net_gradcam(cilrs_net* net, const cilrs_buffers* bufs, const float* sp
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (layer == 4) {
         // the fast path: average pooling sits on layer4, so dA = (dy / d pooled) / (h * w)
-        plan_features(net, bufs, &ha.pooled, &ha.pooled_ld, &ha.featmap, &ha.HW);
+        ha.src = plan_features(net, bufs);
         ha.speed = speed; ha.cmd = reinterpret_cast<const long long*>(command);
         ha.B = net->B; ha.g = scratch; ha.out4 = scratch + (size_t)net->B * A.feat;
-        ha.status = reinterpret_cast<int*>(reinterpret_cast<char*>(bufs->workspace) + net->status_b);
+        ha.status = status_words(net, bufs);
         ma.g = scratch;
         RUN(net, "gradcam", 4.0 * net->B * 180480.0, 0.0, s, launch_heads_input_grad(ha, s));
     } else {
@@ -2846,7 +2836,7 @@ int cilrs_feature_moments(const float* features, int ld, const float* featmap, i
     CILRS_CHECK(pivot && table, "feature_moments: NULL tensor");
     if (nov_check("feature_moments", features, ld, featmap, hw, command, batch, F, NC)) return 1;
     NoveltyMomentsArgs a;
-    a.features = features; a.ld = ld; a.featmap = featmap; a.HW = hw;
+    a.src = {features, ld, featmap, hw};
     a.cmd = reinterpret_cast<const long long*>(command);
     a.B = batch; a.F = F; a.NC = NC; a.pivot = pivot; a.table = table; a.status = status;
     return launch_novelty_moments(a, reinterpret_cast<hipStream_t>(stream));
@@ -2864,7 +2854,7 @@ int cilrs_feature_novelty(const float* features, int ld, const float* featmap, i
     if (nov_check("feature_novelty", features, ld, featmap, hw, command, batch, F, NC)) return 1;
     if (nov_score_check("feature_novelty", mean, W, d2, scratch, scratch_floats, F, batch)) return 1;
     NoveltyScoreArgs a;
-    a.features = features; a.ld = ld; a.featmap = featmap; a.HW = hw;
+    a.src = {features, ld, featmap, hw};
     a.cmd = reinterpret_cast<const long long*>(command);
     a.B = batch; a.F = F; a.NC = NC; a.mean = mean; a.W = W; a.d2 = d2; a.status = status;
     return launch_novelty_score(a, scratch, reinterpret_cast<hipStream_t>(stream));
@@ -2875,13 +2865,12 @@ int cilrs_net_feature_moments(cilrs_net* net, const cilrs_buffers* bufs, const i
     if (check_bufs(net, bufs, false)) return 1;
     CILRS_CHECK(command && pivot && table, "net_feature_moments: NULL tensor");
     NoveltyMomentsArgs a;
-    if (plan_features_checked("net_feature_moments", net, bufs, &a.features, &a.ld, &a.featmap, &a.HW))
-        return 1;
+    if (plan_features_checked("net_feature_moments", net, bufs, &a.src)) return 1;
     const Arch& A = *net->A;
     CILRS_CHECK(net->B <= kNovMaxBatch, "net_feature_moments: batch %d above %d", net->B, kNovMaxBatch);
     a.cmd = reinterpret_cast<const long long*>(command);
     a.B = net->B; a.F = A.feat; a.NC = A.ncmd; a.pivot = pivot; a.table = table;
-    a.status = reinterpret_cast<int*>(reinterpret_cast<char*>(bufs->workspace) + net->status_b);
+    a.status = status_words(net, bufs);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     RUN(net, "feature_moments", (double)net->B * A.feat * (A.feat + 1), 0.0, s,
         launch_novelty_moments(a, s));
@@ -2897,10 +2886,10 @@ int cilrs_net_novelty(cilrs_net* net, const cilrs_buffers* bufs, const int64_t* 
     CILRS_CHECK(net->B <= kNovMaxBatch, "net_novelty: batch %d above %d", net->B, kNovMaxBatch);
     if (nov_score_check("net_novelty", mean, W, d2, scratch, scratch_floats, A.feat, net->B)) return 1;
     NoveltyScoreArgs a;
-    if (plan_features_checked("net_novelty", net, bufs, &a.features, &a.ld, &a.featmap, &a.HW)) return 1;
+    if (plan_features_checked("net_novelty", net, bufs, &a.src)) return 1;
     a.cmd = reinterpret_cast<const long long*>(command);
     a.B = net->B; a.F = A.feat; a.NC = A.ncmd; a.mean = mean; a.W = W; a.d2 = d2;
-    a.status = reinterpret_cast<int*>(reinterpret_cast<char*>(bufs->workspace) + net->status_b);
+    a.status = status_words(net, bufs);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     RUN(net, "novelty", (double)net->B * A.feat * (A.feat + 1), 0.0, s,
         launch_novelty_score(a, scratch, s));
@@ -2925,7 +2914,7 @@ int cilrs_feature_whiten(const float* features, int ld, int batch, int F, const 
                 (size_t)batch * F);
     CILRS_CHECK(((uintptr_t)W & 15) == 0 && ((uintptr_t)scratch & 15) == 0,
                 "feature_whiten: W and scratch must be 16-byte aligned");
-    const NoveltyWhitenArgs a{features, ld, nullptr, 0, batch, F, origin, W, scratch, y};
+    const NoveltyWhitenArgs a{{features, ld, nullptr, 0}, batch, F, origin, W, scratch, y};
     return launch_novelty_whiten(a, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -2956,7 +2945,7 @@ int cilrs_net_knn(cilrs_net* net, const cilrs_buffers* bufs, const float* X, lon
               reinterpret_cast<char*>(scratch) + 2 * rows};
     if (knn_check("net_knn", k, scratch_bytes - 2 * rows)) return 1;
     NoveltyWhitenArgs a;
-    if (plan_features_checked("net_knn", net, bufs, &a.features, &a.ld, &a.featmap, &a.HW)) return 1;
+    if (plan_features_checked("net_knn", net, bufs, &a.src)) return 1;
     a.B = B; a.F = F; a.origin = origin; a.W = W; a.u = u; a.y = u + (size_t)B * F;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     RUN(net, "knn_features", W ? (double)B * F * (F + 1) : 0.0, 0.0, s, launch_novelty_whiten(a, s));

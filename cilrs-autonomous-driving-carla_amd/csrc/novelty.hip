@@ -9,7 +9,7 @@
 // value in the table: two updates of 2 + 3 rows are bit for bit one update of 5.  The diagonal tiles
 // carry the per-command sums of their 64 columns along, tile (0, 0) the counts and the status word.
 // No atomics, no hand-off between workgroups.  Where the source is a feature map every workgroup
-// pools its own 128 columns (cell order, as mc_pre_kernel does).
+// pools its own 128 columns (pooled_feature in common.h, as every consumer of a tick's features).
 //
 // Score: three launches.
 //   nov_u_kernel     u[b][c] = v[b][c] - mean[k_b][c] into the caller's scratch (pooling a feature
@@ -38,22 +38,6 @@ constexpr int kNovRows = 32;           // rows staged per pass of the moment ker
 constexpr int kNovFrames = 4;          // frames per LDS chunk of the triangular GEMV
 constexpr int kNovWgRows = 8;          // rows of W per workgroup (two per wave)
 constexpr int kNovQuads = kMcMaxFeat / 256;   // float4 per lane and row at the widest trunk
-
-__device__ __forceinline__ int nov_cmd(const long long* cmd, const int b, const int nc) {
-    const long long c = cmd[b];
-    return (c < 0 || c >= nc) ? 0 : (int)c;
-}
-
-// pooled fp32 feature c of frame b: the stored one, or AdaptiveAvgPool2d(1,1) in cell order
-__device__ __forceinline__ float nov_feature(const float* __restrict__ feat, const int ld,
-                                             const float* __restrict__ fm, const int HW, const int F,
-                                             const int b, const int c) {
-    if (fm == nullptr) return feat[(size_t)b * ld + c];
-    const float* p = fm + (size_t)b * HW * F + c;
-    float s = 0.f;
-    for (int q = 0; q < HW; ++q) s += p[(size_t)q * F];
-    return s / (float)HW;
-}
 
 __global__ __launch_bounds__(256) void nov_moments_kernel(const NoveltyMomentsArgs a) {
     __shared__ double xi[kNovRows][kNovTile];
@@ -102,11 +86,11 @@ __global__ __launch_bounds__(256) void nov_moments_kernel(const NoveltyMomentsAr
         for (int e = tid; e < nb * 2 * kNovTile; e += 256) {
             const int b = e >> 7, c = e & 127;
             const int col = c < kNovTile ? i0 + c : j0 + c - kNovTile;
-            const float v = nov_feature(a.features, a.ld, a.featmap, a.HW, F, b0 + b, col);
+            const float v = pooled_feature(a.src, F, b0 + b, col);
             const double x = (double)v - (double)a.pivot[col];
             if (c < kNovTile) xi[b][c] = x; else xj[b][c - kNovTile] = x;
         }
-        if (tid < nb) kb[tid] = nov_cmd(a.cmd, b0 + tid, NC);
+        if (tid < nb) kb[tid] = command_branch(a.cmd, b0 + tid, NC);
         __syncthreads();
         for (int b = 0; b < nb; ++b) {
             double vi[4], vj[4];
@@ -150,13 +134,6 @@ __global__ __launch_bounds__(256) void nov_moments_kernel(const NoveltyMomentsAr
     }
 }
 
-// fixed-order butterfly sum over the 64 lanes of a wave
-__device__ __forceinline__ float nov_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // row i of W as a wave holds it: columns 256 q + 4 lane + e; zero where j > i (never loaded)
 __device__ __forceinline__ void nov_load_w(const float* __restrict__ W, const int F, const int i,
                                            const int lane, f32x4 (&w)[kNovQuads]) {
@@ -193,7 +170,7 @@ __device__ __forceinline__ float nov_row_dot(const f32x4 (&w)[kNovQuads], const 
             acc = fmaf(w[q][3], uv[3], acc);
         }
     }
-    return nov_wave_sum(acc);
+    return wave_sum(acc);
 }
 
 // stage frames b0 .. b0 + nb - 1 of u [B][F] in LDS
@@ -209,8 +186,8 @@ __device__ __forceinline__ void nov_stage_u(float (*us)[kMcMaxFeat], const float
 __global__ __launch_bounds__(256) void nov_u_kernel(const NoveltyScoreArgs a) {
     const int parts = a.F >> 8;
     const int b = blockIdx.x / parts, c = (blockIdx.x - b * parts) * 256 + threadIdx.x;
-    const int k = nov_cmd(a.cmd, b, a.NC);
-    const float v = nov_feature(a.features, a.ld, a.featmap, a.HW, a.F, b, c);
+    const int k = command_branch(a.cmd, b, a.NC);
+    const float v = pooled_feature(a.src, a.F, b, c);
     a.u[(size_t)b * a.F + c] = v - a.mean[(size_t)k * a.F + c];
     if (c == 0 && a.status && (a.cmd[b] < 0 || a.cmd[b] >= a.NC)) a.status[0] = 1;
 }
@@ -245,7 +222,7 @@ __global__ __launch_bounds__(256) void nov_gemv_kernel(const NoveltyScoreArgs a)
 __global__ __launch_bounds__(256) void nov_u0_kernel(const NoveltyWhitenArgs a) {
     const int parts = a.F >> 8;
     const int b = blockIdx.x / parts, c = (blockIdx.x - b * parts) * 256 + threadIdx.x;
-    const float v = nov_feature(a.features, a.ld, a.featmap, a.HW, a.F, b, c);
+    const float v = pooled_feature(a.src, a.F, b, c);
     a.u[(size_t)b * a.F + c] = a.origin ? v - a.origin[c] : v;
 }
 

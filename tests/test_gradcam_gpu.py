@@ -737,7 +737,7 @@ def _rederive(pred, layer, w, camera=False):
     if layer < 4:
         dA_d = ws[po.da_off:po.da_off + n].view(po.B, po.h, po.w, po.C).clone()
         return tuple(t.cpu().numpy() for t in eng.run_gradcam_map(A_d, H, W, dact=dA_d))
-    speed, cmd = pred._mc_inputs(camera)
+    speed, cmd = pred._tick_inputs(camera)
     speed_d, cmd_d = speed.cuda(), cmd.cuda()
     if pred.persistent and pred.degraded_ticks_left == 0:
         g, _o = eng.run_heads_input_grad(speed_d, cmd_d, w, featmap=A_d.view(po.B, po.h * po.w, po.C))

@@ -32,6 +32,7 @@ import _knn as KN
 import cilrs_oracle as O
 import test_kcenter_gpu as TK
 import test_mc_dropout_gpu as TM
+import test_novelty_gpu as TN
 
 pytestmark = pytest.mark.gpu
 
@@ -429,6 +430,68 @@ def test_whiten_refusals_launch_nothing():
     lib = L.lib()
     for F_, B_ in ((500, 3), (512, 0), (512, -1), (2048, 65537)):
         assert lib.cilrs_feature_whiten_scratch_floats(F_, B_) == 0
+
+
+# ---- plan level --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(TN.PLAN_CASES))
+def test_plan_level_after_each_eval_realisation(name):
+    """cilrs_net_knn takes the tick's features exactly as the other plan-level entries do:
+    `combined`, or after the persistent launch the cell-order average of the last feature map.  Its
+    (idx, dist) equal, bit for bit, cilrs_knn of those features uploaded as queries -- after
+    cilrs_feature_whiten of them when tables are given."""
+    B, H, W, fwd, _source_name = TN.PLAN_CASES[name]
+    m, _orc = TM._models50() if name == "resnet50" else TM._pair()
+    F, NC = (2048, 4) if name == "resnet50" else (512, 4)
+    N, K = 40, 8
+    eng = m.engine()
+    _img, spd, cmd, _t, u8 = O.synthetic_batch(B, seed=77, h=H, w=W)
+    u8_d, spd_d, cmd_d = torch.from_numpy(u8).cuda(), spd.cuda(), cmd.cuda()
+    ctrl, ps = fwd(eng, u8_d, spd_d, cmd_d)
+    torch.cuda.synchronize()
+    pl = eng.last_plan
+    eng.check_status()
+    before = (ctrl.clone(), ps.clone())
+    v = np.ascontiguousarray(TN._plan_features32(pl, name == "persistent"), dtype=np.float32)
+    assert v.shape == (B, F) and np.isfinite(v).all()
+    v_d = _dev_rows(v, 0)
+    _mean32, _W32, mean_d, W_d = TN._tables(F, NC)
+    origin_d = mean_d[1].contiguous()
+    L = _lib()
+    need = L.lib().cilrs_net_knn_scratch_bytes(F, B, N, K)
+    assert need == 2 * B * F * 4 + L.lib().cilrs_knn_scratch_bytes(N, B, K)
+
+    def net_knn(X_d, origin, Wt):
+        out = _Out(N, B, K)
+        out.scratch, c = G.guarded(need, dtype=torch.uint8, fill=0xA5, name="scratch")
+        out.checks = out.checks[:2] + (c,)
+        ins = G.Inputs(X=X_d)
+        L.check(L.lib().cilrs_net_knn(pl.handle, C.byref(pl.bufs), L.ptr(X_d), X_d.stride(0), N,
+                                      L.ptr(origin), L.ptr(Wt), K, L.ptr(out.idx), L.ptr(out.dist),
+                                      L.ptr(out.scratch), need, _st()))
+        out.check()
+        ins.check()
+        return out.host()
+
+    # origin = W = NULL: the features themselves are the queries
+    X_d = _dev_rows(KC.relu_rows(N, F, 31, scale=float(v.max())), 4)
+    idx, dist = net_knn(X_d, None, None)
+    want_i, want_d = _knn(X_d, N, F, v_d, B, K)
+    assert np.array_equal(idx, want_i) and _same_bits(dist, want_d), name
+    assert (idx >= 0).all() and np.isfinite(dist).all()
+    # with tables: cilrs_feature_whiten of the same features, then cilrs_knn
+    rc, y_d, _s = _whiten(v_d, B, F, origin_d, W_d)
+    assert rc == 0, _err()
+    Xw_d = _dev_rows(KC.relu_rows(N, F, 32, scale=float(y_d.abs().max())), 0)
+    idx, dist = net_knn(Xw_d, origin_d, W_d)
+    want_i, want_d = _knn(Xw_d, N, F, y_d, B, K)
+    assert np.array_equal(idx, want_i) and _same_bits(dist, want_d), name
+    assert (idx >= 0).all() and np.isfinite(dist).all()
+    assert pl.status.tolist()[0] == 0
+    # the forward's own outputs: untouched, and the same from the next forward
+    assert torch.equal(ctrl, before[0]) and torch.equal(ps, before[1])
+    ctrl2, ps2 = fwd(eng, u8_d, spd_d, cmd_d)
+    torch.cuda.synchronize()
+    assert torch.equal(ctrl2, before[0]) and torch.equal(ps2, before[1])
 
 
 # ---- end to end --------------------------------------------------------------------------------------
