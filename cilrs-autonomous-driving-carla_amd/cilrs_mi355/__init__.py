@@ -1,6 +1,7 @@
 """cilrs_mi355 -- MI355X-native engine behind the reference's CILRS nn.Module boundary
 (model/autonomous_drive.py:361-399, notebook/notebook.ipynb:440-555)."""
 from .bn_estimate import BatchNormEstimator, update_bn  # noqa: F401
+from .cluster import Clustering  # noqa: F401
 from .data import BatchLoader, CachedBatchLoader, DeviceDataset  # noqa: F401
 from .model import CILRS, CILRSResNet50  # noqa: F401
 from .neighbours import NeighbourIndex  # noqa: F401

@@ -145,6 +145,42 @@ class FramePool:
             L.ptr(scratch), nbytes, L.C.c_void_p(stream)))
         return sel, radius
 
+    def _kmeans_scratch(self, rows, k):
+        nbytes = L.lib().cilrs_kmeans_scratch_bytes(rows.size(0), rows.size(1), k)
+        return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=rows.device), nbytes
+
+    def _assign_op(self, rows, centres, labels, dist, counts, inertia, changed):
+        """cilrs_kmeans_assign: labels int32 [N] (in: the labels `changed` is counted against), dist
+        float32 [N], counts int64 [K], inertia float64 [1], changed int64 [1]"""
+        self._need_device("cluster")
+        scratch, nbytes = self._kmeans_scratch(rows, centres.size(0))
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        L.check(L.lib().cilrs_kmeans_assign(
+            L.ptr(rows), rows.stride(0), rows.size(0), rows.size(1), L.ptr(centres), centres.stride(0),
+            centres.size(0), L.ptr(labels), L.ptr(dist), L.ptr(counts), L.ptr(inertia), L.ptr(changed),
+            L.ptr(scratch), nbytes, L.C.c_void_p(stream)))
+
+    def _update_op(self, rows, labels, centres, counts):
+        """cilrs_kmeans_update: centres [K, F] become the means of their rows; counts int64 [K]"""
+        self._need_device("cluster")
+        scratch, nbytes = self._kmeans_scratch(rows, centres.size(0))
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        L.check(L.lib().cilrs_kmeans_update(
+            L.ptr(rows), rows.stride(0), rows.size(0), rows.size(1), L.ptr(labels), L.ptr(centres),
+            centres.stride(0), centres.size(0), L.ptr(counts), L.ptr(scratch), nbytes,
+            L.C.c_void_p(stream)))
+
+    def _lloyd_op(self, rows, centres, iters, labels, dist, counts, inertia, changed):
+        """cilrs_kmeans_lloyd: `iters` times (assign, update) and a closing assign, in place;
+        inertia float64 / changed int64 [iters + 1]"""
+        self._need_device("cluster")
+        scratch, nbytes = self._kmeans_scratch(rows, centres.size(0))
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        L.check(L.lib().cilrs_kmeans_lloyd(
+            L.ptr(rows), rows.stride(0), rows.size(0), rows.size(1), L.ptr(centres), centres.stride(0),
+            centres.size(0), iters, L.ptr(labels), L.ptr(dist), L.ptr(counts), L.ptr(inertia),
+            L.ptr(changed), L.ptr(scratch), nbytes, L.C.c_void_p(stream)))
+
     # ---- nearest neighbours (cilrs_mi355.neighbours) -----------------------------------------------
     index_class = None                    # host tests put a NeighbourIndex with replaced launches here
 
@@ -234,3 +270,20 @@ class FramePool:
         if zero.size:
             sel, radius = sel[:zero[0]], radius[:zero[0]]
         return Selection(sel, radius, mind, metric, rows)
+
+    # ---- clustering (cilrs_mi355.cluster) --------------------------------------------------------
+    def cluster(self, k, density=None, iters=50, init="kcenter", check_every=5):
+        """K-means over the rows added so far (include/cilrs_hip.h "K-means"): a Clustering with
+        centres, a label and a squared distance per row, the cluster sizes and the histories.
+
+        density      a finalised FeatureDensity: the Mahalanobis metric of ``select`` (the rows go
+                     through cilrs_feature_whiten, the kernel that whitens every later query).
+                     None: the raw features, Euclidean.
+        init         "kcenter": the picks of ``select(k, density=density)`` (raises when the pool holds
+                     fewer than k distinct rows); int64 row indices [k]; or float32 centres
+                     [k, >= F] of raw features, whitened first when a density is given.
+        iters        at most this many (assign, update) iterations, then a closing assign.
+        check_every  iterations per cilrs_kmeans_lloyd call: one synchronise per block, and the run
+                     stops at the first block that holds an assignment with no change."""
+        from .cluster import cluster
+        return cluster(self, k, density, iters, init, check_every)

@@ -578,6 +578,61 @@ int cilrs_net_knn(cilrs_net* net, const cilrs_buffers* bufs, const float* X, lon
                   const float* origin, const float* W, int K, int64_t* idx, float* dist,
                   void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- K-means: what a pool consists of, and how much of each kind (csrc/kmeans.hip) ----------------
+ * Greedy k-center picks extremes and the neighbour query answers for one tick; neither says which
+ * scenario modes a recorded drive holds.  Lloyd's iteration (1982) partitions the pool: centres, a
+ * label and a distance per row, the rows per cluster.  The reference balances its sampler by command
+ * only; it has no such path, and parity is pinned by this definition (restated in float64 by
+ * tests/_kmeans.py).
+ *   Inputs   rows X fp32 [N][ld] and centres C fp32 [K][ldc], the first D columns of both used
+ *            (columns D.. are never read or written).
+ *   Distance d(x, c) is exactly the distance of "Greedy k-center" above: the same lane chains and
+ *            butterfly, the same bits (the device code is shared, csrc/kc_dist.h).
+ *   Assign   label[i], dist[i]: the centre smallest in the total order (d, m), one entry preceding
+ *            another by d < d' || (d == d' && m < m'); a centre whose distance is NaN is no
+ *            candidate, +inf is an ordinary value; with no candidate label = -1 and dist = +inf.
+ *            By construction bit for bit the nearest-neighbour entry above with X = C, Y = X_i and
+ *            K = 1.  changed: the rows whose label differs from the value label[i] held before the
+ *            call.  inertia: the float64 sum of dist[i] over the rows with label >= 0, in an order
+ *            fixed by N alone (rows in blocks of 256 ceil(N / 2^19); thread t of 256 adds its rows
+ *            t, t + 256, .. in turn, a halving tree joins the threads, thread t of 1,024 adds the
+ *            blocks t, t + 1,024, .. and a halving tree joins those).  counts int64 [K]: the rows
+ *            per label.
+ *   Update   for every m with counts[m] > 0: C[m][j] = (float)(S / counts[m]), S the float64 sum of
+ *            X[i][j] over the rows labelled m -- the rows in ascending i, cut into runs of
+ *            256 ceil(N / 2^19), each run a sequential chain, the runs added in order --, the division
+ *            in float64.  A cluster with no rows keeps its centre; rows whose label is outside
+ *            0..K-1 (-1 among them) take no part.
+ *   Lloyd    `iters` times (assign, update), then one closing assign: at exit label, dist and counts
+ *            belong to the returned centres.  inertia float64 [iters + 1] and changed int64
+ *            [iters + 1] hold one entry per assignment.  Once changed[t] == 0 every later iteration
+ *            is a fixed point bit for bit, so running past convergence is harmless, and iters1
+ *            followed by iters2 on the same label / C is iters1 + iters2.
+ *            Min, comparison and the tie rule are exact, every distance has fixed bits and every
+ *            float64 order is a function of N and the labels alone: the result is bit-identical
+ *            from run to run and does not depend on how rows are spread over waves and workgroups.
+ * Launches on `stream` and nothing else: per assignment four (the distances with up to 128 KiB of
+ * centres staged in LDS, X read once per such chunk; the labels' histogram; its scan in two), per
+ * update three more after those (a stable counting sort of the row indices by label, the float64
+ * sums of the gathered rows, the centres).  No floating-point atomics (integer LDS atomics build the
+ * histogram), no fences, no grid barrier, no host synchronisation.  label int32 [N], dist fp32 [N],
+ * counts, inertia, changed and C are device memory; scratch: cilrs_kmeans_scratch_bytes(N, D, K)
+ * bytes (0 for arguments outside the ranges), 16-byte aligned, contents irrelevant before and after.
+ * Refused (non-zero, text in cilrs_last_error, nothing launched): NULL tensors; N outside 1..2^24;
+ * D outside 4..2048 or not a multiple of 4; ld or ldc below D or not a multiple of 4; X, C or the
+ * scratch not 16-byte aligned; K outside 1..min(N, 1024); iters outside 0..10,000; a scratch
+ * smaller than asked. */
+size_t cilrs_kmeans_scratch_bytes(int N, int D, int K);
+int cilrs_kmeans_assign(const float* X, long ld, int N, int D, const float* C, long ldc, int K,
+                        int32_t* label, float* dist, int64_t* counts, double* inertia,
+                        int64_t* changed, void* scratch, size_t scratch_bytes, void* stream);
+int cilrs_kmeans_update(const float* X, long ld, int N, int D, const int32_t* label, float* C,
+                        long ldc, int K, int64_t* counts, void* scratch, size_t scratch_bytes,
+                        void* stream);
+int cilrs_kmeans_lloyd(const float* X, long ld, int N, int D, float* C, long ldc, int K, int iters,
+                       int32_t* label, float* dist, int64_t* counts, double* inertia,
+                       int64_t* changed, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Same, fed with uint8 RGB HWC frames [B,H,W,3]: fuses preprocess_image's /255, HWC->CHW and
  * Normalize(mean,std) (autonomous_drive.py:897-902; the cv2.resize is the caller's). */
 int cilrs_net_forward_u8(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* frames,
