@@ -93,6 +93,9 @@ SIGNATURES = {
     "cilrs_kcenter_greedy": (i32, [vp, C.c_long, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
     "cilrs_knn_scratch_bytes": (sz, [i32, i32, i32]),
     "cilrs_knn": (i32, [vp, C.c_long, i32, i32, vp, C.c_long, i32, vp, i32, vp, vp, vp, sz, vp]),
+    "cilrs_knn_join_candidates": (i32, [i32]),
+    "cilrs_knn_join_scratch_bytes": (sz, [i32, i32, i32, i32]),
+    "cilrs_knn_join": (i32, [vp, C.c_long, i32, i32, vp, C.c_long, i32, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
     "cilrs_kmeans_scratch_bytes": (sz, [i32, i32, i32]),
     "cilrs_kmeans_assign": (i32, [vp, C.c_long, i32, i32, vp, C.c_long, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "cilrs_kmeans_update": (i32, [vp, C.c_long, i32, i32, vp, vp, C.c_long, i32, vp, vp, sz, vp]),

@@ -3,13 +3,18 @@
 ``saliency``, ``attribution`` and ``gradcam`` explain a tick through pixels, ``predict_novelty`` gives
 one number under a Gaussian assumption.  This module answers with examples: the k pool rows nearest
 to a feature vector, defined in include/cilrs_hip.h ("Nearest neighbours") and computed by one
-streaming pass over the pool per eight queries (csrc/knn.hip).  The distance to the k-th neighbour is
-the non-parametric novelty score of Sun et al. (2022); the same query de-duplicates new frames against
-a labelled set and picks the labelled frames that sit next to a new one in a fine-tuning batch.
+streaming pass over the pool per eight queries (csrc/knn.hip), or for many queries at once by a
+matrix-core screen with an exact re-score and a per-query certificate (csrc/knn_join.hip, "Bulk
+nearest neighbours"; what it cannot certify goes through the streaming pass).  The distance to the
+k-th neighbour is the non-parametric novelty score of Sun et al. (2022); the same query
+de-duplicates new frames against a labelled set and picks the labelled frames that sit next to a new
+one in a fine-tuning batch.
 
     index = pool.index(density=fd)                      # Mahalanobis; pool.index() is Euclidean
     idx, dist = index.query(pool.features()[:4], k=8)   # device tensors, no synchronise
     index.calibrate(k=8)                                # leave-one-out over the index's own rows
+    idx, dist = index.join(drive_features, k=8)         # query() for a whole drive: the same bits, k <= 16,
+    idx, dist = index.graph(k=8)                        #   and for the index's own rows (leave-one-out)
     controls, pred_speed, idx, dist = predictor.predict_neighbours(frames, kmh, commands, index, k=8)
     if index.percentile(dist[0, -1]) > 99.0: ...        # a threshold with a meaning
 
@@ -28,6 +33,10 @@ METRICS = ("euclidean", "mahalanobis")
 WHITEN_CHUNK = 4096       # rows per cilrs_feature_whiten call (its scratch is chunk * F floats)
 QUERY_CHUNK = 4096        # queries per cilrs_knn call of calibrate()
 MAX_K = 64
+JOIN_MAX_K = 16           # cilrs_knn_join keeps K + 8 <= 24 candidates per lane in LDS
+JOIN_CHUNK = 65536        # queries per cilrs_knn_join call
+JOIN_MIN_Q = 64           # below this many queries join() is query(): the measured crossover at 176,256 x 512
+                          # (profiles/knn_join_bench.log; 32 queries for k = 1, 64 for k = 8 and 16)
 
 
 class NeighbourIndex:
@@ -61,6 +70,7 @@ class NeighbourIndex:
         self.rows = rows.contiguous() if whitened or self.W is None else self.whiten(rows)
         self._capacity = int(capacity)
         self.log, self.log_count, self.log_k, self._sorted = None, 0, 0, None
+        self.last_join = None                 # {"queries", "uncertified"} of the last join / graph
 
     def __len__(self):
         return int(self.rows.size(0))
@@ -93,6 +103,20 @@ class NeighbourIndex:
         L.check(L.lib().cilrs_knn(
             L.ptr(self.rows), self.rows.stride(0), n, self.F, L.ptr(queries), queries.stride(0), q,
             L.ptr(skip), k, L.ptr(idx), L.ptr(dist), L.ptr(scratch), nbytes, L.C.c_void_p(stream)))
+
+    def _join_op(self, queries, k, skip, idx, dist, uncertified, n_uncertified):
+        """cilrs_knn_join of queries [Q <= 65536, ld >= F] against the rows: idx / dist as _knn_op for
+        the certified queries, -2 / NaN and uncertified[q] = 1 (int32 [Q], their count in int32 [1])
+        for the others"""
+        self._need_device("join")
+        n, q = self.rows.size(0), queries.size(0)
+        nbytes = L.lib().cilrs_knn_join_scratch_bytes(n, q, self.F, k)
+        scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        L.check(L.lib().cilrs_knn_join(
+            L.ptr(self.rows), self.rows.stride(0), n, self.F, L.ptr(queries), queries.stride(0), q,
+            L.ptr(skip), k, L.ptr(idx), L.ptr(dist), L.ptr(uncertified), L.ptr(n_uncertified),
+            L.ptr(scratch), nbytes, L.C.c_void_p(stream)))
 
     # ---- queries ---------------------------------------------------------------------------------
     def _check_features(self, features, who):
@@ -150,6 +174,80 @@ class NeighbourIndex:
                     torch.empty(0, k, dtype=torch.float32, device=self.device))
         return self._query_rows(self.whiten(features) if self.W is not None else features, k, skip)
 
+    def _check_join_k(self, k, who):
+        k = int(k)
+        if not 1 <= k <= JOIN_MAX_K:
+            raise ValueError(f"NeighbourIndex.{who}: k must be in 1..{JOIN_MAX_K}; NeighbourIndex.query "
+                             f"takes k up to {MAX_K}")
+        return k
+
+    def _join_rows(self, queries, k, skip):
+        """_query_rows through the matrix-core screen: cilrs_knn_join per 65,536 queries, then the
+        queries it could not certify through cilrs_knn.  Bit for bit _query_rows' result.  One
+        synchronise per chunk (the count of flagged queries is read on the host).  Returns
+        (idx, dist, flagged queries)."""
+        q = queries.size(0)
+        idx = torch.empty(q, k, dtype=torch.int64, device=self.device)
+        dist = torch.empty(q, k, dtype=torch.float32, device=self.device)
+        if skip is not None:
+            skip = torch.as_tensor(skip, dtype=torch.int64).reshape(-1).to(self.device).contiguous()
+            if skip.numel() != q:
+                raise RuntimeError(f"NeighbourIndex.join: skip must hold one row index per query "
+                                   f"({q}), got {skip.numel()}")
+        flagged = 0
+        for q0 in range(0, q, JOIN_CHUNK):
+            y = queries[q0:q0 + JOIN_CHUNK]
+            sk = None if skip is None else skip[q0:q0 + JOIN_CHUNK]
+            unc = torch.empty(y.size(0), dtype=torch.int32, device=self.device)
+            n_unc = torch.empty(1, dtype=torch.int32, device=self.device)
+            self._join_op(y, k, sk, idx[q0:q0 + JOIN_CHUNK], dist[q0:q0 + JOIN_CHUNK], unc, n_unc)
+            n = int(n_unc.item())
+            if n:
+                at = unc.nonzero().reshape(-1)
+                i2, d2 = self._query_rows(y.index_select(0, at), k,
+                                          None if sk is None else sk.index_select(0, at))
+                idx[q0:q0 + JOIN_CHUNK].index_copy_(0, at, i2)
+                dist[q0:q0 + JOIN_CHUNK].index_copy_(0, at, d2)
+                flagged += n
+        return idx, dist, flagged
+
+    def join(self, features, k, skip=None):
+        """``query`` for a whole drive: the same contract and the same bits with k <= 16, computed by
+        the matrix-core screen of cilrs_knn_join (include/cilrs_hip.h "Bulk nearest neighbours") and,
+        for the queries the screen cannot certify, by ``query``'s own kernel.  Synchronises once per
+        65,536 queries.  ``last_join`` = {"queries": Q, "uncertified": queries that fell back}.
+        Below JOIN_MIN_Q queries it is ``query``."""
+        k = self._check_join_k(k, "join")
+        features = self._check_features(features, "join")
+        return self._join_whitened(self.whiten(features) if self.W is not None else features, k, skip)
+
+    def _join_whitened(self, queries, k, skip=None):
+        """join of queries already in the rows' coordinates (FramePool.select has them)"""
+        q = queries.size(0)
+        if q < JOIN_MIN_Q:
+            self.last_join = {"queries": q, "uncertified": 0}
+            return self._query_rows(queries, k, skip)
+        idx, dist, flagged = self._join_rows(queries, k, skip)
+        self.last_join = {"queries": q, "uncertified": flagged}
+        return idx, dist
+
+    def graph(self, k):
+        """The k nearest other rows of every row of the index (the leave-one-out self-join):
+        ``query(rows, k, skip=arange(N))`` bit for bit, through ``join``'s kernels on views of the
+        rows."""
+        k = self._check_join_k(k, "graph")
+        n = len(self)
+        idx = torch.empty(n, k, dtype=torch.int64, device=self.device)
+        dist = torch.empty(n, k, dtype=torch.float32, device=self.device)
+        flagged = 0
+        for q0 in range(0, n, JOIN_CHUNK):
+            q1 = min(n, q0 + JOIN_CHUNK)
+            i2, d2, f = self._join_rows(self.rows[q0:q1], k, torch.arange(q0, q1, dtype=torch.int64))
+            idx[q0:q1], dist[q0:q1] = i2, d2
+            flagged += f
+        self.last_join = {"queries": n, "uncertified": flagged}
+        return idx, dist
+
     def score(self, features, k):
         """The squared distance to the k-th nearest row, float32 [Q] on the device."""
         return self.query(features, k)[1][:, self._check_k(k) - 1]
@@ -165,11 +263,12 @@ class NeighbourIndex:
             self.log = grown
         return self.log[self.log_count:self.log_count + b]
 
-    def calibrate(self, k, rows=None):
+    def calibrate(self, k, rows=None, bulk=False):
         """Leave-one-out k-th neighbour distances of the index's own rows -- all, or the subset
         ``rows`` (int64 indices) -- into a device log; ``quantile`` / ``percentile`` read from it.
-        Every call with another k starts the log again."""
-        k = self._check_k(k)
+        Every call with another k starts the log again.  ``bulk``: through ``join``'s kernels
+        (k <= 16, one synchronise per 65,536 rows): the same log bit for bit."""
+        k = self._check_join_k(k, "calibrate(bulk=True)") if bulk else self._check_k(k)
         n = len(self)
         if rows is None:
             rows = torch.arange(n, dtype=torch.int64)
@@ -179,9 +278,13 @@ class NeighbourIndex:
         if k != self.log_k:
             self.log_count, self.log_k, self._sorted = 0, k, None
         rows = rows.to(self.device)
-        for q0 in range(0, rows.numel(), QUERY_CHUNK):
-            r = rows[q0:q0 + QUERY_CHUNK]
-            _idx, dist = self._query_rows(self.rows.index_select(0, r), k, r)
+        chunk = JOIN_CHUNK if bulk else QUERY_CHUNK
+        for q0 in range(0, rows.numel(), chunk):
+            r = rows[q0:q0 + chunk]
+            if bulk:
+                dist = self._join_rows(self.rows.index_select(0, r), k, r)[1]
+            else:
+                dist = self._query_rows(self.rows.index_select(0, r), k, r)[1]
             self._log_room(r.numel()).copy_(dist[:, k - 1])
             self.log_count += r.numel()
             self._sorted = None

@@ -202,6 +202,30 @@ class FramePool:
                    weights_key=density.fit_weights_key or self.weights_key, commands=density.NC,
                    whitened=False)
 
+    def _check_index(self, index, who):
+        """an index of ANOTHER set whose rows the pool's features can be compared with"""
+        if index.F != self.F:
+            raise RuntimeError(f"FramePool.{who}: the index holds {index.F} features, the pool "
+                               f"{self.F}")
+        if index.device != self.device:
+            raise RuntimeError(f"FramePool.{who}: the index is on {index.device}, the pool on "
+                               f"{self.device}")
+        if self.count == 0:
+            raise RuntimeError(f"FramePool.{who}: the pool is empty")
+
+    def nearest(self, index, k=1):
+        """The k rows of ``index`` (a NeighbourIndex of another set, e.g. everything labelled so far)
+        nearest to every row of the pool, in the index's metric: ``index.join(pool.features(), k)``,
+        (idx int64 [count, k], dist float32 [count, k]) on the device."""
+        self._check_index(index, "nearest")
+        return index.join(self.features(), k)
+
+    def novel_rows(self, index, radius2):
+        """The pool rows whose nearest row of ``index`` is farther than the squared distance
+        ``radius2``, int64 ascending on the device: what a drive adds to the labelled set."""
+        _idx, dist = self.nearest(index, 1)
+        return (dist[:, 0] > float(radius2)).nonzero().reshape(-1)
+
     # ---- selection -------------------------------------------------------------------------------
     @staticmethod
     def _kernel_rows(t):
@@ -210,7 +234,7 @@ class FramePool:
             t = t.contiguous()
         return t
 
-    def select(self, k, density=None, covered=None, first=None) -> Selection:
+    def select(self, k, density=None, covered=None, first=None, covered_index=None) -> Selection:
         """Greedy k-center over the rows added so far: up to ``k`` picks, each the row farthest from
         everything covered before it.
 
@@ -218,7 +242,14 @@ class FramePool:
                   metric) and the fit's command means count as covered.  None: the raw features,
                   Euclidean.
         covered   float32 [M, >= F] of frames already labelled or chosen earlier; covered as well.
-        first     with nothing to cover, the row that is the first centre (default row 0)."""
+        first     with nothing to cover, the row that is the first centre (default row 0).
+        covered_index  a NeighbourIndex of the labelled set, of any size, in the metric of this
+                  call; its rows count as covered, through ``NeighbourIndex.join``'s kernels.
+                  The index's rows are compared with this call's rows as they are: with rows
+                  ``density.whiten(C)`` (``whitened=True``) the picks and radii are those of
+                  ``covered=C`` bit for bit; ``index(density)`` of another pool whitens through
+                  cilrs_feature_whiten, whose rounding differs from ``density.whiten``'s in the
+                  last bits."""
         n, k = self.count, int(k)
         if n == 0:
             raise RuntimeError("FramePool.select: the pool is empty")
@@ -250,10 +281,25 @@ class FramePool:
             if not 0 <= first < n:
                 raise ValueError(f"first must be in 0..{n - 1}")
             centres.append(rows[first:first + 1])
+        if covered_index is not None:
+            if first is not None:
+                raise ValueError("first: only with nothing to cover (no covered_index)")
+            self._check_index(covered_index, "select")
+            want = "euclidean" if density is None else "mahalanobis"
+            if covered_index.metric != want:
+                raise RuntimeError(f"FramePool.select: covered_index is {covered_index.metric}, this "
+                                   f"selection {want}")
+            if density is not None and not (torch.equal(covered_index.origin, density._origin().to(
+                    covered_index.device)) and torch.equal(covered_index.W, density.W.to(covered_index.device))):
+                raise RuntimeError("FramePool.select: covered_index was whitened with other tables than "
+                                   "`density`")
         rows = self._kernel_rows(rows)
         mind = torch.full((n,), float("inf"), dtype=torch.float32, device=rows.device)
         for c in centres:
             self._cover_op(rows, self._kernel_rows(c), mind)
+        if covered_index is not None:
+            d = covered_index._join_whitened(rows, 1)[1][:, 0]     # rows: this call's coordinates
+            mind = torch.where(d < mind, d, mind)
         picks = k if first is None else k - 1
         if picks:
             sel, radius = self._greedy_op(rows, mind, picks)

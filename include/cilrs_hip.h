@@ -578,6 +578,68 @@ int cilrs_net_knn(cilrs_net* net, const cilrs_buffers* bufs, const float* X, lon
                   const float* origin, const float* W, int K, int64_t* idx, float* dist,
                   void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Bulk nearest neighbours: a whole drive against a pool on the matrix cores (csrc/knn_join.hip) --
+ * cilrs_knn reads the pool once per eight queries; a recorded drive against the labelled set, or the
+ * leave-one-out self-join of a pool, is hundreds of thousands of queries.  The GEMM form
+ * |x|^2 + |y|^2 - 2 x.y has other bits than the distance above, so here it only SCREENS: it keeps a
+ * few more rows per query than asked for, the shared distance re-scores those, and a derived error
+ * bound certifies per query that no other row can belong to the result.  What a certified query gets
+ * is bit for bit cilrs_knn's; the others are flagged and left to cilrs_knn.
+ *   Inputs   X, Y, skip, candidates, the order (d, i) and the -1 / +inf fill are those of "Nearest
+ *            neighbours"; K is 1..16 and K_s = cilrs_knn_join_candidates(K) = K + 8.
+ *   Screen   nx_i, ny_q: the fp32 sum of squares of a row -- lane l of a wave runs a = fmaf(x_j, x_j, a)
+ *            from a = 0 over its columns j = 256 t + 4 l + e < D (t ascending, then e = 0..3), the 64
+ *            lane sums are combined by a += shfl_xor(a, o), o = 32, 16, .., 1.  p(q, i): the fp32 dot
+ *            product on v_mfma_f32_32x32x2_f32, one fmaf chain from 0 over the columns in the order
+ *            16 c + 8 u + e, 16 c + 8 u + 4 + e for c = 0.., u = 0, 1, e = 0..3 (columns past D are
+ *            zeros made in LDS).  s(q, i) = fmaf(-2, p, nx_i).  Row i is screened out if
+ *            i == skip[q] or s is NaN; the candidates of q are the K_s remaining rows smallest in
+ *            (s, i), or all of them when they are fewer; sigma_q is the largest kept s.
+ *   Re-score d(X_i, Y_q) of the candidates is the distance of "Greedy k-center" (csrc/kc_dist.h, the
+ *            pool row first as in cilrs_knn: the same bits).  Candidates with a NaN d are dropped, the
+ *            rest sorted by (d, i), the first K written.
+ *   Certificate  in float64, per query.  q is certified if
+ *            (a) every row other than skip[q] is a candidate (none fell to the K_s limit and none
+ *                to a NaN s: the re-score then IS the definition), or
+ *            (b) max_i nx_i, ny_q and sigma_q are finite, max_i nx_i + ny_q < 2^125, K results exist,
+ *                dist[q][K-1] is finite and  dist[q][K-1] < (1 - b) (sigma_q + ny_q - E_q)  with
+ *                b = (4 ceil(D / 256) + 9) 2^-24, the bound of one distance (tests/_kcenter.py), and
+ *                E_q = c_D 2^-24 (max_i nx_i + ny_q), c_D = 2 D + 16.
+ *            Why (b) is sound: with u = 2^-24, the chain of p makes at most D roundings on partial
+ *            sums bounded by sum |x_j y_j| <= (nx + ny) / 2, so |2 p - 2 x.y| <= D u (nx + ny); nx_i
+ *            and ny_q carry r_D = min(D, 4 ceil(D / 256) + 6) roundings each (a lane's fmas and the
+ *            butterfly; below 16 columns the butterfly adds zeros), the final fma one on a value of
+ *            at most 2 (nx + ny): in all (D + 2 r_D + 3) u (max nx + ny) to first order, and
+ *            2 r_D + 3 <= D + 16 for every D (smallest margin 9 u, at D = 4), which covers the second-order terms.
+ *            Hence every row outside the candidates has a true squared distance of at least
+ *            sigma_q + ny_q - E_q, its fp32 distance is at least (1 - b) times that, and the strict
+ *            inequality keeps it behind the K-th result even on a tie.  Below 2^125 no partial sum of
+ *            p overflows, so with finite norms no s is NaN and only skip[q] was screened out.  c_D
+ *            comes from the chain lengths, not from measurements.  A pool row or query with a NaN or
+ *            an infinity, or a square that overflows, makes (b) false for the queries it touches (a
+ *            pool row: for all of them).
+ *   Output   certified: idx / dist rows as cilrs_knn writes them, uncertified[q] = 0.  Otherwise
+ *            uncertified[q] = 1, idx = -2 and dist = NaN in all K slots.  n_uncertified[0] is the
+ *            count.  Everything, flags included, is the same from run to run and does not depend on
+ *            how rows and queries are spread over tiles, workgroups, slices or calls: p's chain is
+ *            fixed, max / min / comparisons are exact, max_i nx_i belongs to the pool alone.
+ * cilrs_knn_join: six launches on `stream` (norms of X, their max, norms of Y, the screen, merge +
+ * re-score + certificate, the count); no atomics, no fences, no grid barrier, no host synchronisation.
+ * idx, dist, uncertified int32 [Q] and n_uncertified int32 [1] are device memory.  scratch:
+ * cilrs_knn_join_scratch_bytes(N, Q, D, K) bytes (0 outside the ranges) =
+ * 4 N + 4 Q + 4 min(1024, ceil(N / 4)) + 16, each part rounded up to 16, + 16 Q S K_s for the lanes'
+ * lists, S = the pool slices of the screen (1 from 65,536 queries on, so that Q S <= 2 * 65,536:
+ * 25 MB at K = 16 and Q = 65,536 whatever N); 16-byte aligned, contents irrelevant before and after.
+ * Refused (non-zero, text in cilrs_last_error, nothing launched or written): NULL tensors (skip is
+ * exempt); N outside 1..2^24; D outside 4..2048 or not a multiple of 4; ld or ldq below D or not a
+ * multiple of 4; X, Y or the scratch not 16-byte aligned; Q outside 1..65536; K outside 1..16; a
+ * scratch smaller than asked. */
+int cilrs_knn_join_candidates(int K);
+size_t cilrs_knn_join_scratch_bytes(int N, int Q, int D, int K);
+int cilrs_knn_join(const float* X, long ld, int N, int D, const float* Y, long ldq, int Q,
+                   const int64_t* skip, int K, int64_t* idx, float* dist, int32_t* uncertified,
+                   int32_t* n_uncertified, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- K-means: what a pool consists of, and how much of each kind (csrc/kmeans.hip) ----------------
  * Greedy k-center picks extremes and the neighbour query answers for one tick; neither says which
  * scenario modes a recorded drive holds.  Lloyd's iteration (1982) partitions the pool: centres, a
