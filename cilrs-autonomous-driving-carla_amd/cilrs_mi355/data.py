@@ -11,6 +11,10 @@ augmentation itself, /255 and Normalize run as one HIP kernel (`cilrs_augment_u8
 `BatchLoader` decodes every frame every epoch.  When the decoded frames fit in device memory,
 `DeviceDataset` decodes them once into HBM and `CachedBatchLoader` builds the same batches, bit
 for bit, with one `cilrs_batch_assemble` launch each.
+
+Both loaders take a `WeatherMix`: per-sample weather records (tone, fog, rain: the reference's
+weather profiles as an image-space model) applied to the source frames inside the same launch
+(`cilrs_augment_weather_u8`, `cilrs_batch_assemble_weather`).  Without one nothing differs.
 """
 from __future__ import annotations
 
@@ -110,11 +114,191 @@ def check_params(p: np.ndarray, height: int, width: int):
         raise RuntimeError("dropout hole outside the frame")
 
 
+# ---- weather: tone, fog and rain in front of the augmentation -----------------------------------
+# numpy mirror of `cilrs_weather_params` (include/cilrs_hip.h, where the stages are defined), 96 bytes
+WEATHER_DTYPE = np.dtype([
+    ("rain_seed", np.uint64), ("tone_on", np.int32), ("gain", np.float32, 3),
+    ("lift255", np.float32, 3), ("fog_on", np.int32), ("fog_t0", np.float32),
+    ("fog_t1", np.float32), ("fog_horizon", np.float32), ("fog_near", np.float32),
+    ("fog_rgb255", np.float32, 3), ("rain_len", np.int32), ("rain_slant_q4", np.int32),
+    ("rain_thresh24", np.uint32), ("rain_alpha", np.float32), ("rain_v255", np.float32),
+    ("reserved", np.int32, 2)], align=True)
+assert WEATHER_DTYPE.itemsize == 96
+
+# the reference's five weather profiles (configs/weather_config.json), clear first
+WEATHER_CONDITIONS = ("clear", "fog", "night", "rain", "hardrain")
+WEATHER_MAX_WIDTH = 65536 - 128       # streak heads are hashed from (row + 64, column + 64) in 16 bits each
+WEATHER_MAX_RAIN_LEN = 16
+WEATHER_STREAM = 0x57454154           # "WEAT": third key of the loaders' weather record stream
+FOG_HORIZON, FOG_NEAR = 0.45, 0.08    # of the frame height: horizon row, nearest ground depth
+
+# Initial constants, linear in severity s in [0, 1]; CARLA's renderer is not available here, so the
+# look is parity-unpinned.  tint * (1 - dim * s) = tone gain; beta * s = fog extinction at depth 1;
+# p0 + p1 * s = streak-head probability; round(len0 + len1 * s) = streak length; a0 + a1 * s = alpha.
+_CONDITION_TABLE = {
+    "fog": dict(dim=0.10, tint=(1.0, 1.0, 1.0), beta=3.0, air=(200.0, 205.0, 210.0)),
+    "night": dict(dim=0.78, tint=(0.90, 0.95, 1.10), beta=0.0, air=(0.0, 0.0, 0.0)),
+    "rain": dict(dim=0.20, tint=(1.0, 1.0, 1.0), beta=0.8, air=(165.0, 170.0, 175.0),
+                 p=(0.003, 0.009), length=(4.0, 4.0), alpha=(0.30, 0.15), v=215.0),
+    "hardrain": dict(dim=0.35, tint=(1.0, 1.0, 1.0), beta=1.6, air=(150.0, 155.0, 160.0),
+                     p=(0.008, 0.022), length=(6.0, 10.0), alpha=(0.35, 0.25), v=215.0),
+}
+
+
+def identity_weather(batch: int) -> np.ndarray:
+    """Every weather stage off: the records under which the weather kernels give what the plain
+    ones give."""
+    p = np.zeros(batch, dtype=WEATHER_DTYPE)
+    p["gain"] = 1.0
+    return p
+
+
+def fog_transmission(beta: float, height: int):
+    """(t0, t1) of t(d) = t0 + t1 * d with t(1) = exp(-beta) and t(d_min) = exp(-beta * d_min),
+    d_min = near / (H - 1 - horizon) the depth of the bottom row: Koschmieder's law interpolated
+    linearly in depth between the far and the near end.  Computed in double."""
+    horizon, near = FOG_HORIZON * height, FOG_NEAR * height
+    span = height - 1 - horizon
+    d_min = near / span if span > near else 1.0
+    far = float(np.exp(-beta))
+    if d_min >= 1.0:
+        return far, 0.0
+    t1 = (far - float(np.exp(-beta * d_min))) / (1.0 - d_min)
+    return far - t1, t1
+
+
+def _condition_records(names, severity, height, seeds, slants) -> np.ndarray:
+    """One record per sample from its condition name, severity, rain seed and slant."""
+    n = len(names)
+    p = identity_weather(n)
+    for i in range(n):
+        name, s = names[i], float(severity[i])
+        if name not in WEATHER_CONDITIONS:
+            raise ValueError(f"unknown weather condition {name!r}; one of {WEATHER_CONDITIONS}")
+        if not (0.0 <= s <= 1.0):
+            raise ValueError(f"weather severity {s} outside [0, 1]")
+        if name == "clear" or s == 0.0:
+            continue
+        c, r = _CONDITION_TABLE[name], p[i:i + 1]
+        r["tone_on"] = 1
+        r["gain"] = [(1.0 - c["dim"] * s) * t for t in c["tint"]]
+        beta = c["beta"] * s
+        if beta > 0.0:
+            r["fog_on"] = 1
+            r["fog_t0"], r["fog_t1"] = fog_transmission(beta, height)
+            r["fog_horizon"], r["fog_near"] = FOG_HORIZON * height, FOG_NEAR * height
+            r["fog_rgb255"] = c["air"]
+        if "p" in c:
+            r["rain_len"] = int(np.floor(c["length"][0] + c["length"][1] * s + 0.5))
+            r["rain_thresh24"] = int(round((c["p"][0] + c["p"][1] * s) * (1 << 24)))
+            r["rain_alpha"] = c["alpha"][0] + c["alpha"][1] * s
+            r["rain_v255"] = c["v"]
+            r["rain_slant_q4"] = int(slants[i])
+            r["rain_seed"] = seeds[i]
+    return p
+
+
+def _draw_rain_keys(rng: np.random.Generator, n: int):
+    """Per-sample rain seed and slant (uniform integer in [-8, 8] columns per 16 rows); drawn for
+    every sample, rainy or not, so the stream advances the same way under any mix."""
+    return rng.integers(0, 1 << 63, n, dtype=np.uint64), rng.integers(-8, 9, n)
+
+
+def weather_condition(name: str, severity: float, n: int, height: int = IMG_HEIGHT,
+                      rng: np.random.Generator = None) -> np.ndarray:
+    """n records of condition `name` (one of WEATHER_CONDITIONS) at `severity` in [0, 1]; severity
+    0 is the identity for every name.  The rain seed and slant are drawn per sample from `rng`."""
+    rng = np.random.default_rng(0) if rng is None else rng
+    seeds, slants = _draw_rain_keys(rng, n)
+    return _condition_records([name] * n, np.full(n, float(severity)), height, seeds, slants)
+
+
+class WeatherMix:
+    """What weather a loader draws: condition `name` with probability probs[name], its severity
+    uniform in `severity` = (low, high)."""
+
+    DEFAULT_PROBS = {"clear": .5, "fog": .125, "night": .125, "rain": .15, "hardrain": .10}
+
+    def __init__(self, probs: dict = None, severity=(0.2, 1.0)):
+        probs = dict(self.DEFAULT_PROBS if probs is None else probs)
+        for k, v in probs.items():
+            if k not in WEATHER_CONDITIONS:
+                raise ValueError(f"unknown weather condition {k!r}; one of {WEATHER_CONDITIONS}")
+            if not (v >= 0.0):
+                raise ValueError(f"probability of {k!r} must be non-negative")
+        total = float(sum(probs.values()))
+        if not (total > 0.0):
+            raise ValueError("WeatherMix: the probabilities sum to zero")
+        lo, hi = float(severity[0]), float(severity[1])
+        if not (0.0 <= lo <= hi <= 1.0):
+            raise ValueError("WeatherMix: severity must be (low, high) with 0 <= low <= high <= 1")
+        self.names = tuple(k for k in WEATHER_CONDITIONS if probs.get(k, 0.0) > 0.0)
+        self.cum = np.cumsum([probs[k] / total for k in self.names])
+        self.cum[-1] = 1.0
+        self.severity = (lo, hi)
+
+    @classmethod
+    def fixed(cls, name: str, severity: float):
+        """Every sample gets condition `name` at `severity`."""
+        return cls({name: 1.0}, (severity, severity))
+
+    def draw(self, rng: np.random.Generator, n: int, height: int = IMG_HEIGHT,
+             width: int = IMG_WIDTH) -> np.ndarray:
+        """n records; advances `rng` by the same amount whatever is drawn."""
+        if width > WEATHER_MAX_WIDTH:
+            raise RuntimeError(f"weather: width {width} above {WEATHER_MAX_WIDTH}")
+        pick = np.searchsorted(self.cum, rng.random(n), side="right")
+        pick = np.minimum(pick, len(self.names) - 1)
+        sev = rng.uniform(self.severity[0], self.severity[1], n)
+        seeds, slants = _draw_rain_keys(rng, n)
+        return _condition_records([self.names[k] for k in pick], sev, height, seeds, slants)
+
+
+def check_weather(p: np.ndarray, height: int, width: int):
+    if not isinstance(p, np.ndarray) or p.dtype != WEATHER_DTYPE:
+        raise RuntimeError("weather records must use data.WEATHER_DTYPE")
+    if width > WEATHER_MAX_WIDTH:
+        raise RuntimeError(f"weather: width {width} above {WEATHER_MAX_WIDTH}")
+    for k in ("gain", "lift255", "fog_t0", "fog_t1", "fog_horizon", "fog_near", "fog_rgb255",
+              "rain_alpha", "rain_v255"):
+        if not np.isfinite(p[k]).all():
+            raise RuntimeError(f"weather: {k} must be finite")
+    if not np.isin(p["tone_on"], (0, 1)).all() or not np.isin(p["fog_on"], (0, 1)).all():
+        raise RuntimeError("weather: tone_on and fog_on must be 0 or 1")
+    if (p["gain"] < 0).any():
+        raise RuntimeError("weather: gain must be non-negative")
+    fog = p["fog_on"] == 1
+    if (p["fog_near"][fog] <= 0).any():
+        raise RuntimeError("weather: fog_near must be positive where fog is on")
+    if (p["fog_rgb255"] < 0).any() or (p["fog_rgb255"] > 255).any():
+        raise RuntimeError("weather: fog_rgb255 must lie in [0, 255]")
+    if (p["rain_len"] < 0).any() or (p["rain_len"] > WEATHER_MAX_RAIN_LEN).any():
+        raise RuntimeError(f"weather: rain_len must be 0..{WEATHER_MAX_RAIN_LEN}")
+    if (np.abs(p["rain_slant_q4"].astype(np.int64)) > 16).any():
+        raise RuntimeError("weather: rain_slant_q4 must lie in [-16, 16]")
+    if (p["rain_thresh24"] > (1 << 24)).any():
+        raise RuntimeError("weather: rain_thresh24 must be at most 2^24")
+    if (p["rain_alpha"] < 0).any() or (p["rain_alpha"] > 1).any():
+        raise RuntimeError("weather: rain_alpha must lie in [0, 1]")
+    if (p["rain_v255"] < 0).any() or (p["rain_v255"] > 255).any():
+        raise RuntimeError("weather: rain_v255 must lie in [0, 255]")
+
+
+def _records_to_device(rec: np.ndarray, device) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(rec).view(np.uint8).reshape(
+        len(rec), rec.dtype.itemsize)).to(device, non_blocking=False)
+
+
 def augment_u8(frames_u8: torch.Tensor, params: np.ndarray, want_u8: bool = False,
-               params_dev: torch.Tensor = None):
+               params_dev: torch.Tensor = None, weather: np.ndarray = None,
+               weather_dev: torch.Tensor = None):
     """frames uint8 [B,H,W,3] on the device + per-sample parameters -> normalised image as the
     logical NCHW float tensor `CILRS.forward` takes (a permuted view of the NHWC result, like the
-    reference's permute at notebook.ipynb:413) [, augmented uint8 frames]."""
+    reference's permute at notebook.ipynb:413) [, augmented uint8 frames].
+
+    weather: one WEATHER_DTYPE record per frame, applied to the source pixels in the same launch
+    (`cilrs_augment_weather_u8`); None is the plain `cilrs_augment_u8`.  weather_dev: the same
+    records already on the device (uint8 [B, 96]), like params_dev."""
     if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.size(3) != 3 \
             or frames_u8.device.type != "cuda":
         raise RuntimeError("augment_u8: frames must be uint8 [B,H,W,3] on the GPU (no CPU fallback)")
@@ -122,6 +306,12 @@ def augment_u8(frames_u8: torch.Tensor, params: np.ndarray, want_u8: bool = Fals
     if params.shape != (b,):
         raise RuntimeError("augment_u8: one parameter record per frame")
     check_params(params, h, w)
+    if weather is None and weather_dev is not None:
+        raise RuntimeError("augment_u8: weather_dev needs the host records in `weather` too")
+    if weather is not None:
+        if weather.shape != (b,):
+            raise RuntimeError("augment_u8: one weather record per frame")
+        check_weather(weather, h, w)
     frames_u8 = frames_u8.contiguous()
     # params_dev: the same records already on the device (uint8 [B, 112]; the loader uploads them
     # from pinned memory on its copy stream).  Without it they go up from pageable memory, which
@@ -136,13 +326,49 @@ def augment_u8(frames_u8: torch.Tensor, params: np.ndarray, want_u8: bool = Fals
     else:
         pdev = torch.from_numpy(params.view(np.uint8).reshape(b, AUG_DTYPE.itemsize)).to(
             frames_u8.device, non_blocking=False)
+    wdev = None
+    if weather_dev is not None:
+        if weather_dev.dtype != torch.uint8 \
+                or tuple(weather_dev.shape) != (b, WEATHER_DTYPE.itemsize) \
+                or weather_dev.device != frames_u8.device:
+            raise RuntimeError("augment_u8: weather_dev must be uint8 [B, %d] on the frames' device"
+                               % WEATHER_DTYPE.itemsize)
+        wdev = weather_dev.contiguous()
+    elif weather is not None:
+        wdev = _records_to_device(weather, frames_u8.device)
     out = torch.empty(b, h, w, 3, dtype=torch.float32, device=frames_u8.device)
     out8 = torch.empty_like(frames_u8) if want_u8 else None
     stream = torch.cuda.current_stream(frames_u8.device).cuda_stream
-    L.check(L.lib().cilrs_augment_u8(L.ptr(frames_u8), L.ptr(pdev), b, h, w, L.ptr(out),
-                                     L.ptr(out8), C.c_void_p(stream)))
+    if wdev is None:
+        L.check(L.lib().cilrs_augment_u8(L.ptr(frames_u8), L.ptr(pdev), b, h, w, L.ptr(out),
+                                         L.ptr(out8), C.c_void_p(stream)))
+    else:
+        L.check(L.lib().cilrs_augment_weather_u8(L.ptr(frames_u8), L.ptr(pdev), L.ptr(wdev), b, h,
+                                                 w, L.ptr(out), L.ptr(out8), C.c_void_p(stream)))
     img = out.permute(0, 3, 1, 2)
     return (img, out8) if want_u8 else img
+
+
+def weather_u8(frames_u8: torch.Tensor, weather: np.ndarray) -> torch.Tensor:
+    """frames uint8 [B,H,W,3] on the device + one WEATHER_DTYPE record per frame -> the frames
+    under that weather, uint8 [B,H,W,3]: what the model is shown, to look at or to hand to a
+    `Predictor`.  One `cilrs_augment_weather_u8` launch with every augmentation off and only the
+    byte output asked for."""
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.size(3) != 3 \
+            or frames_u8.device.type != "cuda":
+        raise RuntimeError("weather_u8: frames must be uint8 [B,H,W,3] on the GPU (no CPU fallback)")
+    b, h, w = frames_u8.size(0), frames_u8.size(1), frames_u8.size(2)
+    if not isinstance(weather, np.ndarray) or weather.shape != (b,):
+        raise RuntimeError("weather_u8: one weather record per frame")
+    check_weather(weather, h, w)
+    frames_u8 = frames_u8.contiguous()
+    pdev = _records_to_device(identity_params(b), frames_u8.device)
+    wdev = _records_to_device(weather, frames_u8.device)
+    out8 = torch.empty_like(frames_u8)
+    stream = torch.cuda.current_stream(frames_u8.device).cuda_stream
+    L.check(L.lib().cilrs_augment_weather_u8(L.ptr(frames_u8), L.ptr(pdev), L.ptr(wdev), b, h, w,
+                                             None, L.ptr(out8), C.c_void_p(stream)))
+    return out8
 
 
 # ---- dataset on disk -------------------------------------------------------------------------
@@ -212,7 +438,8 @@ class BatchLoader:
 
     def __init__(self, sessions: Sessions, indices, batch_size: int, device, train: bool,
                  seed: int = 0, workers: int = 8, height: int = IMG_HEIGHT, width: int = IMG_WIDTH,
-                 processes: bool = False, rank: int = 0, world_size: int = 1):
+                 processes: bool = False, rank: int = 0, world_size: int = 1,
+                 weather: "WeatherMix" = None):
         """processes=True decodes in `workers` spawned processes (no GIL contention: what a
         B=128 / 14 ms training step needs); the default thread pool starts instantly.
 
@@ -223,7 +450,12 @@ class BatchLoader:
         at batch N*B would.  The order is cut to a multiple of world_size * batch_size when
         training (drop_last on the GLOBAL batch) so every rank runs the same number of steps --
         a rank with one batch more would hang the others' all-reduce.  Augmentation parameters
-        come from a rank-offset stream."""
+        come from a rank-offset stream.
+
+        weather: a `WeatherMix`; every sample's weather record is drawn batch by batch from a
+        stream of its own and applied in the augmentation launch (train or not).  The sample order
+        and the augmentation records are those of the same loader without it; None launches the
+        plain kernel."""
         if not (0 <= rank < world_size):
             raise ValueError(f"rank {rank} outside world of {world_size}")
         self.s, self.idx = sessions, np.asarray(indices)
@@ -231,6 +463,8 @@ class BatchLoader:
         self.h, self.w = height, width
         self.rank, self.world = rank, world_size
         self.rng = np.random.default_rng([seed, rank])
+        self.weather = weather
+        self.wrng = np.random.default_rng([seed, rank, WEATHER_STREAM])
         self.gen = torch.Generator().manual_seed(seed)
         self.workers = max(1, workers)
         self.processes = processes
@@ -314,7 +548,8 @@ class BatchLoader:
                 meta = (torch.zeros(self.bs, dtype=torch.float32).pin_memory(),
                         torch.zeros(self.bs, dtype=torch.int64).pin_memory(),
                         torch.zeros(self.bs, 3, dtype=torch.float32).pin_memory(),
-                        torch.zeros(self.bs, AUG_DTYPE.itemsize, dtype=torch.uint8).pin_memory())
+                        torch.zeros(self.bs, AUG_DTYPE.itemsize, dtype=torch.uint8).pin_memory(),
+                        torch.zeros(self.bs, WEATHER_DTYPE.itemsize, dtype=torch.uint8).pin_memory())
                 self._slots.append((t, t.numpy(), meta))
             # host-to-device copies run on a stream of their own: the wait that frees a staging
             # slot then waits for the COPY, not for the train step the copy would otherwise queue
@@ -339,7 +574,9 @@ class BatchLoader:
                         k += len(part)
                     params = draw_aug_params(self.rng, len(ids), self.h, self.w) if self.train \
                         else identity_params(len(ids))
-                    q.put((slot, params, ids))
+                    wrec = self.weather.draw(self.wrng, len(ids), self.h, self.w) \
+                        if self.weather is not None else None
+                    q.put((slot, params, wrec, ids))
                 q.put(None)
             except Exception as e:          # surface decode errors in the consumer
                 q.put(e)
@@ -350,10 +587,12 @@ class BatchLoader:
                 return
             if isinstance(item, Exception):
                 raise item
-            slot, params, ids = item
+            slot, params, wrec, ids = item
             n = len(ids)
-            pinned, _view, (sp_p, cm_p, tg_p, par_p) = self._slots[slot]
+            pinned, _view, (sp_p, cm_p, tg_p, par_p, wx_p) = self._slots[slot]
             par_p[:n] = torch.from_numpy(params.view(np.uint8).reshape(n, AUG_DTYPE.itemsize))
+            if wrec is not None:
+                wx_p[:n] = torch.from_numpy(wrec.view(np.uint8).reshape(n, WEATHER_DTYPE.itemsize))
             sp_p[:n] = torch.from_numpy(np.ascontiguousarray(self.s.speed[ids], dtype=np.float32))
             cm_p[:n] = torch.from_numpy(np.ascontiguousarray(self.s.command[ids], dtype=np.int64))
             tg_p[:n] = torch.from_numpy(np.ascontiguousarray(self.s.targets[ids], dtype=np.float32))
@@ -366,12 +605,14 @@ class BatchLoader:
                 cmds = cm_p[:n].to(self.device, non_blocking=True)
                 tgts = tg_p[:n].to(self.device, non_blocking=True)
                 pars = par_p[:n].to(self.device, non_blocking=True)
+                wxs = wx_p[:n].to(self.device, non_blocking=True) if wrec is not None else None
                 copied = torch.cuda.Event()
                 copied.record(cs)
             main.wait_event(copied)          # device side: the consumers run behind the copies
-            for t in (frames, speeds, cmds, tgts, pars):
-                t.record_stream(main)        # (allocated under the copy stream, used on `main`)
-            img = augment_u8(frames, params, params_dev=pars)
+            for t in (frames, speeds, cmds, tgts, pars, wxs):
+                if t is not None:
+                    t.record_stream(main)    # (allocated under the copy stream, used on `main`)
+            img = augment_u8(frames, params, params_dev=pars, weather=wrec, weather_dev=wxs)
             batch = (img, speeds, cmds, tgts)
             copied.synchronize()            # the staging slot may be refilled now
             free.put(slot)
@@ -558,9 +799,11 @@ class DeviceDataset:
             bad = index[(index < 0) | (index >= self.n)][0]
             raise RuntimeError(f"DeviceDataset: index {int(bad)} outside [0, {self.n})")
 
-    def _launch(self, index_ptr: int, params_ptr: int, b: int, want_u8: bool = False):
+    def _launch(self, index_ptr: int, params_ptr: int, b: int, want_u8: bool = False,
+                weather_ptr: int = None):
         """One cilrs_batch_assemble launch on the current stream from device-resident index /
-        parameter records (already checked on the host)."""
+        parameter records (already checked on the host); with weather_ptr (device-resident
+        weather records), one cilrs_batch_assemble_weather launch."""
         dev = self.device
         out = torch.empty(b, self.h, self.w, 3, dtype=torch.float32, device=dev)
         out8 = torch.empty(b, self.h, self.w, 3, dtype=torch.uint8, device=dev) if want_u8 else None
@@ -568,18 +811,28 @@ class DeviceDataset:
         cmd = torch.empty(b, dtype=torch.int64, device=dev)
         tgt = torch.empty(b, 3, dtype=torch.float32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        L.check(L.lib().cilrs_batch_assemble(
-            L.ptr(self.cache), self.n, L.ptr(self.speed), L.ptr(self.command_dev),
-            L.ptr(self.targets), C.c_void_p(index_ptr), C.c_void_p(params_ptr), b, self.h, self.w,
-            L.ptr(out), L.ptr(out8), L.ptr(spd), L.ptr(cmd), L.ptr(tgt), C.c_void_p(stream)))
+        if weather_ptr is None:
+            L.check(L.lib().cilrs_batch_assemble(
+                L.ptr(self.cache), self.n, L.ptr(self.speed), L.ptr(self.command_dev),
+                L.ptr(self.targets), C.c_void_p(index_ptr), C.c_void_p(params_ptr), b, self.h,
+                self.w, L.ptr(out), L.ptr(out8), L.ptr(spd), L.ptr(cmd), L.ptr(tgt),
+                C.c_void_p(stream)))
+        else:
+            L.check(L.lib().cilrs_batch_assemble_weather(
+                L.ptr(self.cache), self.n, L.ptr(self.speed), L.ptr(self.command_dev),
+                L.ptr(self.targets), C.c_void_p(index_ptr), C.c_void_p(params_ptr),
+                C.c_void_p(weather_ptr), b, self.h, self.w, L.ptr(out), L.ptr(out8), L.ptr(spd),
+                L.ptr(cmd), L.ptr(tgt), C.c_void_p(stream)))
         img = out.permute(0, 3, 1, 2)              # the NCHW view `augment_u8` returns
         return (img, spd, cmd, tgt, out8) if want_u8 else (img, spd, cmd, tgt)
 
-    def assemble(self, index, params: np.ndarray, want_u8: bool = False):
+    def assemble(self, index, params: np.ndarray, want_u8: bool = False,
+                 weather: np.ndarray = None):
         """index (host integers [B], any order, repeats allowed) + one parameter record per sample
         -> (image, speed, command, targets[, augmented uint8 frames]) on the device: what
         `augment_u8(cache[index], params)` and an index_select of the labels give.  The index is
-        checked on the host before anything is launched."""
+        checked on the host before anything is launched.  weather: one WEATHER_DTYPE record per
+        sample, applied to the source frames in the same launch (`augment_u8(..., weather=)`)."""
         if isinstance(index, torch.Tensor):
             index = index.cpu().numpy()
         index = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
@@ -589,15 +842,22 @@ class DeviceDataset:
         if params.shape != index.shape:
             raise RuntimeError("DeviceDataset.assemble: one parameter record per index")
         check_params(params, self.h, self.w)
+        if weather is not None:
+            if not isinstance(weather, np.ndarray) or weather.shape != index.shape:
+                raise RuntimeError("DeviceDataset.assemble: one weather record per index")
+            check_weather(weather, self.h, self.w)
         if not self.filled:
             raise RuntimeError("DeviceDataset.assemble: the cache is not filled (call fill())")
         b = index.size
         idx_dev = torch.from_numpy(index).to(self.device)
         par_dev = torch.from_numpy(params.view(np.uint8).reshape(b, AUG_DTYPE.itemsize)).to(
             self.device)
-        res = self._launch(idx_dev.data_ptr(), par_dev.data_ptr(), b, want_u8)
-        for t in (idx_dev, par_dev):
-            t.record_stream(torch.cuda.current_stream(self.device))
+        wx_dev = _records_to_device(weather, self.device) if weather is not None else None
+        res = self._launch(idx_dev.data_ptr(), par_dev.data_ptr(), b, want_u8,
+                           wx_dev.data_ptr() if wx_dev is not None else None)
+        for t in (idx_dev, par_dev, wx_dev):
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(self.device))
         return res
 
 
@@ -632,10 +892,15 @@ class CachedBatchLoader:
     no copy, pinned ring, event wait or host synchronisation per step.  Drawing a training
     epoch's parameters is host work of a few hundred microseconds a batch, so while one epoch
     runs the next one's plan is drawn on a background thread: the device does not idle at the
-    epoch boundary."""
+    epoch boundary.
+
+    weather (a `WeatherMix`): as for `BatchLoader`, from the same stream of its own, so the two
+    loaders stay bit-identical with it; the epoch's weather records (96 bytes a sample) are drawn
+    with the plan and go up with it, and every batch is one `cilrs_batch_assemble_weather`
+    launch.  train=False with a mix scores a validation set under that weather."""
 
     def __init__(self, dataset, indices, batch_size: int, train: bool, seed: int = 0,
-                 rank: int = 0, world_size: int = 1):
+                 rank: int = 0, world_size: int = 1, weather: "WeatherMix" = None):
         if not (0 <= rank < world_size):
             raise ValueError(f"rank {rank} outside world of {world_size}")
         self.ds, self.idx = dataset, np.asarray(indices)
@@ -644,6 +909,8 @@ class CachedBatchLoader:
         self.w = getattr(dataset, "w", IMG_WIDTH)
         self.rank, self.world = rank, world_size
         self.rng = np.random.default_rng([seed, rank])
+        self.weather = weather
+        self.wrng = np.random.default_rng([seed, rank, WEATHER_STREAM])
         self.gen = torch.Generator().manual_seed(seed)
         self.weights = class_balanced_weights(dataset.command[self.idx]) if train else None
         self._ahead = None
@@ -663,10 +930,15 @@ class CachedBatchLoader:
 
     def epoch_plan(self):
         """(order, params) of the next epoch, on the host: this rank's sample order (int64 [n])
-        and the augmentation records of its batches back to back (AUG_DTYPE [n]).  Touches no GPU;
-        advances the sampler and parameter streams exactly as one `BatchLoader` epoch does.
-        Successive calls, by the caller or by iteration, give successive epochs: a plan already
-        drawn ahead (`_plan_ahead`) is handed out before a new one is drawn."""
+        and the augmentation records of its batches back to back (AUG_DTYPE [n]); with a weather
+        mix (order, params, weather), the weather records (WEATHER_DTYPE [n]) last.  Touches no
+        GPU; advances the sampler, parameter and weather streams exactly as one `BatchLoader`
+        epoch does.  Successive calls, by the caller or by iteration, give successive epochs: a
+        plan already drawn ahead (`_plan_ahead`) is handed out before a new one is drawn."""
+        plan = self._next_plan()
+        return plan if self.weather is not None else plan[:2]
+
+    def _next_plan(self):
         ahead, self._ahead = self._ahead, None
         return ahead.result() if ahead is not None else self._draw_plan()
 
@@ -679,19 +951,26 @@ class CachedBatchLoader:
         order = np.ascontiguousarray(self._order(), dtype=np.int64)
         nb = len(self)
         order = order[:nb * self.bs]
-        parts = []
+        parts, wparts = [], []
         for b in range(nb):
             n = len(order[b * self.bs:(b + 1) * self.bs])
             parts.append(draw_aug_params(self.rng, n, self.h, self.w) if self.train
                          else identity_params(n))
+            if self.weather is not None:
+                wparts.append(self.weather.draw(self.wrng, n, self.h, self.w))
         params = np.concatenate(parts) if parts else np.zeros(0, dtype=AUG_DTYPE)
-        return order, params
+        weather = None
+        if self.weather is not None:
+            weather = np.concatenate(wparts) if wparts else np.zeros(0, dtype=WEATHER_DTYPE)
+        return order, params, weather
 
     def __iter__(self):
         ds = self.ds
-        order, params = self.epoch_plan()
+        order, params, weather = self._next_plan()
         ds.check_index(order)
         check_params(params, self.h, self.w)
+        if weather is not None:
+            check_weather(weather, self.h, self.w)
         if not ds.filled:
             raise RuntimeError("CachedBatchLoader: the dataset's cache is not filled")
         n = len(order)
@@ -702,8 +981,14 @@ class CachedBatchLoader:
         order_dev = torch.from_numpy(order).pin_memory().to(ds.device, non_blocking=True)
         params_dev = torch.from_numpy(params.view(np.uint8).reshape(n, AUG_DTYPE.itemsize)) \
             .pin_memory().to(ds.device, non_blocking=True)
+        weather_dev = None
+        if weather is not None:
+            weather_dev = torch.from_numpy(weather.view(np.uint8).reshape(
+                n, WEATHER_DTYPE.itemsize)).pin_memory().to(ds.device, non_blocking=True)
         if self.train:
             self._plan_ahead()
         ip, pp = order_dev.data_ptr(), params_dev.data_ptr()
+        wp = weather_dev.data_ptr() if weather_dev is not None else None
         for b0 in range(0, n, self.bs):
-            yield ds._launch(ip + b0 * 8, pp + b0 * AUG_DTYPE.itemsize, min(self.bs, n - b0))
+            yield ds._launch(ip + b0 * 8, pp + b0 * AUG_DTYPE.itemsize, min(self.bs, n - b0),
+                             weather_ptr=None if wp is None else wp + b0 * WEATHER_DTYPE.itemsize)

@@ -133,3 +133,49 @@ def evaluate(model, batches, **report_kw):
     for imgs, speeds, cmds, tgts in batches:
         ev.update(imgs, speeds, cmds, tgts)
     return ev.report(**report_kw)
+
+
+def weather_sweep(model, dataset, indices, conditions=None, severities=(0.25, 0.5, 0.75, 1.0),
+                  batch_size: int = 128, seed: int = 0, **report_kw):
+    """How far the metrics move under synthetic weather, without a simulator: `evaluate` over
+    `CachedBatchLoader(dataset, indices, train=False, weather=WeatherMix.fixed(name, severity))`
+    for every (condition, severity) cell, and once with no weather.  dataset: a filled
+    `DeviceDataset`.  conditions default to every name of `data.WEATHER_CONDITIONS` but "clear".
+
+    -> {"clear": report, name: {severity: report}, "steer_mae": {"clear": mae, name: {severity:
+    {"mae": mae, "ratio_to_clear": mae / clear mae}}}}.  The weather model is an image-space
+    restatement (include/cilrs_hip.h), not CARLA's renderer."""
+    from . import data as D
+    conditions = D.WEATHER_CONDITIONS[1:] if conditions is None else tuple(conditions)
+    for name in conditions:
+        if name not in D.WEATHER_CONDITIONS:
+            raise ValueError(f"unknown weather condition {name!r}; one of {D.WEATHER_CONDITIONS}")
+
+    def run(mix):
+        return evaluate(model, D.CachedBatchLoader(dataset, indices, batch_size, train=False,
+                                                   seed=seed, weather=mix), **report_kw)
+
+    def mae(rep):
+        return rep["overall_metrics"]["Steer"]["MAE"]
+
+    out = {"clear": run(None)}
+    base = mae(out["clear"])
+    table = {"clear": base}
+    for name in conditions:
+        out[name], table[name] = {}, {}
+        for s in severities:
+            s = float(s)
+            rep = run(D.WeatherMix.fixed(name, s))
+            out[name][s] = rep
+            table[name][s] = {"mae": mae(rep),
+                              "ratio_to_clear": mae(rep) / base if base > 0 else float("nan")}
+    out["steer_mae"] = table
+    return out
+
+
+def write_weather_sweep(path, model, dataset, indices, **kw):
+    """`weather_sweep` written as JSON (severities become string keys)."""
+    rep = weather_sweep(model, dataset, indices, **kw)
+    with open(path, "w") as f:
+        json.dump(rep, f, indent=2)
+    return rep

@@ -8,6 +8,14 @@
 // albumentations and cv2 are absent from the build image, so each step restates the libraries'
 // published behaviour (PARITY UNPINNED against them); the arithmetic below is mirrored operation
 // by operation by oracle/augment_oracle.py, which the tests compare against.
+//
+// Weather (cilrs_weather_params: tone, fog, rain) is a second, optional source stage in front of
+// those five: a pure function of the uint8 source pixel, its position and the sample's record,
+// applied wherever a source pixel is read -- the blur's taps included -- so the `_weather`
+// kernels give what the plain ones give on frames that were put through the weather first and
+// stored as uint8.  It is the <true> instantiation of the same pixel function; the plain entry
+// points keep the <false> one.  No transcendental runs here: what needs exp() is folded into the
+// record on the host (cilrs_mi355/data.py), and tests/_weather.py mirrors the arithmetic.
 #include "common.h"
 
 namespace cilrs {
@@ -17,11 +25,9 @@ namespace {
 
 __device__ __forceinline__ float clip255(float v) { return fminf(fmaxf(v, 0.f), 255.f); }
 
-// stages 1-2 for one pixel: brightness/contrast LUT, then the HSV shifts.  Returns uint8-valued
-// floats in rgb[3].
-__device__ __forceinline__ void colour_stages(const unsigned char* __restrict__ p,
-                                              const cilrs_aug_params& a, float rgb[3]) {
-    float c[3] = {(float)p[0], (float)p[1], (float)p[2]};
+// stages 1-2 for one pixel: brightness/contrast LUT, then the HSV shifts, in place on the
+// uint8-valued floats c[3].
+__device__ __forceinline__ void colour_stages(const cilrs_aug_params& a, float c[3]) {
     if (a.rbc_on) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -74,7 +80,14 @@ __device__ __forceinline__ void colour_stages(const unsigned char* __restrict__ 
         c[1] = rintf(clip255(G));
         c[2] = rintf(clip255(B));
     }
-    rgb[0] = c[0]; rgb[1] = c[1]; rgb[2] = c[2];
+}
+
+// blur_w[|d|] as a select among the three weights read beforehand: an index into the record
+// computed at run time would put the whole record into scratch memory
+__device__ __forceinline__ float blur_tap(const float w0, const float w1, const float w2,
+                                          const int d) {
+    const int ad = d < 0 ? -d : d;
+    return ad == 0 ? w0 : (ad == 1 ? w1 : w2);
 }
 
 __device__ __forceinline__ int reflect101(int i, const int n) {
@@ -90,16 +103,85 @@ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
     return x ^ (x >> 31);
 }
 
+// Weather for source pixel (y, x), in place on the uint8-valued floats c[3]: tone, fog, rain.
+__device__ __forceinline__ void weather_stages(const cilrs_weather_params& w, const int y,
+                                               const int x, float c[3]) {
+    if (w.tone_on) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            float t = c[k] * w.gain[k];
+            t = t + w.lift255[k];
+            c[k] = truncf(clip255(t));
+        }
+    }
+    if (w.fog_on) {
+        // flat-ground pseudo-depth from the row alone, d in (0, 1]; transmission linear in d
+        const float yf = (float)y;
+        float d = 1.f;
+        if (yf > w.fog_horizon) d = w.fog_near / fmaxf(yf - w.fog_horizon, w.fog_near);
+        float t = w.fog_t1 * d;
+        t = w.fog_t0 + t;
+        t = fminf(fmaxf(t, 0.f), 1.f);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            float u = c[k] - w.fog_rgb255[k];
+            u = u * t;
+            u = w.fog_rgb255[k] + u;
+            c[k] = rintf(clip255(u));
+        }
+    }
+    const int L = min(w.rain_len, 16);
+    if (L > 0) {
+        // tail position j of a streak covers (y, x) when (y - j, x - floor(j * slant / 16)) is a
+        // head; the smallest covering j gives the largest alpha.  L is uniform over the sample, so
+        // the loop runs to its end on every lane and the first hit is selected, not branched on.
+        int jmin = L;
+        for (int j = L - 1; j >= 0; --j) {
+            const int hy = y - j, hx = x - ((j * w.rain_slant_q4) >> 4);
+            const unsigned long long e =
+                (unsigned long long)(hy + 64) * 65536ull + (unsigned long long)(hx + 64);
+            const unsigned long long hsh = splitmix64(w.rain_seed + e * 0xD1B54A32D192ED03ull);
+            jmin = ((unsigned int)(hsh >> 40) < w.rain_thresh24) ? j : jmin;
+        }
+        if (jmin < L) {
+            float a = (float)(L - jmin) / (float)L;
+            a = w.rain_alpha * a;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                float u = w.rain_v255 - c[k];
+                u = a * u;
+                u = c[k] + u;
+                c[k] = rintf(clip255(u));
+            }
+        }
+    }
+}
+
+// Source pixel (y, x) of one sample as uint8-valued floats: the stored bytes, behind the sample's
+// weather when WX.  `w` is not read otherwise.
+template <bool WX>
+__device__ __forceinline__ void source_pixel(const unsigned char* __restrict__ img,
+                                             const cilrs_weather_params& w, const int y,
+                                             const int x, const int W, float c[3]) {
+    const unsigned char* p = img + ((size_t)y * W + x) * 3;
+    c[0] = (float)p[0]; c[1] = (float)p[1]; c[2] = (float)p[2];
+    if constexpr (WX) weather_stages(w, y, x, c);
+}
+
 // Mean / std of the final Normalize, passed by value to the kernels.
 struct NormConsts {
     float m0, m1, m2, d0, d1, d2;
 };
 
 // Every stage for output pixel (y, x) of one sample: `img` is that sample's uint8 [H][W][3] source
-// frame, `i` the pixel's index in the output batch.  Both kernels below are this function behind
-// two ways of finding `img`, so their results are the same element for element.
+// frame, `i` the pixel's index in the output batch.  The kernels below are this function behind
+// two ways of finding `img`, so their results are the same element for element; WX puts the
+// sample's weather `wx` in front of every source pixel read.
+template <bool WX>
 __device__ __forceinline__ void augment_pixel(const unsigned char* __restrict__ img,
-                                              const cilrs_aug_params& a, const int y, const int x,
+                                              const cilrs_aug_params& a,
+                                              const cilrs_weather_params& wx, const int y,
+                                              const int x,
                                               const int H, const int W, const size_t i,
                                               float* __restrict__ out_f32,
                                               unsigned char* __restrict__ out_u8,
@@ -109,6 +191,7 @@ __device__ __forceinline__ void augment_pixel(const unsigned char* __restrict__ 
         // separable Gaussian written as one fixed-order 2-D sum over the colour-adjusted taps
         // (cv2.GaussianBlur semantics: reflect-101 border)
         const int r = min(a.blur_k >> 1, 2);
+        const float w0 = a.blur_w[0], w1 = a.blur_w[1], w2 = a.blur_w[2];
         float acc[3] = {0.f, 0.f, 0.f};
         for (int dy = -r; dy <= r; ++dy) {
             const int yy = reflect101(y + dy, H);
@@ -116,19 +199,21 @@ __device__ __forceinline__ void augment_pixel(const unsigned char* __restrict__ 
             for (int dx = -r; dx <= r; ++dx) {
                 const int xx = reflect101(x + dx, W);
                 float t[3];
-                colour_stages(img + ((size_t)yy * W + xx) * 3, a, t);
-                const float w = a.blur_w[dx < 0 ? -dx : dx];
+                source_pixel<WX>(img, wx, yy, xx, W, t);
+                colour_stages(a, t);
+                const float w = blur_tap(w0, w1, w2, dx);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) row[k] = row[k] + w * t[k];
             }
-            const float w = a.blur_w[dy < 0 ? -dy : dy];
+            const float w = blur_tap(w0, w1, w2, dy);
 #pragma unroll
             for (int k = 0; k < 3; ++k) acc[k] = acc[k] + w * row[k];
         }
 #pragma unroll
         for (int k = 0; k < 3; ++k) c[k] = rintf(clip255(acc[k]));
     } else {
-        colour_stages(img + ((size_t)y * W + x) * 3, a, c);
+        source_pixel<WX>(img, wx, y, x, W, c);
+        colour_stages(a, c);
     }
     if (a.noise_std255 > 0.f) {
         // per-channel Gaussian noise: Box-Muller on a counter-based hash of (seed, element)
@@ -143,8 +228,10 @@ __device__ __forceinline__ void augment_pixel(const unsigned char* __restrict__ 
             c[k] = rintf(clip255(c[k] + n * a.noise_std255));
         }
     }
-    for (int hI = 0; hI < min(a.nholes, 3); ++hI)
-        if (y >= a.hole_y0[hI] && y < a.hole_y1[hI] && x >= a.hole_x0[hI] && x < a.hole_x1[hI])
+#pragma unroll
+    for (int hI = 0; hI < 3; ++hI)               // unrolled: constant indices into the record
+        if (hI < a.nholes && y >= a.hole_y0[hI] && y < a.hole_y1[hI] && x >= a.hole_x0[hI] &&
+            x < a.hole_x1[hI])
             c[0] = c[1] = c[2] = 0.f;            // CoarseDropout fill = 0
     if (out_u8) {
         unsigned char* o = out_u8 + i * 3;
@@ -158,15 +245,20 @@ __device__ __forceinline__ void augment_pixel(const unsigned char* __restrict__ 
     }
 }
 
+// `weather` [B] is read by the WX instantiation only (the plain entry point passes nullptr).
+template <bool WX>
 __global__ __launch_bounds__(256) void augment_u8_kernel(
     const unsigned char* __restrict__ frames, const cilrs_aug_params* __restrict__ params,
-    const int B, const int H, const int W, float* __restrict__ out_f32,
-    unsigned char* __restrict__ out_u8, const NormConsts nc) {
+    const cilrs_weather_params* __restrict__ weather, const int B, const int H, const int W,
+    float* __restrict__ out_f32, unsigned char* __restrict__ out_u8, const NormConsts nc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * H * W) return;
     const int x = i % W, y = (i / W) % H, b = i / (W * H);
     const cilrs_aug_params a = params[b];
-    augment_pixel(frames + (size_t)b * H * W * 3, a, y, x, H, W, (size_t)i, out_f32, out_u8, nc);
+    cilrs_weather_params w;
+    if constexpr (WX) w = weather[b];
+    augment_pixel<WX>(frames + (size_t)b * H * W * 3, a, w, y, x, H, W, (size_t)i, out_f32, out_u8,
+                      nc);
 }
 
 // A whole training batch from the device-resident dataset: sample b of the batch is frame
@@ -183,11 +275,13 @@ struct AssembleLabels {
     float* out_targets;
 };
 
+template <bool WX>
 __global__ __launch_bounds__(256) void batch_assemble_kernel(
     const unsigned char* __restrict__ cache, const long long n_frames,
-    const long long* __restrict__ index, const cilrs_aug_params* __restrict__ params, const int B,
-    const int H, const int W, float* __restrict__ out_f32, unsigned char* __restrict__ out_u8,
-    const AssembleLabels lab, const NormConsts nc) {
+    const long long* __restrict__ index, const cilrs_aug_params* __restrict__ params,
+    const cilrs_weather_params* __restrict__ weather, const int B, const int H, const int W,
+    float* __restrict__ out_f32, unsigned char* __restrict__ out_u8, const AssembleLabels lab,
+    const NormConsts nc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * H * W) return;
     const int x = i % W, y = (i / W) % H, b = i / (W * H);
@@ -202,22 +296,58 @@ __global__ __launch_bounds__(256) void batch_assemble_kernel(
         }
     }
     const cilrs_aug_params a = params[b];
-    augment_pixel(cache + (size_t)src * H * W * 3, a, y, x, H, W, (size_t)i, out_f32, out_u8, nc);
+    cilrs_weather_params w;
+    if constexpr (WX) w = weather[b];
+    augment_pixel<WX>(cache + (size_t)src * H * W * 3, a, w, y, x, H, W, (size_t)i, out_f32, out_u8,
+                      nc);
 }
 
 constexpr NormConsts kNorm = {kImageMean[0], kImageMean[1], kImageMean[2],
                               kImageStd[0],  kImageStd[1],  kImageStd[2]};
 
+// rain heads are hashed from (row + 64, column + 64) packed into 16 bits each
+constexpr int kWeatherMaxWidth = 65536 - 128;
+
+template <bool WX>
+int launch_augment(const unsigned char* frames, const cilrs_aug_params* params,
+                   const cilrs_weather_params* weather, int B, int H, int W, float* out_f32,
+                   unsigned char* out_u8, hipStream_t s) {
+    CILRS_CHECK(B >= 1 && H >= 2 && W >= 2 && (size_t)B * H * W < (1u << 31),
+                "augment: bad batch geometry");
+    augment_u8_kernel<WX><<<cdiv(B * H * W, 256), 256, 0, s>>>(frames, params, weather, B, H, W,
+                                                               out_f32, out_u8, kNorm);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
+template <bool WX>
+int launch_assemble(const unsigned char* cache, long long n_frames, const AssembleLabels& lab,
+                    const long long* index, const cilrs_aug_params* params,
+                    const cilrs_weather_params* weather, int B, int H, int W, float* out_f32,
+                    unsigned char* out_u8, hipStream_t s) {
+    // the guard is on the BATCH (thread and output indices are int); the cache is addressed in
+    // 64 bits and may be any size
+    CILRS_CHECK(B >= 1 && H >= 2 && W >= 2 && (size_t)B * H * W < (1u << 31),
+                "batch_assemble: bad batch geometry");
+    CILRS_CHECK(n_frames >= 1, "batch_assemble: empty frame cache");
+    batch_assemble_kernel<WX><<<cdiv(B * H * W, 256), 256, 0, s>>>(
+        cache, n_frames, index, params, weather, B, H, W, out_f32, out_u8, lab, kNorm);
+    CILRS_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace
 
 int launch_augment_u8(const unsigned char* frames, const cilrs_aug_params* params, int B, int H,
                       int W, float* out_f32, unsigned char* out_u8, hipStream_t s) {
-    CILRS_CHECK(B >= 1 && H >= 2 && W >= 2 && (size_t)B * H * W < (1u << 31),
-                "augment: bad batch geometry");
-    augment_u8_kernel<<<cdiv(B * H * W, 256), 256, 0, s>>>(frames, params, B, H, W, out_f32, out_u8,
-                                                           kNorm);
-    CILRS_LAUNCH_CHECK();
-    return 0;
+    return launch_augment<false>(frames, params, nullptr, B, H, W, out_f32, out_u8, s);
+}
+
+int launch_augment_weather_u8(const unsigned char* frames, const cilrs_aug_params* params,
+                              const cilrs_weather_params* weather, int B, int H, int W,
+                              float* out_f32, unsigned char* out_u8, hipStream_t s) {
+    CILRS_CHECK(W <= kWeatherMaxWidth, "augment_weather: width %d above %d", W, kWeatherMaxWidth);
+    return launch_augment<true>(frames, params, weather, B, H, W, out_f32, out_u8, s);
 }
 
 int launch_batch_assemble(const unsigned char* cache, long long n_frames, const float* speed,
@@ -225,16 +355,23 @@ int launch_batch_assemble(const unsigned char* cache, long long n_frames, const 
                           const cilrs_aug_params* params, int B, int H, int W, float* out_f32,
                           unsigned char* out_u8, float* out_speed, long long* out_command,
                           float* out_targets, hipStream_t s) {
-    // the guard is on the BATCH (thread and output indices are int); the cache is addressed in
-    // 64 bits and may be any size
-    CILRS_CHECK(B >= 1 && H >= 2 && W >= 2 && (size_t)B * H * W < (1u << 31),
-                "batch_assemble: bad batch geometry");
-    CILRS_CHECK(n_frames >= 1, "batch_assemble: empty frame cache");
     const AssembleLabels lab = {speed, command, targets, out_speed, out_command, out_targets};
-    batch_assemble_kernel<<<cdiv(B * H * W, 256), 256, 0, s>>>(cache, n_frames, index, params, B, H,
-                                                               W, out_f32, out_u8, lab, kNorm);
-    CILRS_LAUNCH_CHECK();
-    return 0;
+    return launch_assemble<false>(cache, n_frames, lab, index, params, nullptr, B, H, W, out_f32,
+                                  out_u8, s);
+}
+
+int launch_batch_assemble_weather(const unsigned char* cache, long long n_frames,
+                                  const float* speed, const long long* command,
+                                  const float* targets, const long long* index,
+                                  const cilrs_aug_params* params,
+                                  const cilrs_weather_params* weather, int B, int H, int W,
+                                  float* out_f32, unsigned char* out_u8, float* out_speed,
+                                  long long* out_command, float* out_targets, hipStream_t s) {
+    CILRS_CHECK(W <= kWeatherMaxWidth, "batch_assemble_weather: width %d above %d", W,
+                kWeatherMaxWidth);
+    const AssembleLabels lab = {speed, command, targets, out_speed, out_command, out_targets};
+    return launch_assemble<true>(cache, n_frames, lab, index, params, weather, B, H, W, out_f32,
+                                 out_u8, s);
 }
 
 }  // namespace cilrs

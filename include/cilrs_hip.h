@@ -1016,6 +1016,51 @@ int cilrs_batch_assemble(const uint8_t* cache, int64_t n_frames, const float* sp
                          float* out_f32, uint8_t* out_u8, float* out_speed, int64_t* out_command,
                          float* out_targets, void* stream);
 
+/* ---- weather on the device: tone, fog and rain in front of the augmentation --------------------
+ * The reference scores its checkpoint under five weather profiles (configs/weather_config.json:
+ * clear, rain, fog, night, hardrain) and names domain randomisation as a way forward; CARLA's
+ * renderer is not available here, so this is a parity-unpinned image-space model.  Weather is a pure
+ * function of the uint8 source pixel c, its position (y, x) and the sample's record, applied before
+ * the colour stages above to every source pixel they read (the blur's taps included).  All float32,
+ * one rounding per operation, nothing transcendental: what needs exp() is folded into the record by
+ * the host (cilrs_mi355/data.py).  In order:
+ *   tone  c_k = trunc(clip255(c_k * gain_k + lift255_k))
+ *   fog   d = 1 for (float)y <= fog_horizon, else fog_near / max((float)y - fog_horizon, fog_near);
+ *         t = clip(fog_t0 + fog_t1 * d, 0, 1);  c_k = rint(clip255(A_k + (c_k - A_k) * t)), A = fog_rgb255
+ *   rain  a streak head sits at integer (yy, xx), inside the frame or not, when
+ *         splitmix64(rain_seed + ((yy + 64) * 65536 + (xx + 64)) * 0xD1B54A32D192ED03) >> 40 < rain_thresh24;
+ *         tail position j in [0, rain_len) covers (y, x) when (y - j, x - ((j * rain_slant_q4) >> 4))
+ *         is a head; with the smallest covering j, a = rain_alpha * ((float)(L - j) / (float)L) and
+ *         c_k = rint(clip255(c_k + a * (rain_v255 - c_k))); uncovered pixels are untouched
+ * A record with all three off (zeroes) is the identity. */
+typedef struct {
+    uint64_t rain_seed;      /* key of this sample's streak heads                                  */
+    int tone_on;
+    float gain[3], lift255[3];
+    int fog_on;
+    float fog_t0, fog_t1;    /* transmission = clip(t0 + t1 * d)                                   */
+    float fog_horizon, fog_near;     /* rows                                                       */
+    float fog_rgb255[3];     /* airlight                                                           */
+    int rain_len;            /* 0 = off, at most 16                                                */
+    int rain_slant_q4;       /* columns per 16 rows, in [-16, 16]                                  */
+    uint32_t rain_thresh24;  /* head probability * 2^24                                            */
+    float rain_alpha, rain_v255;
+    int reserved[2];
+} cilrs_weather_params;      /* 96 bytes */
+
+/* cilrs_augment_u8 / cilrs_batch_assemble with weather [B] (device) in front, one launch each:
+ * element for element what the plain entry point gives on frames that were first put through the
+ * weather and stored as uint8 (the kernels share their device code).  width <= 65,408. */
+int cilrs_augment_weather_u8(const uint8_t* frames, const cilrs_aug_params* params,
+                             const cilrs_weather_params* weather, int batch, int height, int width,
+                             float* out_f32, uint8_t* out_u8, void* stream);
+int cilrs_batch_assemble_weather(const uint8_t* cache, int64_t n_frames, const float* speed,
+                                 const int64_t* command, const float* targets,
+                                 const int64_t* index, const cilrs_aug_params* params,
+                                 const cilrs_weather_params* weather, int batch, int height,
+                                 int width, float* out_f32, uint8_t* out_u8, float* out_speed,
+                                 int64_t* out_command, float* out_targets, void* stream);
+
 /* ---- evaluation report accumulators (metrics schema evaluation_report.json:1-73; the reference
  *      ships the report, not the code that made it) ---------------------------------------------
  * acc: cilrs_eval_acc_doubles() doubles on the device, zeroed by the caller before the first
