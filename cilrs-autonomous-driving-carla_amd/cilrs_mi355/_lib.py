@@ -169,6 +169,9 @@ SIGNATURES = {
     "cilrs_augment_weather_u8": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "cilrs_batch_assemble_weather": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp,
                                            vp, vp, vp]),
+    "cilrs_augment_view_u8": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "cilrs_batch_assemble_view": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp,
+                                        vp, vp, vp, vp]),
     "cilrs_eval_acc_doubles": (i32, []),
     "cilrs_eval_accumulate": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, vp]),
     "cilrs_net_profile_enable": (i32, [vp, i32]),

@@ -15,6 +15,11 @@ for bit, with one `cilrs_batch_assemble` launch each.
 Both loaders take a `WeatherMix`: per-sample weather records (tone, fog, rain: the reference's
 weather profiles as an image-space model) applied to the source frames inside the same launch
 (`cilrs_augment_weather_u8`, `cilrs_batch_assemble_weather`).  Without one nothing differs.
+
+Both also take a `ViewShift`: per-sample viewpoint records (a camera moved sideways and yawed,
+as two homographies split at the horizon) applied in front of the weather in the same launch
+(`cilrs_augment_view_u8`, `cilrs_batch_assemble_view`), with the steer label corrected by a
+pure-pursuit rule.  Without one nothing differs either.
 """
 from __future__ import annotations
 
@@ -284,6 +289,187 @@ def check_weather(p: np.ndarray, height: int, width: int):
         raise RuntimeError("weather: rain_v255 must lie in [0, 255]")
 
 
+# ---- viewpoint: lateral offset and yaw in front of the weather -----------------------------------
+# numpy mirror of `cilrs_view_params` (include/cilrs_hip.h, where the warp is defined), 96 bytes
+VIEW_DTYPE = np.dtype([
+    ("on", np.int32), ("split_row", np.float32), ("far", np.float32, 9),
+    ("ground", np.float32, 9), ("steer_delta", np.float32), ("lateral_m", np.float32),
+    ("yaw_rad", np.float32), ("reserved", np.int32)], align=True)
+assert VIEW_DTYPE.itemsize == 96
+
+VIEW_STREAM = 0x56494557              # "VIEW": third key of the loaders' viewpoint record stream
+VIEW_MIN_W = 0.25                     # smallest homogeneous w a record may reach inside the frame
+SPEED_NORM_KMH = 40.0                 # speed_normalized = km/h / 40 (model/collect_data.py)
+
+
+class CameraModel:
+    """The reference's camera (model/collect_data.py Config, model/prepare_dataset.py): 800x600 at
+    100 degrees horizontal field of view, no pitch, `height_m` above a flat road, resized to the
+    training frame without cropping -- so the two focal lengths differ."""
+
+    def __init__(self, width0: int = 800, height0: int = 600, fov_deg: float = 100.0,
+                 height_m: float = 1.4):
+        self.width0, self.height0 = int(width0), int(height0)
+        self.fov_deg, self.height_m = float(fov_deg), float(height_m)
+        if not (0.0 < self.fov_deg < 180.0) or not (self.height_m > 0.0):
+            raise ValueError("CameraModel: fov_deg in (0, 180) and height_m > 0")
+        self.f0 = 0.5 * self.width0 / np.tan(np.radians(0.5 * self.fov_deg))
+
+    def intrinsics(self, height: int, width: int):
+        """(fx, fy, cx, cy) of the H x W training frame, float64."""
+        return (self.f0 * width / self.width0, self.f0 * height / self.height0,
+                0.5 * (width - 1), 0.5 * (height - 1))
+
+
+def identity_view(n: int) -> np.ndarray:
+    """n records that are off (and hold the identity map): under them the view entry points give
+    what the weather / plain ones give."""
+    p = np.zeros(n, dtype=VIEW_DTYPE)
+    p["far"] = p["ground"] = np.eye(3, dtype=np.float32).reshape(9)
+    return p
+
+
+def steer_correction(lateral_m, yaw_rad, speed_norm, lookahead_s: float = 1.0,
+                     min_lookahead_m: float = 4.0, wheelbase_m: float = 2.875,
+                     max_steer_deg: float = 70.0) -> np.ndarray:
+    """Pure pursuit towards the expert's path from the displaced pose, float64 [n]: the point the
+    expert reaches after the look-ahead L = max(lookahead_s * v, min_lookahead_m) lies
+    yt = -t cos(psi) - L sin(psi) to the right of the virtual camera's axis, and the bicycle model
+    steers atan(wheelbase * 2 yt / L^2), as a share of the largest wheel angle.  v is the speed in
+    m/s (speed_norm * 40 km/h).  The defaults are the reference's Tesla Model 3 in CARLA and a
+    one-second look-ahead: stated assumptions, not measured ones."""
+    t = np.asarray(lateral_m, dtype=np.float64)
+    psi = np.asarray(yaw_rad, dtype=np.float64)
+    v = np.asarray(speed_norm, dtype=np.float64) * SPEED_NORM_KMH / 3.6
+    t, psi, v = np.broadcast_arrays(t, psi, v)
+    look = np.maximum(lookahead_s * v, min_lookahead_m)
+    yt = 0.0 - t * np.cos(psi) - look * np.sin(psi)              # (0, 0) gives +0.0
+    return np.arctan(wheelbase_m * 2.0 * yt / (look * look)) / np.radians(max_steer_deg)
+
+
+def view_records(lateral_m, yaw_rad, speed_norm, height: int = IMG_HEIGHT,
+                 width: int = IMG_WIDTH, camera: CameraModel = None, **steer_kw) -> np.ndarray:
+    """One record (on = 1) per sample for a virtual camera moved `lateral_m` to the right and yawed
+    `yaw_rad` to the right of the recording one: X' = R (X - T), T = (t, 0, 0), camera x right,
+    y down, z forward.  Points at infinity map by K R K^-1 (`far`), points of the flat road
+    n^T X = h, n = (0, 1, 0), by K R (I - T n^T / h) K^-1 (`ground`); both are built in float64,
+    inverted in closed form ((I - T n^T / h)^-1 = I + T n^T / h because n^T T = 0), scaled so that
+    w = 1 at the principal point and cast to float32.  The horizon row (H-1)/2 stays put under
+    this motion and the two maps agree on it: it is the split row.  A zero motion gives the
+    identity map exactly.  steer_kw: the arguments of `steer_correction`."""
+    camera = CameraModel() if camera is None else camera
+    t, psi, spd = np.broadcast_arrays(np.atleast_1d(np.asarray(lateral_m, dtype=np.float64)),
+                                      np.atleast_1d(np.asarray(yaw_rad, dtype=np.float64)),
+                                      np.atleast_1d(np.asarray(speed_norm, dtype=np.float64)))
+    n = len(t)
+    fx, fy, cx, cy = camera.intrinsics(height, width)
+    K = np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
+    Kinv = np.array([[1.0 / fx, 0.0, -cx / fx], [0.0, 1.0 / fy, -cy / fy], [0.0, 0.0, 1.0]])
+    centre = np.array([cx, cy, 1.0])
+    p = identity_view(n)
+    p["on"] = 1
+    p["split_row"] = cy
+    p["lateral_m"], p["yaw_rad"] = t, psi
+    p["steer_delta"] = steer_correction(t, psi, spd, **steer_kw)
+    eye = np.eye(3)
+    c, s = np.cos(psi), np.sin(psi)
+    Rt = np.zeros((n, 3, 3))                                                # R^T: R yaws right
+    Rt[:, 0, 0], Rt[:, 0, 2], Rt[:, 1, 1], Rt[:, 2, 0], Rt[:, 2, 2] = c, s, 1.0, -s, c
+    shear = np.broadcast_to(eye, (n, 3, 3)).copy()                          # I + T n^T / h
+    shear[:, 0, 1] = t / camera.height_m
+    for name, B in (("far", Rt), ("ground", shear @ Rt)):
+        M = K @ B @ Kinv
+        M = M / (M[:, 2, :] @ centre)[:, None, None]
+        M[(B == eye).all(axis=(1, 2))] = eye                                # K I K^-1, exactly
+        p[name] = M.reshape(n, 9)
+    return p
+
+
+def _view_w_min(p: np.ndarray, height: int, width: int) -> np.ndarray:
+    """Smallest w of each record over the rows its two matrices serve, float64 [n]; w is linear in
+    (x, y), so the corners of the two row bands suffice."""
+    split = p["split_row"].astype(np.float64)
+    last_far = np.clip(np.floor(split), -1, height - 1)          # far: rows 0 .. last_far
+    wmin = np.full(len(p), np.inf)
+    for name, y_lo, y_hi in (("far", np.zeros(len(p)), last_far),
+                             ("ground", last_far + 1, np.full(len(p), height - 1.0))):
+        m = p[name].astype(np.float64)
+        served = y_hi >= y_lo
+        for y in (y_lo, y_hi):
+            for x in (0.0, width - 1.0):
+                w = m[:, 6] * x + m[:, 7] * y + m[:, 8]
+                wmin = np.where(served, np.minimum(wmin, w), wmin)
+    return wmin
+
+
+def check_view(p: np.ndarray, height: int, width: int):
+    if not isinstance(p, np.ndarray) or p.dtype != VIEW_DTYPE:
+        raise RuntimeError("view records must use data.VIEW_DTYPE")
+    for k in ("split_row", "far", "ground", "steer_delta", "lateral_m", "yaw_rad"):
+        if not np.isfinite(p[k]).all():
+            raise RuntimeError(f"view: {k} must be finite")
+    if not np.isin(p["on"], (0, 1)).all():
+        raise RuntimeError("view: on must be 0 or 1")
+    if (p["split_row"] < -1).any() or (p["split_row"] > height).any():
+        raise RuntimeError(f"view: split_row must lie in [-1, {height}]")
+    if (np.abs(p["steer_delta"]) > 2).any():
+        raise RuntimeError("view: |steer_delta| must be at most 2")
+    if len(p) and (_view_w_min(p, height, width) < VIEW_MIN_W).any():
+        raise RuntimeError(f"view: w falls below {VIEW_MIN_W} inside the frame (the motion is too "
+                           "large for this camera)")
+
+
+class ViewShift:
+    """What viewpoint a loader draws: with probability p a sample is seen from a camera moved
+    uniformly in `lateral_m` = (low, high) metres and yawed uniformly in `yaw_deg` = (low, high)
+    degrees, and its steer label is corrected by `steer_correction`; the other samples get an off
+    record.  steer_kw: the arguments of `steer_correction`."""
+
+    def __init__(self, p: float = 0.5, lateral_m=(-0.5, 0.5), yaw_deg=(-5.0, 5.0),
+                 camera: CameraModel = None, **steer_kw):
+        if not (0.0 <= p <= 1.0):
+            raise ValueError("ViewShift: p must lie in [0, 1]")
+        self.p = float(p)
+        self.lateral_m = (float(lateral_m[0]), float(lateral_m[1]))
+        self.yaw_deg = (float(yaw_deg[0]), float(yaw_deg[1]))
+        if self.lateral_m[0] > self.lateral_m[1] or self.yaw_deg[0] > self.yaw_deg[1]:
+            raise ValueError("ViewShift: ranges are (low, high) with low <= high")
+        self.camera = CameraModel() if camera is None else camera
+        steer_correction(0.0, 0.0, 0.0, **steer_kw)            # refuses an unknown argument now
+        self.steer_kw = steer_kw
+
+    @classmethod
+    def fixed(cls, lateral_m: float, yaw_deg: float, **kw):
+        """Every sample from the one viewpoint (lateral_m, yaw_deg)."""
+        return cls(1.0, (lateral_m, lateral_m), (yaw_deg, yaw_deg), **kw)
+
+    def draw(self, rng: np.random.Generator, n: int, speed_norm, height: int = IMG_HEIGHT,
+             width: int = IMG_WIDTH) -> np.ndarray:
+        """n records for samples of normalised speed `speed_norm` [n]; advances `rng` by the same
+        amount whatever is drawn."""
+        speed_norm = np.asarray(speed_norm, dtype=np.float64).reshape(-1)
+        if speed_norm.shape != (n,):
+            raise RuntimeError("ViewShift.draw: one speed per sample")
+        on = rng.random(n) < self.p
+        lat = rng.uniform(self.lateral_m[0], self.lateral_m[1], n)
+        yaw = np.radians(rng.uniform(self.yaw_deg[0], self.yaw_deg[1], n))
+        rec = identity_view(n)
+        if on.any():
+            rec[on] = view_records(lat[on], yaw[on], speed_norm[on], height, width, self.camera,
+                                   **self.steer_kw)
+        return rec
+
+
+def correct_steer(targets: np.ndarray, view: np.ndarray) -> np.ndarray:
+    """targets float32 [n, 3] with the steer column corrected as `cilrs_batch_assemble_view` does:
+    one float32 add and a clip to [-1, 1] where the record is on, a copy where it is off."""
+    out = np.array(targets, dtype=np.float32, copy=True)
+    on = view["on"] != 0
+    moved = out[on, 0] + view["steer_delta"][on]
+    out[on, 0] = np.fmin(np.fmax(moved, np.float32(-1)), np.float32(1))
+    return out
+
+
 def _records_to_device(rec: np.ndarray, device) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(rec).view(np.uint8).reshape(
         len(rec), rec.dtype.itemsize)).to(device, non_blocking=False)
@@ -291,14 +477,19 @@ def _records_to_device(rec: np.ndarray, device) -> torch.Tensor:
 
 def augment_u8(frames_u8: torch.Tensor, params: np.ndarray, want_u8: bool = False,
                params_dev: torch.Tensor = None, weather: np.ndarray = None,
-               weather_dev: torch.Tensor = None):
+               weather_dev: torch.Tensor = None, view: np.ndarray = None,
+               view_dev: torch.Tensor = None):
     """frames uint8 [B,H,W,3] on the device + per-sample parameters -> normalised image as the
     logical NCHW float tensor `CILRS.forward` takes (a permuted view of the NHWC result, like the
     reference's permute at notebook.ipynb:413) [, augmented uint8 frames].
 
     weather: one WEATHER_DTYPE record per frame, applied to the source pixels in the same launch
     (`cilrs_augment_weather_u8`); None is the plain `cilrs_augment_u8`.  weather_dev: the same
-    records already on the device (uint8 [B, 96]), like params_dev."""
+    records already on the device (uint8 [B, 96]), like params_dev.
+
+    view / view_dev: one VIEW_DTYPE record per frame, likewise; the frames are seen from the
+    records' viewpoints before the weather and everything else (`cilrs_augment_view_u8`, with or
+    without weather).  The label correction is the caller's (`correct_steer`)."""
     if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.size(3) != 3 \
             or frames_u8.device.type != "cuda":
         raise RuntimeError("augment_u8: frames must be uint8 [B,H,W,3] on the GPU (no CPU fallback)")
@@ -312,6 +503,12 @@ def augment_u8(frames_u8: torch.Tensor, params: np.ndarray, want_u8: bool = Fals
         if weather.shape != (b,):
             raise RuntimeError("augment_u8: one weather record per frame")
         check_weather(weather, h, w)
+    if view is None and view_dev is not None:
+        raise RuntimeError("augment_u8: view_dev needs the host records in `view` too")
+    if view is not None:
+        if not isinstance(view, np.ndarray) or view.shape != (b,):
+            raise RuntimeError("augment_u8: one view record per frame")
+        check_view(view, h, w)
     frames_u8 = frames_u8.contiguous()
     # params_dev: the same records already on the device (uint8 [B, 112]; the loader uploads them
     # from pinned memory on its copy stream).  Without it they go up from pageable memory, which
@@ -336,10 +533,23 @@ def augment_u8(frames_u8: torch.Tensor, params: np.ndarray, want_u8: bool = Fals
         wdev = weather_dev.contiguous()
     elif weather is not None:
         wdev = _records_to_device(weather, frames_u8.device)
+    vdev = None
+    if view_dev is not None:
+        if view_dev.dtype != torch.uint8 or tuple(view_dev.shape) != (b, VIEW_DTYPE.itemsize) \
+                or view_dev.device != frames_u8.device:
+            raise RuntimeError("augment_u8: view_dev must be uint8 [B, %d] on the frames' device"
+                               % VIEW_DTYPE.itemsize)
+        vdev = view_dev.contiguous()
+    elif view is not None:
+        vdev = _records_to_device(view, frames_u8.device)
     out = torch.empty(b, h, w, 3, dtype=torch.float32, device=frames_u8.device)
     out8 = torch.empty_like(frames_u8) if want_u8 else None
     stream = torch.cuda.current_stream(frames_u8.device).cuda_stream
-    if wdev is None:
+    if vdev is not None:
+        L.check(L.lib().cilrs_augment_view_u8(L.ptr(frames_u8), L.ptr(pdev), L.ptr(wdev),
+                                              L.ptr(vdev), b, h, w, L.ptr(out), L.ptr(out8),
+                                              C.c_void_p(stream)))
+    elif wdev is None:
         L.check(L.lib().cilrs_augment_u8(L.ptr(frames_u8), L.ptr(pdev), b, h, w, L.ptr(out),
                                          L.ptr(out8), C.c_void_p(stream)))
     else:
@@ -368,6 +578,27 @@ def weather_u8(frames_u8: torch.Tensor, weather: np.ndarray) -> torch.Tensor:
     stream = torch.cuda.current_stream(frames_u8.device).cuda_stream
     L.check(L.lib().cilrs_augment_weather_u8(L.ptr(frames_u8), L.ptr(pdev), L.ptr(wdev), b, h, w,
                                              None, L.ptr(out8), C.c_void_p(stream)))
+    return out8
+
+
+def view_u8(frames_u8: torch.Tensor, view: np.ndarray) -> torch.Tensor:
+    """frames uint8 [B,H,W,3] on the device + one VIEW_DTYPE record per frame -> the frames from
+    those viewpoints, uint8 [B,H,W,3]: what the model is shown.  One `cilrs_augment_view_u8`
+    launch with no weather, every augmentation off and only the byte output asked for."""
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.size(3) != 3 \
+            or frames_u8.device.type != "cuda":
+        raise RuntimeError("view_u8: frames must be uint8 [B,H,W,3] on the GPU (no CPU fallback)")
+    b, h, w = frames_u8.size(0), frames_u8.size(1), frames_u8.size(2)
+    if not isinstance(view, np.ndarray) or view.shape != (b,):
+        raise RuntimeError("view_u8: one view record per frame")
+    check_view(view, h, w)
+    frames_u8 = frames_u8.contiguous()
+    pdev = _records_to_device(identity_params(b), frames_u8.device)
+    vdev = _records_to_device(view, frames_u8.device)
+    out8 = torch.empty_like(frames_u8)
+    stream = torch.cuda.current_stream(frames_u8.device).cuda_stream
+    L.check(L.lib().cilrs_augment_view_u8(L.ptr(frames_u8), L.ptr(pdev), None, L.ptr(vdev), b, h,
+                                          w, None, L.ptr(out8), C.c_void_p(stream)))
     return out8
 
 
@@ -439,7 +670,7 @@ class BatchLoader:
     def __init__(self, sessions: Sessions, indices, batch_size: int, device, train: bool,
                  seed: int = 0, workers: int = 8, height: int = IMG_HEIGHT, width: int = IMG_WIDTH,
                  processes: bool = False, rank: int = 0, world_size: int = 1,
-                 weather: "WeatherMix" = None):
+                 weather: "WeatherMix" = None, view: "ViewShift" = None):
         """processes=True decodes in `workers` spawned processes (no GIL contention: what a
         B=128 / 14 ms training step needs); the default thread pool starts instantly.
 
@@ -455,7 +686,12 @@ class BatchLoader:
         weather: a `WeatherMix`; every sample's weather record is drawn batch by batch from a
         stream of its own and applied in the augmentation launch (train or not).  The sample order
         and the augmentation records are those of the same loader without it; None launches the
-        plain kernel."""
+        plain kernel.
+
+        view: a `ViewShift`; every sample's viewpoint record is drawn batch by batch from a third
+        stream of its own (its speed feeds the steering rule), the steer labels are corrected on
+        the host with the kernel's float32 add and clip, and the frames are warped in the same
+        launch, in front of the weather.  Order, augmentation and weather records are unchanged."""
         if not (0 <= rank < world_size):
             raise ValueError(f"rank {rank} outside world of {world_size}")
         self.s, self.idx = sessions, np.asarray(indices)
@@ -465,6 +701,8 @@ class BatchLoader:
         self.rng = np.random.default_rng([seed, rank])
         self.weather = weather
         self.wrng = np.random.default_rng([seed, rank, WEATHER_STREAM])
+        self.view = view
+        self.vrng = np.random.default_rng([seed, rank, VIEW_STREAM])
         self.gen = torch.Generator().manual_seed(seed)
         self.workers = max(1, workers)
         self.processes = processes
@@ -549,7 +787,8 @@ class BatchLoader:
                         torch.zeros(self.bs, dtype=torch.int64).pin_memory(),
                         torch.zeros(self.bs, 3, dtype=torch.float32).pin_memory(),
                         torch.zeros(self.bs, AUG_DTYPE.itemsize, dtype=torch.uint8).pin_memory(),
-                        torch.zeros(self.bs, WEATHER_DTYPE.itemsize, dtype=torch.uint8).pin_memory())
+                        torch.zeros(self.bs, WEATHER_DTYPE.itemsize, dtype=torch.uint8).pin_memory(),
+                        torch.zeros(self.bs, VIEW_DTYPE.itemsize, dtype=torch.uint8).pin_memory())
                 self._slots.append((t, t.numpy(), meta))
             # host-to-device copies run on a stream of their own: the wait that frees a staging
             # slot then waits for the COPY, not for the train step the copy would otherwise queue
@@ -576,7 +815,9 @@ class BatchLoader:
                         else identity_params(len(ids))
                     wrec = self.weather.draw(self.wrng, len(ids), self.h, self.w) \
                         if self.weather is not None else None
-                    q.put((slot, params, wrec, ids))
+                    vrec = self.view.draw(self.vrng, len(ids), self.s.speed[ids], self.h, self.w) \
+                        if self.view is not None else None
+                    q.put((slot, params, wrec, vrec, ids))
                 q.put(None)
             except Exception as e:          # surface decode errors in the consumer
                 q.put(e)
@@ -587,15 +828,19 @@ class BatchLoader:
                 return
             if isinstance(item, Exception):
                 raise item
-            slot, params, wrec, ids = item
+            slot, params, wrec, vrec, ids = item
             n = len(ids)
-            pinned, _view, (sp_p, cm_p, tg_p, par_p, wx_p) = self._slots[slot]
+            pinned, _view, (sp_p, cm_p, tg_p, par_p, wx_p, vw_p) = self._slots[slot]
             par_p[:n] = torch.from_numpy(params.view(np.uint8).reshape(n, AUG_DTYPE.itemsize))
             if wrec is not None:
                 wx_p[:n] = torch.from_numpy(wrec.view(np.uint8).reshape(n, WEATHER_DTYPE.itemsize))
             sp_p[:n] = torch.from_numpy(np.ascontiguousarray(self.s.speed[ids], dtype=np.float32))
             cm_p[:n] = torch.from_numpy(np.ascontiguousarray(self.s.command[ids], dtype=np.int64))
-            tg_p[:n] = torch.from_numpy(np.ascontiguousarray(self.s.targets[ids], dtype=np.float32))
+            tgt = np.ascontiguousarray(self.s.targets[ids], dtype=np.float32)
+            if vrec is not None:
+                vw_p[:n] = torch.from_numpy(vrec.view(np.uint8).reshape(n, VIEW_DTYPE.itemsize))
+                tgt = correct_steer(tgt, vrec)
+            tg_p[:n] = torch.from_numpy(tgt)
             cs = self._copy_stream
             main = torch.cuda.current_stream(self.device)
             with torch.cuda.stream(cs):
@@ -606,13 +851,15 @@ class BatchLoader:
                 tgts = tg_p[:n].to(self.device, non_blocking=True)
                 pars = par_p[:n].to(self.device, non_blocking=True)
                 wxs = wx_p[:n].to(self.device, non_blocking=True) if wrec is not None else None
+                vws = vw_p[:n].to(self.device, non_blocking=True) if vrec is not None else None
                 copied = torch.cuda.Event()
                 copied.record(cs)
             main.wait_event(copied)          # device side: the consumers run behind the copies
-            for t in (frames, speeds, cmds, tgts, pars, wxs):
+            for t in (frames, speeds, cmds, tgts, pars, wxs, vws):
                 if t is not None:
                     t.record_stream(main)    # (allocated under the copy stream, used on `main`)
-            img = augment_u8(frames, params, params_dev=pars, weather=wrec, weather_dev=wxs)
+            img = augment_u8(frames, params, params_dev=pars, weather=wrec, weather_dev=wxs,
+                             view=vrec, view_dev=vws)
             batch = (img, speeds, cmds, tgts)
             copied.synchronize()            # the staging slot may be refilled now
             free.put(slot)
@@ -660,6 +907,7 @@ class DeviceDataset:
         self.workers, self.processes = max(1, workers), processes
         self.chunk_frames = max(1, chunk_frames)
         self.command = sessions.command           # host copy: the sampler's class weights
+        self.speed_host = getattr(sessions, "speed", None)    # host copy: the steering rule's
         self.cache = self.speed = self.command_dev = self.targets = None
         need = self.cache_bytes(self.n, height, width)
         if budget_bytes is None:
@@ -694,6 +942,7 @@ class DeviceDataset:
         self.n, self.h, self.w = n, cache.size(1), cache.size(2)
         self.device = cache.device
         self.command = command.cpu().numpy()
+        self.speed_host = speed.cpu().numpy()
         self.cache, self.speed, self.command_dev, self.targets = cache, speed, command, targets
         self.budget_bytes = None
         return self
@@ -800,10 +1049,11 @@ class DeviceDataset:
             raise RuntimeError(f"DeviceDataset: index {int(bad)} outside [0, {self.n})")
 
     def _launch(self, index_ptr: int, params_ptr: int, b: int, want_u8: bool = False,
-                weather_ptr: int = None):
+                weather_ptr: int = None, view_ptr: int = None):
         """One cilrs_batch_assemble launch on the current stream from device-resident index /
         parameter records (already checked on the host); with weather_ptr (device-resident
-        weather records), one cilrs_batch_assemble_weather launch."""
+        weather records), one cilrs_batch_assemble_weather launch; with view_ptr (device-resident
+        viewpoint records), one cilrs_batch_assemble_view launch, with or without weather."""
         dev = self.device
         out = torch.empty(b, self.h, self.w, 3, dtype=torch.float32, device=dev)
         out8 = torch.empty(b, self.h, self.w, 3, dtype=torch.uint8, device=dev) if want_u8 else None
@@ -811,7 +1061,13 @@ class DeviceDataset:
         cmd = torch.empty(b, dtype=torch.int64, device=dev)
         tgt = torch.empty(b, 3, dtype=torch.float32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if weather_ptr is None:
+        if view_ptr is not None:
+            L.check(L.lib().cilrs_batch_assemble_view(
+                L.ptr(self.cache), self.n, L.ptr(self.speed), L.ptr(self.command_dev),
+                L.ptr(self.targets), C.c_void_p(index_ptr), C.c_void_p(params_ptr),
+                C.c_void_p(weather_ptr), C.c_void_p(view_ptr), b, self.h, self.w, L.ptr(out),
+                L.ptr(out8), L.ptr(spd), L.ptr(cmd), L.ptr(tgt), C.c_void_p(stream)))
+        elif weather_ptr is None:
             L.check(L.lib().cilrs_batch_assemble(
                 L.ptr(self.cache), self.n, L.ptr(self.speed), L.ptr(self.command_dev),
                 L.ptr(self.targets), C.c_void_p(index_ptr), C.c_void_p(params_ptr), b, self.h,
@@ -827,12 +1083,14 @@ class DeviceDataset:
         return (img, spd, cmd, tgt, out8) if want_u8 else (img, spd, cmd, tgt)
 
     def assemble(self, index, params: np.ndarray, want_u8: bool = False,
-                 weather: np.ndarray = None):
+                 weather: np.ndarray = None, view: np.ndarray = None):
         """index (host integers [B], any order, repeats allowed) + one parameter record per sample
         -> (image, speed, command, targets[, augmented uint8 frames]) on the device: what
         `augment_u8(cache[index], params)` and an index_select of the labels give.  The index is
         checked on the host before anything is launched.  weather: one WEATHER_DTYPE record per
-        sample, applied to the source frames in the same launch (`augment_u8(..., weather=)`)."""
+        sample, applied to the source frames in the same launch (`augment_u8(..., weather=)`).
+        view: one VIEW_DTYPE record per sample; the frames are seen from those viewpoints first and
+        the steer targets corrected, in the same launch (`cilrs_batch_assemble_view`)."""
         if isinstance(index, torch.Tensor):
             index = index.cpu().numpy()
         index = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
@@ -846,6 +1104,10 @@ class DeviceDataset:
             if not isinstance(weather, np.ndarray) or weather.shape != index.shape:
                 raise RuntimeError("DeviceDataset.assemble: one weather record per index")
             check_weather(weather, self.h, self.w)
+        if view is not None:
+            if not isinstance(view, np.ndarray) or view.shape != index.shape:
+                raise RuntimeError("DeviceDataset.assemble: one view record per index")
+            check_view(view, self.h, self.w)
         if not self.filled:
             raise RuntimeError("DeviceDataset.assemble: the cache is not filled (call fill())")
         b = index.size
@@ -853,9 +1115,11 @@ class DeviceDataset:
         par_dev = torch.from_numpy(params.view(np.uint8).reshape(b, AUG_DTYPE.itemsize)).to(
             self.device)
         wx_dev = _records_to_device(weather, self.device) if weather is not None else None
+        vw_dev = _records_to_device(view, self.device) if view is not None else None
         res = self._launch(idx_dev.data_ptr(), par_dev.data_ptr(), b, want_u8,
-                           wx_dev.data_ptr() if wx_dev is not None else None)
-        for t in (idx_dev, par_dev, wx_dev):
+                           wx_dev.data_ptr() if wx_dev is not None else None,
+                           vw_dev.data_ptr() if vw_dev is not None else None)
+        for t in (idx_dev, par_dev, wx_dev, vw_dev):
             if t is not None:
                 t.record_stream(torch.cuda.current_stream(self.device))
         return res
@@ -897,10 +1161,17 @@ class CachedBatchLoader:
     weather (a `WeatherMix`): as for `BatchLoader`, from the same stream of its own, so the two
     loaders stay bit-identical with it; the epoch's weather records (96 bytes a sample) are drawn
     with the plan and go up with it, and every batch is one `cilrs_batch_assemble_weather`
-    launch.  train=False with a mix scores a validation set under that weather."""
+    launch.  train=False with a mix scores a validation set under that weather.
+
+    view (a `ViewShift`): likewise from a third stream; the dataset's host copy of the speeds
+    (`speed_host`) feeds the steering rule, the epoch's viewpoint records (96 bytes a sample) go up
+    with the plan, and every batch is one `cilrs_batch_assemble_view` launch that warps the frames
+    and corrects the steer labels.  train=False with a mix scores a validation set from the
+    shifted viewpoint."""
 
     def __init__(self, dataset, indices, batch_size: int, train: bool, seed: int = 0,
-                 rank: int = 0, world_size: int = 1, weather: "WeatherMix" = None):
+                 rank: int = 0, world_size: int = 1, weather: "WeatherMix" = None,
+                 view: "ViewShift" = None):
         if not (0 <= rank < world_size):
             raise ValueError(f"rank {rank} outside world of {world_size}")
         self.ds, self.idx = dataset, np.asarray(indices)
@@ -911,6 +1182,11 @@ class CachedBatchLoader:
         self.rng = np.random.default_rng([seed, rank])
         self.weather = weather
         self.wrng = np.random.default_rng([seed, rank, WEATHER_STREAM])
+        self.view = view
+        self.vrng = np.random.default_rng([seed, rank, VIEW_STREAM])
+        if view is not None and getattr(dataset, "speed_host", None) is None:
+            raise RuntimeError("CachedBatchLoader: view= needs the dataset's host speeds "
+                               "(speed_host)")
         self.gen = torch.Generator().manual_seed(seed)
         self.weights = class_balanced_weights(dataset.command[self.idx]) if train else None
         self._ahead = None
@@ -931,12 +1207,14 @@ class CachedBatchLoader:
     def epoch_plan(self):
         """(order, params) of the next epoch, on the host: this rank's sample order (int64 [n])
         and the augmentation records of its batches back to back (AUG_DTYPE [n]); with a weather
-        mix (order, params, weather), the weather records (WEATHER_DTYPE [n]) last.  Touches no
-        GPU; advances the sampler, parameter and weather streams exactly as one `BatchLoader`
-        epoch does.  Successive calls, by the caller or by iteration, give successive epochs: a
-        plan already drawn ahead (`_plan_ahead`) is handed out before a new one is drawn."""
-        plan = self._next_plan()
-        return plan if self.weather is not None else plan[:2]
+        mix (order, params, weather), the weather records (WEATHER_DTYPE [n]) follow, and with a
+        view mix the viewpoint records (VIEW_DTYPE [n]) come last.  Touches no GPU; advances the
+        sampler, parameter, weather and viewpoint streams exactly as one `BatchLoader` epoch does.
+        Successive calls, by the caller or by iteration, give successive epochs: a plan already
+        drawn ahead (`_plan_ahead`) is handed out before a new one is drawn."""
+        order, params, weather, view = self._next_plan()
+        return (order, params) + (() if self.weather is None else (weather,)) \
+            + (() if self.view is None else (view,))
 
     def _next_plan(self):
         ahead, self._ahead = self._ahead, None
@@ -951,26 +1229,34 @@ class CachedBatchLoader:
         order = np.ascontiguousarray(self._order(), dtype=np.int64)
         nb = len(self)
         order = order[:nb * self.bs]
-        parts, wparts = [], []
+        parts, wparts, vparts = [], [], []
         for b in range(nb):
             n = len(order[b * self.bs:(b + 1) * self.bs])
             parts.append(draw_aug_params(self.rng, n, self.h, self.w) if self.train
                          else identity_params(n))
             if self.weather is not None:
                 wparts.append(self.weather.draw(self.wrng, n, self.h, self.w))
+            if self.view is not None:
+                ids = order[b * self.bs:(b + 1) * self.bs]
+                vparts.append(self.view.draw(self.vrng, n, self.ds.speed_host[ids], self.h, self.w))
         params = np.concatenate(parts) if parts else np.zeros(0, dtype=AUG_DTYPE)
         weather = None
         if self.weather is not None:
             weather = np.concatenate(wparts) if wparts else np.zeros(0, dtype=WEATHER_DTYPE)
-        return order, params, weather
+        view = None
+        if self.view is not None:
+            view = np.concatenate(vparts) if vparts else np.zeros(0, dtype=VIEW_DTYPE)
+        return order, params, weather, view
 
     def __iter__(self):
         ds = self.ds
-        order, params, weather = self._next_plan()
+        order, params, weather, view = self._next_plan()
         ds.check_index(order)
         check_params(params, self.h, self.w)
         if weather is not None:
             check_weather(weather, self.h, self.w)
+        if view is not None:
+            check_view(view, self.h, self.w)
         if not ds.filled:
             raise RuntimeError("CachedBatchLoader: the dataset's cache is not filled")
         n = len(order)
@@ -985,10 +1271,16 @@ class CachedBatchLoader:
         if weather is not None:
             weather_dev = torch.from_numpy(weather.view(np.uint8).reshape(
                 n, WEATHER_DTYPE.itemsize)).pin_memory().to(ds.device, non_blocking=True)
+        view_dev = None
+        if view is not None:
+            view_dev = torch.from_numpy(view.view(np.uint8).reshape(
+                n, VIEW_DTYPE.itemsize)).pin_memory().to(ds.device, non_blocking=True)
         if self.train:
             self._plan_ahead()
         ip, pp = order_dev.data_ptr(), params_dev.data_ptr()
         wp = weather_dev.data_ptr() if weather_dev is not None else None
+        vp = view_dev.data_ptr() if view_dev is not None else None
         for b0 in range(0, n, self.bs):
             yield ds._launch(ip + b0 * 8, pp + b0 * AUG_DTYPE.itemsize, min(self.bs, n - b0),
-                             weather_ptr=None if wp is None else wp + b0 * WEATHER_DTYPE.itemsize)
+                             weather_ptr=None if wp is None else wp + b0 * WEATHER_DTYPE.itemsize,
+                             view_ptr=None if vp is None else vp + b0 * VIEW_DTYPE.itemsize)

@@ -173,6 +173,78 @@ def weather_sweep(model, dataset, indices, conditions=None, severities=(0.25, 0.
     return out
 
 
+def _slope(xs, ys):
+    """least-squares slope of ys over xs, or None with fewer than two distinct xs"""
+    xs, ys = np.asarray(xs, dtype=np.float64), np.asarray(ys, dtype=np.float64)
+    if len(xs) < 2 or np.ptp(xs) == 0:
+        return None
+    return float(np.polyfit(xs, ys, 1)[0])
+
+
+def view_sweep(model, dataset, indices, lateral_m=(-1.0, -0.5, 0.0, 0.5, 1.0),
+               yaw_deg=(-6.0, -3.0, 0.0, 3.0, 6.0), weather=None, batch_size: int = 128,
+               seed: int = 0, **view_kw):
+    """Does the checkpoint steer back when displaced -- without a simulator: one pass over
+    `CachedBatchLoader(dataset, indices, train=False, weather=weather,
+    view=ViewShift.fixed(lateral, yaw, **view_kw))` for every (lateral, yaw) cell, and one with no
+    view (the centre).  dataset: a filled `DeviceDataset`; weather: a `WeatherMix` or None.
+
+    -> {"centre": report, "cells": {lateral: {yaw: cell}}, "slopes": {...}} where a cell holds
+      "report"       the evaluation report against the CORRECTED labels
+      "steer_mae"    its steer MAE
+      "steer_shift"  mean predicted steer minus the centre's
+      "steer_delta"  mean correction the pure-pursuit rule asks for (`data.steer_correction`)
+      "gain"         steer_shift / steer_delta, the response gain (None where the rule asks 0)
+    and the slopes are least-squares fits of steer_shift: "steer_per_m" over the cells at yaw 0,
+    "steer_per_deg" over the cells at lateral 0 (None when that row or column is not in the grid).
+    A network that has only seen the lane centre is expected to show a gain near zero.  The warp
+    is a flat-road model (include/cilrs_hip.h), not a renderer."""
+    from . import data as D
+    speeds = np.asarray(dataset.speed_host, dtype=np.float64)[np.asarray(indices)]
+    steer_kw = {k: v for k, v in view_kw.items() if k != "camera"}
+
+    def run(view):
+        ev = Evaluator(model)
+        for imgs, spd, cmds, tgts in D.CachedBatchLoader(dataset, indices, batch_size,
+                                                         train=False, seed=seed, weather=weather,
+                                                         view=view):
+            ev.update(imgs, spd, cmds, tgts)
+        a = ev.acc.cpu().numpy()
+        return ev.report(), float(a[1] / a[0])               # steer: [n, Sp, ...]
+
+    centre, centre_steer = run(None)
+    out = {"centre": centre, "cells": {}}
+    for lat in lateral_m:
+        lat = float(lat)
+        out["cells"][lat] = {}
+        for yaw in yaw_deg:
+            yaw = float(yaw)
+            rep, steer = run(D.ViewShift.fixed(lat, yaw, **view_kw))
+            delta = float(D.steer_correction(lat, np.radians(yaw), speeds, **steer_kw)
+                          .astype(np.float32).mean(dtype=np.float64))
+            shift = steer - centre_steer
+            out["cells"][lat][yaw] = {
+                "report": rep, "steer_mae": rep["overall_metrics"]["Steer"]["MAE"],
+                "steer_shift": shift, "steer_delta": delta,
+                "gain": shift / delta if delta != 0.0 else None}
+    cells = out["cells"]
+    lats, yaws = [float(v) for v in lateral_m], [float(v) for v in yaw_deg]
+    out["slopes"] = {
+        "steer_per_m": _slope(lats, [cells[v][0.0]["steer_shift"] for v in lats])
+        if 0.0 in yaws else None,
+        "steer_per_deg": _slope(yaws, [cells[0.0][v]["steer_shift"] for v in yaws])
+        if 0.0 in lats else None}
+    return out
+
+
+def write_view_sweep(path, model, dataset, indices, **kw):
+    """`view_sweep` written as JSON (offsets and yaws become string keys)."""
+    rep = view_sweep(model, dataset, indices, **kw)
+    with open(path, "w") as f:
+        json.dump(rep, f, indent=2)
+    return rep
+
+
 def write_weather_sweep(path, model, dataset, indices, **kw):
     """`weather_sweep` written as JSON (severities become string keys)."""
     rep = weather_sweep(model, dataset, indices, **kw)

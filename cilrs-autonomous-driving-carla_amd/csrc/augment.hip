@@ -16,6 +16,13 @@
 // stored as uint8.  It is the <true> instantiation of the same pixel function; the plain entry
 // points keep the <false> one.  No transcendental runs here: what needs exp() is folded into the
 // record on the host (cilrs_mi355/data.py), and tests/_weather.py mirrors the arithmetic.
+//
+// The viewpoint (cilrs_view_params: two inverse homographies split at a row) is a third, optional
+// source stage in front of the weather: wherever a source pixel (y, x) is read, the `_view`
+// kernels read the virtual frame V(y, x) instead, four stored pixels blended bilinearly and
+// rounded to a grey level, so they give what the others give on frames that were warped first
+// and stored as uint8.  It is the VW flag of the same pixel function, instantiated only for the
+// `_view` entry points; tests/_view.py mirrors the arithmetic.
 #include "common.h"
 
 namespace cilrs {
@@ -157,14 +164,56 @@ __device__ __forceinline__ void weather_stages(const cilrs_weather_params& w, co
     }
 }
 
-// Source pixel (y, x) of one sample as uint8-valued floats: the stored bytes, behind the sample's
-// weather when WX.  `w` is not read otherwise.
-template <bool WX>
+// Pixel (y, x) of the virtual frame of one sample: destination -> source through the record's far
+// or ground map, clamped into the frame (replicate border; the nesting sends a NaN to 0, so no
+// address outside the frame is formed whatever the record holds), bilinear, rounded to a grey
+// level.  The map is selected element by element and the record indexed with constants only.
+__device__ __forceinline__ void view_pixel(const unsigned char* __restrict__ img,
+                                           const cilrs_view_params& v, const int y, const int x,
+                                           const int H, const int W, float c[3]) {
+    const float xf = (float)x, yf = (float)y;
+    const bool g = yf > v.split_row;
+    const float m0 = g ? v.ground[0] : v.far[0], m1 = g ? v.ground[1] : v.far[1];
+    const float m2 = g ? v.ground[2] : v.far[2], m3 = g ? v.ground[3] : v.far[3];
+    const float m4 = g ? v.ground[4] : v.far[4], m5 = g ? v.ground[5] : v.far[5];
+    const float m6 = g ? v.ground[6] : v.far[6], m7 = g ? v.ground[7] : v.far[7];
+    const float m8 = g ? v.ground[8] : v.far[8];
+    const float u = (m0 * xf + m1 * yf) + m2;
+    const float t = (m3 * xf + m4 * yf) + m5;
+    const float w = (m6 * xf + m7 * yf) + m8;
+    const float sx = fminf(fmaxf(u / w, 0.f), (float)(W - 1));
+    const float sy = fminf(fmaxf(t / w, 0.f), (float)(H - 1));
+    const int x0 = (int)floorf(sx), y0 = (int)floorf(sy);
+    const float ax = sx - (float)x0, ay = sy - (float)y0;
+    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+    const unsigned char* r0 = img + (size_t)y0 * W * 3;
+    const unsigned char* r1 = img + (size_t)y1 * W * 3;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float p00 = (float)r0[x0 * 3 + k], p01 = (float)r0[x1 * 3 + k];
+        const float p10 = (float)r1[x0 * 3 + k], p11 = (float)r1[x1 * 3 + k];
+        const float top = p00 + ax * (p01 - p00);
+        const float bot = p10 + ax * (p11 - p10);
+        c[k] = rintf(clip255(top + ay * (bot - top)));
+    }
+}
+
+// Source pixel (y, x) of one sample as uint8-valued floats: the stored bytes, or with VW and the
+// record on the virtual frame's pixel, behind the sample's weather when WX.  `w` / `v` are not
+// read otherwise.
+template <bool WX, bool VW>
 __device__ __forceinline__ void source_pixel(const unsigned char* __restrict__ img,
-                                             const cilrs_weather_params& w, const int y,
-                                             const int x, const int W, float c[3]) {
-    const unsigned char* p = img + ((size_t)y * W + x) * 3;
-    c[0] = (float)p[0]; c[1] = (float)p[1]; c[2] = (float)p[2];
+                                             const cilrs_weather_params& w,
+                                             const cilrs_view_params& v, const int y,
+                                             const int x, const int H, const int W, float c[3]) {
+    bool stored = true;
+    if constexpr (VW) stored = v.on == 0;
+    if (stored) {
+        const unsigned char* p = img + ((size_t)y * W + x) * 3;
+        c[0] = (float)p[0]; c[1] = (float)p[1]; c[2] = (float)p[2];
+    } else {
+        view_pixel(img, v, y, x, H, W, c);
+    }
     if constexpr (WX) weather_stages(w, y, x, c);
 }
 
@@ -176,11 +225,13 @@ struct NormConsts {
 // Every stage for output pixel (y, x) of one sample: `img` is that sample's uint8 [H][W][3] source
 // frame, `i` the pixel's index in the output batch.  The kernels below are this function behind
 // two ways of finding `img`, so their results are the same element for element; WX puts the
-// sample's weather `wx` in front of every source pixel read.
-template <bool WX>
+// sample's weather `wx` in front of every source pixel read, VW its viewpoint `vw` in front of
+// that.
+template <bool WX, bool VW>
 __device__ __forceinline__ void augment_pixel(const unsigned char* __restrict__ img,
                                               const cilrs_aug_params& a,
-                                              const cilrs_weather_params& wx, const int y,
+                                              const cilrs_weather_params& wx,
+                                              const cilrs_view_params& vw, const int y,
                                               const int x,
                                               const int H, const int W, const size_t i,
                                               float* __restrict__ out_f32,
@@ -199,7 +250,7 @@ __device__ __forceinline__ void augment_pixel(const unsigned char* __restrict__ 
             for (int dx = -r; dx <= r; ++dx) {
                 const int xx = reflect101(x + dx, W);
                 float t[3];
-                source_pixel<WX>(img, wx, yy, xx, W, t);
+                source_pixel<WX, VW>(img, wx, vw, yy, xx, H, W, t);
                 colour_stages(a, t);
                 const float w = blur_tap(w0, w1, w2, dx);
 #pragma unroll
@@ -212,7 +263,7 @@ __device__ __forceinline__ void augment_pixel(const unsigned char* __restrict__ 
 #pragma unroll
         for (int k = 0; k < 3; ++k) c[k] = rintf(clip255(acc[k]));
     } else {
-        source_pixel<WX>(img, wx, y, x, W, c);
+        source_pixel<WX, VW>(img, wx, vw, y, x, H, W, c);
         colour_stages(a, c);
     }
     if (a.noise_std255 > 0.f) {
@@ -245,27 +296,33 @@ __device__ __forceinline__ void augment_pixel(const unsigned char* __restrict__ 
     }
 }
 
-// `weather` [B] is read by the WX instantiation only (the plain entry point passes nullptr).
-template <bool WX>
+// `weather` [B] is read by the WX instantiations only and `view` [B] by the VW ones (the other
+// entry points pass nullptr).
+template <bool WX, bool VW>
 __global__ __launch_bounds__(256) void augment_u8_kernel(
     const unsigned char* __restrict__ frames, const cilrs_aug_params* __restrict__ params,
-    const cilrs_weather_params* __restrict__ weather, const int B, const int H, const int W,
-    float* __restrict__ out_f32, unsigned char* __restrict__ out_u8, const NormConsts nc) {
+    const cilrs_weather_params* __restrict__ weather, const cilrs_view_params* __restrict__ view,
+    const int B, const int H, const int W, float* __restrict__ out_f32,
+    unsigned char* __restrict__ out_u8, const NormConsts nc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * H * W) return;
     const int x = i % W, y = (i / W) % H, b = i / (W * H);
     const cilrs_aug_params a = params[b];
     cilrs_weather_params w;
     if constexpr (WX) w = weather[b];
-    augment_pixel<WX>(frames + (size_t)b * H * W * 3, a, w, y, x, H, W, (size_t)i, out_f32, out_u8,
-                      nc);
+    cilrs_view_params v;
+    if constexpr (VW) v = view[b];
+    augment_pixel<WX, VW>(frames + (size_t)b * H * W * 3, a, w, v, y, x, H, W, (size_t)i, out_f32,
+                          out_u8, nc);
 }
 
 // A whole training batch from the device-resident dataset: sample b of the batch is frame
 // index[b] of the cache (64-bit offset: the cache passes 4 GiB at 81.4 K reference-size frames),
 // augmented exactly as augment_u8_kernel would, and its labels are gathered by the same index by
 // the thread of the sample's first pixel.  An index outside [0, n_frames) is the caller's error
-// (checked on the host, cilrs_mi355/data.py); such a sample is skipped, never read.
+// (checked on the host, cilrs_mi355/data.py); such a sample is skipped, never read.  With VW and
+// the sample's record on, the same thread adds the record's steer_delta to the steer label and
+// clips it to [-1, 1]; an off record copies the three targets (a stored -0.0 stays -0.0).
 struct AssembleLabels {
     const float* speed;
     const long long* command;
@@ -275,31 +332,39 @@ struct AssembleLabels {
     float* out_targets;
 };
 
-template <bool WX>
+template <bool WX, bool VW>
 __global__ __launch_bounds__(256) void batch_assemble_kernel(
     const unsigned char* __restrict__ cache, const long long n_frames,
     const long long* __restrict__ index, const cilrs_aug_params* __restrict__ params,
-    const cilrs_weather_params* __restrict__ weather, const int B, const int H, const int W,
-    float* __restrict__ out_f32, unsigned char* __restrict__ out_u8, const AssembleLabels lab,
-    const NormConsts nc) {
+    const cilrs_weather_params* __restrict__ weather, const cilrs_view_params* __restrict__ view,
+    const int B, const int H, const int W, float* __restrict__ out_f32,
+    unsigned char* __restrict__ out_u8, const AssembleLabels lab, const NormConsts nc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * H * W) return;
     const int x = i % W, y = (i / W) % H, b = i / (W * H);
     const long long src = index[b];
     if (src < 0 || src >= n_frames) return;
+    cilrs_view_params v;
+    if constexpr (VW) v = view[b];
     if (x == 0 && y == 0) {
         if (lab.out_speed) lab.out_speed[b] = lab.speed[src];
         if (lab.out_command) lab.out_command[b] = lab.command[src];
         if (lab.out_targets) {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) lab.out_targets[b * 3 + k] = lab.targets[src * 3 + k];
+            for (int k = 0; k < 3; ++k) {
+                float t = lab.targets[src * 3 + k];
+                if constexpr (VW) {
+                    if (k == 0 && v.on != 0) t = fminf(fmaxf(t + v.steer_delta, -1.f), 1.f);
+                }
+                lab.out_targets[b * 3 + k] = t;
+            }
         }
     }
     const cilrs_aug_params a = params[b];
     cilrs_weather_params w;
     if constexpr (WX) w = weather[b];
-    augment_pixel<WX>(cache + (size_t)src * H * W * 3, a, w, y, x, H, W, (size_t)i, out_f32, out_u8,
-                      nc);
+    augment_pixel<WX, VW>(cache + (size_t)src * H * W * 3, a, w, v, y, x, H, W, (size_t)i, out_f32,
+                          out_u8, nc);
 }
 
 constexpr NormConsts kNorm = {kImageMean[0], kImageMean[1], kImageMean[2],
@@ -308,30 +373,30 @@ constexpr NormConsts kNorm = {kImageMean[0], kImageMean[1], kImageMean[2],
 // rain heads are hashed from (row + 64, column + 64) packed into 16 bits each
 constexpr int kWeatherMaxWidth = 65536 - 128;
 
-template <bool WX>
+template <bool WX, bool VW>
 int launch_augment(const unsigned char* frames, const cilrs_aug_params* params,
-                   const cilrs_weather_params* weather, int B, int H, int W, float* out_f32,
-                   unsigned char* out_u8, hipStream_t s) {
+                   const cilrs_weather_params* weather, const cilrs_view_params* view, int B,
+                   int H, int W, float* out_f32, unsigned char* out_u8, hipStream_t s) {
     CILRS_CHECK(B >= 1 && H >= 2 && W >= 2 && (size_t)B * H * W < (1u << 31),
                 "augment: bad batch geometry");
-    augment_u8_kernel<WX><<<cdiv(B * H * W, 256), 256, 0, s>>>(frames, params, weather, B, H, W,
-                                                               out_f32, out_u8, kNorm);
+    augment_u8_kernel<WX, VW><<<cdiv(B * H * W, 256), 256, 0, s>>>(
+        frames, params, weather, view, B, H, W, out_f32, out_u8, kNorm);
     CILRS_LAUNCH_CHECK();
     return 0;
 }
 
-template <bool WX>
+template <bool WX, bool VW>
 int launch_assemble(const unsigned char* cache, long long n_frames, const AssembleLabels& lab,
                     const long long* index, const cilrs_aug_params* params,
-                    const cilrs_weather_params* weather, int B, int H, int W, float* out_f32,
-                    unsigned char* out_u8, hipStream_t s) {
+                    const cilrs_weather_params* weather, const cilrs_view_params* view, int B,
+                    int H, int W, float* out_f32, unsigned char* out_u8, hipStream_t s) {
     // the guard is on the BATCH (thread and output indices are int); the cache is addressed in
     // 64 bits and may be any size
     CILRS_CHECK(B >= 1 && H >= 2 && W >= 2 && (size_t)B * H * W < (1u << 31),
                 "batch_assemble: bad batch geometry");
     CILRS_CHECK(n_frames >= 1, "batch_assemble: empty frame cache");
-    batch_assemble_kernel<WX><<<cdiv(B * H * W, 256), 256, 0, s>>>(
-        cache, n_frames, index, params, weather, B, H, W, out_f32, out_u8, lab, kNorm);
+    batch_assemble_kernel<WX, VW><<<cdiv(B * H * W, 256), 256, 0, s>>>(
+        cache, n_frames, index, params, weather, view, B, H, W, out_f32, out_u8, lab, kNorm);
     CILRS_LAUNCH_CHECK();
     return 0;
 }
@@ -340,14 +405,16 @@ int launch_assemble(const unsigned char* cache, long long n_frames, const Assemb
 
 int launch_augment_u8(const unsigned char* frames, const cilrs_aug_params* params, int B, int H,
                       int W, float* out_f32, unsigned char* out_u8, hipStream_t s) {
-    return launch_augment<false>(frames, params, nullptr, B, H, W, out_f32, out_u8, s);
+    return launch_augment<false, false>(frames, params, nullptr, nullptr, B, H, W, out_f32, out_u8,
+                                        s);
 }
 
 int launch_augment_weather_u8(const unsigned char* frames, const cilrs_aug_params* params,
                               const cilrs_weather_params* weather, int B, int H, int W,
                               float* out_f32, unsigned char* out_u8, hipStream_t s) {
     CILRS_CHECK(W <= kWeatherMaxWidth, "augment_weather: width %d above %d", W, kWeatherMaxWidth);
-    return launch_augment<true>(frames, params, weather, B, H, W, out_f32, out_u8, s);
+    return launch_augment<true, false>(frames, params, weather, nullptr, B, H, W, out_f32, out_u8,
+                                       s);
 }
 
 int launch_batch_assemble(const unsigned char* cache, long long n_frames, const float* speed,
@@ -356,8 +423,8 @@ int launch_batch_assemble(const unsigned char* cache, long long n_frames, const 
                           unsigned char* out_u8, float* out_speed, long long* out_command,
                           float* out_targets, hipStream_t s) {
     const AssembleLabels lab = {speed, command, targets, out_speed, out_command, out_targets};
-    return launch_assemble<false>(cache, n_frames, lab, index, params, nullptr, B, H, W, out_f32,
-                                  out_u8, s);
+    return launch_assemble<false, false>(cache, n_frames, lab, index, params, nullptr, nullptr, B,
+                                         H, W, out_f32, out_u8, s);
 }
 
 int launch_batch_assemble_weather(const unsigned char* cache, long long n_frames,
@@ -370,8 +437,37 @@ int launch_batch_assemble_weather(const unsigned char* cache, long long n_frames
     CILRS_CHECK(W <= kWeatherMaxWidth, "batch_assemble_weather: width %d above %d", W,
                 kWeatherMaxWidth);
     const AssembleLabels lab = {speed, command, targets, out_speed, out_command, out_targets};
-    return launch_assemble<true>(cache, n_frames, lab, index, params, weather, B, H, W, out_f32,
-                                 out_u8, s);
+    return launch_assemble<true, false>(cache, n_frames, lab, index, params, weather, nullptr, B, H,
+                                        W, out_f32, out_u8, s);
+}
+
+// weather may be nullptr (the viewpoint alone); the width limit is the weather's
+int launch_augment_view_u8(const unsigned char* frames, const cilrs_aug_params* params,
+                           const cilrs_weather_params* weather, const cilrs_view_params* view,
+                           int B, int H, int W, float* out_f32, unsigned char* out_u8,
+                           hipStream_t s) {
+    if (!weather)
+        return launch_augment<false, true>(frames, params, nullptr, view, B, H, W, out_f32, out_u8,
+                                           s);
+    CILRS_CHECK(W <= kWeatherMaxWidth, "augment_view: width %d above %d", W, kWeatherMaxWidth);
+    return launch_augment<true, true>(frames, params, weather, view, B, H, W, out_f32, out_u8, s);
+}
+
+int launch_batch_assemble_view(const unsigned char* cache, long long n_frames, const float* speed,
+                               const long long* command, const float* targets,
+                               const long long* index, const cilrs_aug_params* params,
+                               const cilrs_weather_params* weather, const cilrs_view_params* view,
+                               int B, int H, int W, float* out_f32, unsigned char* out_u8,
+                               float* out_speed, long long* out_command, float* out_targets,
+                               hipStream_t s) {
+    const AssembleLabels lab = {speed, command, targets, out_speed, out_command, out_targets};
+    if (!weather)
+        return launch_assemble<false, true>(cache, n_frames, lab, index, params, nullptr, view, B,
+                                            H, W, out_f32, out_u8, s);
+    CILRS_CHECK(W <= kWeatherMaxWidth, "batch_assemble_view: width %d above %d", W,
+                kWeatherMaxWidth);
+    return launch_assemble<true, true>(cache, n_frames, lab, index, params, weather, view, B, H, W,
+                                       out_f32, out_u8, s);
 }
 
 }  // namespace cilrs

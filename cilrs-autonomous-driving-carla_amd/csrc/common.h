@@ -388,6 +388,17 @@ int launch_batch_assemble_weather(const unsigned char* cache, long long n_frames
                                   const cilrs_weather_params* weather, int B, int H, int W,
                                   float* out_f32, unsigned char* out_u8, float* out_speed,
                                   long long* out_command, float* out_targets, hipStream_t s);
+int launch_augment_view_u8(const unsigned char* frames, const cilrs_aug_params* params,
+                           const cilrs_weather_params* weather, const cilrs_view_params* view,
+                           int B, int H, int W, float* out_f32, unsigned char* out_u8,
+                           hipStream_t s);
+int launch_batch_assemble_view(const unsigned char* cache, long long n_frames, const float* speed,
+                               const long long* command, const float* targets,
+                               const long long* index, const cilrs_aug_params* params,
+                               const cilrs_weather_params* weather, const cilrs_view_params* view,
+                               int B, int H, int W, float* out_f32, unsigned char* out_u8,
+                               float* out_speed, long long* out_command, float* out_targets,
+                               hipStream_t s);
 // ---- single-frame inference convolution (conv_small.hip) --------------------------------------
 struct ConvSmallArgs {
     const float* x; const float* w; float* y;      // NHWC / OHWI / NHWC, dense

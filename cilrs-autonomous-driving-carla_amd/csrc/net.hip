@@ -3580,6 +3580,35 @@ int cilrs_batch_assemble_weather(const uint8_t* cache, int64_t n_frames, const f
                                          reinterpret_cast<hipStream_t>(stream));
 }
 
+int cilrs_augment_view_u8(const uint8_t* frames, const cilrs_aug_params* params,
+                          const cilrs_weather_params* weather, const cilrs_view_params* view,
+                          int batch, int height, int width, float* out_f32, uint8_t* out_u8,
+                          void* stream) {
+    CILRS_CHECK(frames && params && view && (out_f32 || out_u8), "augment_view: NULL argument");
+    static_assert(sizeof(cilrs_view_params) == 96, "cilrs_view_params layout");
+    return launch_augment_view_u8(frames, params, weather, view, batch, height, width, out_f32,
+                                  out_u8, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cilrs_batch_assemble_view(const uint8_t* cache, int64_t n_frames, const float* speed,
+                              const int64_t* command, const float* targets, const int64_t* index,
+                              const cilrs_aug_params* params, const cilrs_weather_params* weather,
+                              const cilrs_view_params* view, int batch, int height, int width,
+                              float* out_f32, uint8_t* out_u8, float* out_speed,
+                              int64_t* out_command, float* out_targets, void* stream) {
+    CILRS_CHECK(batch >= 1, "batch_assemble_view: batch must be at least 1");
+    CILRS_CHECK(cache && index && params && view && (out_f32 || out_u8),
+                "batch_assemble_view: NULL argument");
+    CILRS_CHECK((!out_speed || speed) && (!out_command || command) && (!out_targets || targets),
+                "batch_assemble_view: a label output needs its label array");
+    return launch_batch_assemble_view(cache, n_frames, speed,
+                                      reinterpret_cast<const long long*>(command), targets,
+                                      reinterpret_cast<const long long*>(index), params, weather,
+                                      view, batch, height, width, out_f32, out_u8, out_speed,
+                                      reinterpret_cast<long long*>(out_command), out_targets,
+                                      reinterpret_cast<hipStream_t>(stream));
+}
+
 // op-level nn.Linear (the kernels the heads launch, one group)
 int cilrs_linear_fwd(const float* x, const float* w, const float* bias, float* y, int batch,
                      int in_features, int out_features, int x_ld, int y_ld, int relu,

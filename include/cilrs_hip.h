@@ -1061,6 +1061,55 @@ int cilrs_batch_assemble_weather(const uint8_t* cache, int64_t n_frames, const f
                                  int width, float* out_f32, uint8_t* out_u8, float* out_speed,
                                  int64_t* out_command, float* out_targets, void* stream);
 
+/* ---- viewpoint on the device: lateral offset and yaw in front of everything else ---------------
+ * The reference records an expert that never leaves the lane centre (model/collect_data.py: one
+ * camera at y = 0, the autopilot, no steering noise), so its network never sees a recovery.  The
+ * remedy since PilotNet is shifted and rotated views with a corrected steering label.  Here that is
+ * a per-sample piecewise projective warp: two inverse homographies (destination pixel -> source
+ * pixel, row-major), `far` for rows at or above split_row and `ground` for the rows below it.
+ * Wherever a stage above reads source pixel (y, x) -- the blur's taps after reflect-101 included --
+ * it reads pixel (y, x) of the virtual frame V instead.  All float32, one rounding per operation,
+ * in this order (p is the stored uint8 frame [H][W][3]):
+ *   M  = ((float)y > split_row) ? ground : far
+ *   u  = (M0*(float)x + M1*(float)y) + M2;  v = (M3*x + M4*y) + M5;  w = (M6*x + M7*y) + M8
+ *   sx = fminf(fmaxf(u / w, 0), (float)(W-1));  sy = fminf(fmaxf(v / w, 0), (float)(H-1))
+ *        (replicate border; this nesting sends a NaN to 0, so whatever the record holds no
+ *        address outside the sample's frame is formed)
+ *   x0 = (int)floorf(sx);  ax = sx - (float)x0;  x1 = min(x0 + 1, W-1);   the same for y
+ *   top = p[y0][x0] + ax * (p[y0][x1] - p[y0][x0]);  bot likewise on row y1
+ *   V[y][x][k] = rintf(clip255(top + ay * (bot - top)))
+ * Weather and the augmentation then act on V at V's own coordinates: the entry points below give,
+ * element for element, what cilrs_augment_[weather_]u8 / cilrs_batch_assemble[_weather] give on
+ * frames first put through the warp and stored as uint8.  A record with on == 0 reads the stored
+ * byte and nothing else.  steer_delta corrects the label (cilrs_batch_assemble_view); lateral_m and
+ * yaw_rad are carried for the caller and not read by the kernels. */
+typedef struct {
+    int on;
+    float split_row;         /* rows with (float)y > split_row use `ground`                        */
+    float far[9], ground[9]; /* destination -> source, row-major                                   */
+    float steer_delta;       /* added to the steer label where on != 0                             */
+    float lateral_m, yaw_rad;
+    int reserved;
+} cilrs_view_params;         /* 96 bytes */
+
+/* cilrs_augment_weather_u8 / cilrs_batch_assemble_weather with view [B] (device, never NULL) in
+ * front, one launch each; weather may be NULL (no weather stage, and no width limit).  The assemble
+ * entry also corrects the label: where on != 0,
+ *   out_targets[b][0] = fminf(fmaxf(targets[index[b]][0] + steer_delta, -1), 1)
+ * and where on == 0 the three targets are copied, never added to (a stored -0.0 stays -0.0).
+ * Throttle, brake, speed and command are gathered unchanged.  NULL view, bad geometry and, with
+ * weather, width > 65,408 are refused before any launch. */
+int cilrs_augment_view_u8(const uint8_t* frames, const cilrs_aug_params* params,
+                          const cilrs_weather_params* weather, const cilrs_view_params* view,
+                          int batch, int height, int width, float* out_f32, uint8_t* out_u8,
+                          void* stream);
+int cilrs_batch_assemble_view(const uint8_t* cache, int64_t n_frames, const float* speed,
+                              const int64_t* command, const float* targets, const int64_t* index,
+                              const cilrs_aug_params* params, const cilrs_weather_params* weather,
+                              const cilrs_view_params* view, int batch, int height, int width,
+                              float* out_f32, uint8_t* out_u8, float* out_speed,
+                              int64_t* out_command, float* out_targets, void* stream);
+
 /* ---- evaluation report accumulators (metrics schema evaluation_report.json:1-73; the reference
  *      ships the report, not the code that made it) ---------------------------------------------
  * acc: cilrs_eval_acc_doubles() doubles on the device, zeroed by the caller before the first
