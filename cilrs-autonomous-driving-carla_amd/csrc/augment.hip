@@ -9,6 +9,13 @@
 // published behaviour (PARITY UNPINNED against them); the arithmetic below is mirrored operation
 // by operation by oracle/augment_oracle.py, which the tests compare against.
 //
+// Two edges are part of the contract.  The shifted hue lies in [0, 179]: it is the LUT
+// trunc(mod(arange(180) + hue, 180)) to within one step (float32 rounds H + hue once), and a
+// wrap that rounds up to 180 is folded to 0, never decoded as a seventh sector.  The blur's border
+// is reflect-101 with period 2(n - 1) at every n >= 2, so a dimension of two pixels under five
+// taps reads indices -2, -1, 2, 3 as 0, 1, 0, 1 (np.pad "reflect", scipy "mirror") and no tap
+// leaves the sample's frame.
+//
 // Weather (cilrs_weather_params: tone, fog, rain) is a second, optional source stage in front of
 // those five: a pure function of the uint8 source pixel, its position and the sample's record,
 // applied wherever a source pixel is read -- the blur's taps included -- so the `_weather`
@@ -62,6 +69,7 @@ __device__ __forceinline__ void colour_stages(const cilrs_aug_params& a, float c
         // the three LUTs (hue wraps mod 180, sat / val clip), truncated to uint8
         float H2 = fmodf(H + a.hue, 180.f);
         if (H2 < 0.f) H2 = H2 + 180.f;
+        if (H2 >= 180.f) H2 = 0.f;               // a tiny negative H2 + 180 rounds to 180: wrap it
         H2 = truncf(H2);
         const float S2 = truncf(clip255(S + a.sat));
         const float V2 = truncf(clip255(V + a.val));
@@ -97,9 +105,13 @@ __device__ __forceinline__ float blur_tap(const float w0, const float w1, const 
     return ad == 0 ? w0 : (ad == 1 ? w1 : w2);
 }
 
+// reflect-101 index of i in [-2, n + 1] for any n >= 2: period 2(n - 1), as np.pad "reflect".  The
+// second fold leaves [0, n) only when n == 2 (i == 3 -> -1 -> 1); for n >= 3 the last line never
+// fires.
 __device__ __forceinline__ int reflect101(int i, const int n) {
     if (i < 0) i = -i;
     if (i >= n) i = 2 * n - 2 - i;
+    if (i < 0) i = -i;
     return i;
 }
 

@@ -982,9 +982,15 @@ typedef struct {
     uint64_t noise_seed;     /* counter-based RNG key of this sample's Gaussian noise            */
     int rbc_on;              /* v' = trunc(clip(v * alpha + beta255))                             */
     float alpha, beta255;
-    int hsv_on;              /* 8-bit HSV (H in half-degrees): H+hue mod 180, S+sat, V+val clipped */
+    int hsv_on;              /* 8-bit HSV (H in half-degrees): H+hue mod 180, S+sat, V+val clipped.
+                              * The shifted hue is the LUT trunc(mod(arange(180) + hue, 180)) to
+                              * within one step and always lies in [0, 179]: a wrap that float32
+                              * rounds up to 180 becomes 0                                         */
     float hue, sat, val;
-    int blur_k;              /* 0/1 = off, 3 or 5 = Gaussian taps; blur_w = centre, +-1, +-2      */
+    int blur_k;              /* 0/1 = off, 3 or 5 = Gaussian taps; blur_w = centre, +-1, +-2.
+                              * Border: reflect-101 with period 2(n-1) at every n >= 2, so height
+                              * or width 2 is valid with five taps too: indices -2, -1, 2, 3 read
+                              * 0, 1, 0, 1 (np.pad "reflect"); no tap leaves the sample's frame    */
     float blur_w[3];
     float noise_std255;      /* 0 = off; sigma in grey levels                                      */
     int nholes;              /* 0..3 rectangles [y0,y1) x [x0,x1) set to 0                         */

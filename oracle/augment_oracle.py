@@ -8,6 +8,11 @@ the libraries' published behaviour -- float32 brightness/contrast LUT truncated 
 with H in half-degrees, shifted through three LUTs; Gaussian taps exp(-x^2 / 2 sigma^2) normalised,
 reflect-101 border; per-channel additive Gaussian noise; zero-filled rectangles.  All arithmetic is
 float32, one rounding per operation, in the order csrc/augment.hip performs it.
+
+The hue shift is DEFINED by the float64 LUT trunc(mod(arange(180) + hue, 180)) (tests/_augment.py
+hue_lut64): the float32 arithmetic here rounds H + hue once, so it may differ from that LUT by one
+step modulo 180, and its result always lies in [0, 179] -- a wrap that rounds up to 180 is folded
+to 0.  The blur's border is np.pad "reflect" (period 2(n-1)), defined for every dimension >= 2.
 """
 from __future__ import annotations
 
@@ -20,6 +25,15 @@ IMG_STD = (0.229, 0.224, 0.225)
 
 def _clip255(x):
     return np.minimum(np.maximum(x, F(0)), F(255))
+
+
+def hue_shift(H, hue):
+    """Half-degree hue H (float32, integer-valued, [0, 180)) shifted by `hue`: the kernel's wrap,
+    operation for operation.  H + hue slightly below zero makes H2 + 180 round to 180; that is
+    folded to 0, so the result lies in [0, 179]."""
+    H2 = np.fmod(np.asarray(H, dtype=F) + F(hue), F(180))
+    H2 = np.where(H2 < 0, H2 + F(180), H2).astype(F)
+    return np.trunc(np.where(H2 >= 180, F(0), H2).astype(F))
 
 
 def _colour_stages(img_f, p):
@@ -45,8 +59,7 @@ def _colour_stages(img_f, p):
         H = np.rint(h * F(0.5))
         H = np.where(H >= 180, H - F(180), H).astype(F)
         S = np.rint(s)
-        H2 = np.fmod(H + F(p["hue"]), F(180))
-        H2 = np.trunc(np.where(H2 < 0, H2 + F(180), H2).astype(F))
+        H2 = hue_shift(H, p["hue"])
         S2 = np.trunc(_clip255(S + F(p["sat"])))
         V2 = np.trunc(_clip255(v + F(p["val"])))
         hh = H2 * F(2) / F(60)
