@@ -186,6 +186,7 @@ SIGNATURES = {
     "cilrs_conv2d_dgrad_bnbwd": (i32, [vp] * 7 + [i32, vp, C.POINTER(i32)] + [i32] * 10
                                  + [vp, sz, vp]),
     "cilrs_conv2d_takes_classes": (i32, [i32] * 9 + [sz, i32]),
+    "cilrs_conv2d_plan_info": (i32, [i32] * 9 + [sz, i32, i32] + [C.POINTER(i32)] * 4),
     "cilrs_net_conv_classes": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32)]),
     "cilrs_conv2d_wgrad_scratch_floats": (sz, [i32] * 9),
     "cilrs_conv2d_wgrad": (i32, [vp, vp, vp, vp] + [i32] * 10 + [vp]),

@@ -163,6 +163,15 @@ struct DgradArgs {
     float* bwd_partial; int* bwd_nblk;
 };
 int launch_conv_dgrad(const DgradArgs& a, hipStream_t s);
+// What launch_conv_igemm / launch_conv_dgrad would run for these arguments (pointers are not read,
+// except that split-K needs scratch != NULL): host only, no launch, no state.  cfg / splitk: tile
+// config and split count; class_tiles: tiles of the position-class launch (0: single problem);
+// parity_fused, for a stride-2 data gradient: 1 = the four parity classes in one launch (cfg /
+// splitk are that launch's), 0 = four launches (cfg / splitk of class (0,0); cfg -1 if no tap
+// reaches it); -1 otherwise.
+struct ConvPlanInfo { int cfg, splitk, class_tiles, parity_fused; };
+int conv_igemm_plan_info(const ConvArgs& a, ConvPlanInfo* info);
+int conv_dgrad_plan_info(const DgradArgs& a, ConvPlanInfo* info);
 
 // ---- static wave priorities --------------------------------------------------------------------
 // Blocks that share a CU run the same K loop: [index math, LDS write, barrier, first LDS reads]

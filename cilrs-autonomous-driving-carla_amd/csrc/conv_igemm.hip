@@ -1114,8 +1114,82 @@ void dense_taps(ConvArgs& a) {
     }
 }
 
-// one launch over the sub-problems of a.multi (64x64 register-staged tile); M_all: pixels of the
-// whole output = pitch of a split-K slab
+// What launch_conv_igemm fills in for its caller: the dense output grid and, on the uniform path,
+// the dense KH x KW tap table.  *class_candidate: the dense problem the caller left to the launcher
+// (the only one position classes are considered for).
+int normalise(ConvArgs& a, bool* class_candidate) {
+    *class_candidate = a.out_H == 0 && a.ntaps == 0 && a.multi.n == 0;
+    if (a.out_H == 0) {          // dense output
+        a.out_H = a.Ho; a.out_W = a.Wo; a.out_sh = a.out_sw = 1; a.out_h0 = a.out_w0 = 0;
+    }
+    if ((a.Cin % BK) == 0 && a.ntaps == 0) {   // dense KH x KW table, forward order
+        CILRS_CHECK(a.KH * a.KW <= 16, "conv_igemm: more than 16 taps on the uniform path");
+        dense_taps(a);
+    }
+    return 0;
+}
+
+// The problem every data-gradient launch starts from: gathers dy, writes the forward Cin columns.
+// Stride 1 is complete (dense table with flipped taps, BatchNorm-backward hooks); stride 2 still
+// needs its parity classes.
+ConvArgs dgrad_problem(const DgradArgs& d) {
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = d.dy; a.w = d.w; a.y = d.dx; a.addend = d.addend;
+    a.mask = d.mask; a.mask_ld = d.mask_ld; a.mask_scale = d.mask_scale;
+    a.N = d.N; a.H = d.Ho; a.W = d.Wo; a.Cin = d.Cout;     // gathered tensor = dy
+    a.Cout = d.Cin;                                        // columns written = forward Cin
+    a.KH = a.KW = d.K;
+    a.x_ld = d.dy_ld; a.y_ld = d.dx_ld; a.w_mode = 1; a.w_cin = d.Cin;
+    a.scratch = d.scratch; a.scratch_floats = d.scratch_floats;
+    a.force_cfg = d.force_cfg; a.force_splitk = d.force_splitk;
+    if (d.stride == 1) {
+        a.bwd_z = d.bwd_z; a.bwd_y = d.bwd_y; a.bwd_stats = d.bwd_stats; a.bwd_relu = d.bwd_relu;
+        a.bwd_partial = d.bwd_partial; a.bwd_nblk = d.bwd_nblk;
+        a.Ho = d.H; a.Wo = d.W; a.stride = 1; a.pad = d.K - 1 - d.pad;
+    }
+    return a;
+}
+
+// Stride-2 data gradient: ALL FOUR parity classes in one launch while a class alone does not fill
+// the chip (a class alone is 0.4 rounds of blocks with a quarter of the K length; launched
+// separately they ran at 52-61 TF).  A class that brings a full round of blocks of its own (the
+// ResNet-50 variant at 176x400: 2,200 tiles per class) runs 36 % FASTER as four launches with the
+// cost model's own tile per class (tools/conv_bench.py --r50: 257 vs 349 us).  A forced tile or
+// split always takes the four launches.
+bool dgrad_fuses_parity(const DgradArgs& d) {
+    const long cls_tiles = (long)cdiv(d.N * ((d.H + 1) / 2) * ((d.W + 1) / 2), 64) * (d.Cin / 64);
+    return d.force_cfg < 0 && d.force_splitk <= 0 && (d.Cout % BK) == 0 && (d.Cin % 64) == 0 &&
+           cls_tiles < 1280;
+}
+
+// Parity class (ph, pw) of a stride-2 data gradient as a launch of its own: a = dgrad_problem(d);
+// c gets the class's enumerated grid, its place in dx and its tap table (c.ntaps == 0: no tap
+// reaches the class).  False for a class without pixels.
+bool parity_problem(const DgradArgs& d, const ConvArgs& a, int ph, int pw, ConvArgs& c) {
+    c = a;
+    c.Ho = (d.H - ph + 1) / 2; c.Wo = (d.W - pw + 1) / 2;
+    if (c.Ho <= 0 || c.Wo <= 0) return false;
+    c.stride = 1; c.pad = 0;
+    c.out_H = d.H; c.out_W = d.W; c.out_sh = 2; c.out_sw = 2; c.out_h0 = ph; c.out_w0 = pw;
+    int nt = 0;
+    for (int kh = 0; kh < d.K; ++kh) {
+        if ((ph + d.pad - kh) & 1) continue;
+        for (int kw = 0; kw < d.K; ++kw) {
+            if ((pw + d.pad - kw) & 1) continue;
+            c.tap_dh[nt] = (ph + d.pad - kh) / 2;     // exact: numerator is even
+            c.tap_dw[nt] = (pw + d.pad - kw) / 2;
+            c.tap_w[nt] = kh * d.K + kw;
+            ++nt;
+        }
+    }
+    c.ntaps = nt;
+    return true;
+}
+
+// one launch over the sub-problems of a.multi (64x64 register-staged tile: kMultiCfg); M_all:
+// pixels of the whole output = pitch of a split-K slab
+constexpr int kMultiCfg = 2;
 static_assert(sizeof(ConvArgs) + 3 * sizeof(int) <= 4096, "kernel arguments exceed the launch limit");
 template <int W_MODE>
 int launch_multi(const ConvArgs& a, int tiles, int M_all, int kt_per_split, hipStream_t s) {
@@ -1165,20 +1239,13 @@ int launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     a.prio_mode = wave_priority_mode();
     const int M = a.N * a.Ho * a.Wo;
     const bool uniform = (a.Cin % BK) == 0;
-    // position classes: only for the dense problem the caller left to the launcher
-    const bool class_candidate = a_in.out_H == 0 && a_in.ntaps == 0 && a_in.multi.n == 0;
     // the uniform path addresses both operands with 32-bit byte offsets (buffer loads)
     CILRS_CHECK(!uniform || ((size_t)a.N * a.H * a.W * a.x_ld * sizeof(float) < (1ull << 32) &&
                              (size_t)(a.w_mode == 0 ? a.Cout : a.Cin) * a.KH * a.KW *
                                      (a.w_mode == 0 ? a.Cin : a.w_cin) * sizeof(float) < (1ull << 32)),
                 "conv_igemm: tensor larger than 4 GB");
-    if (a.out_H == 0) {          // dense output
-        a.out_H = a.Ho; a.out_W = a.Wo; a.out_sh = a.out_sw = 1; a.out_h0 = a.out_w0 = 0;
-    }
-    if (uniform && a.ntaps == 0) {   // dense KH x KW table, forward order
-        CILRS_CHECK(a.KH * a.KW <= 16, "conv_igemm: more than 16 taps on the uniform path");
-        dense_taps(a);
-    }
+    bool class_candidate = false;
+    if (normalise(a, &class_candidate)) return 1;
     const int KT = uniform ? a.ntaps * (a.Cin / BK) : cdiv(a.KH * a.KW * a.Cin, BK);
     // W_MODE 0 weight rows are addressed with the forward row pitch KH*KW*Cin
     const int Krow = a.KH * a.KW * a.Cin;
@@ -1306,37 +1373,16 @@ int launch_slab_reduce_cols(int mode, const float* slabs, int splits, float* y, 
 int launch_conv_dgrad(const DgradArgs& d, hipStream_t s) {
     CILRS_CHECK(d.stride == 1 || d.stride == 2, "dgrad: stride must be 1 or 2");
     CILRS_CHECK(d.K * d.K <= 16, "dgrad: filter too large");
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = d.dy; a.w = d.w; a.y = d.dx; a.addend = d.addend;
-    a.mask = d.mask; a.mask_ld = d.mask_ld; a.mask_scale = d.mask_scale;
-    a.N = d.N; a.H = d.Ho; a.W = d.Wo; a.Cin = d.Cout;     // gathered tensor = dy
-    a.Cout = d.Cin;                                        // columns written = forward Cin
-    a.KH = a.KW = d.K;
-    a.x_ld = d.dy_ld; a.y_ld = d.dx_ld; a.w_mode = 1; a.w_cin = d.Cin;
-    a.scratch = d.scratch; a.scratch_floats = d.scratch_floats;
-    a.force_cfg = d.force_cfg; a.force_splitk = d.force_splitk;
+    const ConvArgs a = dgrad_problem(d);
     if (d.bwd_nblk) *d.bwd_nblk = 0;
-    if (d.stride == 1) {
-        a.bwd_z = d.bwd_z; a.bwd_y = d.bwd_y; a.bwd_stats = d.bwd_stats; a.bwd_relu = d.bwd_relu;
-        a.bwd_partial = d.bwd_partial; a.bwd_nblk = d.bwd_nblk;
-        a.Ho = d.H; a.Wo = d.W; a.stride = 1; a.pad = d.K - 1 - d.pad;
-        return launch_conv_igemm(a, s);           // dense table with flipped taps
-    }
+    if (d.stride == 1) return launch_conv_igemm(a, s);           // dense table with flipped taps
     // stride 2: dx pixel (hi, wi) = (2*oh + ph, 2*ow + pw) only sees taps kh with
     // (ph + pad - kh) even, reading dy row oh + (ph + pad - kh)/2
     //
-    // Default: ALL FOUR parity classes in one launch (a class alone is 0.4 rounds of blocks with a
-    // quarter of the K length; launched separately they ran at 52-61 TF).  Classes are ordered by
-    // K length, longest first; a class no tap reaches (1x1 / s2) still gets blocks: with zero
-    // K-tiles they write the addend (or zeros) through the ordinary epilogue.
-    // ... when a class alone does not fill the chip.  A class that brings a full round of blocks
-    // of its own (the ResNet-50 variant at 176x400: 2,200 tiles per class) runs 36 % FASTER as four
-    // launches with the cost model's own tile per class (tools/conv_bench.py --r50: 257 vs 349 us).
-    const long cls_tiles = (long)cdiv(d.N * ((d.H + 1) / 2) * ((d.W + 1) / 2), 64) * (d.Cin / 64);
-    const bool fuse = d.force_cfg < 0 && d.force_splitk <= 0 && (d.Cout % BK) == 0 &&
-                      (d.Cin % 64) == 0 && cls_tiles < 1280;
-    if (fuse) {
+    // Default (dgrad_fuses_parity): one launch.  Classes are ordered by K length, longest first; a
+    // class no tap reaches (1x1 / s2) still gets blocks: with zero K-tiles they write the addend
+    // (or zeros) through the ordinary epilogue.
+    if (dgrad_fuses_parity(d)) {
         ConvArgs c = a;
         c.stride = 1; c.pad = 0;
         c.out_H = d.H; c.out_W = d.W; c.out_sh = 2; c.out_sw = 2; c.out_h0 = c.out_w0 = 0;
@@ -1401,24 +1447,9 @@ int launch_conv_dgrad(const DgradArgs& d, hipStream_t s) {
     }
     for (int ph = 0; ph < 2; ++ph)
         for (int pw = 0; pw < 2; ++pw) {
-            ConvArgs c = a;
-            c.Ho = (d.H - ph + 1) / 2; c.Wo = (d.W - pw + 1) / 2;
-            if (c.Ho <= 0 || c.Wo <= 0) continue;
-            c.stride = 1; c.pad = 0;
-            c.out_H = d.H; c.out_W = d.W; c.out_sh = 2; c.out_sw = 2; c.out_h0 = ph; c.out_w0 = pw;
-            int nt = 0;
-            for (int kh = 0; kh < d.K; ++kh) {
-                if ((ph + d.pad - kh) & 1) continue;
-                for (int kw = 0; kw < d.K; ++kw) {
-                    if ((pw + d.pad - kw) & 1) continue;
-                    c.tap_dh[nt] = (ph + d.pad - kh) / 2;     // exact: numerator is even
-                    c.tap_dw[nt] = (pw + d.pad - kw) / 2;
-                    c.tap_w[nt] = kh * d.K + kw;
-                    ++nt;
-                }
-            }
-            c.ntaps = nt;
-            if (nt == 0) {
+            ConvArgs c;
+            if (!parity_problem(d, a, ph, pw, c)) continue;
+            if (c.ntaps == 0) {
                 const int M = c.N * c.Ho * c.Wo;
                 const size_t total = (size_t)M * (c.Cout / 4);
                 const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
@@ -1428,6 +1459,35 @@ int launch_conv_dgrad(const DgradArgs& d, hipStream_t s) {
             }
             if (launch_conv_igemm(c, s)) return 1;
         }
+    return 0;
+}
+
+int conv_igemm_plan_info(const ConvArgs& a_in, ConvPlanInfo* info) {
+    ConvArgs a = a_in;
+    bool class_candidate = false;
+    if (normalise(a, &class_candidate)) return 1;
+    const IgemmPlan plan = plan_igemm(a, class_candidate, a.multi);
+    *info = ConvPlanInfo{plan.ch.cfg, plan.ch.splitk, plan.class_tiles, -1};
+    return 0;
+}
+
+int conv_dgrad_plan_info(const DgradArgs& d, ConvPlanInfo* info) {
+    CILRS_CHECK(d.stride == 1 || d.stride == 2, "dgrad: stride must be 1 or 2");
+    CILRS_CHECK(d.K * d.K <= 16, "dgrad: filter too large");
+    const ConvArgs a = dgrad_problem(d);
+    if (d.stride == 1) return conv_igemm_plan_info(a, info);
+    if (dgrad_fuses_parity(d)) {       // launch_multi's tile, never split
+        *info = ConvPlanInfo{kMultiCfg, 1, 0, 1};
+        return 0;
+    }
+    ConvArgs c;
+    parity_problem(d, a, 0, 0, c);     // class (0,0): never empty
+    if (c.ntaps == 0) {                // a fill, no GEMM
+        *info = ConvPlanInfo{-1, 0, 0, 0};
+        return 0;
+    }
+    if (conv_igemm_plan_info(c, info)) return 1;
+    info->parity_fused = 0;
     return 0;
 }
 

@@ -3698,9 +3698,10 @@ int cilrs_net_profile_reset(cilrs_net* net) {
 // ------------------------------------------------------------------------------------------------
 // op-level entry points (unit parity tests)
 // ------------------------------------------------------------------------------------------------
-int cilrs_conv2d_fwd(const float* x, const float* w, float* y, int N, int H, int W, int Cin,
-                     int Cout, int KH, int KW, int stride, int pad, int force_cfg,
-                     int force_splitk, float* scratch, size_t scratch_floats, void* stream) {
+// the problems the op-level convolution entries hand the launchers: dense NHWC / OHWI tensors
+static ConvArgs make_conv_fwd(const float* x, const float* w, float* y, int N, int H, int W, int Cin,
+                              int Cout, int KH, int KW, int stride, int pad, int force_cfg,
+                              int force_splitk, float* scratch, size_t scratch_floats) {
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     a.x = x; a.w = w; a.y = y;
@@ -3710,6 +3711,30 @@ int cilrs_conv2d_fwd(const float* x, const float* w, float* y, int N, int H, int
     a.x_ld = Cin; a.y_ld = Cout; a.w_mode = 0; a.w_cin = Cin;
     a.scratch = scratch; a.scratch_floats = scratch_floats;
     a.force_cfg = force_cfg; a.force_splitk = force_splitk;
+    return a;
+}
+
+static DgradArgs make_conv_dgrad(const float* dy, const float* w, float* dx, const float* addend,
+                                 int N, int H, int W, int Cin, int Cout, int K, int stride, int pad,
+                                 int force_cfg, int force_splitk, float* scratch,
+                                 size_t scratch_floats) {
+    DgradArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dy = dy; a.w = w; a.dx = dx; a.addend = addend;
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin;
+    a.Ho = (H + 2 * pad - K) / stride + 1; a.Wo = (W + 2 * pad - K) / stride + 1;
+    a.Cout = Cout; a.K = K; a.stride = stride; a.pad = pad;
+    a.dy_ld = Cout; a.dx_ld = Cin;
+    a.scratch = scratch; a.scratch_floats = scratch_floats;
+    a.force_cfg = force_cfg; a.force_splitk = force_splitk;
+    return a;
+}
+
+int cilrs_conv2d_fwd(const float* x, const float* w, float* y, int N, int H, int W, int Cin,
+                     int Cout, int KH, int KW, int stride, int pad, int force_cfg,
+                     int force_splitk, float* scratch, size_t scratch_floats, void* stream) {
+    const ConvArgs a = make_conv_fwd(x, w, y, N, H, W, Cin, Cout, KH, KW, stride, pad, force_cfg,
+                                     force_splitk, scratch, scratch_floats);
     return launch_conv_igemm(a, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -3718,15 +3743,8 @@ int cilrs_conv2d_dgrad(const float* dy, const float* w, float* dx, const float* 
                        int force_cfg, int force_splitk, float* scratch, size_t scratch_floats,
                        void* stream) {
     CILRS_CHECK(KH == KW, "dgrad: square kernels only");
-    DgradArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dy = dy; a.w = w; a.dx = dx; a.addend = addend;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin;
-    a.Ho = (H + 2 * pad - KH) / stride + 1; a.Wo = (W + 2 * pad - KW) / stride + 1;
-    a.Cout = Cout; a.K = KH; a.stride = stride; a.pad = pad;
-    a.dy_ld = Cout; a.dx_ld = Cin;
-    a.scratch = scratch; a.scratch_floats = scratch_floats;
-    a.force_cfg = force_cfg; a.force_splitk = force_splitk;
+    const DgradArgs a = make_conv_dgrad(dy, w, dx, addend, N, H, W, Cin, Cout, KH, stride, pad,
+                                        force_cfg, force_splitk, scratch, scratch_floats);
     return launch_conv_dgrad(a, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -3735,15 +3753,8 @@ int cilrs_conv2d_fwd_stats(const float* x, const float* w, float* y, float* part
                            int force_cfg, int force_splitk, float* scratch, size_t scratch_floats,
                            void* stream) {
     CILRS_CHECK(x && w && y && partial && nblk, "conv2d_fwd_stats: NULL argument");
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.w = w; a.y = y;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin;
-    a.Ho = (H + 2 * pad - K) / stride + 1; a.Wo = (W + 2 * pad - K) / stride + 1; a.Cout = Cout;
-    a.KH = a.KW = K; a.stride = stride; a.pad = pad;
-    a.x_ld = Cin; a.y_ld = Cout; a.w_mode = 0; a.w_cin = Cin;
-    a.scratch = scratch; a.scratch_floats = scratch_floats;
-    a.force_cfg = force_cfg; a.force_splitk = force_splitk;
+    ConvArgs a = make_conv_fwd(x, w, y, N, H, W, Cin, Cout, K, K, stride, pad, force_cfg,
+                               force_splitk, scratch, scratch_floats);
     a.bn_partial = partial; a.bn_nblk = nblk; *nblk = 0;
     // the caller's buffer holds cilrs_bn_partial_floats(Cout): as many row groups as the BatchNorm kernels use
     CILRS_CHECK((size_t)(cdiv(N * a.Ho * a.Wo, 64) + kConvMultiMax) * 2 * Cout <= bn_partial_floats(Cout),
@@ -3759,15 +3770,8 @@ int cilrs_conv2d_dgrad_bnbwd(const float* dy, const float* w, float* dx, const f
     CILRS_CHECK(dy && w && dx && bwd_y && bwd_stats && partial && nblk && (bwd_z || !bwd_relu),
                 "conv2d_dgrad_bnbwd: NULL argument");
     CILRS_CHECK(stride == 1, "conv2d_dgrad_bnbwd: stride 1 only");
-    DgradArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dy = dy; a.w = w; a.dx = dx; a.addend = addend;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin;
-    a.Ho = H + 2 * pad - K + 1; a.Wo = W + 2 * pad - K + 1;
-    a.Cout = Cout; a.K = K; a.stride = stride; a.pad = pad;
-    a.dy_ld = Cout; a.dx_ld = Cin;
-    a.scratch = scratch; a.scratch_floats = scratch_floats;
-    a.force_cfg = force_cfg; a.force_splitk = force_splitk;
+    DgradArgs a = make_conv_dgrad(dy, w, dx, addend, N, H, W, Cin, Cout, K, stride, pad, force_cfg,
+                                  force_splitk, scratch, scratch_floats);
     a.bwd_z = bwd_z; a.bwd_y = bwd_y; a.bwd_stats = bwd_stats; a.bwd_relu = bwd_relu;
     a.bwd_partial = partial; a.bwd_nblk = nblk; *nblk = 0;
     CILRS_CHECK((size_t)(cdiv(N * H * W, 64) + kConvMultiMax) * 2 * Cin <= bn_partial_floats(Cin),
@@ -3779,6 +3783,36 @@ int cilrs_conv2d_takes_classes(int N, int H, int W, int Cin, int Cout, int K, in
                                int dgrad, size_t scratch_floats, int force_splitk) {
     return conv_igemm_takes_classes(N, H, W, Cin, Cout, K, stride, pad, dgrad != 0, scratch_floats,
                                     force_splitk) ? 1 : 0;
+}
+
+int cilrs_conv2d_plan_info(int N, int H, int W, int Cin, int Cout, int K, int stride, int pad,
+                           int dgrad, size_t scratch_floats, int force_cfg, int force_splitk,
+                           int* cfg, int* splitk, int* class_tiles, int* parity_fused) {
+    CILRS_CHECK(cfg && splitk && class_tiles && parity_fused, "conv2d_plan_info: NULL argument");
+    CILRS_CHECK(N >= 1 && K >= 1 && K * K <= 16 && (stride == 1 || stride == 2) && pad >= 0 &&
+                    H + 2 * pad >= K && W + 2 * pad >= K,
+                "conv2d_plan_info: bad geometry");
+    CILRS_CHECK(Cin >= 4 && Cin % 4 == 0 && Cout >= 4 && Cout % 4 == 0 &&
+                    (dgrad ? Cin : Cout) % 64 == 0,
+                "conv2d_plan_info: channel counts %d -> %d", Cin, Cout);
+    // (never read: split-K is only considered when there is a scratch pointer)
+    float* const scratch = scratch_floats ? reinterpret_cast<float*>(sizeof(float) * 4) : nullptr;
+    ConvPlanInfo info;
+    if (dgrad) {
+        if (conv_dgrad_plan_info(make_conv_dgrad(nullptr, nullptr, nullptr, nullptr, N, H, W, Cin, Cout,
+                                                 K, stride, pad, force_cfg, force_splitk, scratch,
+                                                 scratch_floats),
+                                 &info))
+            return 1;
+    } else if (conv_igemm_plan_info(make_conv_fwd(nullptr, nullptr, nullptr, N, H, W, Cin, Cout, K, K,
+                                                  stride, pad, force_cfg, force_splitk, scratch,
+                                                  scratch_floats),
+                                    &info)) {
+        return 1;
+    }
+    *cfg = info.cfg; *splitk = info.splitk; *class_tiles = info.class_tiles;
+    *parity_fused = info.parity_fused;
+    return 0;
 }
 
 int cilrs_net_conv_classes(const cilrs_net* net, int conv, int* fwd, int* dgrad) {

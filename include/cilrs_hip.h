@@ -1179,6 +1179,17 @@ int cilrs_conv2d_dgrad_bnbwd(const float* dy, const float* w, float* dx, const f
 int cilrs_conv2d_takes_classes(int N, int H, int W, int Cin, int Cout, int K, int stride, int pad,
                                int dgrad, size_t scratch_floats, int force_splitk);
 int cilrs_net_conv_classes(const cilrs_net* net, int conv, int* fwd, int* dgrad);
+/* What cilrs_conv2d_fwd (dgrad != 0: cilrs_conv2d_dgrad) would launch for this problem with
+ * `scratch_floats` floats of split-K scratch and these force_cfg / force_splitk (test aid: the
+ * launchers' own decision code, no launch, no state kept).  *cfg: the tile config (as force_cfg);
+ * *splitk: the split count (1: unsplit); *class_tiles: tiles of the position-class launch, 0 for a
+ * single problem; *parity_fused, for a stride-2 data gradient: 1 = the four output-parity classes
+ * in one launch (*cfg / *splitk are that launch's), 0 = four launches, *cfg / *splitk being those of
+ * parity class (0,0) (*cfg -1 if no filter tap reaches that class); -1 when the problem has no
+ * parity classes.  The fused hooks of cilrs_conv2d_fwd_stats / _dgrad_bnbwd do not change any of it. */
+int cilrs_conv2d_plan_info(int N, int H, int W, int Cin, int Cout, int K, int stride, int pad,
+                           int dgrad, size_t scratch_floats, int force_cfg, int force_splitk,
+                           int* cfg, int* splitk, int* class_tiles, int* parity_fused);
 /* d(loss)/dw (OHWI, Cin_dst channels kept); scratch from cilrs_conv2d_wgrad_scratch_floats */
 size_t cilrs_conv2d_wgrad_scratch_floats(int N, int H, int W, int Cin, int Cout, int KH, int KW,
                                          int stride, int pad);

@@ -261,6 +261,7 @@ GPU_CASES = [
     case("ft3_b8", mode="ft", e=3),
     case("resnet50_b4", trunk="resnet50", B=4, H=64, W=64, seed=34),
     case("nc6_b12", nc=6, B=12, H=64, W=64, seed=35),
+    case("resnet50_b3_odd", trunk="resnet50", B=3, H=90, W=202, seed=36),
 ]
 
 

@@ -23,6 +23,9 @@ The cases (_masked_grads.GPU_CASES) are the smallest that reach each backward ke
                         stops at the cut, trainable tensors only
   resnet50_b4           ResNet-50 (4,64,64): Bottleneck blocks, 1x1 and 2048-wide layers
   nc6_b12               num_commands = 6 (12,64,64): grouped head gradients, two rows per branch
+  resnet50_b3_odd       ResNet-50 (3,90,202): train_b3_odd's odd maps (45x101 -> 3x7) through
+                        Bottleneck blocks -- ragged tiles of the 1x1 and 2048-wide layers, stride-2
+                        parity classes of different sizes
 
 R: MEASURED_RATIOS below are the largest e_hip / max(e_cpu, floor) per case on an MI355X (L2 and
 element), kept with the report line in profiles/masked_grad_floor.log; R = twice the largest of
@@ -54,6 +57,7 @@ MEASURED_RATIOS = {
     "ft3_b8": (1.303, 1.865, 2.79e-06),
     "resnet50_b4": (1.114, 1.489, 1.41e-05),       # 1.41e-5: visual_encoder.7.2.conv3.weight, CPU 1.4e-5 too
     "nc6_b12": (1.255, 1.519, 3.73e-06),
+    "resnet50_b3_odd": (1.188, 1.510, 1.21e-05),   # 1.21e-5: visual_encoder.7.2.conv3.weight again
 }
 R = 5           # ceil(2 x 2.166)
 
@@ -69,7 +73,8 @@ def _run(name):
     return be, res
 
 
-@pytest.mark.parametrize("name", ["train_b8", "train_b3_odd", "train_b1", "resnet50_b4", "nc6_b12"])
+@pytest.mark.parametrize("name", ["train_b8", "train_b3_odd", "train_b1", "resnet50_b4", "nc6_b12",
+                                  "resnet50_b3_odd"])
 def test_train_mode_gradients(name):
     _run(name)
 

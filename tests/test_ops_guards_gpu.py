@@ -18,6 +18,13 @@ Which case exercises an entry's ragged tail / its plan at the benchmark batch (N
                                every forced tile and split-K / TRUNK_SHAPES at N = 128, auto plan;
                                each with scratch capacity 0 (NULL), one slab, the plan's 36 M floats
   conv2d_wgrad                 the same M = 21 case / (128,) + TRUNK_SHAPES (K-slabs over grid.z)
+  the three above, Bottleneck  BOTTLENECK_GUARD_CASES: (1, 3, 7, 2048, 512, 1, 1, 0), M = 21 under the
+                               longest 1x1 K loop; (7, 3, 7, 512, 2048, 1, 1, 0) and (5, 6, 13, 1024,
+                               2048, 1, 2, 0), the widest rows; (2, 22, 50, 64, 64, 1, 1, 0), the shortest
+                               K loop and a one-tile weight gradient / none
+  conv2d_fwd_stats, conv2d_dgrad_bnbwd   the same four (the data-gradient form: the stride-1 ones), a
+                               128-row tile, the 64-row tile, the automatic plan and two forced slabs,
+                               partial buffer of exactly bn_partial_floats / none
   stem_conv_fwd, _wgrad        (9, 86, 199) and (2, 26, 400): partial last tiles / (128, 88, 200)
   stem_conv_dgrad              (1, 37, 51), (9, 86, 199), pitched rows / (128, 88, 200)
   conv2d_wino_fwd, _pre, _split, _fold_fwd, _dgrad, _wgrad, wino_filter_transform
@@ -46,6 +53,7 @@ import torch
 
 from _guards import Inputs, all_finite, guarded, guarded_rows
 from test_infer16_gpu import BOTTLENECK_CASES, RAGGED_CASES
+from test_ops_bottleneck_gpu import BOTTLENECK_F32_CASES, STATS_PLANS
 from test_ops_gpu import (CONV16_CASES, CONV16T_CASES, CONV_CASES, LINEAR_CASES,
                           PLAN_KSPLIT_FLOATS, TRUNK_SHAPES, WINO_CASES)
 
@@ -157,9 +165,13 @@ def test_guards_notice_a_store_on_either_side_and_in_a_pad_column(dtype):
 FWD_PLANS = [(-1, 0), (0, 1), (1, 1), (2, 1), (1, 3), (2, 2), (3, 1), (4, 1), (5, 1), (5, 2), (4, 3)]
 DGRAD_PLANS = [(-1, 0), (1, 1), (2, 2), (4, 1), (5, 2), (5, 1)]
 CAPACITIES = ["none", "one_slab", "plan"]
-FWD_CASES = [(c, cfg, sk) for c in CONV_CASES for cfg, sk in FWD_PLANS
+# the ragged and the widest of the ResNet-50 variant's shapes
+BOTTLENECK_GUARD_CASES = [(1, 3, 7, 2048, 512, 1, 1, 0), (7, 3, 7, 512, 2048, 1, 1, 0),
+                          (5, 6, 13, 1024, 2048, 1, 2, 0), (2, 22, 50, 64, 64, 1, 1, 0)]
+assert set(BOTTLENECK_GUARD_CASES) <= set(BOTTLENECK_F32_CASES)
+FWD_CASES = [(c, cfg, sk) for c in CONV_CASES + BOTTLENECK_GUARD_CASES for cfg, sk in FWD_PLANS
              if not (cfg in (0, 3) and c[4] % 128)]          # the 128-wide tile needs Cout % 128 == 0
-DGRAD_CASES = [(c, cfg, sk) for c in CONV_CASES for cfg, sk in DGRAD_PLANS]
+DGRAD_CASES = [(c, cfg, sk) for c in CONV_CASES + BOTTLENECK_GUARD_CASES for cfg, sk in DGRAD_PLANS]
 
 
 def _capacity(g, kind, out_numel):
@@ -232,8 +244,70 @@ def test_conv_fwd_dgrad_guards_at_benchmark_batch(shape):
     _conv_dgrad(128, *shape, -1, 0)
 
 
+# ---- the same two with the fused BatchNorm reductions ----------------------------------------------
+@pytest.mark.parametrize("cfg,splitk", STATS_PLANS)
+@pytest.mark.parametrize("case", BOTTLENECK_GUARD_CASES)
+def test_conv_fwd_stats_guards(case, cfg, splitk):
+    """the column partials land in a buffer of exactly cilrs_bn_partial_floats(Cout) floats, and
+    [2][Cout][*nblk] of it is written"""
+    L = _L()
+    lib = L.lib()
+    N, H, W, Cin, Cout, k, s, p = case
+    Ho, Wo = out_hw(H, W, k, s, p)
+    x, w = R(N, H, W, Cin), R(Cout, k, k, Cin, scale=(k * k * Cin) ** -0.5)
+    npart = lib.cilrs_bn_partial_floats(Cout)
+    for kind in CAPACITIES:
+        g = Guards()
+        y = g.buf((N, Ho, Wo, Cout), guard=128 * Cout, name=f"fwd_stats y ({kind})")
+        part = g.buf(npart, guard=npart, name=f"fwd_stats partial ({kind})", finite=False)
+        scr, cap = _capacity(g, kind, y.numel())
+        nblk = C.c_int(-1)
+        g.const(x=x, w=w)
+        rc = lib.cilrs_conv2d_fwd_stats(L.ptr(x), L.ptr(w), L.ptr(y), L.ptr(part), C.byref(nblk), N, H,
+                                        W, Cin, Cout, k, s, p, cfg, splitk, L.ptr(scr), cap, stream())
+        _ok_or_refused(rc, "conv2d_fwd_stats")
+        if rc != 0:
+            g.finite = []
+        g.verify()
+        if rc == 0:
+            assert 0 <= nblk.value and 2 * Cout * nblk.value <= npart
+            all_finite(part[:2 * Cout * nblk.value], "fwd_stats partial [2][Cout][nblk]")
+
+
+@pytest.mark.parametrize("cfg,splitk", STATS_PLANS)
+@pytest.mark.parametrize("case", [c for c in BOTTLENECK_GUARD_CASES if c[6] == 1])
+def test_conv_dgrad_bnbwd_guards(case, cfg, splitk):
+    L = _L()
+    lib = L.lib()
+    N, H, W, Cin, Cout, k, s, p = case
+    Ho, Wo = out_hw(H, W, k, s, p)
+    M = N * H * W
+    dy, w = R(N, Ho, Wo, Cout), R(Cout, k, k, Cin, scale=(k * k * Cin) ** -0.5)
+    add, bz, by = R(M, Cin), R(M, Cin), R(M, Cin)
+    bstats = torch.cat([R(Cin, scale=0.1), torch.rand(Cin, device="cuda") + 0.5, R(2 * Cin)])
+    npart = lib.cilrs_bn_partial_floats(Cin)
+    for kind in CAPACITIES:
+        g = Guards()
+        dx = g.buf((M, Cin), guard=128 * Cin, name=f"dgrad_bnbwd dx ({kind})")
+        part = g.buf(npart, guard=npart, name=f"dgrad_bnbwd partial ({kind})", finite=False)
+        scr, cap = _capacity(g, kind, dx.numel())
+        nblk = C.c_int(-1)
+        g.const(dy=dy, w=w, addend=add, bwd_z=bz, bwd_y=by, bwd_stats=bstats)
+        rc = lib.cilrs_conv2d_dgrad_bnbwd(L.ptr(dy), L.ptr(w), L.ptr(dx), L.ptr(add), L.ptr(bz),
+                                          L.ptr(by), L.ptr(bstats), 1, L.ptr(part), C.byref(nblk), N, H,
+                                          W, Cin, Cout, k, s, p, cfg, splitk, L.ptr(scr), cap, stream())
+        _ok_or_refused(rc, "conv2d_dgrad_bnbwd")
+        if rc != 0:
+            g.finite = []
+        g.verify()
+        if rc == 0:
+            assert 0 <= nblk.value and 2 * Cin * nblk.value <= npart
+            all_finite(part[:2 * Cin * nblk.value], "dgrad_bnbwd partial [2][Cin][nblk]")
+
+
 # ---- fp32 weight gradient, the stem's three kernels ------------------------------------------------
-WGRAD_CASES = CONV_CASES + [(4, 22, 50, 64, 64, 3, 1, 1)] + [(128,) + s for s in TRUNK_SHAPES]
+WGRAD_CASES = (CONV_CASES + [(4, 22, 50, 64, 64, 3, 1, 1)] + [(128,) + s for s in TRUNK_SHAPES]
+               + BOTTLENECK_GUARD_CASES)
 
 
 @pytest.mark.parametrize("case", WGRAD_CASES)
