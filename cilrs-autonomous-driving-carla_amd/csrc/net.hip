@@ -102,6 +102,7 @@ struct Arch {
     LinT se0, se3, br[kMaxCmd][3], sp0, sp3, sp5;
     size_t arena_floats = 0, count = 0, bn_floats = 0;
     size_t seg_begin[6], seg_end[6];    // 0 heads, 1 layer4, 2 layer3, 3 layer2, 4 layer1, 5 stem
+    int layer_first[5];                 // blocks[] index of layer L+1's first block; [4] = blocks.size()
 
     size_t add_param(const std::string& name, int ndim, int s0, int s1 = 1, int s2 = 1,
                      int s3 = 1) {
@@ -155,6 +156,7 @@ struct Arch {
         int inpl = 64;
         for (int L = 0; L < 4; ++L) {
             layer_begin[L] = arena_floats;
+            layer_first[L] = (int)blocks.size();
             for (int b = 0; b < nblk[L]; ++b) {
                 const std::string p =
                     "visual_encoder." + std::to_string(4 + L) + "." + std::to_string(b);
@@ -185,6 +187,7 @@ struct Arch {
         }
         feat = inpl;
         layer_begin[4] = arena_floats;
+        layer_first[4] = (int)blocks.size();
         se0 = add_lin("speed_encoder.0", 1, 128);
         se3 = add_lin("speed_encoder.3", 128, 128);
         for (int k = 0; k < ncmd; ++k) {
@@ -300,7 +303,6 @@ constexpr int kRingIdx[kDyRing] = {0, 4};
 
 struct cilrs_net {
     const Arch* A = nullptr;               // architecture variant of this plan
-    const cilrs_adam_args* fused_adam = nullptr;   // set for the duration of cilrs_net_backward_step
     int B, H, W;
     std::vector<ConvG> cg;                 // geometry + workspace offsets (floats) per conv
     int H0, W0, H1, W1;                    // stem conv out, maxpool out
@@ -321,13 +323,23 @@ struct cilrs_net {
     bool streams_ready = false;
     hipStream_t side[1];                   // weight-gradient stream
     hipEvent_t fork_ev, gbuf_ev[kNumG], wprep_ev, branch_ev, heads_ev;
-    bool heads_pending = false;            // the heads' weight gradients of this backward pass are on the side stream
-    int side_branch = 0;                   // conv_fwd / conv_fwd16 are building a down-sample branch: no split-K scratch;
+    int side_branch = 0;                  // conv_fwd / conv_fwd16 are building a down-sample branch: no split-K scratch;
                                            // 1 = on the side stream, with column-partial scratch of its own
     bool wprep_pending = false;            // this step's weight images are being built on the side stream
-    bool gbuf_pending[kNumG] = {};
-    int dy_pos = 0;
-    int bwd_nblk_next = 0;                 // fused BN-backward partials waiting for their BN
+    // What the backward pass carries from one launch to a later one, and from one call to the next
+    // (everything else of a call is in its BwdPass).
+    struct BwdState {
+        // side stream 0 still reads gradient buffer gi.  Set by gbuf_side_end behind a weight
+        // gradient, cleared by gbuf_acquire when the main stream has waited for it: gbuf_join_all
+        // at the end of every backward call leaves all of them clear.
+        bool gbuf_pending[kNumG] = {};
+        // the heads' weight gradients are on the side stream.  Set by backward_heads (segment 0),
+        // cleared by backward_join at the end of the same call.
+        bool heads_pending = false;
+        // next slot of the dy ring.  Advanced by BwdPass::next_ring, never reset: it lives as long
+        // as the plan, so the two slots may swap roles from one step to the next.
+        int dy_pos = 0;
+    } bwd;
     BnEvalTable bn_table;
     BnStatsTable bn_stats;                 // re-estimation table layout, indexed by BatchNorm layer
     FoldF16Table f16_table;                // fp16 inference: folded weights / biases / activations
@@ -509,24 +521,27 @@ hipStream_t side_or(cilrs_net* net, hipStream_t main, int i) {
 }
 // gradient buffer `gi` is about to be overwritten on `main`: wait for a side-stream reader
 int gbuf_acquire(cilrs_net* net, hipStream_t main, int gi) {
-    if (net->gbuf_pending[gi]) {
+    if (net->bwd.gbuf_pending[gi]) {
         CILRS_HIP(hipStreamWaitEvent(main, net->gbuf_ev[gi], 0));
-        net->gbuf_pending[gi] = false;
+        net->bwd.gbuf_pending[gi] = false;
     }
     return 0;
 }
-// side stream 0 will read gradient buffer `gi` (just produced on `main`)
-int gbuf_side_begin(cilrs_net* net, hipStream_t main) {
+// side stream 0 continues from here on `main`: what it runs next sees everything `main` has been
+// given so far (the weight images, a down-sample branch, the heads' weight gradients, a fused
+// Adam launch, a weight gradient reading the buffer `main` has just produced)
+int side_fork(cilrs_net* net, hipStream_t main) {
     if (!use_overlap(net)) return 0;
     if (ensure_streams(net)) return 1;
     CILRS_HIP(hipEventRecord(net->fork_ev, main));
     CILRS_HIP(hipStreamWaitEvent(net->side[0], net->fork_ev, 0));
     return 0;
 }
+// side stream 0 has been given its reader of gradient buffer `gi`
 int gbuf_side_end(cilrs_net* net, int gi) {
     if (!use_overlap(net)) return 0;
     CILRS_HIP(hipEventRecord(net->gbuf_ev[gi], net->side[0]));
-    net->gbuf_pending[gi] = true;
+    net->bwd.gbuf_pending[gi] = true;
     return 0;
 }
 int gbuf_join_all(cilrs_net* net, hipStream_t main) {
@@ -1434,7 +1449,7 @@ static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train,
         hipStream_t ts = s;
         const bool fork = use_overlap(net) && (net->wino_table.n || bf16t);
         if (fork) {
-            if (gbuf_side_begin(net, s)) return 1;
+            if (side_fork(net, s)) return 1;
             ts = net->side[0];
         }
         if (net->wino_table.n && ft_groups == 0) {
@@ -1531,7 +1546,7 @@ static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train,
             return 0;
         };
         if (branch_aside) {
-            if (gbuf_side_begin(net, s)) return 1;            // the side stream sees the block's input
+            if (side_fork(net, s)) return 1;            // the side stream sees the block's input
             if (down_branch(net->side[0], true)) return 1;
             CILRS_HIP(hipEventRecord(net->branch_ev, net->side[0]));
             branch_pending = true;
@@ -2722,10 +2737,7 @@ size_t cilrs_gradcam_scratch_floats(int variant, int batch) {
 
 // last convolution of trunk group `layer` (1..4)
 static int gc_group_conv(const Arch& A, int layer) {
-    const int nblk[4] = {3, 4, 6, 3};
-    int last = -1;
-    for (int L = 1; L <= layer; ++L) last += nblk[L - 1];
-    const BlockT& blk = A.blocks[last];
+    const BlockT& blk = A.blocks[A.layer_first[layer] - 1];
     return blk.conv3 >= 0 ? blk.conv3 : blk.conv2;
 }
 
@@ -2956,48 +2968,113 @@ int cilrs_net_knn(cilrs_net* net, const cilrs_buffers* bufs, const float* X, lon
 // ------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------
-static int backward_heads(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
-                          const float* dps, bool data_only, hipStream_t s);
-
-// data_only (cilrs_net_backward_data): the data-gradient chain alone -- no weight gradient, no head
-// dW / db, nothing on the side stream, bufs->grads never touched; a frozen graph's BatchNorm
-// backward is then one reduction-free launch per layer
-static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
-                         const float* dpred_speed, int seg_begin, int seg_end, void* stream,
-                         const bool data_only) {
-    if (check_bufs(net, bufs, !data_only)) return 1;
-    CILRS_CHECK(net->last.keeps_graph(), "backward needs a preceding train-mode forward on this plan");
-    CILRS_CHECK(0 <= seg_begin && seg_begin <= seg_end && seg_end <= 6, "bad segment range");
+// One backward call: what every launch of the pass is made from.  backward_impl fills it once; the
+// per-segment functions below take it and keep nothing of their own between calls (what does
+// outlive a launch or a call is cilrs_net::bwd).
+struct BwdPass {
+    cilrs_net* net;
+    const cilrs_buffers* bufs;
+    const Arch& A;
+    float* ws;
+    const float* P;
+    float* Gp;                 // the gradient arena; nullptr in a data-only pass
+    hipStream_t s;
+    // data_only (cilrs_net_backward_data): the data-gradient chain alone -- no weight gradient, no
+    // head dW / db, nothing on the side stream, bufs->grads never touched
+    bool data_only;
+    // data-only pass over a frozen graph: BatchNorm backward without reductions (one launch per
+    // layer), data gradients without the BatchNorm-partials epilogue
+    bool lean_bn;
+    bool bf16t;                // bf16 training mode: the trunk's tensors after the stem are bf16
     // fine-tuning: the graph ends where the frozen prefix begins -- segments of frozen groups are
     // not run, and the first block of the last trainable group hands nothing further down
-    const int cut = net->ft_grad;
-    if (seg_end > 6 - cut) seg_end = 6 - cut;
-    if (seg_begin > seg_end) seg_begin = seg_end;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const Arch& A = *net->A;
-    float* ws = reinterpret_cast<float*>(bufs->workspace);
-    net->ws_base = ws;
-    const float* P = bufs->params;
-    float* Gp = data_only ? nullptr : bufs->grads;
-    const int B = net->B;
-    // data-only pass over a frozen graph: BatchNorm backward without reductions, data gradients
-    // without the BatchNorm-partials epilogue
-    const bool lean_bn = data_only && net->last.frozen();
+    int cut;
+    // cilrs_net_backward_step: Adam's update of a segment follows its gradients (nullptr: none)
+    const cilrs_adam_args* fused_adam;
+
+    // gradient buffers by index: [3] d(block input / output), [1] identity-path gradient, [2]
+    // d(input of a main-branch convolution), ring slots = dy tensors; fp32 mode: ws + G[i]; bf16
+    // mode: the bf16 buffer G16[i]
+    float* Gf(int gi) const { return ws + net->G[gi]; }
+    cilrs_half* Gh(int gi) const { return h16(ws, net->G16[gi]); }
+    cilrs_half* z16_of(int ci) const { return h16(ws, net->z16[ci]); }
+    int next_ring() const {
+        const int gi = kRingIdx[net->bwd.dy_pos];
+        net->bwd.dy_pos = (net->bwd.dy_pos + 1) % kDyRing;
+        return gi;
+    }
     // where a BatchNorm backward leaves dgamma / dbeta: the arena, or (data-only pass over a
     // train-mode graph, whose reductions still feed dx) a scratch nobody reads
-    auto dgamma_of = [&](const BnT& b) { return data_only ? ws + net->bn_coef + 3 * 2048 : Gp + b.gamma; };
-    auto dbeta_of = [&](const BnT& b) { return data_only ? ws + net->bn_coef + 4 * 2048 : Gp + b.beta; };
-    auto last_conv = [&](const BlockT& blk) { return blk.conv3 >= 0 ? blk.conv3 : blk.conv2; };
+    float* dgamma_of(const BnT& b) const { return data_only ? ws + net->bn_coef + 3 * 2048 : Gp + b.gamma; }
+    float* dbeta_of(const BnT& b) const { return data_only ? ws + net->bn_coef + 4 * 2048 : Gp + b.beta; }
+
+    // weight gradient of conv `c` from dy (buffer gi): runs on side stream 0, concurrently with
+    // the data gradients (x: the conv's input activation; x16: its bf16 form)
+    int wgrad_side(const ConvT& c, const ConvG& g, const float* x, const cilrs_half* x16, int gi,
+                   size_t dw_off) const {
+        if (data_only) return 0;
+        float* const dwdst = Gp + dw_off;
+        if (side_fork(net, s)) return 1;
+        if (bf16t) {
+            if (conv_wgrad16(net, c, g, x16, Gh(gi), dwdst, ws, side_or(net, s, 0))) return 1;
+        } else {
+            if (conv_wgrad(net, c, g, x, c.cin, Gf(gi), dwdst, ws, side_or(net, s, 0))) return 1;
+        }
+        return gbuf_side_end(net, gi);
+    }
+    // data gradient of conv `ci`: dy (buffer gi) -> buffer go (+ buffer gadd, -1: none); bn_of /
+    // nbp: the convolution whose BatchNorm-backward reductions ride on the epilogue, and where the
+    // number of partials goes; out32: the bf16 mode's last data gradient of the trunk, handed to
+    // the fp32 stem
+    int dgrad(int ci, int gi, int go, int gadd, const ConvG* bn_of, int* nbp,
+              bool out32 = false) const {
+        const ConvT& c = A.convs[ci];
+        const ConvG& g = net->cg[ci];
+        if (lean_bn) { bn_of = nullptr; nbp = nullptr; }
+        if (bf16t)
+            return conv_dgrad16(net, c, g, ci, Gh(gi), out32 ? nullptr : Gh(go),
+                                out32 ? Gf(go) : nullptr, gadd >= 0 ? Gh(gadd) : nullptr, ws, s,
+                                bn_of, nbp);
+        return conv_dgrad(net, c, g, Gf(gi), P + c.w, Gf(go), gadd >= 0 ? Gf(gadd) : nullptr, ws, s,
+                          bn_of, 1, nbp);
+    }
+    // BatchNorm backward of conv `ci`: dz (buffer gz) -> dy (buffer gdy), masked gradient ->
+    // buffer gg (-1: not needed); pre_nblk: partials a data gradient's epilogue already left
+    int bnb(int ci, int gz, int relu, int gdy, int gg, int pre_nblk, double passes) const {
+        const ConvT& c = A.convs[ci];
+        const ConvG& g = net->cg[ci];
+        const BnT& b = A.bns[c.bn];
+        const std::string label = std::string("bn_bwd.") + kGroupName[c.group];
+        if (lean_bn) {
+            RUN(net, label, 0.0,
+                4.0 * g.M * c.cout * (2.0 + (relu ? 1.0 : 0.0) + (gg >= 0 ? 1.0 : 0.0)), s,
+                launch_bn_bwd_frozen(Gf(gz), relu ? ws + g.z : nullptr, g.M, c.cout, P + b.gamma,
+                                     ws + g.stats, relu, Gf(gdy), gg >= 0 ? Gf(gg) : nullptr, s));
+        } else if (bf16t) {
+            RUN(net, label, 0.0, 2.0 * g.M * c.cout * passes, s,
+                launch_bn16_bwd(Gh(gz), relu ? z16_of(ci) : nullptr, y16_of(net, ws, ci), g.M,
+                                c.cout, P + b.gamma, ws + g.stats, relu, dgamma_of(b), dbeta_of(b),
+                                ws + net->bn_coef, ws + net->bn_partial, Gh(gdy),
+                                gg >= 0 ? Gh(gg) : nullptr, pre_nblk, s));
+        } else {
+            RUN(net, label, 0.0, 4.0 * g.M * c.cout * passes, s,
+                launch_bn_bwd(Gf(gz), relu ? ws + g.z : nullptr, ws + g.y, g.M, c.cout, P + b.gamma,
+                              ws + g.stats, relu, dgamma_of(b), dbeta_of(b), 0, ws + net->bn_coef,
+                              ws + net->bn_partial, Gf(gdy), gg >= 0 ? Gf(gg) : nullptr, pre_nblk,
+                              s, nullptr, net->last.frozen() ? 1 : 0));
+        }
+        return 0;
+    }
     // cilrs_net_backward_step: segment `seg`'s gradients are complete once the main stream reaches
     // this point (BatchNorm / head gradients) and the side stream has run what it holds (weight
     // gradients): its Adam update goes on the side stream behind both
-    auto segment_done = [&](int seg) -> int {
-        const cilrs_adam_args* o = net->fused_adam;
+    int segment_done(int seg) const {
+        const cilrs_adam_args* o = fused_adam;
         if (!o) return 0;
         const size_t b = A.seg_begin[seg], n = A.seg_end[seg] - A.seg_begin[seg];
         hipStream_t st = s;
         if (use_overlap(net)) {
-            if (gbuf_side_begin(net, s)) return 1;       // side waits for the main stream's part
+            if (side_fork(net, s)) return 1;       // side waits for the main stream's part
             st = net->side[0];
         }
         RUN(net, "adam", 0.0, 28.0 * n, st,
@@ -3005,320 +3082,26 @@ static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float*
                         o->beta1, o->beta2, o->eps, o->weight_decay, (long long)o->step, nullptr,
                         o->grad_scale, st));
         return 0;
-    };
-
-    // (segment 0 rewrites d(speed encoder); segments 1..5 cycle the buffer G[1] that segment 5
-    //  leaves d(stem conv output) in)
-    if (seg_begin == 0) net->last.bwd_done = 0;
-    if (seg_begin <= 5 && seg_end > 1) net->last.bwd_done &= ~(1u << 5);
-    // where G[3] stands once this call has gone through (cilrs_net_gradcam): a run from segment 0,
-    // or the continuation of one (every forward resets gc_bwd_end); until then nothing
-    const bool gc_run = seg_begin == 0 || net->last.gc_bwd_end == seg_begin;
-    net->last.gc_bwd_end = -1;
-    for (int seg = seg_begin; seg < seg_end; ++seg) {
-        if (seg == 0) {
-            CILRS_CHECK(dcontrols && dpred_speed, "backward: output gradients missing");
-            net->bwd_nblk_next = 0;
-            if (backward_heads(net, bufs, dcontrols, dpred_speed, data_only, s)) return 1;
-            // d visual -> avgpool backward -> grad of the last block's output, in G[3]
-            if (cut == 5) {
-                // (whole trunk frozen: nobody reads d(feature map))
-            } else if (net->bf16_train)
-                RUN(net, "heads_bwd", 0.0, 0.0, s,
-                    launch_avgpool_bwd16(ws + net->dcombined, h16(ws, net->G16[3]), B, net->featHW,
-                                         A.feat, A.feat + 128, s));
-            else
-                RUN(net, "heads_bwd", 0.0, 0.0, s,
-                    launch_avgpool_bwd(ws + net->dcombined, ws + net->G[3], B, net->featHW, A.feat,
-                                       A.feat + 128, s));
-            if (segment_done(seg)) return 1;
-            net->last.bwd_done |= 1u;
-            continue;
-        }
-        if (seg >= 1 && seg <= 4) {
-            const int layer = 5 - seg;                 // 4,3,2,1
-            // blocks of this layer, last to first; gradient of the block output is in G[3]
-            int first = 0;
-            const int nblk[4] = {3, 4, 6, 3};
-            for (int L = 1; L < layer; ++L) first += nblk[L - 1];
-            for (int bi = first + nblk[layer - 1] - 1; bi >= first; --bi) {
-                const BlockT& blk = A.blocks[bi];
-                // (boundary block of a fine-tuning cut: no data gradient leaves it, and a data-only
-                //  pass wants none of its weight gradients)
-                if (data_only && layer == cut && bi == first) {
-                    net->bwd_nblk_next = 0;
-                    continue;
-                }
-                // conv-BN pairs of the main branch, in forward order (2: BasicBlock, 3: Bottleneck)
-                const int chain[3] = {blk.conv1, blk.conv2, blk.conv3};
-                const int nchain = blk.conv3 >= 0 ? 3 : 2;
-                const ConvT& c1 = A.convs[blk.conv1];
-                const ConvG& g1 = net->cg[blk.conv1];
-                // block input activation
-                const float* xin;
-                if (bi == 0) xin = ws + net->pool;
-                else xin = ws + net->cg[last_conv(A.blocks[bi - 1])].z;
-                const std::string grp = kGroupName[c1.group];
-                // weight gradients run on side stream 0, concurrently with the data gradients
-                const bool bf16t = net->bf16_train;
-                // gradient buffers by index: [3] d(block input / output), [1] identity-path
-                // gradient, [2] d(input of a main-branch convolution), ring slots = dy tensors;
-                // fp32 mode: ws + G[i]; bf16 mode: the bf16 buffer G16[i]
-                auto Gf = [&](int gi) { return ws + net->G[gi]; };
-                auto Gh = [&](int gi) { return h16(ws, net->G16[gi]); };
-                // (x: the conv's input activation; x16: its bf16 form)
-                auto wgrad_side = [&](const ConvT& c, const ConvG& g, const float* x,
-                                      const cilrs_half* x16, int gi, size_t dw_off) -> int {
-                    if (data_only) return 0;
-                    float* const dwdst = Gp + dw_off;
-                    if (gbuf_side_begin(net, s)) return 1;
-                    if (bf16t) {
-                        if (conv_wgrad16(net, c, g, x16, Gh(gi), dwdst, ws, side_or(net, s, 0)))
-                            return 1;
-                    } else {
-                        if (conv_wgrad(net, c, g, x, c.cin, Gf(gi), dwdst, ws, side_or(net, s, 0)))
-                            return 1;
-                    }
-                    return gbuf_side_end(net, gi);
-                };
-                // data gradient of conv `ci`: dy (buffer gi) -> buffer go (+ buffer gadd, -1: none);
-                // out32: the bf16 mode's last data gradient of the trunk, handed to the fp32 stem
-                auto dgrad = [&](int ci, int gi, int go, int gadd, const ConvG* bn_of, int* nbp,
-                                 bool out32 = false) -> int {
-                    const ConvT& c = A.convs[ci];
-                    const ConvG& g = net->cg[ci];
-                    if (lean_bn) { bn_of = nullptr; nbp = nullptr; }
-                    if (bf16t)
-                        return conv_dgrad16(net, c, g, ci, Gh(gi), out32 ? nullptr : Gh(go),
-                                            out32 ? Gf(go) : nullptr, gadd >= 0 ? Gh(gadd) : nullptr,
-                                            ws, s, bn_of, nbp);
-                    return conv_dgrad(net, c, g, Gf(gi), P + c.w, Gf(go), gadd >= 0 ? Gf(gadd) : nullptr,
-                                      ws, s, bn_of, 1, nbp);
-                };
-                // BatchNorm backward of conv `ci`: dz (buffer gz) -> dy (buffer gdy), masked
-                // gradient -> buffer gg (-1: not needed)
-                auto bnb = [&](int ci, int gz, int relu, int gdy, int gg, int pre_nblk,
-                               double passes) -> int {
-                    const ConvT& c = A.convs[ci];
-                    const ConvG& g = net->cg[ci];
-                    const BnT& b = A.bns[c.bn];
-                    if (lean_bn) {
-                        RUN(net, "bn_bwd." + grp, 0.0,
-                            4.0 * g.M * c.cout * (2.0 + (relu ? 1.0 : 0.0) + (gg >= 0 ? 1.0 : 0.0)), s,
-                            launch_bn_bwd_frozen(Gf(gz), relu ? ws + g.z : nullptr, g.M, c.cout,
-                                                 P + b.gamma, ws + g.stats, relu, Gf(gdy),
-                                                 gg >= 0 ? Gf(gg) : nullptr, s));
-                    } else if (bf16t) {
-                        RUN(net, "bn_bwd." + grp, 0.0, 2.0 * g.M * c.cout * passes, s,
-                            launch_bn16_bwd(Gh(gz), relu ? h16(ws, net->z16[ci]) : nullptr,
-                                            y16_of(net, ws, ci), g.M, c.cout, P + b.gamma,
-                                            ws + g.stats, relu, dgamma_of(b), dbeta_of(b),
-                                            ws + net->bn_coef, ws + net->bn_partial, Gh(gdy),
-                                            gg >= 0 ? Gh(gg) : nullptr, pre_nblk, s));
-                    } else {
-                        RUN(net, "bn_bwd." + grp, 0.0, 4.0 * g.M * c.cout * passes, s,
-                            launch_bn_bwd(Gf(gz), relu ? ws + g.z : nullptr, ws + g.y, g.M, c.cout,
-                                          P + b.gamma, ws + g.stats, relu, dgamma_of(b),
-                                          dbeta_of(b), 0, ws + net->bn_coef, ws + net->bn_partial,
-                                          Gf(gdy), gg >= 0 ? Gf(gg) : nullptr, pre_nblk, s, nullptr,
-                                          net->last.frozen() ? 1 : 0));
-                    }
-                    return 0;
-                };
-                auto z16_of = [&](int ci) { return h16(ws, net->z16[ci]); };
-                const cilrs_half* xin16 =
-                    bi == 0 ? h16(ws, net->pool16) : z16_of(last_conv(A.blocks[bi - 1]));
-                auto next_ring = [&]() {
-                    const int gi = kRingIdx[net->dy_pos];
-                    net->dy_pos = (net->dy_pos + 1) % kDyRing;
-                    return gi;
-                };
-                // 1. out = relu(bn_last(y_last) + identity): masked grad -> [1], dy_last -> ga
-                int ga = next_ring();
-                if (gbuf_acquire(net, s, ga) || gbuf_acquire(net, s, 1)) return 1;
-                if (bnb(chain[nchain - 1], 3, 1, ga, 1, net->bwd_nblk_next, 8.0)) return 1;
-                net->bwd_nblk_next = 0;
-                // 2. walk the main branch backwards: dW_i (side), d(input of conv_i) -> [2], then
-                //    a = relu(bn_{i-1}(y_{i-1})): dy_{i-1} -> the next dy buffer
-                for (int i = nchain - 1; i >= 1; --i) {
-                    const ConvT& c = A.convs[chain[i]];
-                    const ConvG& g = net->cg[chain[i]];
-                    const ConvG& gp = net->cg[chain[i - 1]];
-                    if (wgrad_side(c, g, ws + gp.z, z16_of(chain[i - 1]), ga, c.w)) return 1;
-                    if (gbuf_acquire(net, s, 2)) return 1;
-                    int nbp = 0;    // the previous BatchNorm's reductions ride on this dgrad's epilogue
-                    if (dgrad(chain[i], ga, 2, -1, &gp, &nbp)) return 1;
-                    ga = next_ring();
-                    if (gbuf_acquire(net, s, ga)) return 1;
-                    if (bnb(chain[i - 1], 2, 1, ga, -1, nbp, 7.0)) return 1;
-                }
-                // 3. dW1 (side)
-                if (wgrad_side(c1, g1, xin, xin16, ga, c1.w)) return 1;
-                if (layer == cut && bi == first) {
-                    // boundary block of a fine-tuning step: its input belongs to the frozen
-                    // prefix -- no data gradient leaves it; the down-sample branch still takes
-                    // its own BatchNorm backward and weight gradient
-                    net->bwd_nblk_next = 0;
-                    if (blk.down >= 0) {
-                        const ConvT& cd = A.convs[blk.down];
-                        const ConvG& gd = net->cg[blk.down];
-                        const int gdn = next_ring();
-                        if (gbuf_acquire(net, s, gdn)) return 1;
-                        if (bnb(blk.down, 1, 0, gdn, -1, 0, 6.0)) return 1;
-                        if (wgrad_side(cd, gd, xin, xin16, gdn, cd.w)) return 1;
-                    }
-                } else if (blk.down < 0) {
-                    // 4. dx = dgrad(conv1) + identity grad [1] -> [3]
-                    // ... and carries the reductions of the previous block's last BatchNorm
-                    // (not for a block the data-only pass is going to skip: nobody would read them)
-                    const bool prev_skipped = data_only && layer == cut && bi - 1 == first;
-                    const ConvG* prev =
-                        bi > 0 && !prev_skipped ? &net->cg[last_conv(A.blocks[bi - 1])] : nullptr;
-                    if (dgrad(blk.conv1, ga, 3, 1, prev, &net->bwd_nblk_next, bi == 0)) return 1;
-                } else {
-                    const ConvT& cd = A.convs[blk.down];
-                    const ConvG& gd = net->cg[blk.down];
-                    if (dgrad(blk.conv1, ga, 3, -1, nullptr, nullptr)) return 1;
-                    // 5. identity = bn_d(conv_d(x)) (no ReLU): dy_d -> a dy buffer
-                    const int gdn = next_ring();
-                    if (gbuf_acquire(net, s, gdn)) return 1;
-                    if (bnb(blk.down, 1, 0, gdn, -1, 0, 6.0)) return 1;
-                    if (wgrad_side(cd, gd, xin, xin16, gdn, cd.w)) return 1;
-                    // 6. dx += dgrad(conv_d)
-                    if (dgrad(blk.down, gdn, 3, 3, nullptr, nullptr, bi == 0)) return 1;
-                }
-            }
-            // (the segment's weight gradients are complete when this call returns its work: the
-            //  side stream joins at the end of the call -- between the segments of ONE call the
-            //  data-gradient chain does not wait for the weight gradients any more)
-            if (segment_done(seg)) return 1;
-            continue;
-        }
-        // seg == 5: stem.  G[3] holds d(maxpool output)
-        {
-            const ConvT& c0 = A.convs[0];
-            const ConvG& g0 = net->cg[0];
-            const BnT& b0 = A.bns[c0.bn];
-            const unsigned char* argmax =
-                reinterpret_cast<const unsigned char*>(bufs->workspace) + net->argmax_b;
-            // max-pool backward + ReLU mask are rebuilt inside the BatchNorm-backward passes
-            if (gbuf_acquire(net, s, 1)) return 1;           // G[1] is rewritten below
-            if (lean_bn)
-                RUN(net, "bn_bwd.stem", 0.0, 4.0 * g0.M * 64 * 2.5, s,
-                    launch_bn_bwd_pool_frozen(ws + net->G[3], argmax, ws + g0.y, B, net->H0, net->W0,
-                                              64, P + b0.gamma, ws + g0.stats, ws + net->G[1], s));
-            else
-                RUN(net, "bn_bwd.stem", 0.0, 4.0 * g0.M * 64 * 3.0, s,
-                    launch_bn_bwd_pool(ws + net->G[3], argmax, ws + g0.y, B, net->H0, net->W0, 64,
-                                       P + b0.gamma, ws + g0.stats, dgamma_of(b0), dbeta_of(b0),
-                                       ws + net->bn_coef, ws + net->bn_partial, ws + net->G[1], s,
-                                       net->last.frozen() ? 1 : 0));
-            // the stem's weight gradient runs on the main stream and uses the same slab scratch as
-            // the weight gradients of the side stream: those must have finished (between the
-            // segments of one call nothing else joins the two streams any more)
-            if (gbuf_join_all(net, s)) return 1;
-            const size_t sw = stem_wgrad_f32_scratch_floats(B, net->H, net->W);
-            if (data_only) {
-                // (no weight gradient)
-            } else if (sw > 0 && sw <= net->slabs_floats) {
-                // (the reduction over pixels on the matrix pipe, dy from global memory, the input
-                //  rows in LDS: stem_f32.hip)
-                RUN(net, "conv_wgrad.stem", 2.0 * g0.M * 64 * 147,
-                    16.0 * B * net->H * net->W + 4.0 * g0.M * 64, s,
-                    launch_stem_wgrad_f32(ws + net->x4, ws + net->G[1], Gp + c0.w, ws + net->slabs, B,
-                                          net->H, net->W, s));
-            } else if (conv_wgrad(net, c0, g0, ws + net->x4, 4, ws + net->G[1], Gp + c0.w, ws, s)) {
-                return 1;
-            }
-            if (segment_done(seg)) return 1;
-            net->last.bwd_done |= 1u << 5;
-        }
     }
-    // everything the side stream still runs (weight gradients, fused Adam launches) joins here
-    if (gbuf_join_all(net, s)) return 1;
-    if (net->heads_pending) {
-        CILRS_HIP(hipStreamWaitEvent(s, net->heads_ev, 0));
-        net->heads_pending = false;
-    }
-    if (net->fused_adam && use_overlap(net)) {
-        CILRS_HIP(hipEventRecord(net->fork_ev, net->side[0]));
-        CILRS_HIP(hipStreamWaitEvent(s, net->fork_ev, 0));
-    }
-    if (gc_run) net->last.gc_bwd_end = seg_end;
-    return 0;
-}
+};
 
-int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
-                       const float* dpred_speed, int seg_begin, int seg_end, void* stream) {
-    return backward_impl(net, bufs, dcontrols, dpred_speed, seg_begin, seg_end, stream, false);
-}
+static int last_conv(const BlockT& blk) { return blk.conv3 >= 0 ? blk.conv3 : blk.conv2; }
 
-int cilrs_net_backward_data(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
-                            const float* dpred_speed, int seg_begin, int seg_end, void* stream) {
-    return backward_impl(net, bufs, dcontrols, dpred_speed, seg_begin, seg_end, stream, true);
-}
-
-// Backward of every segment with torch.optim.Adam.step() (notebook/notebook.ipynb:555) fused in:
-// the update of a segment's parameter range is enqueued -- on the weight-gradient stream, behind
-// that segment's weight gradients -- as soon as the segment's gradients are complete, so the
-// HBM-bound update of layer4 (13 M of the 21 M parameters) runs under the matrix-pipe-bound data
-// gradients of layers 3..1 instead of after the stem.  Same arithmetic per element as
-// cilrs_adam_step over the whole arena (no gradient clipping: the global norm needs every
-// gradient first -- callers that clip use cilrs_net_backward + cilrs_grad_sqnorm + cilrs_adam_step).
-int cilrs_net_backward_step(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
-                            const float* dpred_speed, const cilrs_adam_args* opt, void* stream) {
-    CILRS_CHECK(net && opt && opt->exp_avg && opt->exp_avg_sq, "backward_step: NULL argument");
-    CILRS_CHECK(opt->step >= 1, "backward_step: step must be >= 1");
-    CILRS_CHECK(net->ft_grad == 0, "backward_step: the last forward froze %d trunk group(s); one step "
-                "count for the whole arena cannot serve it (use cilrs_net_backward + cilrs_adam_step "
-                "on the trainable range)", net->ft_grad);
-    net->fused_adam = opt;
-    const int rc = cilrs_net_backward(net, bufs, dcontrols, dpred_speed, 0, 6, stream);
-    net->fused_adam = nullptr;
-    return rc;
-}
-
-int cilrs_net_input_grads(cilrs_net* net, const cilrs_buffers* bufs, float* dimage, long sn, long sc,
-                          long sh, long sw, float* dspeed, void* stream) {
-    if (check_bufs(net, bufs, false)) return 1;
-    CILRS_CHECK(net->last.keeps_graph(), "input_grads needs a preceding graph-keeping forward on this plan");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const Arch& A = *net->A;
-    float* ws = reinterpret_cast<float*>(bufs->workspace);
-    const int B = net->B;
-    if (dspeed) {
-        CILRS_CHECK(net->last.bwd_done & 1u, "input_grads: dspeed needs segment 0 (heads) of "
-                    "cilrs_net_backward after the forward");
-        // speed -> Linear(1, 128): d speed = d(pre-activation) . W_se0 (ds1 is masked by ReLU and
-        // dropout and dropout-scaled in backward_heads)
-        RUN(net, "heads_bwd.dspeed", 2.0 * B * 128, 4.0 * B * 129, s,
-            launch_rowdot(ws + net->ds1, bufs->params + A.se0.w, dspeed, B, 128, 128, s));
-    }
-    if (dimage) {
-        CILRS_CHECK(net->ft_grad == 0, "input_grads: the last forward froze %d trunk group(s); the "
-                    "backward pass stops there, there is no image gradient", net->ft_grad);
-        CILRS_CHECK(net->last.bwd_done & (1u << 5), "input_grads: dimage needs segment 5 (stem) of "
-                    "cilrs_net_backward after the forward");
-        const ConvG& g0 = net->cg[0];
-        RUN(net, "conv_dgrad.stem", 2.0 * g0.M * 64 * 147,
-            4.0 * g0.M * 64 + 12.0 * B * net->H * net->W, s,
-            launch_stem_dgrad_f32(ws + net->G[1], bufs->params + A.convs[0].w, dimage, sn, sc, sh, sw,
-                                  B, net->H, net->W, s));
-    }
-    return 0;
-}
-
-static int backward_heads(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
-                          const float* dps, const bool data_only, hipStream_t s) {
-    const Arch& A = *net->A;
+// the heads of segment 0: d controls / d predicted speed -> d combined (ws + dcombined), d(speed
+// encoder) in ws + ds1, and every head layer's dW / db
+static int backward_heads(const BwdPass& bp, const float* dcontrols, const float* dps) {
+    cilrs_net* net = bp.net;
+    const Arch& A = bp.A;
     const int feat = A.feat, comb = A.feat + 128;
-    float* ws = reinterpret_cast<float*>(bufs->workspace);
-    const float* P = bufs->params;
-    float* Gp = data_only ? nullptr : bufs->grads;
+    float* ws = bp.ws;
+    const float* P = bp.P;
+    float* Gp = bp.Gp;
+    const bool data_only = bp.data_only;
+    hipStream_t s = bp.s;
     const int B = net->B;
     const float dscale = net->last.dropout > 0.f ? 1.0f / (1.0f - net->last.dropout) : 1.0f;
     const long long* cmd = reinterpret_cast<const long long*>(
-        reinterpret_cast<const char*>(bufs->workspace) + net->cmd_b);
+        reinterpret_cast<const char*>(bp.bufs->workspace) + net->cmd_b);
     float* dcomb = ws + net->dcombined;
 
     // weight + bias gradient of layer l:  dW[out][in] = dy^T x,  db = colsum(dy)
@@ -3338,7 +3121,7 @@ static int backward_heads(cilrs_net* net, const cilrs_buffers* bufs, const float
     };
     // mode 2 = weight + bias gradients: nothing on the main stream reads them -- they go to the side
     // stream (idle at this point of the backward pass, and these launches occupy a handful of
-    // CUs), behind the output gradient they multiply; cilrs_net_backward joins them at its end
+    // CUs), behind the output gradient they multiply; backward_join joins them at the call's end
     auto run = [&](int mode, HGemmArgs& h, int n) -> int {
         if (mode == 2 && data_only) return 0;
         h.ngroups = n; h.relu = 0; h.accumulate = 0; h.drop_p = 0.f; h.seed = 0;
@@ -3346,13 +3129,13 @@ static int backward_heads(cilrs_net* net, const cilrs_buffers* bufs, const float
         for (int i = 0; i < n; ++i) fl += 2.0 * h.g[i].M * h.g[i].N * h.g[i].K;
         hipStream_t st = s;
         if (mode == 2 && use_overlap(net)) {
-            if (gbuf_side_begin(net, s)) return 1;
+            if (side_fork(net, s)) return 1;
             st = net->side[0];
         }
         RUN(net, "heads_bwd", fl, 0.0, st, launch_hgemm(mode, h, st));
         if (st != s) {
             CILRS_HIP(hipEventRecord(net->heads_ev, st));
-            net->heads_pending = true;
+            net->bwd.heads_pending = true;
         }
         return 0;
     };
@@ -3409,6 +3192,284 @@ static int backward_heads(cilrs_net* net, const cilrs_buffers* bufs, const float
     if (run(1, h, 1)) return 1;
     wg(h.g[0], ws + net->ds1, 128, ws + net->speed_in, 1, A.se0);
     if (run(2, h, 1)) return 1;
+    return 0;
+}
+
+// segment 0: the heads, then d visual -> avgpool backward -> grad of the last block's output, in G[3]
+static int backward_head_segment(const BwdPass& bp, const float* dcontrols,
+                                 const float* dpred_speed) {
+    cilrs_net* net = bp.net;
+    const Arch& A = bp.A;
+    float* ws = bp.ws;
+    hipStream_t s = bp.s;
+    CILRS_CHECK(dcontrols && dpred_speed, "backward: output gradients missing");
+    if (backward_heads(bp, dcontrols, dpred_speed)) return 1;
+    if (bp.cut == 5) {
+        // (whole trunk frozen: nobody reads d(feature map))
+    } else if (bp.bf16t)
+        RUN(net, "heads_bwd", 0.0, 0.0, s,
+            launch_avgpool_bwd16(ws + net->dcombined, bp.Gh(3), net->B, net->featHW, A.feat,
+                                 A.feat + 128, s));
+    else
+        RUN(net, "heads_bwd", 0.0, 0.0, s,
+            launch_avgpool_bwd(ws + net->dcombined, bp.Gf(3), net->B, net->featHW, A.feat,
+                               A.feat + 128, s));
+    return bp.segment_done(0);
+}
+
+// One residual block, blocks[bi]; the gradient of its output is in G[3], that of its input ends
+// there.  boundary: the first block of the last trainable group of a fine-tuning step.
+// prev_runs: the block below belongs to this layer walk (it is neither another layer's nor one the
+// walk skips).  *nblk_next: BatchNorm-backward partials that the block above left for this
+// block's last BatchNorm on its way in, and those this block leaves for the next on its way out.
+static int backward_block(const BwdPass& bp, int bi, bool boundary, bool prev_runs,
+                          int* nblk_next) {
+    cilrs_net* net = bp.net;
+    const Arch& A = bp.A;
+    float* ws = bp.ws;
+    hipStream_t s = bp.s;
+    const BlockT& blk = A.blocks[bi];
+    // conv-BN pairs of the main branch, in forward order (2: BasicBlock, 3: Bottleneck)
+    const int chain[3] = {blk.conv1, blk.conv2, blk.conv3};
+    const int nchain = blk.conv3 >= 0 ? 3 : 2;
+    const ConvT& c1 = A.convs[blk.conv1];
+    const ConvG& g1 = net->cg[blk.conv1];
+    // block input activation, and its bf16 form
+    const float* xin = bi == 0 ? ws + net->pool : ws + net->cg[last_conv(A.blocks[bi - 1])].z;
+    const cilrs_half* xin16 =
+        bi == 0 ? h16(ws, net->pool16) : bp.z16_of(last_conv(A.blocks[bi - 1]));
+    // 1. out = relu(bn_last(y_last) + identity): masked grad -> [1], dy_last -> ga
+    int ga = bp.next_ring();
+    if (gbuf_acquire(net, s, ga) || gbuf_acquire(net, s, 1)) return 1;
+    if (bp.bnb(chain[nchain - 1], 3, 1, ga, 1, *nblk_next, 8.0)) return 1;
+    *nblk_next = 0;
+    // 2. walk the main branch backwards: dW_i (side), d(input of conv_i) -> [2], then
+    //    a = relu(bn_{i-1}(y_{i-1})): dy_{i-1} -> the next dy buffer
+    for (int i = nchain - 1; i >= 1; --i) {
+        const ConvT& c = A.convs[chain[i]];
+        const ConvG& g = net->cg[chain[i]];
+        const ConvG& gp = net->cg[chain[i - 1]];
+        if (bp.wgrad_side(c, g, ws + gp.z, bp.z16_of(chain[i - 1]), ga, c.w)) return 1;
+        if (gbuf_acquire(net, s, 2)) return 1;
+        int nbp = 0;    // the previous BatchNorm's reductions ride on this dgrad's epilogue
+        if (bp.dgrad(chain[i], ga, 2, -1, &gp, &nbp)) return 1;
+        ga = bp.next_ring();
+        if (gbuf_acquire(net, s, ga)) return 1;
+        if (bp.bnb(chain[i - 1], 2, 1, ga, -1, nbp, 7.0)) return 1;
+    }
+    // 3. dW1 (side)
+    if (bp.wgrad_side(c1, g1, xin, xin16, ga, c1.w)) return 1;
+    if (boundary) {
+        // its input belongs to the frozen prefix -- no data gradient leaves it (*nblk_next stays
+        // 0); the down-sample branch still takes its own BatchNorm backward and weight gradient
+        if (blk.down >= 0) {
+            const ConvT& cd = A.convs[blk.down];
+            const ConvG& gd = net->cg[blk.down];
+            const int gdn = bp.next_ring();
+            if (gbuf_acquire(net, s, gdn)) return 1;
+            if (bp.bnb(blk.down, 1, 0, gdn, -1, 0, 6.0)) return 1;
+            if (bp.wgrad_side(cd, gd, xin, xin16, gdn, cd.w)) return 1;
+        }
+    } else if (blk.down < 0) {
+        // 4. dx = dgrad(conv1) + identity grad [1] -> [3]
+        // ... and carries the reductions of the previous block's last BatchNorm
+        const ConvG* prev = prev_runs ? &net->cg[last_conv(A.blocks[bi - 1])] : nullptr;
+        if (bp.dgrad(blk.conv1, ga, 3, 1, prev, nblk_next, bi == 0)) return 1;
+    } else {
+        const ConvT& cd = A.convs[blk.down];
+        const ConvG& gd = net->cg[blk.down];
+        if (bp.dgrad(blk.conv1, ga, 3, -1, nullptr, nullptr)) return 1;
+        // 5. identity = bn_d(conv_d(x)) (no ReLU): dy_d -> a dy buffer
+        const int gdn = bp.next_ring();
+        if (gbuf_acquire(net, s, gdn)) return 1;
+        if (bp.bnb(blk.down, 1, 0, gdn, -1, 0, 6.0)) return 1;
+        if (bp.wgrad_side(cd, gd, xin, xin16, gdn, cd.w)) return 1;
+        // 6. dx += dgrad(conv_d)
+        if (bp.dgrad(blk.down, gdn, 3, 3, nullptr, nullptr, bi == 0)) return 1;
+    }
+    return 0;
+}
+
+// segments 1..4 = layer4..layer1: the layer's blocks, last to first
+static int backward_layer(const BwdPass& bp, int seg) {
+    const int layer = 5 - seg;
+    const int first = bp.A.layer_first[layer - 1], end = bp.A.layer_first[layer];
+    const int cut_block = layer == bp.cut ? first : -1;      // boundary block of a fine-tuning cut
+    // Partials of a block's last BatchNorm backward, written by the data gradient of the block
+    // above.  Only a block without a down-sample branch hands them on, and only to a block of the
+    // same layer: a layer's first block either has that branch or is block 0, and a boundary block
+    // hands on nothing, so the count is 0 wherever a layer ends.
+    int nblk_next = 0;
+    for (int bi = end - 1; bi >= first; --bi) {
+        // (boundary block: no data gradient leaves it, and a data-only pass wants none of its
+        //  weight gradients -- nor, in the block above, the reductions nobody would read)
+        const bool skipped = bp.data_only && bi == cut_block;
+        const bool prev_skipped = bp.data_only && bi - 1 == cut_block;
+        if (skipped) continue;
+        if (backward_block(bp, bi, bi == cut_block, bi > first && !prev_skipped, &nblk_next))
+            return 1;
+    }
+    // (the segment's weight gradients are complete when this call returns its work: the side
+    //  stream joins at the end of the call -- between the segments of ONE call the data-gradient
+    //  chain does not wait for the weight gradients any more)
+    return bp.segment_done(seg);
+}
+
+// segment 5: the stem.  G[3] holds d(maxpool output)
+static int backward_stem(const BwdPass& bp) {
+    cilrs_net* net = bp.net;
+    float* ws = bp.ws;
+    const float* P = bp.P;
+    hipStream_t s = bp.s;
+    const int B = net->B;
+    const ConvT& c0 = bp.A.convs[0];
+    const ConvG& g0 = net->cg[0];
+    const BnT& b0 = bp.A.bns[c0.bn];
+    const unsigned char* argmax =
+        reinterpret_cast<const unsigned char*>(bp.bufs->workspace) + net->argmax_b;
+    // max-pool backward + ReLU mask are rebuilt inside the BatchNorm-backward passes
+    if (gbuf_acquire(net, s, 1)) return 1;           // G[1] is rewritten below
+    if (bp.lean_bn)
+        RUN(net, "bn_bwd.stem", 0.0, 4.0 * g0.M * 64 * 2.5, s,
+            launch_bn_bwd_pool_frozen(ws + net->G[3], argmax, ws + g0.y, B, net->H0, net->W0, 64,
+                                      P + b0.gamma, ws + g0.stats, ws + net->G[1], s));
+    else
+        RUN(net, "bn_bwd.stem", 0.0, 4.0 * g0.M * 64 * 3.0, s,
+            launch_bn_bwd_pool(ws + net->G[3], argmax, ws + g0.y, B, net->H0, net->W0, 64,
+                               P + b0.gamma, ws + g0.stats, bp.dgamma_of(b0), bp.dbeta_of(b0),
+                               ws + net->bn_coef, ws + net->bn_partial, ws + net->G[1], s,
+                               net->last.frozen() ? 1 : 0));
+    // the stem's weight gradient runs on the main stream and uses the same slab scratch as the
+    // weight gradients of the side stream: those must have finished (between the segments of one
+    // call nothing else joins the two streams any more)
+    if (gbuf_join_all(net, s)) return 1;
+    const size_t sw = stem_wgrad_f32_scratch_floats(B, net->H, net->W);
+    if (bp.data_only) {
+        // (no weight gradient)
+    } else if (sw > 0 && sw <= net->slabs_floats) {
+        // (the reduction over pixels on the matrix pipe, dy from global memory, the input rows in
+        //  LDS: stem_f32.hip)
+        RUN(net, "conv_wgrad.stem", 2.0 * g0.M * 64 * 147,
+            16.0 * B * net->H * net->W + 4.0 * g0.M * 64, s,
+            launch_stem_wgrad_f32(ws + net->x4, ws + net->G[1], bp.Gp + c0.w, ws + net->slabs, B,
+                                  net->H, net->W, s));
+    } else if (conv_wgrad(net, c0, g0, ws + net->x4, 4, ws + net->G[1], bp.Gp + c0.w, ws, s)) {
+        return 1;
+    }
+    return bp.segment_done(5);
+}
+
+// end of a call: everything the side stream still runs (weight gradients, the heads' weight
+// gradients, fused Adam launches) joins the main stream here
+static int backward_join(const BwdPass& bp) {
+    cilrs_net* net = bp.net;
+    if (gbuf_join_all(net, bp.s)) return 1;
+    if (net->bwd.heads_pending) {
+        CILRS_HIP(hipStreamWaitEvent(bp.s, net->heads_ev, 0));
+        net->bwd.heads_pending = false;
+    }
+    if (bp.fused_adam && use_overlap(net)) {
+        CILRS_HIP(hipEventRecord(net->fork_ev, net->side[0]));
+        CILRS_HIP(hipStreamWaitEvent(bp.s, net->fork_ev, 0));
+    }
+    return 0;
+}
+
+// segments [seg_begin, seg_end) of the backward pass on the plan's last graph-keeping forward:
+// argument checks, the cut, the record in cilrs_net::last, one function per segment, the join
+static int backward_impl(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
+                         const float* dpred_speed, int seg_begin, int seg_end, void* stream,
+                         const bool data_only, const cilrs_adam_args* fused_adam = nullptr) {
+    if (check_bufs(net, bufs, !data_only)) return 1;
+    CILRS_CHECK(net->last.keeps_graph(), "backward needs a preceding train-mode forward on this plan");
+    CILRS_CHECK(0 <= seg_begin && seg_begin <= seg_end && seg_end <= 6, "bad segment range");
+    const int cut = net->ft_grad;
+    if (seg_end > 6 - cut) seg_end = 6 - cut;
+    if (seg_begin > seg_end) seg_begin = seg_end;
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
+    net->ws_base = ws;
+    const BwdPass bp{net, bufs, *net->A, ws, bufs->params, data_only ? nullptr : bufs->grads,
+                     reinterpret_cast<hipStream_t>(stream), data_only,
+                     data_only && net->last.frozen(), net->bf16_train, cut, fused_adam};
+
+    // (segment 0 rewrites d(speed encoder); segments 1..5 cycle the buffer G[1] that segment 5
+    //  leaves d(stem conv output) in)
+    if (seg_begin == 0) net->last.bwd_done = 0;
+    if (seg_begin <= 5 && seg_end > 1) net->last.bwd_done &= ~(1u << 5);
+    // where G[3] stands once this call has gone through (cilrs_net_gradcam): a run from segment 0,
+    // or the continuation of one (every forward resets gc_bwd_end); until then nothing
+    const bool gc_run = seg_begin == 0 || net->last.gc_bwd_end == seg_begin;
+    net->last.gc_bwd_end = -1;
+    for (int seg = seg_begin; seg < seg_end; ++seg) {
+        if (seg == 0) {
+            if (backward_head_segment(bp, dcontrols, dpred_speed)) return 1;
+            net->last.bwd_done |= 1u;
+        } else if (seg <= 4) {
+            if (backward_layer(bp, seg)) return 1;
+        } else {
+            if (backward_stem(bp)) return 1;
+            net->last.bwd_done |= 1u << 5;
+        }
+    }
+    if (backward_join(bp)) return 1;
+    if (gc_run) net->last.gc_bwd_end = seg_end;
+    return 0;
+}
+
+int cilrs_net_backward(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
+                       const float* dpred_speed, int seg_begin, int seg_end, void* stream) {
+    return backward_impl(net, bufs, dcontrols, dpred_speed, seg_begin, seg_end, stream, false);
+}
+
+int cilrs_net_backward_data(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
+                            const float* dpred_speed, int seg_begin, int seg_end, void* stream) {
+    return backward_impl(net, bufs, dcontrols, dpred_speed, seg_begin, seg_end, stream, true);
+}
+
+// Backward of every segment with torch.optim.Adam.step() (notebook/notebook.ipynb:555) fused in:
+// the update of a segment's parameter range is enqueued -- on the weight-gradient stream, behind
+// that segment's weight gradients -- as soon as the segment's gradients are complete, so the
+// HBM-bound update of layer4 (13 M of the 21 M parameters) runs under the matrix-pipe-bound data
+// gradients of layers 3..1 instead of after the stem.  Same arithmetic per element as
+// cilrs_adam_step over the whole arena (no gradient clipping: the global norm needs every
+// gradient first -- callers that clip use cilrs_net_backward + cilrs_grad_sqnorm + cilrs_adam_step).
+int cilrs_net_backward_step(cilrs_net* net, const cilrs_buffers* bufs, const float* dcontrols,
+                            const float* dpred_speed, const cilrs_adam_args* opt, void* stream) {
+    CILRS_CHECK(net && opt && opt->exp_avg && opt->exp_avg_sq, "backward_step: NULL argument");
+    CILRS_CHECK(opt->step >= 1, "backward_step: step must be >= 1");
+    CILRS_CHECK(net->ft_grad == 0, "backward_step: the last forward froze %d trunk group(s); one step "
+                "count for the whole arena cannot serve it (use cilrs_net_backward + cilrs_adam_step "
+                "on the trainable range)", net->ft_grad);
+    return backward_impl(net, bufs, dcontrols, dpred_speed, 0, 6, stream, false, opt);
+}
+
+int cilrs_net_input_grads(cilrs_net* net, const cilrs_buffers* bufs, float* dimage, long sn, long sc,
+                          long sh, long sw, float* dspeed, void* stream) {
+    if (check_bufs(net, bufs, false)) return 1;
+    CILRS_CHECK(net->last.keeps_graph(), "input_grads needs a preceding graph-keeping forward on this plan");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const Arch& A = *net->A;
+    float* ws = reinterpret_cast<float*>(bufs->workspace);
+    const int B = net->B;
+    if (dspeed) {
+        CILRS_CHECK(net->last.bwd_done & 1u, "input_grads: dspeed needs segment 0 (heads) of "
+                    "cilrs_net_backward after the forward");
+        // speed -> Linear(1, 128): d speed = d(pre-activation) . W_se0 (ds1 is masked by ReLU and
+        // dropout and dropout-scaled in backward_heads)
+        RUN(net, "heads_bwd.dspeed", 2.0 * B * 128, 4.0 * B * 129, s,
+            launch_rowdot(ws + net->ds1, bufs->params + A.se0.w, dspeed, B, 128, 128, s));
+    }
+    if (dimage) {
+        CILRS_CHECK(net->ft_grad == 0, "input_grads: the last forward froze %d trunk group(s); the "
+                    "backward pass stops there, there is no image gradient", net->ft_grad);
+        CILRS_CHECK(net->last.bwd_done & (1u << 5), "input_grads: dimage needs segment 5 (stem) of "
+                    "cilrs_net_backward after the forward");
+        const ConvG& g0 = net->cg[0];
+        RUN(net, "conv_dgrad.stem", 2.0 * g0.M * 64 * 147,
+            4.0 * g0.M * 64 + 12.0 * B * net->H * net->W, s,
+            launch_stem_dgrad_f32(ws + net->G[1], bufs->params + A.convs[0].w, dimage, sn, sc, sh, sw,
+                                  B, net->H, net->W, s));
+    }
     return 0;
 }
 
