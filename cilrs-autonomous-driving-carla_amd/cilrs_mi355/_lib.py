@@ -163,6 +163,13 @@ SIGNATURES = {
     "cilrs_adam_step_groups_ema": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, vp, f64, f64, f64, f64, vp,
                                          f32, vp, f32, vp]),
     "cilrs_swap": (i32, [vp, vp, sz, vp]),
+    "cilrs_optim_chunk_floats": (i32, []),
+    "cilrs_optim_table_bytes": (sz, [vp, i32]),
+    "cilrs_optim_table_create": (i32, [vp, vp, i32, sz, vp, sz, vp, C.POINTER(vp)]),
+    "cilrs_optim_table_destroy": (None, [vp]),
+    "cilrs_optim_scratch_bytes": (sz, [vp]),
+    "cilrs_optim_step": (i32, [i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, f64, f64, f64,
+                               f64, f64, vp, f32, vp, vp, vp]),
     "cilrs_augment_u8": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
     "cilrs_batch_assemble": (i32, [vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,
                                    vp]),

@@ -74,13 +74,41 @@ def load_optimizer_state_dict(trainer, sd):
     trainer.lr = float(sd["param_groups"][0]["lr"])
 
 
+# TrainConfig fields of the optimizer / schedule options: recorded only where they differ from their
+# defaults, so that a file written with none of them set has the keys it always had
+_OPTIONAL_FIELDS = ("optimizer", "decay_exempt_1d", "trust_clip", "warmup_steps", "lr_schedule",
+                    "lr_epochs", "lr_min")
+
+
+def _set_options(cfg):
+    """{field: value} of the optional TrainConfig fields that differ from their defaults."""
+    from .train import TrainConfig
+    base = TrainConfig()
+    return {k: getattr(cfg, k) for k in _OPTIONAL_FIELDS
+            if hasattr(cfg, k) and getattr(cfg, k) != getattr(base, k)}
+
+
 def _config_dict(trainer):
-    """TrainConfig as a plain dict; the EMA fields appear only when the EMA is on."""
+    """TrainConfig as a plain dict; the EMA fields appear only when the EMA is on, the optimizer /
+    schedule options only where they are set."""
     cfg = dict(trainer.cfg.__dict__)
     if cfg.get("ema_decay") is None:
         cfg.pop("ema_decay", None)
         cfg.pop("ema_warmup", None)
+    keep = _set_options(trainer.cfg)
+    for k in _OPTIONAL_FIELDS:
+        if k not in keep:
+            cfg.pop(k, None)
     return cfg
+
+
+def _check_same_optimizer(trainer, ck, path):
+    """The moments share one layout, but they are another optimizer's trajectory: refuse."""
+    saved = (ck.get("config") or {}).get("optimizer", "adam")
+    mine = getattr(trainer.cfg, "optimizer", "adam")
+    if saved != mine:
+        raise ValueError(f"{path}: written by optimizer={saved!r}, this Trainer runs "
+                         f"optimizer={mine!r}; resume with the same TrainConfig.optimizer")
 
 
 def save_best(path, model, trainer, epoch, val_loss, val_steer, cmd_steer_errors, config=None,
@@ -118,6 +146,9 @@ def save_latest(path, model, trainer, epoch, loop_state=None):
     }
     if loop_state is not None:
         d["loop_state"] = loop_state
+    if _set_options(trainer.cfg):       # what a resume checks (another optimizer is refused)
+        d["config"] = {k: (list(v) if isinstance(v, tuple) else v)
+                       for k, v in _config_dict(trainer).items()}
     if getattr(trainer, "ema", None) is not None:       # raw weights above, the average beside them
         d["ema_state_dict"] = trainer.ema_state_dict()
         d["ema_updates"] = int(trainer.ema_updates)
@@ -158,6 +189,8 @@ def load_file(path, map_location=None):
 def load(path, model, trainer=None, map_location=None):
     """autonomous_drive.py:496-497 (+ the resume path the reference lacks)."""
     ck = load_file(path, map_location)
+    if trainer is not None and "optimizer_state_dict" in ck:
+        _check_same_optimizer(trainer, ck, path)
     model.load_state_dict(ck["model_state_dict"], strict=True)
     if trainer is not None and "optimizer_state_dict" in ck:
         load_optimizer_state_dict(trainer, ck["optimizer_state_dict"])

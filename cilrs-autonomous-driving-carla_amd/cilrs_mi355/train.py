@@ -47,6 +47,19 @@ class TrainConfig:
     # initialisation at full weight.
     ema_decay: float = None
     ema_warmup: bool = True
+    # the update rule (include/cilrs_hip.h "AdamW and LAMB"): "adam" = torch.optim.Adam with coupled
+    # L2 decay, the reference's; "adamw" = decoupled decay; "lamb" = layer-wise adaptive, one trust
+    # ratio per parameter tensor.  The moments have one layout in all three.
+    optimizer: str = "adam"
+    # every tensor with ndim <= 1 (BatchNorm weight and bias, Linear bias) takes no weight decay
+    # and, under "lamb", the trust ratio 1.  Not with "adam" (its decay is one scalar per launch).
+    decay_exempt_1d: bool = False
+    trust_clip: float = 0.0                            # LAMB: ||p|| is capped here; 0 = off
+    # the rate of optimizer step t (1-based) is lr * min(1, t / warmup_steps); 0 = off
+    warmup_steps: int = 0
+    lr_schedule: str = "step"                          # "step" (StepLR) | "cosine"
+    lr_epochs: int = 20                                # cosine: epochs down to lr_min
+    lr_min: float = 0.0
 
 
 GROUP_NAMES = ("stem", "layer1", "layer2", "layer3", "layer4", "heads")
@@ -61,6 +74,63 @@ def steplr(cfg: TrainConfig, epoch: int) -> float:
     """lr in effect AFTER `epoch` scheduler steps of torch.optim.lr_scheduler.StepLR(step_size,
     gamma) (nb:535-536: StepLR(8, 0.5), stepped once per epoch, nb:604)."""
     return cfg.lr * (cfg.lr_gamma ** (epoch // cfg.lr_step_size))
+
+
+def cosine_lr(cfg: TrainConfig, epoch: int) -> float:
+    """lr in effect AFTER `epoch` scheduler steps of the cosine schedule: from cfg.lr at epoch 0 down
+    to cfg.lr_min at cfg.lr_epochs, where it stays."""
+    e = min(int(epoch), int(cfg.lr_epochs))
+    return cfg.lr_min + 0.5 * (cfg.lr - cfg.lr_min) * (1.0 + math.cos(math.pi * e / cfg.lr_epochs))
+
+
+def scheduled_lr(cfg: TrainConfig, epoch: int) -> float:
+    return cosine_lr(cfg, epoch) if cfg.lr_schedule == "cosine" else steplr(cfg, epoch)
+
+
+def warmup_factor(warmup_steps: int, t: int) -> float:
+    """min(1, t / warmup_steps) for optimizer step t (1-based); 1 with the warm-up off."""
+    if warmup_steps <= 0 or t >= warmup_steps:
+        return 1.0
+    return max(t, 1) / float(warmup_steps)
+
+
+OPTIMIZERS = ("adam", "adamw", "lamb")
+SEG_NO_DECAY, SEG_NO_ADAPT = 1, 2                      # CILRS_SEG_* of include/cilrs_hip.h
+OPTIM_KIND = {"adamw": 1, "lamb": 2}                   # CILRS_OPTIM_*
+
+
+def check_optim_config(cfg: TrainConfig):
+    """ValueError for what no Trainer can serve, before anything is built."""
+    if cfg.optimizer not in OPTIMIZERS:
+        raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {cfg.optimizer!r}")
+    if cfg.lr_schedule not in ("step", "cosine"):
+        raise ValueError(f"lr_schedule must be 'step' or 'cosine', got {cfg.lr_schedule!r}")
+    if not (isinstance(cfg.warmup_steps, int) and cfg.warmup_steps >= 0):
+        raise ValueError(f"warmup_steps must be an integer >= 0, got {cfg.warmup_steps!r}")
+    if not (isinstance(cfg.trust_clip, (int, float)) and math.isfinite(cfg.trust_clip)
+            and cfg.trust_clip >= 0):
+        raise ValueError(f"trust_clip must be finite and >= 0 (0 = off), got {cfg.trust_clip!r}")
+    if cfg.decay_exempt_1d and cfg.optimizer == "adam":
+        raise ValueError("decay_exempt_1d has no effect with optimizer='adam' (its coupled decay is "
+                         "one scalar for the whole launch); use 'adamw' or 'lamb'")
+    if cfg.lr_schedule == "cosine":
+        if not (isinstance(cfg.lr_epochs, int) and cfg.lr_epochs >= 1):
+            raise ValueError(f"lr_epochs must be an integer >= 1, got {cfg.lr_epochs!r}")
+        if not (math.isfinite(cfg.lr_min) and 0.0 <= cfg.lr_min <= cfg.lr):
+            raise ValueError(f"lr_min must lie in [0, lr], got {cfg.lr_min!r}")
+
+
+def segment_table(params_layout, n_arena, decay_exempt_1d=False, lamb=False):
+    """(ends, flags) of the optimizer's segment table: one segment per parameter tensor, from its
+    arena offset to the next tensor's (the last one to the arena's end).  decay_exempt_1d: tensors
+    with ndim <= 1 carry NO_DECAY, and NO_ADAPT too under LAMB."""
+    offs = [p[1] for p in params_layout]
+    if not offs or offs[0] != 0 or any(b <= a for a, b in zip(offs, offs[1:])):
+        raise RuntimeError("parameter layout does not start at 0 with increasing offsets")
+    ends = offs[1:] + [int(n_arena)]
+    exempt = SEG_NO_DECAY | (SEG_NO_ADAPT if lamb else 0)
+    flags = [exempt if decay_exempt_1d and len(p[3]) <= 1 else 0 for p in params_layout]
+    return ends, flags
 
 
 def ema_decay_at(decay: float, t: int, warmup: bool = True) -> float:
@@ -99,6 +169,7 @@ class Trainer:
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16'")
         ema_decay = None if cfg.ema_decay is None else check_ema_decay(cfg.ema_decay)
+        check_optim_config(cfg)
         self.model = model
         self.cfg = cfg
         self.eng = model.engine()
@@ -161,6 +232,11 @@ class Trainer:
         self.ema_fused = False
         self._ema_w = 0.0
         self._in_ema = False
+        # AdamW / LAMB: the segment table (one segment per parameter tensor) on the device, built
+        # once; LAMB's partial sums and the per-tensor trust ratios of the last step
+        self._optim_table = None
+        if cfg.optimizer != "adam":
+            self._build_optim_table()
         self.reducer = None
         self.rank = 0
         if process_group is not None:
@@ -169,6 +245,68 @@ class Trainer:
             self.reducer = BucketedAllReduce(self.eng.grads, process_group,
                                              variant=self.eng.variant)
             self.rank = dist.get_rank(process_group)
+
+    # -- AdamW / LAMB ---------------------------------------------------------------------------
+    def _build_optim_table(self):
+        lib, eng, cfg = L.lib(), self.eng, self.cfg
+        ends, flags = segment_table(eng.params_layout, eng.n_arena, cfg.decay_exempt_1d,
+                                    cfg.optimizer == "lamb")
+        k = len(ends)
+        c_ends, c_flags = (C.c_size_t * k)(*ends), (C.c_int * k)(*flags)
+        nbytes = lib.cilrs_optim_table_bytes(c_ends, k)
+        if nbytes == 0:
+            raise RuntimeError("cilrs_optim_table_bytes refused the parameter layout")
+        self._seg_ends = ends
+        self._seg_index_of_start = {b: i for i, b in enumerate([0] + ends[:-1])}
+        self._seg_index_of_end = {e: i for i, e in enumerate(ends)}
+        self._optim_table_mem = torch.empty(nbytes, dtype=torch.uint8, device=eng.device)
+        handle = C.c_void_p()
+        L.check(lib.cilrs_optim_table_create(c_ends, c_flags, k, eng.n_arena,
+                                             L.ptr(self._optim_table_mem), nbytes, self._stream(),
+                                             C.byref(handle)))
+        self._optim_table = handle
+        self._optim_scratch = torch.empty(max(lib.cilrs_optim_scratch_bytes(handle), 16),
+                                          dtype=torch.uint8, device=eng.device)
+        self._ratios = torch.ones(k, dtype=torch.float32, device=eng.device)
+
+    def __del__(self):
+        handle = getattr(self, "_optim_table", None)
+        if handle is not None:
+            self._optim_table = None
+            try:
+                L.lib().cilrs_optim_table_destroy(handle)
+            except Exception:
+                pass
+
+    def trust_ratios(self):
+        """LAMB's trust ratio r_s of every parameter tensor at its last update (1 before the first
+        one, and always for NO_ADAPT tensors): a CPU fp32 tensor in params_layout order."""
+        if self.cfg.optimizer != "lamb":
+            raise RuntimeError("trust ratios exist under optimizer='lamb' only")
+        return self._ratios.detach().cpu().clone()
+
+    def lr_at(self, t):
+        """Learning rate of optimizer step t (1-based): the scheduled per-epoch `lr` times the
+        warm-up factor min(1, t / warmup_steps)."""
+        f = warmup_factor(self.cfg.warmup_steps, t)
+        return self.lr if f == 1.0 else self.lr * f
+
+    @property
+    def lr_now(self):
+        """The effective rate of optimizer step `step_count` (before the first step: of step 1)."""
+        return self.lr_at(max(self.step_count, 1))
+
+    def _refuse_unserved_optimizer(self):
+        if self.cfg.optimizer == "adam":
+            return
+        if self.fuse_optimizer:
+            raise RuntimeError(f"Trainer.fuse_optimizer cannot serve optimizer={self.cfg.optimizer!r}"
+                               ": cilrs_net_backward_step's per-segment launches are Adam's (leave "
+                               "fuse_optimizer off, the default)")
+        if self.ema_fused:
+            raise RuntimeError(f"Trainer.ema_fused cannot serve optimizer={self.cfg.optimizer!r}: "
+                               "only the Adam launches carry the average (leave ema_fused off, the "
+                               "default; the separate cilrs_ema_update pass follows the step)")
 
     # -- pieces ---------------------------------------------------------------------------------
     def _stream(self):
@@ -238,6 +376,7 @@ class Trainer:
         trainable range when a prefix of the trunk is frozen (frozen parameters and their moments
         are not touched and take no weight decay, like torch.optim.Adam's `grad is None`)."""
         self._refuse_inside_ema_weights("optimizer_step")
+        self._refuse_unserved_optimizer()
         lib = L.lib()
         eng, cfg = self.eng, self.cfg
         e, g = self._freeze_state()
@@ -263,6 +402,7 @@ class Trainer:
     def train_step(self, imgs, speeds, cmds, tgts):
         """Returns the device loss buffer [>=6] (LOSS_KEYS order); reading it is the only sync."""
         self._refuse_inside_ema_weights("train_step")
+        self._refuse_unserved_optimizer()
         if self.ema is not None and self.fuse_optimizer:
             raise RuntimeError("Trainer.fuse_optimizer cannot serve ema_decay: cilrs_net_backward_"
                                "step's per-segment Adam launches carry no average (leave "
@@ -290,7 +430,7 @@ class Trainer:
             self._advance_steps(0)
             self.arena_grad_scale = 1.0
             eng.run_backward_step(pl, dc, dp, self.exp_avg, self.exp_avg_sq,
-                                  self.lr * self.lr_mult[0], self.cfg.betas, self.cfg.eps,
+                                  self.lr_now * self.lr_mult[0], self.cfg.betas, self.cfg.eps,
                                   self.cfg.weight_decay, self.group_steps[0])
         elif self.reducer is None:
             eng.run_backward(pl, dc, dp)
@@ -321,13 +461,14 @@ class Trainer:
         _groups_ema); this step's weight on every range."""
         eng, cfg = self.eng, self.cfg
         steps = self.group_steps
+        lr_now = self.lr_now                  # == self.lr with the warm-up off or over
         runs = []                             # [begin, end, lr, step]
         for i in range(frozen_groups, 6):
             b, e = eng.group_ranges[i]
             b, e = max(b, begin), min(e, end)
             if b >= e:
                 continue
-            lr = self.lr * self.lr_mult[i]
+            lr = lr_now * self.lr_mult[i]
             if runs and runs[-1][1] == b and runs[-1][2] == lr and runs[-1][3] == steps[i]:
                 runs[-1][1] = e
             else:
@@ -335,6 +476,11 @@ class Trainer:
         if not runs:
             return
         b, e = runs[0][0], runs[-1][1]
+        if cfg.optimizer != "adam":
+            self._optim_runs(runs, grad_scale, clip_ptr)
+            if self.ema is not None:
+                self._ema_pass(b, e)
+            return
         fused_ema = self.ema is not None and self.ema_fused
         if len(runs) == 1:
             _, _, lr, step = runs[0]
@@ -371,6 +517,32 @@ class Trainer:
             cfg.eps, cfg.weight_decay, clip_ptr, float(grad_scale), self._stream()))
         if self.ema is not None:
             self._ema_pass(b, e)
+
+    def _optim_runs(self, runs, grad_scale, clip_ptr):
+        """AdamW / LAMB over adjacent runs [begin, end, lr, step] of whole parameter tensors: one
+        cilrs_optim_step over their segments, the runs as its groups."""
+        eng, cfg = self.eng, self.cfg
+        b, e = runs[0][0], runs[-1][1]
+        try:
+            first = self._seg_index_of_start[b]
+            last = self._seg_index_of_end[e]
+            for r in runs:
+                self._seg_index_of_end[r[1]]
+        except KeyError:
+            raise RuntimeError(f"optimizer range [{b}, {e}) does not consist of whole parameter "
+                               "tensors") from None
+        k = len(runs)
+        ends = (C.c_size_t * k)(*[r[1] for r in runs])
+        lrs = (C.c_double * k)(*[r[2] for r in runs])
+        steps = (C.c_int64 * k)(*[r[3] for r in runs])
+        lamb = cfg.optimizer == "lamb"
+        L.check(L.lib().cilrs_optim_step(
+            OPTIM_KIND[cfg.optimizer], self._optim_table, first, last - first + 1,
+            L.ptr(eng.params), L.ptr(eng.grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), k,
+            ends, lrs, steps, cfg.betas[0], cfg.betas[1], cfg.eps, cfg.weight_decay,
+            float(cfg.trust_clip), clip_ptr, float(grad_scale),
+            L.ptr(self._optim_scratch) if lamb else None, L.ptr(self._ratios) if lamb else None,
+            self._stream()))
 
     # -- EMA of the weights ------------------------------------------------------------------------
     def _need_ema(self):
@@ -545,7 +717,7 @@ class Trainer:
     # -- StepLR (nb:535-536, 604) ----------------------------------------------------------------
     def scheduler_step(self):
         self.epoch += 1
-        self.lr = steplr(self.cfg, self.epoch)
+        self.lr = scheduled_lr(self.cfg, self.epoch)
 
     # -- validate() (nb:563-585) -------------------------------------------------------------------
     def validate(self, batches, ema=False):

@@ -925,6 +925,79 @@ int cilrs_adam_step_groups_ema(float* params, const float* grads, float* exp_avg
                                const double* lrs, const int64_t* steps, double beta1, double beta2,
                                double eps, double weight_decay, const float* clip_out2,
                                float grad_scale, float* ema, float ema_w, void* stream);
+/* ---- AdamW and LAMB with per-tensor trust ratios ---------------------------------------------------
+ * The reference trains with torch.optim.Adam alone and torch ships no LAMB, so this text is the
+ * definition of both.  All arithmetic is fp32 unless a line says double.  gs is the gradient scale
+ * of cilrs_adam_step: clip_out2[1] * grad_scale, or grad_scale alone.  The scalars 1-beta1, beta2,
+ * 1-beta2, eps, wd, bc1 = 1-beta1^t, bc2_sqrt = sqrt(1-beta2^t), 1/bc1, -lr/bc1 and 1-lr*wd are
+ * prepared on the host in double and rounded to fp32 once.
+ *
+ * Both kinds share the moment update of cilrs_adam_step without its L2 term:
+ *     g' = g * gs
+ *     m  = m + (1-beta1) * (g' - m)
+ *     v  = v * beta2 + ((1-beta2) * g') * g'
+ *     denom = sqrtf(v) / bc2_sqrt + eps
+ *
+ * A SEGMENT is one parameter tensor: the arena range from its offset to the next tensor's offset.
+ * Segment ends are multiples of 4; the padding floats are zero in all four arrays and stay zero.
+ * Each segment carries two flag bits: CILRS_SEG_NO_DECAY (the decay term is dropped for that tensor,
+ * wd_s = 0; otherwise wd_s = wd) and CILRS_SEG_NO_ADAPT (LAMB only: the trust ratio is 1).
+ *
+ * CILRS_OPTIM_ADAMW (torch.optim.AdamW, decoupled decay), per element:
+ *     p = p * (1 - lr*wd_s)                    [the factor is 1 under NO_DECAY]
+ *     p = p + ((-lr/bc1) * m) / denom
+ *
+ * CILRS_OPTIM_LAMB (You et al. 2020, in the form apex and timm use), per element:
+ *     u = (m * (1/bc1)) / denom + wd_s * p     [four separately rounded operations, no FMA]
+ * per segment s without NO_ADAPT, np = sqrt(sum p^2) and nu = sqrt(sum u^2), both sums accumulated
+ * in double from the fp32 values and the square roots taken in double; if trust_clip > 0,
+ * np = min(np, trust_clip); r_s = np / nu in double when both are positive, else 1.  Under NO_ADAPT
+ * r_s = 1.  Then
+ *     p = p - (float)(lr * r_s) * u            [lr * r_s in double]
+ * where the p in u and in the norms is the parameter before the step.
+ *
+ * Work decomposition: every segment is cut, from its own start, into chunks of at most
+ * cilrs_optim_chunk_floats floats; one workgroup reduces one chunk in a fixed tree, and one wave
+ * adds a segment's chunk sums (lane l takes sums l, l + 64, ... in table order, a fixed tree adds the
+ * lanes).  No floating-point atomics: results are bit-identical from
+ * run to run, and a tensor's new p, m, v and r_s are a function of its own data and scalars only --
+ * not of where it sits in the arena, what stands before it or how many segments a call covers.
+ *
+ * The segment table is built and validated once (ends increasing, multiples of 4, the last one = n,
+ * flags in range) and uploaded into caller-owned device memory of cilrs_optim_table_bytes bytes
+ * (16-byte aligned; 0 = unusable ends); the returned handle keeps the host mirror that every later
+ * refusal is decided on.  ends / flags: host arrays of nseg entries. */
+#define CILRS_SEG_NO_DECAY 1
+#define CILRS_SEG_NO_ADAPT 2
+#define CILRS_OPTIM_ADAMW 1
+#define CILRS_OPTIM_LAMB 2
+typedef struct cilrs_optim_table cilrs_optim_table;
+int cilrs_optim_chunk_floats(void);
+size_t cilrs_optim_table_bytes(const size_t* ends, int nseg);
+int cilrs_optim_table_create(const size_t* ends, const int* flags, int nseg, size_t n,
+                             void* device_table, size_t device_bytes, void* stream,
+                             cilrs_optim_table** out);
+void cilrs_optim_table_destroy(cilrs_optim_table* table);
+/* device scratch of a LAMB step over any run of the table: two doubles per chunk, one float per
+ * segment; 16-byte aligned */
+size_t cilrs_optim_scratch_bytes(const cilrs_optim_table* table);
+/* One optimizer step of `kind` over the whole segments [first_seg, first_seg + count) of the table.
+ * params / grads / exp_avg / exp_avg_sq: the WHOLE arrays the table describes (n floats, 16-byte
+ * aligned); nothing outside the run is read or written.  ngroups (1..8) adjacent groups with a
+ * learning rate and a 1-based step count each, as cilrs_adam_step_groups takes them: group_ends are
+ * arena offsets in floats, each the end of a segment of the run, increasing, the last one the end of
+ * the run; host arrays.  clip_out2 (may be NULL) and grad_scale: as cilrs_adam_step.  trust_clip:
+ * 0 = off (LAMB only).  scratch: LAMB only (AdamW: may be NULL).  ratio_out (device, fp32, one per
+ * segment OF THE TABLE, may be NULL): LAMB writes r_s of the run's segments at their table index.
+ * AdamW is one launch; LAMB is three on `stream` with no host synchronisation.  No allocation or
+ * upload per step; every refusal happens before any launch. */
+int cilrs_optim_step(int kind, const cilrs_optim_table* table, int first_seg, int count,
+                     float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                     int ngroups, const size_t* group_ends, const double* lrs, const int64_t* steps,
+                     double beta1, double beta2, double eps, double weight_decay, double trust_clip,
+                     const float* clip_out2, float grad_scale, void* scratch, float* ratio_out,
+                     void* stream);
+
 /* In-place exchange of two arrays of n floats that do not overlap, in one pass.  The plans cache the
  * parameter arena's address: averaged weights are evaluated by swapping them into the arena and
  * out again, never by re-binding pointers. */
