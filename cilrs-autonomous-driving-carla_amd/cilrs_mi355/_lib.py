@@ -35,6 +35,14 @@ class AdamArgs(C.Structure):
                 ("step", C.c_int64), ("grad_scale", C.c_float)]
 
 
+class ReplayConfig(C.Structure):
+    """struct cilrs_replay_config"""
+    _fields_ = [(k, C.c_double) for k in (
+        "dt_s", "speed_unit_ms", "wheelbase_m", "max_wheel_rad", "lookahead_s", "min_lookahead_m",
+        "fx", "fy", "cx", "cy", "height_m", "max_lateral_m", "max_yaw_rad", "recover_m")] \
+        + [("taps", C.c_double * 8), ("ntaps", C.c_int), ("closed_loop", C.c_int)]
+
+
 # symbol -> (restype, argtypes); every symbol include/cilrs_hip.h declares is listed here
 SIGNATURES = {
     "cilrs_version": (i32, []),
@@ -179,6 +187,14 @@ SIGNATURES = {
     "cilrs_augment_view_u8": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "cilrs_batch_assemble_view": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp,
                                         vp, vp, vp, vp]),
+    "cilrs_replay_state_doubles": (i32, []),
+    "cilrs_replay_metric_doubles": (i32, []),
+    "cilrs_replay_begin": (i32, [C.POINTER(ReplayConfig), i32, i32, i64, vp, vp, vp, vp, vp, vp, vp,
+                                 vp, vp]),
+    "cilrs_replay_step": (i32, [C.POINTER(ReplayConfig), i32, i32, vp, vp, vp, i64, vp, vp, vp, vp,
+                                vp, vp, vp, vp]),
+    "cilrs_replay_finish": (i32, [C.POINTER(ReplayConfig), i32, i32, vp, vp, vp, i64, vp, vp, vp, vp,
+                                  vp, vp]),
     "cilrs_eval_acc_doubles": (i32, []),
     "cilrs_eval_accumulate": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, vp]),
     "cilrs_net_profile_enable": (i32, [vp, i32]),

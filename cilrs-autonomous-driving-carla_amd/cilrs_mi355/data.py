@@ -640,6 +640,30 @@ class Sessions:
         return tr, va
 
 
+def drive_ranges(sessions: "Sessions", max_gap: int = 1) -> list:
+    """[(begin, end), ...]: the half-open index ranges of `sessions` that are one unbroken drive.
+    A range ends where the session directory changes and wherever the frame number in
+    `frame_%08d.jpg` moves by anything but 1 .. max_gap: the recorder does not save the frames it
+    skips as stuck (model/collect_data.py), so a session is not one drive.  What
+    `evaluate.replay` replays must lie inside one range; the starts are the caller's choice."""
+    import re
+    if max_gap < 1:
+        raise ValueError("drive_ranges: max_gap must be at least 1")
+    keys = []
+    for p in sessions.paths:
+        m = re.fullmatch(r"frame_(\d+)\.\w+", os.path.basename(p))
+        if m is None:
+            raise RuntimeError(f"drive_ranges: no frame number in {p!r}")
+        keys.append((os.path.dirname(os.path.dirname(p)), int(m.group(1))))
+    out, begin = [], 0
+    for i in range(1, len(keys) + 1):
+        if i == len(keys) or keys[i][0] != keys[i - 1][0] \
+                or not (1 <= keys[i][1] - keys[i - 1][1] <= max_gap):
+            out.append((begin, i))
+            begin = i
+    return out
+
+
 def class_balanced_weights(command: np.ndarray) -> np.ndarray:
     """Per-sample weight len / (4 * count[command]) (notebook.ipynb:383-384, 421)."""
     counts = np.bincount(command, minlength=4).astype(np.float64)

@@ -6,6 +6,10 @@ errors, steer |error| percentiles and accuracy buckets) but not the code that pr
 module emits the same JSON schema.  Every batch costs one eval forward (the HIP plan) plus one
 `cilrs_eval_accumulate` launch that adds the batch's sums to a 72-double table in HBM; nothing is
 copied to the host until `report()`.
+
+`weather_sweep` and `view_sweep` score a checkpoint frame by frame under synthetic weather and from
+displaced viewpoints; `replay` closes the loop: recorded drives driven by the network's own steer,
+with the state, the view records and the metrics on the device (csrc/replay.hip).
 """
 from __future__ import annotations
 
@@ -235,6 +239,238 @@ def view_sweep(model, dataset, indices, lateral_m=(-1.0, -0.5, 0.0, 0.5, 1.0),
         "steer_per_deg": _slope(yaws, [cells[0.0][v]["steer_shift"] for v in yaws])
         if 0.0 in lats else None}
     return out
+
+
+# ---- closed-loop replay -------------------------------------------------------------------------
+# the metrics row of `cilrs_replay_step` (include/cilrs_hip.h), in its order
+REPLAY_METRICS = ("ticks", "lateral_interventions", "yaw_interventions", "nonfinite", "sum_abs_e",
+                  "sum_e2", "max_abs_e", "sum_abs_psi", "max_abs_psi", "sum_abs_steer_err",
+                  "sum_abs_steer_err_corrected", "sum_dsteer2", "recover_tick", "steer_ticks")
+REPLAY_MAX_TAPS = 8
+REPLAY_FLAGS = {"lateral": 1, "yaw": 2, "nonfinite": 4, "view_on": 8}
+
+
+def _replay_summary(m: dict, dt: float, penalty_s: float) -> dict:
+    """per-segment (or summed) metrics -> the derived figures"""
+    ticks, steer = m["ticks"], m["steer_ticks"]
+    n_int = m["lateral_interventions"] + m["yaw_interventions"] + m["nonfinite"]
+    out = dict(m)
+    out["interventions"] = n_int
+    out["autonomy"] = max(0.0, 1.0 - penalty_s * n_int / (ticks * dt)) if ticks > 0 else None
+    out["mean_abs_e"] = m["sum_abs_e"] / ticks if ticks > 0 else None
+    out["rms_e"] = float(np.sqrt(m["sum_e2"] / ticks)) if ticks > 0 else None
+    out["mean_abs_psi"] = m["sum_abs_psi"] / ticks if ticks > 0 else None
+    out["steer_mae"] = m["sum_abs_steer_err"] / steer if steer > 0 else None
+    out["steer_mae_corrected"] = m["sum_abs_steer_err_corrected"] / steer if steer > 0 else None
+    return out
+
+
+def replay(model, dataset, starts, ticks, *, lateral_m=0.0, yaw_deg=0.0, dt=0.05,
+           max_lateral_m=1.0, max_yaw_deg=10.0, recover_m=0.1, penalty_s=6.0, steer_filter=(),
+           closed_loop=True, weather=None, seed=0, camera=None, trace=False, batch_size=128,
+           **steer_kw):
+    """Closed-loop replay of recorded drives, without a simulator (PilotNet's re-simulator on the
+    device; the definition is in include/cilrs_hip.h, "closed-loop replay").  Every segment
+    `starts[s] .. starts[s] + ticks` of `dataset` (a filled `DeviceDataset`; consecutive frames of
+    one drive, see `data.drive_ranges`) is driven by the model's steer: a kinematic bicycle moves the
+    car off the recorded path by (e metres, psi radians), the next recorded frame is shown from
+    there (`cilrs_batch_assemble_view`; speed and command stay the recorded ones), and leaving the
+    box (+-max_lateral_m, +-max_yaw_deg) is an intervention that puts the car back on the path.
+    Segments start at (`lateral_m`, `yaw_deg`), scalars or one value per segment.
+
+    A tick is three launches on the current stream -- `cilrs_replay_step`, the assemble, the eval
+    forward -- and no host synchronisation; `batch_size` segments run at once; the results are read
+    back once at the end.  steer_filter: 0 to 8 weights, oldest to newest, of a running weighted
+    mean of the predicted steer (the reference agent's `smooth_steering`,
+    model/autonomous_drive.py:925-932, is (0.1, 0.15, 0.2, 0.25, 0.3)).  closed_loop=False keeps
+    every segment at its start pose: a `view_sweep` cell over consecutive frames.  weather: a
+    `WeatherMix`, its [ticks, segments] records drawn up front from `seed`.  steer_kw: the
+    arguments of `data.steer_correction` (the vehicle and the look-ahead).
+
+    Limits of the model: the small-offset Frenet form (the factor cos(psi) / (1 - e kappa) on the
+    expert's curvature is dropped); longitudinal motion stays the expert's (throttle and brake are
+    not simulated); the warp is a flat-road model.
+
+    -> {"config", "segments": [per-segment metrics, "autonomy" = max(0, 1 - penalty_s *
+    interventions / (ticks * dt)), ...], "overall"}; with trace=True also "trace": per tick
+    [ticks, segments] "e", "psi", "raw_steer", "steer", "flags" (`REPLAY_FLAGS`), "controls"
+    [ticks, segments, 3], "index" and the raw view records "view" (VIEW_DTYPE)."""
+    from . import data as D
+    ticks = int(ticks)
+    if ticks < 1:
+        raise RuntimeError("replay: ticks must be at least 1")
+    if not getattr(dataset, "filled", False):
+        raise RuntimeError("replay: the dataset's cache is not filled (call fill())")
+    if getattr(dataset, "speed_host", None) is None \
+            or not np.isfinite(np.asarray(dataset.speed_host, dtype=np.float64)).all():
+        raise RuntimeError("replay: needs the dataset's host speeds (speed_host), all finite")
+    starts = np.ascontiguousarray(np.asarray(starts, dtype=np.int64).reshape(-1))
+    n_seg, n, h, w = len(starts), len(dataset), dataset.h, dataset.w
+    if n_seg < 1:
+        raise RuntimeError("replay: no segments")
+    if int(starts.min()) < 0 or int(starts.max()) + ticks > n:
+        bad = starts[(starts < 0) | (starts + ticks > n)][0]
+        raise RuntimeError(f"replay: segment [{int(bad)}, {int(bad) + ticks}) outside the "
+                           f"dataset's [0, {n})")
+    taps = [float(t) for t in steer_filter]
+    if len(taps) > REPLAY_MAX_TAPS:
+        raise RuntimeError(f"replay: {len(taps)} filter taps, at most {REPLAY_MAX_TAPS}")
+    if taps and (not np.isfinite(taps).all() or min(taps) < 0 or not taps[-1] > 0):
+        raise RuntimeError("replay: filter taps must be finite and non-negative, the newest positive")
+    if batch_size < 1:
+        raise RuntimeError("replay: batch_size must be at least 1")
+    lat0 = np.ascontiguousarray(np.broadcast_to(np.asarray(lateral_m, dtype=np.float64), (n_seg,)))
+    yaw0 = np.ascontiguousarray(np.radians(np.broadcast_to(
+        np.asarray(yaw_deg, dtype=np.float64), (n_seg,))))
+    camera = D.CameraModel() if camera is None else camera
+    D.steer_correction(0.0, 0.0, 0.0, **steer_kw)              # refuses an unknown argument now
+    max_yaw_rad = float(np.radians(max_yaw_deg))
+    if not (max_lateral_m > 0 and 0 < max_yaw_rad < 1.5 and dt > 0 and recover_m >= 0):
+        raise RuntimeError("replay: max_lateral_m, max_yaw_deg (below 85) and dt must be positive, "
+                           "recover_m non-negative")
+    if not (np.isfinite(lat0).all() and np.isfinite(yaw0).all()
+            and (np.abs(lat0) <= max_lateral_m).all() and (np.abs(yaw0) <= max_yaw_rad).all()):
+        raise RuntimeError("replay: a segment starts outside the box (+-max_lateral_m, "
+                           "+-max_yaw_deg)")
+    # every record the loop can write lies in the box: w of both matrices depends on psi only and
+    # |steer_delta| falls with the look-ahead, so the four corners at standstill bound them all
+    D.check_view(D.view_records([max_lateral_m, max_lateral_m, -max_lateral_m, -max_lateral_m],
+                                [max_yaw_rad, -max_yaw_rad, max_yaw_rad, -max_yaw_rad], 0.0, h, w,
+                                camera, **steer_kw), h, w)
+    if weather is not None and w > D.WEATHER_MAX_WIDTH:
+        raise RuntimeError(f"weather: width {w} above {D.WEATHER_MAX_WIDTH}")
+    dev = dataset.device
+    if next(model.parameters()).device != dev:
+        raise RuntimeError("replay: model and dataset must be on the same GPU (no CPU fallback)")
+
+    kw = dict(lookahead_s=1.0, min_lookahead_m=4.0, wheelbase_m=2.875, max_steer_deg=70.0)
+    kw.update(steer_kw)
+    fx, fy, cx, cy = camera.intrinsics(h, w)
+    cfg = L.ReplayConfig(
+        dt_s=float(dt), speed_unit_ms=D.SPEED_NORM_KMH / 3.6, wheelbase_m=float(kw["wheelbase_m"]),
+        max_wheel_rad=float(np.radians(kw["max_steer_deg"])), lookahead_s=float(kw["lookahead_s"]),
+        min_lookahead_m=float(kw["min_lookahead_m"]), fx=fx, fy=fy, cx=cx, cy=cy,
+        height_m=camera.height_m, max_lateral_m=float(max_lateral_m), max_yaw_rad=max_yaw_rad,
+        recover_m=float(recover_m), taps=(L.C.c_double * 8)(*taps), ntaps=len(taps),
+        closed_loop=1 if closed_loop else 0)
+    lib = L.lib()
+    ns, nm = lib.cilrs_replay_state_doubles(), lib.cilrs_replay_metric_doubles()
+    assert nm == len(REPLAY_METRICS)
+    vsz, wsz = D.VIEW_DTYPE.itemsize, D.WEATHER_DTYPE.itemsize
+    wrng = np.random.default_rng([seed, D.WEATHER_STREAM])
+    vp = L.C.c_void_p
+    modes = [(m, m.training) for m in model.modules()]
+    model.eval()
+    kept = []
+    try:
+        with torch.no_grad():
+            for b0 in range(0, n_seg, batch_size):
+                b = min(batch_size, n_seg - b0)
+                stream = vp(torch.cuda.current_stream(dev).cuda_stream)
+                state = torch.empty(b, ns, dtype=torch.float64, device=dev)
+                metrics = torch.empty(b, nm, dtype=torch.float64, device=dev)
+                index = torch.empty(ticks, b, dtype=torch.int64, device=dev)
+                view = torch.empty(ticks, b, vsz, dtype=torch.uint8, device=dev)
+                pdev = D._records_to_device(D.identity_params(b), dev)
+                wdev = None
+                if weather is not None:
+                    wrec = weather.draw(wrng, ticks * b, h, w)
+                    D.check_weather(wrec, h, w)
+                    wdev = D._records_to_device(wrec, dev).view(ticks, b, wsz)
+                tr = None
+                if trace:
+                    tr = (torch.empty(ticks, b, 2, dtype=torch.float64, device=dev),
+                          torch.empty(ticks, b, 2, dtype=torch.float32, device=dev),
+                          torch.empty(ticks, b, dtype=torch.uint8, device=dev), [])
+
+                def row(k):                  # the trace rows of tick k
+                    return (None,) * 3 if tr is None else tuple(L.ptr(t[k]) for t in tr[:3])
+                L.check(lib.cilrs_replay_begin(
+                    L.C.byref(cfg), b, ticks, n, vp(starts[b0:b0 + b].ctypes.data),
+                    vp(lat0[b0:b0 + b].ctypes.data), vp(yaw0[b0:b0 + b].ctypes.data),
+                    L.ptr(dataset.speed), L.ptr(state), L.ptr(metrics), L.ptr(index[0]),
+                    L.ptr(view[0]), stream))
+                controls = None
+                for k in range(ticks):
+                    if k >= 1:
+                        L.check(lib.cilrs_replay_step(
+                            L.C.byref(cfg), b, k, L.ptr(controls), L.ptr(dataset.speed),
+                            L.ptr(dataset.targets), n, L.ptr(state), L.ptr(metrics),
+                            L.ptr(index[k]), L.ptr(view[k]), *row(k - 1), stream))
+                    img, spd, cmd, _tgt = dataset._launch(
+                        index[k].data_ptr(), pdev.data_ptr(), b,
+                        weather_ptr=None if wdev is None else wdev[k].data_ptr(),
+                        view_ptr=view[k].data_ptr())
+                    controls, _speed = model(img, spd, cmd)
+                    if controls.dtype != torch.float32 or tuple(controls.shape) != (b, 3) \
+                            or not controls.is_contiguous() or controls.device != dev:
+                        raise RuntimeError("replay: the model must return contiguous float32 "
+                                           "[B, 3] controls on the dataset's GPU")
+                    if tr is not None:
+                        tr[3].append(controls)
+                L.check(lib.cilrs_replay_finish(
+                    L.C.byref(cfg), b, ticks, L.ptr(controls), L.ptr(dataset.speed),
+                    L.ptr(dataset.targets), n, L.ptr(state), L.ptr(metrics), *row(ticks - 1),
+                    stream))
+                kept.append((metrics, index, view, tr))
+    finally:
+        for m, t in modes:
+            m.training = t
+        if modes[0][1] and hasattr(model, "weights_changed"):
+            model.weights_changed()
+    # the one read-back
+    table = torch.cat([k[0] for k in kept]).cpu().numpy()
+    segments = []
+    for s in range(n_seg):
+        m = {name: float(table[s, j]) for j, name in enumerate(REPLAY_METRICS)}
+        for name in ("ticks", "lateral_interventions", "yaw_interventions", "nonfinite",
+                     "recover_tick", "steer_ticks"):
+            m[name] = int(m[name])
+        seg = _replay_summary(m, float(dt), float(penalty_s))
+        seg.update(start=int(starts[s]), lateral0_m=float(lat0[s]), yaw0_rad=float(yaw0[s]))
+        segments.append(seg)
+    total = {name: (max if name.startswith("max_") else sum)(g[name] for g in segments)
+             for name in REPLAY_METRICS if name != "recover_tick"}
+    overall = _replay_summary(total, float(dt), float(penalty_s))
+    rec = [g["recover_tick"] for g in segments if abs(g["lateral0_m"]) >= recover_m]
+    overall["segments"] = n_seg
+    overall["started_outside"] = len(rec)
+    overall["recovered"] = sum(r >= 0 for r in rec)
+    overall["mean_recover_tick"] = float(np.mean([r for r in rec if r >= 0])) \
+        if any(r >= 0 for r in rec) else None
+    out = {"config": {"ticks": ticks, "dt": float(dt), "max_lateral_m": float(max_lateral_m),
+                      "max_yaw_deg": float(max_yaw_deg), "recover_m": float(recover_m),
+                      "penalty_s": float(penalty_s), "steer_filter": taps,
+                      "closed_loop": bool(closed_loop), "seed": int(seed),
+                      "weather": None if weather is None else
+                      {"names": list(weather.names), "severity": list(weather.severity)},
+                      "camera": {"width0": camera.width0, "height0": camera.height0,
+                                 "fov_deg": camera.fov_deg, "height_m": camera.height_m},
+                      "steer": {k: float(v) for k, v in kw.items()}},
+           "segments": segments, "overall": overall}
+    if trace:
+        cat = lambda ts: torch.cat(ts, dim=1).cpu().numpy()
+        st = cat([k[3][0] for k in kept])
+        steer = cat([k[3][1] for k in kept])
+        out["trace"] = {
+            "e": st[..., 0], "psi": st[..., 1], "raw_steer": steer[..., 0], "steer": steer[..., 1],
+            "flags": cat([k[3][2] for k in kept]),
+            "controls": cat([torch.stack(k[3][3]) for k in kept]),
+            "index": cat([k[1] for k in kept]),
+            "view": np.ascontiguousarray(cat([k[2] for k in kept])).view(D.VIEW_DTYPE)[..., 0]}
+    return out
+
+
+def write_replay(path, model, dataset, starts, ticks, **kw):
+    """`replay` written as JSON (a trace's arrays become lists; its raw view records are left
+    out)."""
+    rep = replay(model, dataset, starts, ticks, **kw)
+    doc = dict(rep)
+    if "trace" in doc:
+        doc["trace"] = {k: v.tolist() for k, v in doc["trace"].items() if k != "view"}
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=2)
+    return rep
 
 
 def write_view_sweep(path, model, dataset, indices, **kw):

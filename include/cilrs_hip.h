@@ -1189,6 +1189,88 @@ int cilrs_batch_assemble_view(const uint8_t* cache, int64_t n_frames, const floa
                               float* out_f32, uint8_t* out_u8, float* out_speed,
                               int64_t* out_command, float* out_targets, void* stream);
 
+/* ---- closed-loop replay of recorded drives (csrc/replay.hip; evaluate.replay) -------------------
+ * B segments of a recorded drive are replayed at once: the predicted steer moves a kinematic
+ * bicycle off the recorded path, the next recorded frame is shown from where the car now is
+ * (a view record for cilrs_batch_assemble_view), and what a safety driver would have had to do is
+ * counted -- PilotNet's re-simulator, without a renderer.  One thread per segment, all in double,
+ * a*b+c never fused, no atomics: a segment's result does not depend on its place in the batch.
+ *
+ * Per segment b: start[b], lateral0[b], yaw0[b]; state e (metres, right positive), psi (radians,
+ * right positive), a steer history of at most ntaps values.  Tick k = 0 .. T-1 on frame
+ * i = start[b] + k:
+ *   render   v_n = (double)speed[i].  e == 0 and psi == 0: the record is off and holds the
+ *            identity (the bytes of data.identity_view).  Otherwise on = 1, split_row = cy,
+ *              Rt = [c 0 s; 0 1 0; -s 0 c] (c, s = cos, sin psi),  Sh = [c t/h s; 0 1 0; -s 0 c], t = e
+ *              far = K Rt K^-1, ground = K Sh K^-1, each divided by (its third row) . (cx, cy, 1)
+ *              and exactly the identity where its middle factor is,
+ *              L = max(lookahead_s * v, min_lookahead_m), v = v_n * speed_unit_ms
+ *              steer_delta = atan(wheelbase_m * 2 (0 - e cos psi - L sin psi) / L^2) / max_wheel_rad
+ *            built in double, cast to float32 (data.view_records; lateral_m = e, yaw_rad = psi).
+ *            index[b] = i.  The metrics of tick k use this (e, psi).
+ *   forward  the caller's: one cilrs_batch_assemble_view launch on (index, view), then the network.
+ *   advance  raw = (double)controls[b][0], sx = clip((double)targets[i][0], -1, 1) (the stored
+ *            label), delta = the double steer_delta above (0 at e == psi == 0).
+ *            ticks += 1; S|e|, Se^2, max|e|, S|psi|, max|psi| take (e, psi); a segment that
+ *            started with |lateral0| >= recover_m and has had no intervention yet sets
+ *            recover_tick = k at its first |e| < recover_m.
+ *            raw not finite: nonfinite += 1, intervene.  Otherwise raw joins the history (the last
+ *            ntaps values are kept), s = sum(w * hist) / sum(w) summed oldest to newest with w the
+ *            last len(hist) taps (s = raw with ntaps == 0 or one value), s = clip(s, -1, 1);
+ *            steer_ticks += 1; S|s - sx|, S|s - clip(sx + delta, -1, 1)|, and S(s - s_prev)^2 where
+ *            the previous tick of this stretch had a steer.  Then, when closed_loop:
+ *              ds = (v_n * speed_unit_ms) * dt_s
+ *              e' = e + ds * sin(psi)
+ *              psi' = psi + ds * (tan(s * max_wheel_rad) - tan(sx * max_wheel_rad)) / wheelbase_m
+ *              e' or psi' not finite (a non-finite speed or label): nonfinite += 1, intervene
+ *              else |e'| > max_lateral_m: lateral += 1, intervene
+ *              else |psi'| > max_yaw_rad: yaw += 1, intervene
+ *              else (e, psi) = (e', psi').            |e'| == max_lateral_m is no intervention.
+ *            An intervention sets e = psi = 0 (closed loop), empties the history and ends the
+ *            stretch.  With closed_loop == 0 the state stays (lateral0, yaw0).
+ * This is the small-offset Frenet form: the factor cos(psi) / (1 - e kappa) on the expert's
+ * curvature is dropped.  Longitudinal motion stays the expert's; throttle and brake are not
+ * simulated.  The state is finite after every advance, and a render that finds a non-finite state
+ * resets it to (0, 0) first: no record is ever computed from one.
+ *
+ * metrics [B][cilrs_replay_metric_doubles()]: ticks, lateral, yaw, nonfinite, S|e|, Se^2, max|e|,
+ *   S|psi|, max|psi|, S|s - sx|, S|s - corrected|, S(ds)^2, recover_tick (-1: none), steer_ticks.
+ * state [B][cilrs_replay_state_doubles()]: e, psi, len(hist), hist[8], s_prev, has_prev,
+ *   recover_open, lateral0, yaw0, start.  Both are opaque to everything but the tests. */
+typedef struct {
+    double dt_s, speed_unit_ms, wheelbase_m, max_wheel_rad, lookahead_s, min_lookahead_m;
+    double fx, fy, cx, cy, height_m;           /* the camera at the dataset's H x W */
+    double max_lateral_m, max_yaw_rad, recover_m;
+    double taps[8];                            /* oldest to newest; the first ntaps are read */
+    int ntaps, closed_loop;
+} cilrs_replay_config;       /* 184 bytes */
+
+int cilrs_replay_state_doubles(void);
+int cilrs_replay_metric_doubles(void);
+/* start, lateral0, yaw0: HOST arrays [batch].  Refused before any launch: NULL pointers, batch < 1,
+ * ticks < 1, start[b] < 0, start[b] + ticks > n_frames, a non-finite or out-of-box (lateral0, yaw0),
+ * ntaps outside 0..8, taps that are not finite and non-negative with the newest positive, and
+ * configuration values that are not finite and positive.  Writes state, zeroed metrics, and tick
+ * 0's index [batch] and view [batch]; waits once for its own upload. */
+int cilrs_replay_begin(const cilrs_replay_config* cfg, int batch, int ticks, int64_t n_frames,
+                       const int64_t* start, const double* lateral0, const double* yaw0,
+                       const float* speed, double* state, double* metrics, int64_t* index,
+                       cilrs_view_params* view, void* stream);
+/* tick >= 1: advance tick - 1 on controls [batch][3] (its forward's output), then render `tick`
+ * into index and view.  trace_* (each may be NULL) receive tick - 1's row: trace_state [batch][2]
+ * = (e, psi) as rendered, trace_steer [batch][2] = (raw, s; s is NaN where raw is not finite),
+ * trace_flags [batch] = 1 lateral | 2 yaw | 4 nonfinite | 8 the record was on.  A segment whose
+ * frame would fall outside [0, n_frames) is left untouched.  No host synchronisation. */
+int cilrs_replay_step(const cilrs_replay_config* cfg, int batch, int tick, const float* controls,
+                      const float* speed, const float* targets, int64_t n_frames, double* state,
+                      double* metrics, int64_t* index, cilrs_view_params* view,
+                      double* trace_state, float* trace_steer, uint8_t* trace_flags, void* stream);
+/* folds in the last tick: the advance of cilrs_replay_step at tick = ticks, with no render */
+int cilrs_replay_finish(const cilrs_replay_config* cfg, int batch, int ticks, const float* controls,
+                        const float* speed, const float* targets, int64_t n_frames, double* state,
+                        double* metrics, double* trace_state, float* trace_steer,
+                        uint8_t* trace_flags, void* stream);
+
 /* ---- evaluation report accumulators (metrics schema evaluation_report.json:1-73; the reference
  *      ships the report, not the code that made it) ---------------------------------------------
  * acc: cilrs_eval_acc_doubles() doubles on the device, zeroed by the caller before the first
