@@ -62,7 +62,9 @@ constexpr float kImageStd[3] = {0.229f, 0.224f, 0.225f};
 // library is built with -DCILRS_EXPERIMENTS (make CXXEXTRA=-DCILRS_EXPERIMENTS; tools/README.md).
 // Switches a test exercises (CILRS_WINO, CILRS_WINO_TAIL, CILRS_WINO_WGRAD, CILRS_OVERLAP,
 // CILRS_CONV16_TILE, CILRS_B1_STAMPS) and the A/B switch of the position classes
-// (CILRS_IGEMM_CLASSES) stay run-time.
+// (CILRS_IGEMM_CLASSES) stay run-time: env_int(), kept in a static const at each site (read once
+// per process).
+int env_int(const char* name, int dflt);
 #ifdef CILRS_EXPERIMENTS
 int experiment_env(const char* name, int dflt);
 #else

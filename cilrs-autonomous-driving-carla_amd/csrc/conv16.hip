@@ -413,7 +413,7 @@ bool big_ok() {
 Conv16Plan conv16_plan(const ConvF16Args& a) {
     const int cus = device_cus();
     // CILRS_CONV16_TILE: 0 keeps every launch on the 64x64 kernel, 1 / 2 force a large tile (A/B)
-    static const int force = getenv("CILRS_CONV16_TILE") ? atoi(getenv("CILRS_CONV16_TILE")) : -1;
+    static const int force = env_int("CILRS_CONV16_TILE", -1);
     const int M = a.N * a.Ho * a.Wo;
     Conv16Plan p{0, 64, 0, 0};
     if (a.up2 || force == 0) return p;

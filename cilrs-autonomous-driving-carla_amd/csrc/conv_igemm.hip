@@ -971,7 +971,7 @@ Choice choose(int M, int Cout, int KT, bool allow_split, int force_cfg, int forc
 // CILRS_IGEMM_CLASSES=0 in the environment of the process turns the class launch off (the A/B of
 // profiles/igemm_position_classes.log).
 bool classes_enabled() {
-    static const int env = getenv("CILRS_IGEMM_CLASSES") ? atoi(getenv("CILRS_IGEMM_CLASSES")) : 1;
+    static const int env = env_int("CILRS_IGEMM_CLASSES", 1);
     return env != 0;
 }
 // The classes are sorted by K length, so xcd_remap's contiguous chunk of tiles per XCD hands the

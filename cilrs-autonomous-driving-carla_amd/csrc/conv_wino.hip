@@ -1156,7 +1156,7 @@ int wino_prepare() {
 // never, =2 everything on the 16-tile kernel (experiments).
 struct WinoSplit { int full, tail; };
 static WinoSplit wino_split(int N, int H, int W, int K, int no_tail) {
-    static const int mode = getenv("CILRS_WINO_TAIL") ? atoi(getenv("CILRS_WINO_TAIL")) : 1;
+    static const int mode = env_int("CILRS_WINO_TAIL", 1);
     const int cus = device_cus();
     const int tiles = N * ((H + 1) / 2) * ((W + 1) / 2);
     const int groups = cdiv(tiles, WT), nkt = K / WK;

@@ -18,6 +18,7 @@
 
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <string>
@@ -66,6 +67,11 @@ int experiment_env(const char* name, int dflt) {
     return v ? atoi(v) : dflt;
 }
 #endif
+// the run-time switches (common.h); every site keeps the value in a static const: read once per process
+int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
 
 // CILRS_PRIO: static wave priorities of the GEMM kernels (common.h wave_priority)
 int wave_priority_mode() {
@@ -286,7 +292,7 @@ using namespace cilrs;
 // ------------------------------------------------------------------------------------------------
 // The plan
 // ------------------------------------------------------------------------------------------------
-struct ConvG { int H, W, Ho, Wo, M; size_t y, z, stats; };
+struct ConvG { int ci /*index in Arch::convs*/, H, W, Ho, Wo, M; size_t y, z, stats; };
 // The frozen prefix of a fine-tuning step sends the layers the train plan gives to the Winograd
 // kernel through its folded-epilogue variant (conv_wino.hip FOLD) instead of the implicit GEMM
 // (DESIGN.md "Fine-tuning" has the per-shape measurement; CILRS_FT_WINO=0 of an experiments
@@ -301,28 +307,40 @@ constexpr int kDyRing = 2;
 constexpr int kNumG = 5;
 constexpr int kRingIdx[kDyRing] = {0, 4};
 
+// a HIP handle the plan owns: destroyed with the plan if it was ever created
+template <typename T, hipError_t (*Destroy)(T)>
+struct Owned {
+    T h = nullptr;
+    Owned() = default;
+    Owned(const Owned&) = delete;
+    ~Owned() { if (h) (void)Destroy(h); }
+    operator T() const { return h; }
+};
+using OwnedStream = Owned<hipStream_t, hipStreamDestroy>;
+using OwnedEvent = Owned<hipEvent_t, hipEventDestroy>;
+using OwnedGraphExec = Owned<hipGraphExec_t, hipGraphExecDestroy>;
+
 struct cilrs_net {
     const Arch* A = nullptr;               // architecture variant of this plan
-    int B, H, W;
+    int B = 0, H = 0, W = 0;
     std::vector<ConvG> cg;                 // geometry + workspace offsets (floats) per conv
-    int H0, W0, H1, W1;                    // stem conv out, maxpool out
-    int featHW;
+    int H0 = 0, W0 = 0, H1 = 0, W1 = 0, featHW = 0;     // stem conv out, maxpool out, last map's pixels
     // workspace offsets (in floats unless noted)
-    size_t x4, w4, pool, argmax_b /*bytes offset*/, combined, s1, p1, p2, h1[kMaxCmd], h2[kMaxCmd], all_out;
-    size_t dcombined, ds1, dp1, dp2, dh1[kMaxCmd], dh2[kMaxCmd], dcomb_part[kMaxCmd + 1], d_all, speed_in,
-        cmd_b /*bytes offset*/;
+    size_t x4 = 0, w4 = 0, pool = 0, argmax_b = 0 /*bytes offset*/, combined = 0, s1 = 0, p1 = 0, p2 = 0,
+           h1[kMaxCmd] = {}, h2[kMaxCmd] = {}, all_out = 0;
+    size_t dcombined = 0, ds1 = 0, dp1 = 0, dp2 = 0, dh1[kMaxCmd] = {}, dh2[kMaxCmd] = {},
+           dcomb_part[kMaxCmd + 1] = {}, d_all = 0, speed_in = 0, cmd_b = 0 /*bytes offset*/;
     const void* status_cleared_for = nullptr;   // workspace whose status words have been cleared
-    size_t G[kNumG];                       // gradient buffers: [1..3] fixed roles, [0] and [4] = dy ring
-    size_t gmax;
-    size_t bn_partial, bn_partial2, bn_coef, slabs, slabs_floats, ksplit, ksplit_floats, status_b;
-    size_t ws_bytes;
+    size_t G[kNumG] = {};                  // gradient buffers: [1..3] fixed roles, [0] and [4] = dy ring
+    size_t gmax = 0, bn_partial = 0, bn_partial2 = 0, bn_coef = 0, slabs = 0, slabs_floats = 0, ksplit = 0,
+           ksplit_floats = 0, status_b = 0, ws_bytes = 0;
     float* ws_base = nullptr;             // workspace of the current call (set by every entry)
     // side streams: independent kernels (weight-gradient vs data-gradient GEMMs, the five head
     // chains) run concurrently so one launch's tail fills with another's blocks
     bool overlap = true;
-    bool streams_ready = false;
-    hipStream_t side[1];                   // weight-gradient stream
-    hipEvent_t fork_ev, gbuf_ev[kNumG], wprep_ev, branch_ev, heads_ev;
+    bool streams_ready = false;            // ensure_streams has created all of these
+    OwnedStream side[1];                   // weight-gradient stream
+    OwnedEvent fork_ev, gbuf_ev[kNumG], wprep_ev, branch_ev, heads_ev;
     int side_branch = 0;                  // conv_fwd / conv_fwd16 are building a down-sample branch: no split-K scratch;
                                            // 1 = on the side stream, with column-partial scratch of its own
     bool wprep_pending = false;            // this step's weight images are being built on the side stream
@@ -340,13 +358,13 @@ struct cilrs_net {
         // as the plan, so the two slots may swap roles from one step to the next.
         int dy_pos = 0;
     } bwd;
-    BnEvalTable bn_table;
-    BnStatsTable bn_stats;                 // re-estimation table layout, indexed by BatchNorm layer
-    FoldF16Table f16_table;                // fp16 inference: folded weights / biases / activations
-    size_t f16_w, f16_bias, f16_act[5], f16_act_floats;
+    BnEvalTable bn_table = {};
+    BnStatsTable bn_stats = {};            // re-estimation table layout, indexed by BatchNorm layer
+    FoldF16Table f16_table = {};           // fp16 inference: folded weights / biases / activations
+    size_t f16_w = 0, f16_bias = 0, f16_act[5] = {}, f16_act_floats = 0;
     size_t stem16_w = 0, stem16_b = 0;     // folded 16-bit stem weights [64][7][8][4] / fp32 shift
     // cached hipGraph of the uint8 inference path (fixed pointers)
-    hipGraphExec_t graph_exec = nullptr;
+    OwnedGraphExec graph_exec;
     int graph_half = 0;
     const void* graph_key[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                 nullptr};
@@ -395,15 +413,15 @@ struct cilrs_net {
     bool bf16_train = false;
     size_t w16_all = 0, wT16 = 0, pool16 = 0, slabs16 = 0, slabs16_floats = 0;
     size_t z16[kMaxConvs] = {}, wT16_off[kMaxConvs] = {}, G16[kNumG] = {};
-    TransposeF16Table tr_table;
+    TransposeF16Table tr_table = {};
     // Winograd F(2x2, 3x3) (conv_wino.hip) for the stride-1 3x3 convolutions of fp32 train plans
     // where it beats the implicit GEMM (layers of up to 256 channels with enough blocks to fill
     // the chip; CILRS_WINO=0 turns it off): forward + data gradient.  Both transformed-filter
     // images of every such layer live in the workspace and are rebuilt by ONE launch at the top
     // of each training forward (the weights change every step).
-    bool wino_on[kMaxConvs] = {};
+    int wino_slot[kMaxConvs];              // the layer's entry in wino_table, -1: not a Winograd layer
     size_t wino_base = 0;
-    WinoWeightTable wino_table;
+    WinoWeightTable wino_table = {};
     // Fine-tuning (cilrs_net_forward_ft): leading trunk groups (stem, layer1..layer4) of the last
     // graph-keeping forward that ran in eval mode (ft_bn: BatchNorm folded into the convolution
     // epilogues, nothing kept for a backward pass) / whose parameters take no gradient (ft_grad:
@@ -423,6 +441,7 @@ struct cilrs_net {
     int b1_blocks = -1;                    // resident grid (one workgroup per CU); -1 = not asked yet
     const void* b1_ready_for = nullptr;
     Prof prof;
+    cilrs_net() { std::fill(wino_slot, wino_slot + kMaxConvs, -1); }
 };
 
 namespace {
@@ -496,14 +515,13 @@ unsigned stream_event_flags() {
 }
 int ensure_streams(cilrs_net* net) {
     if (net->streams_ready) return 0;
-    // side stream 0 carries the weight-gradient GEMMs
-    CILRS_HIP(hipStreamCreateWithFlags(&net->side[0], hipStreamNonBlocking));
-    for (int i = 0; i < kNumG; ++i)
-        CILRS_HIP(hipEventCreateWithFlags(&net->gbuf_ev[i], stream_event_flags()));
-    CILRS_HIP(hipEventCreateWithFlags(&net->fork_ev, stream_event_flags()));
-    CILRS_HIP(hipEventCreateWithFlags(&net->wprep_ev, stream_event_flags()));
-    CILRS_HIP(hipEventCreateWithFlags(&net->branch_ev, stream_event_flags()));
-    CILRS_HIP(hipEventCreateWithFlags(&net->heads_ev, stream_event_flags()));
+    // side stream 0 carries the weight-gradient GEMMs.  (what a call that failed half-way had
+    // created stays with the plan, which destroys it; a retry creates the rest)
+    if (!net->side[0].h) CILRS_HIP(hipStreamCreateWithFlags(&net->side[0].h, hipStreamNonBlocking));
+    OwnedEvent* evs[kNumG + 4] = {&net->fork_ev, &net->wprep_ev, &net->branch_ev, &net->heads_ev};
+    for (int i = 0; i < kNumG; ++i) evs[4 + i] = &net->gbuf_ev[i];
+    for (OwnedEvent* e : evs)
+        if (!e->h) CILRS_HIP(hipEventCreateWithFlags(&e->h, stream_event_flags()));
     net->streams_ready = true;
     return 0;
 }
@@ -512,7 +530,7 @@ int ensure_streams(cilrs_net* net) {
 bool overlap_configured(cilrs_net* net) {
     // CILRS_OVERLAP=0 serialises everything on the caller's stream (rocprofv3 per-kernel durations
     // then match the hipEvent brackets of the profile mode)
-    static const int env = getenv("CILRS_OVERLAP") ? atoi(getenv("CILRS_OVERLAP")) : 1;
+    static const int env = env_int("CILRS_OVERLAP", 1);
     return env != 0 && net->overlap;
 }
 bool use_overlap(cilrs_net* net) { return overlap_configured(net) && !net->prof.on; }
@@ -550,58 +568,92 @@ int gbuf_join_all(cilrs_net* net, hipStream_t main) {
     return 0;
 }
 
+// ---- one builder per operator's arguments: the geometry of a dense NHWC / OHWI problem.  Pointers,
+//      scratch, epilogue and tuning fields are the caller's (the plan's, or an op-level entry's) ----
+int out_dim(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
+
+ConvArgs conv_args(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin;
+    a.Ho = out_dim(H, KH, stride, pad); a.Wo = out_dim(W, KW, stride, pad); a.Cout = Cout;
+    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
+    a.x_ld = Cin; a.y_ld = Cout; a.w_mode = 0; a.w_cin = Cin;
+    return a;
+}
+DgradArgs dgrad_args(int N, int H, int W, int Cin, int Cout, int K, int stride, int pad) {
+    DgradArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin;
+    a.Ho = out_dim(H, K, stride, pad); a.Wo = out_dim(W, K, stride, pad);
+    a.Cout = Cout; a.K = K; a.stride = stride; a.pad = pad;
+    a.dy_ld = Cout; a.dx_ld = Cin;
+    return a;
+}
+// Cin: channels of x as stored (4 for the stem's channel-padded image), Cin_dst: channels of dw
+WgradArgs wgrad_args(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                     int Cin_dst) {
+    WgradArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin;
+    a.Ho = out_dim(H, KH, stride, pad); a.Wo = out_dim(W, KW, stride, pad); a.Cout = Cout;
+    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
+    a.x_ld = Cin; a.dy_ld = Cout; a.Cin_dst = Cin_dst; a.accumulate = 0;
+    return a;
+}
+// a Winograd launch over the plan's [B][H][W] map of convolution g: C channels gathered, K written
+WinoArgs wino_args(const cilrs_net* net, const ConvG& g, int C, int K) {
+    WinoArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = net->B; a.H = g.H; a.W = g.W; a.C = C; a.K = K;
+    return a;
+}
+
+// ---- profile estimates: the DIRECT convolution's flops, whichever kernel runs it, and ----
+double conv_flops(const ConvT& c, const ConvG& g) { return 2.0 * g.M * c.cout * c.k * c.k * c.cin; }
+// the bytes of input, output (out_passes 2: a residual read beside the write) and weights (wino: the
+// 16-point filter image), each at its element size.  (whole numbers far below 2^53: the sum is exact)
+double conv_bytes(const cilrs_net* net, const ConvT& c, const ConvG& g, double in_size,
+                  double out_size, double w_size, bool wino = false, double out_passes = 1.0) {
+    const double in = (double)net->B * g.H * g.W * c.cin, out = (double)g.M * c.cout;
+    const double w = wino ? 16.0 * c.cout * c.cin : (double)c.cout * c.k * c.k * c.cin;
+    return in_size * in + out_size * out * out_passes + w_size * w;
+}
+
 int conv_fwd(cilrs_net* net, const ConvT& c, const ConvG& g, const float* x, int x_cin,
              const float* w, float* y, float* ws, hipStream_t s, int* bn_nblk = nullptr,
              const float* fold_stats = nullptr, int relu = 0, const float* addend = nullptr,
              int relu_post = 0) {
-    const int ci = (int)(&g - &net->cg[0]);
-    if (bn_nblk && !fold_stats && net->wino_on[ci]) {      // training forward on the Winograd kernel
-        WinoArgs wa;
-        memset(&wa, 0, sizeof(wa));
-        int e = 0;
-        while (net->wino_table.w[e] != (unsigned)c.w) ++e;
+    auto label = [&] { return std::string("conv_fwd.") + kGroupName[c.group]; };     // (profile mode only)
+    const int e = net->wino_slot[g.ci];
+    if (bn_nblk && !fold_stats && e >= 0) {      // training forward on the Winograd kernel
+        WinoArgs wa = wino_args(net, g, c.cin, c.cout);
         wa.x = x; wa.U = ws + net->wino_base + net->wino_table.u[e]; wa.y = y;
-        wa.N = net->B; wa.H = g.H; wa.W = g.W; wa.C = c.cin; wa.K = c.cout;
         wa.bn_partial = ws + net->bn_partial;
         wa.slabs = ws + net->ksplit; wa.slab_floats = net->ksplit_floats;
         wa.scratch_partial = ws + net->bn_partial;
         *bn_nblk = wino_rows(net->B, g.H, g.W, c.cout, 0, c.cin, net->ksplit_floats);
-        const double flops = 2.0 * g.M * c.cout * c.k * c.k * c.cin;      // DIRECT-convolution flops
-        const double bytes = 4.0 * ((double)net->B * g.H * g.W * c.cin + (double)g.M * c.cout +
-                                    16.0 * c.cout * c.cin);
-        RUN(net, std::string("conv_fwd.") + kGroupName[c.group], flops, bytes, s,
+        RUN(net, label(), conv_flops(c, g), conv_bytes(net, c, g, 4, 4, 4, true), s,
             launch_conv_wino(wa, s));
         return 0;
     }
-    if (fold_stats && net->ft_route_wino && net->wino_on[ci] && ft_wino_fold()) {
+    if (fold_stats && net->ft_route_wino && e >= 0 && ft_wino_fold()) {
         // frozen prefix of a fine-tuning step: the Winograd kernel with the folded epilogue
-        WinoArgs wa;
-        memset(&wa, 0, sizeof(wa));
-        int e = 0;
-        while (net->wino_table.w[e] != (unsigned)c.w) ++e;
+        WinoArgs wa = wino_args(net, g, c.cin, c.cout);
         wa.x = x; wa.U = ws + net->wino_base + net->wino_table.u[e]; wa.y = y; wa.addend = addend;
-        wa.N = net->B; wa.H = g.H; wa.W = g.W; wa.C = c.cin; wa.K = c.cout;
         const WinoFold f{fold_stats + 2 * c.cout, fold_stats + 3 * c.cout, relu, relu_post};
-        const double flops = 2.0 * g.M * c.cout * c.k * c.k * c.cin;      // DIRECT-convolution flops
-        const double bytes = 4.0 * ((double)net->B * g.H * g.W * c.cin + (double)g.M * c.cout *
-                                    (addend ? 2.0 : 1.0) + 16.0 * c.cout * c.cin);
-        RUN(net, std::string("conv_fwd.") + kGroupName[c.group], flops, bytes, s,
+        RUN(net, label(), conv_flops(c, g), conv_bytes(net, c, g, 4, 4, 4, true, addend ? 2.0 : 1.0), s,
             launch_conv_wino_fold(wa, f, s));
         ++net->ft_wino;
         return 0;
     }
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
+    ConvArgs a = conv_args(net->B, g.H, g.W, x_cin, c.cout, c.k, c.k, c.stride, c.pad);
     a.x = x; a.w = w; a.y = y;
     if (fold_stats) {            // eval-mode BatchNorm (+ReLU / residual) folded into the epilogue
         a.ch_scale = fold_stats + 2 * c.cout;
         a.ch_shift = fold_stats + 3 * c.cout;
         a.relu = relu; a.addend = addend; a.relu_post = relu_post;
     }
-    a.N = net->B; a.H = g.H; a.W = g.W; a.Cin = x_cin;
-    a.Ho = g.Ho; a.Wo = g.Wo; a.Cout = c.cout;
-    a.KH = a.KW = c.k; a.stride = c.stride; a.pad = c.pad;
-    a.x_ld = x_cin; a.y_ld = c.cout; a.w_mode = 0; a.w_cin = x_cin;
     a.scratch = ws + net->ksplit; a.scratch_floats = net->ksplit_floats;
     if (net->side_branch) { a.scratch = nullptr; a.scratch_floats = 0; }     // (no split-K beside the main stream's)
     a.force_cfg = -1;
@@ -609,11 +661,7 @@ int conv_fwd(cilrs_net* net, const ConvT& c, const ConvG& g, const float* x, int
         a.bn_partial = ws + (net->side_branch == 1 ? net->bn_partial2 : net->bn_partial);
         a.bn_nblk = bn_nblk; *bn_nblk = 0;
     }
-    const double flops = 2.0 * g.M * c.cout * c.k * c.k * c.cin;
-    const double bytes = 4.0 * ((double)net->B * g.H * g.W * c.cin + (double)g.M * c.cout +
-                                (double)c.cout * c.k * c.k * c.cin);
-    RUN(net, std::string("conv_fwd.") + kGroupName[c.group], flops, bytes, s,
-        launch_conv_igemm(a, s));
+    RUN(net, label(), conv_flops(c, g), conv_bytes(net, c, g, 4, 4, 4), s, launch_conv_igemm(a, s));
     return 0;
 }
 
@@ -621,14 +669,11 @@ int conv_fwd(cilrs_net* net, const ConvT& c, const ConvG& g, const float* x, int
 int conv_dgrad(cilrs_net* net, const ConvT& c, const ConvG& g, const float* dy, const float* w,
                float* dx, const float* addend, float* ws, hipStream_t s,
                const ConvG* bn_of = nullptr, int bn_relu = 1, int* bwd_nblk = nullptr) {
-    const int ci = (int)(&g - &net->cg[0]);
-    if (net->wino_on[ci]) {        // the same convolution with the flipped, transposed filter
-        WinoArgs wa;
-        memset(&wa, 0, sizeof(wa));
-        int e = 0;
-        while (net->wino_table.w[e] != (unsigned)c.w) ++e;
+    auto label = [&] { return std::string("conv_dgrad.") + kGroupName[c.group]; };
+    const int e = net->wino_slot[g.ci];
+    if (e >= 0) {                  // the same convolution with the flipped, transposed filter
+        WinoArgs wa = wino_args(net, g, c.cout, c.cin);
         wa.x = dy; wa.U = ws + net->wino_base + net->wino_table.ud[e]; wa.y = dx; wa.addend = addend;
-        wa.N = net->B; wa.H = g.H; wa.W = g.W; wa.C = c.cout; wa.K = c.cin;
         // the 16-tile tail launch pays in the forward pass only: in the backward pass the weight
         // gradients of the side stream already fill the CUs a last round leaves idle, and a
         // second launch per data gradient costs more in boundaries than it gains (step 11.09 vs
@@ -647,31 +692,20 @@ int conv_dgrad(cilrs_net* net, const ConvT& c, const ConvG& g, const float* dy, 
             wa.bwd_relu = bn_relu; wa.bwd_partial = ws + net->bn_partial;
             *bwd_nblk = wino_rows(net->B, g.H, g.W, c.cin, wa.no_tail, c.cout, net->ksplit_floats);
         }
-        const double flops = 2.0 * g.M * c.cout * c.k * c.k * c.cin;
-        const double bytes = 4.0 * ((double)net->B * g.H * g.W * c.cin + (double)g.M * c.cout +
-                                    16.0 * c.cout * c.cin);
-        RUN(net, std::string("conv_dgrad.") + kGroupName[c.group], flops, bytes, s,
+        RUN(net, label(), conv_flops(c, g), conv_bytes(net, c, g, 4, 4, 4, true), s,
             launch_conv_wino(wa, s));
         return 0;
     }
-    DgradArgs a;
-    memset(&a, 0, sizeof(a));
+    DgradArgs a = dgrad_args(net->B, g.H, g.W, c.cin, c.cout, c.k, c.stride, c.pad);
     a.dy = dy; a.w = w; a.dx = dx; a.addend = addend;
     if (bn_of && bwd_nblk) {       // the BatchNorm layer whose output gradient this call produces
         a.bwd_z = ws + bn_of->z; a.bwd_y = ws + bn_of->y; a.bwd_stats = ws + bn_of->stats;
         a.bwd_relu = bn_relu; a.bwd_partial = ws + net->bn_partial; a.bwd_nblk = bwd_nblk;
         *bwd_nblk = 0;
     }
-    a.N = net->B; a.H = g.H; a.W = g.W; a.Cin = c.cin;
-    a.Ho = g.Ho; a.Wo = g.Wo; a.Cout = c.cout; a.K = c.k; a.stride = c.stride; a.pad = c.pad;
-    a.dy_ld = c.cout; a.dx_ld = c.cin;
     a.scratch = ws + net->ksplit; a.scratch_floats = net->ksplit_floats;
     a.force_cfg = -1;
-    const double flops = 2.0 * g.M * c.cout * c.k * c.k * c.cin;
-    const double bytes = 4.0 * ((double)net->B * g.H * g.W * c.cin + (double)g.M * c.cout +
-                                (double)c.cout * c.k * c.k * c.cin);
-    RUN(net, std::string("conv_dgrad.") + kGroupName[c.group], flops, bytes, s,
-        launch_conv_dgrad(a, s));
+    RUN(net, label(), conv_flops(c, g), conv_bytes(net, c, g, 4, 4, 4), s, launch_conv_dgrad(a, s));
     return 0;
 }
 
@@ -679,12 +713,13 @@ int conv_dgrad(cilrs_net* net, const ConvT& c, const ConvG& g, const float* dy, 
 // runs in the Winograd domain (conv_wino.hip: 1.09-1.46x the direct kernel at B=128, all four
 // layers); CILRS_WINO_WGRAD=0 turns it off.  Independent of CILRS_WINO (forward / data gradient).
 static bool wino_wgrad_on(const ConvT& c) {
-    static const int env = getenv("CILRS_WINO_WGRAD") ? atoi(getenv("CILRS_WINO_WGRAD")) : 1;
+    static const int env = env_int("CILRS_WINO_WGRAD", 1);
     return env != 0 && wino_wgrad_supported(c.cin, c.cout, c.k, c.stride, c.pad);
 }
 
 int conv_wgrad(cilrs_net* net, const ConvT& c, const ConvG& g, const float* x, int x_cin,
                const float* dy, float* dw, float* ws, hipStream_t s) {
+    auto label = [&] { return std::string("conv_wgrad.") + kGroupName[c.group]; };
     if (x_cin == c.cin && !net->bf16_train && wino_wgrad_on(c)) {
         WinoWgradArgs wa;
         memset(&wa, 0, sizeof(wa));
@@ -692,26 +727,15 @@ int conv_wgrad(cilrs_net* net, const ConvT& c, const ConvG& g, const float* x, i
         wa.N = net->B; wa.H = g.H; wa.W = g.W; wa.C = c.cin; wa.K = c.cout;
         CILRS_CHECK(wino_wgrad_scratch_floats(net->B, g.H, g.W, c.cin, c.cout) <= net->slabs_floats,
                     "Winograd wgrad scratch too small");
-        const double flops = 2.0 * g.M * c.cout * c.k * c.k * c.cin;      // DIRECT-convolution flops
-        const double bytes = 4.0 * ((double)net->B * g.H * g.W * c.cin + (double)g.M * c.cout +
-                                    (double)c.cout * c.k * c.k * c.cin);
-        RUN(net, std::string("conv_wgrad.") + kGroupName[c.group], flops, bytes, s,
+        RUN(net, label(), conv_flops(c, g), conv_bytes(net, c, g, 4, 4, 4), s,
             launch_conv_wino_wgrad(wa, s));
         return 0;
     }
-    WgradArgs a;
-    memset(&a, 0, sizeof(a));
+    // (the arguments plan_sizes sized the slabs from)
+    WgradArgs a = wgrad_args(net->B, g.H, g.W, x_cin, c.cout, c.k, c.k, c.stride, c.pad, c.cin);
     a.x = x; a.dy = dy; a.dw = dw; a.slabs = ws + net->slabs;
-    a.N = net->B; a.H = g.H; a.W = g.W; a.Cin = x_cin;
-    a.Ho = g.Ho; a.Wo = g.Wo; a.Cout = c.cout;
-    a.KH = a.KW = c.k; a.stride = c.stride; a.pad = c.pad;
-    a.x_ld = x_cin; a.dy_ld = c.cout; a.Cin_dst = c.cin; a.accumulate = 0;
     CILRS_CHECK(wgrad_scratch_floats(a) <= net->slabs_floats, "wgrad scratch too small");
-    const double flops = 2.0 * g.M * c.cout * c.k * c.k * c.cin;
-    const double bytes = 4.0 * ((double)net->B * g.H * g.W * c.cin + (double)g.M * c.cout +
-                                (double)c.cout * c.k * c.k * c.cin);
-    RUN(net, std::string("conv_wgrad.") + kGroupName[c.group], flops, bytes, s,
-        launch_conv_wgrad(a, s));
+    RUN(net, label(), conv_flops(c, g), conv_bytes(net, c, g, 4, 4, 4), s, launch_conv_wgrad(a, s));
     return 0;
 }
 
@@ -725,31 +749,28 @@ cilrs_half* h16(float* ws, size_t off_floats) {
 // keeps its y (same offset, half the bytes), the post-BatchNorm tensor in z16[ci].
 cilrs_half* y16_of(const cilrs_net* net, float* ws, int ci) { return h16(ws, net->cg[ci].y); }
 
-int conv_fwd16(cilrs_net* net, const ConvT& c, const ConvG& g, int ci, const cilrs_half* x16,
+int conv_fwd16(cilrs_net* net, const ConvT& c, const ConvG& g, const cilrs_half* x16,
                float* ws, hipStream_t s, int* bn_nblk) {
     ConvF16Args a;
     memset(&a, 0, sizeof(a));
-    a.x = x16; a.w = h16(ws, net->w16_all) + c.w; a.y16 = y16_of(net, ws, ci);
+    a.x = x16; a.w = h16(ws, net->w16_all) + c.w; a.y16 = y16_of(net, ws, g.ci);
     a.bn_partial = ws + (net->side_branch == 1 ? net->bn_partial2 : net->bn_partial);
     a.N = net->B; a.H = g.H; a.W = g.W; a.Cin = c.cin; a.Ho = g.Ho; a.Wo = g.Wo; a.Cout = c.cout;
     a.K = c.k; a.stride = c.stride; a.pad = c.pad; a.bf16 = 1;
     *bn_nblk = conv_f16_train_mtiles(a);
-    const double flops = 2.0 * g.M * c.cout * c.k * c.k * c.cin;
-    const double bytes = 2.0 * ((double)net->B * g.H * g.W * c.cin + (double)c.cout * c.k * c.k * c.cin +
-                                (double)g.M * c.cout);
-    RUN(net, std::string("conv_fwd.") + kGroupName[c.group], flops, bytes, s,
-        launch_conv_f16_train(a, s));
+    RUN(net, std::string("conv_fwd.") + kGroupName[c.group], conv_flops(c, g),
+        conv_bytes(net, c, g, 2, 2, 2), s, launch_conv_f16_train(a, s));
     return 0;
 }
 
 // dx (16-bit, or fp32 when dx32 is given: the gradient handed to the fp32 stem) = dgrad(dy16)
 // (+ addend16); bn_of: the convolution whose BatchNorm-backward reductions ride on the epilogue
-int conv_dgrad16(cilrs_net* net, const ConvT& c, const ConvG& g, int ci, const cilrs_half* dy16,
+int conv_dgrad16(cilrs_net* net, const ConvT& c, const ConvG& g, const cilrs_half* dy16,
                  cilrs_half* dx16, float* dx32, const cilrs_half* addend16, float* ws,
                  hipStream_t s, const ConvG* bn_of = nullptr, int* bwd_nblk = nullptr) {
     ConvF16Args a;
     memset(&a, 0, sizeof(a));
-    a.x = dy16; a.w = h16(ws, net->wT16) + net->wT16_off[ci];
+    a.x = dy16; a.w = h16(ws, net->wT16) + net->wT16_off[g.ci];
     if (dx32) a.y32 = dx32; else a.y16 = dx16;
     a.addend16 = addend16;
     a.N = net->B; a.H = g.Ho; a.W = g.Wo; a.Cin = c.cout;      // gathered tensor = dy
@@ -759,17 +780,13 @@ int conv_dgrad16(cilrs_net* net, const ConvT& c, const ConvG& g, int ci, const c
     else { a.stride = 2; a.pad = c.pad; a.up2 = 1; }
     if (bwd_nblk) *bwd_nblk = 0;
     if (bn_of && bwd_nblk && conv_f16_train_can_fuse_bwd(a)) {   // the BatchNorm whose output gradient this is
-        const int bi = (int)(bn_of - &net->cg[0]);
-        a.bwd_z16 = h16(ws, net->z16[bi]); a.bwd_y16 = y16_of(net, ws, bi);
+        a.bwd_z16 = h16(ws, net->z16[bn_of->ci]); a.bwd_y16 = y16_of(net, ws, bn_of->ci);
         a.bwd_stats = ws + bn_of->stats;
         a.bwd_relu = 1; a.bwd_partial = ws + net->bn_partial;
         *bwd_nblk = conv_f16_train_mtiles(a);
     }
-    const double flops = 2.0 * g.M * c.cout * c.k * c.k * c.cin;
-    const double bytes = 2.0 * ((double)g.M * c.cout + (double)c.cout * c.k * c.k * c.cin) +
-                         (dx32 ? 4.0 : 2.0) * (double)net->B * g.H * g.W * c.cin;
-    RUN(net, std::string("conv_dgrad.") + kGroupName[c.group], flops, bytes, s,
-        launch_conv_f16_train(a, s));
+    RUN(net, std::string("conv_dgrad.") + kGroupName[c.group], conv_flops(c, g),
+        conv_bytes(net, c, g, dx32 ? 4 : 2, 2, 2), s, launch_conv_f16_train(a, s));
     return 0;
 }
 
@@ -786,11 +803,8 @@ int conv_wgrad16(cilrs_net* net, const ConvT& c, const ConvG& g, const cilrs_hal
     WgradF16Args a = wgrad16_args(net, c, g);
     a.x = x16; a.dy = dy16; a.dw = dw; a.slabs = ws + net->slabs16;
     CILRS_CHECK(wgrad_f16_scratch_floats(a) <= net->slabs16_floats, "wgrad16 scratch too small");
-    const double flops = 2.0 * g.M * c.cout * c.k * c.k * c.cin;
-    const double bytes = 2.0 * ((double)net->B * g.H * g.W * c.cin + (double)g.M * c.cout) +
-                         4.0 * (double)c.cout * c.k * c.k * c.cin;
-    RUN(net, std::string("conv_wgrad.") + kGroupName[c.group], flops, bytes, s,
-        launch_wgrad_f16(a, s));
+    RUN(net, std::string("conv_wgrad.") + kGroupName[c.group], conv_flops(c, g),
+        conv_bytes(net, c, g, 2, 2, 4), s, launch_wgrad_f16(a, s));
     return 0;
 }
 
@@ -928,6 +942,267 @@ int cilrs_net_create_variant(int variant, int batch, int height, int width, cilr
     return cilrs_net_create_ex(variant, batch, height, width, 0u, out);
 }
 
+// Three kinds of step build a plan, in this order: the geometry (pure), the sizes that follow from
+// it (pure), and the placement steps, which take from the Bump in workspace order.
+// Geometry: H / W / Ho / Wo / M of every convolution, the stem and max-pool maps, featHW.  No offsets.
+static int plan_geometry(cilrs_net* n) {
+    const Arch& A = *n->A;
+    n->cg.resize(A.convs.size());
+    auto set = [&](int ci, int in_h, int in_w) {
+        const ConvT& c = A.convs[ci];
+        ConvG& g = n->cg[ci];
+        g.ci = ci; g.H = in_h; g.W = in_w;
+        g.Ho = out_dim(in_h, c.k, c.stride, c.pad); g.Wo = out_dim(in_w, c.k, c.stride, c.pad);
+        g.M = n->B * g.Ho * g.Wo;
+    };
+    set(0, n->H, n->W);
+    n->H0 = n->cg[0].Ho; n->W0 = n->cg[0].Wo;
+    n->H1 = out_dim(n->H0, 3, 2, 1); n->W1 = out_dim(n->W0, 3, 2, 1);
+    int h = n->H1, w = n->W1;
+    for (const BlockT& blk : A.blocks) {
+        set(blk.conv1, h, w);
+        set(blk.conv2, n->cg[blk.conv1].Ho, n->cg[blk.conv1].Wo);
+        const int oh = n->cg[blk.conv2].Ho, ow = n->cg[blk.conv2].Wo;
+        if (blk.conv3 >= 0) set(blk.conv3, oh, ow);
+        if (blk.down >= 0) {
+            set(blk.down, h, w);
+            CILRS_CHECK(n->cg[blk.down].Ho == oh && n->cg[blk.down].Wo == ow,
+                        "downsample geometry mismatch");
+        }
+        h = oh; w = ow;
+    }
+    n->featHW = h * w;
+    return 0;
+}
+
+// Sizes: the maxima over the network that the shared buffers are sized by (floats / elements)
+struct PlanSizes { size_t gmax = 0, actmax = 0, slabs_max = 0, ksplit_max = 0, need = 0; };
+static PlanSizes plan_sizes(const cilrs_net* n) {
+    const Arch& A = *n->A;
+    const int B = n->B;
+    PlanSizes z;
+    auto up = [](size_t& m, size_t v) { if (v > m) m = v; };
+    // gmax: the gradient buffers hold d(block input), d(block output) and every conv output's gradient
+    up(z.gmax, (size_t)n->cg[0].M * 64);
+    for (const BlockT& blk : A.blocks) {
+        const ConvG& g1 = n->cg[blk.conv1];
+        up(z.gmax, (size_t)B * g1.H * g1.W * A.convs[blk.conv1].cin);
+        for (int ci : {blk.conv1, blk.conv2, blk.conv3, blk.down})
+            if (ci >= 0) up(z.gmax, (size_t)n->cg[ci].M * A.convs[ci].cout);
+    }
+    // actmax: the largest trunk tensor (the max-pool output or a convolution's)
+    up(z.actmax, (size_t)B * n->H1 * n->W1 * 64);
+    z.need = bn_partial_floats(512);
+    for (size_t ci = 0; ci < A.convs.size(); ++ci) {
+        const ConvT& c = A.convs[ci];
+        const ConvG& g = n->cg[ci];
+        const size_t fwd = (size_t)g.M * c.cout, bwd = (size_t)B * g.H * g.W * c.cin;
+        up(z.actmax, fwd);
+        // slabs_max: the weight-gradient slabs of every convolution (the stem reads its channel-padded
+        // image), direct and, where conv_wgrad takes it, Winograd.  The stem's own weight-gradient
+        // kernel (stem_f32.hip) is NOT sized for: backward_stem uses it when its scratch happens to
+        // fit and the direct kernel otherwise.  Sizing for it would move every plan's layout.
+        const int x_cin = ci == 0 ? 4 : c.cin;
+        up(z.slabs_max, wgrad_scratch_floats(
+                            wgrad_args(B, g.H, g.W, x_cin, c.cout, c.k, c.k, c.stride, c.pad, c.cin)));
+        if (x_cin == c.cin && wino_wgrad_on(c))
+            up(z.slabs_max, wino_wgrad_scratch_floats(B, g.H, g.W, c.cin, c.cout));
+        // ksplit_max: split-K scratch, only worthwhile for the small-M layers
+        const size_t big = fwd > bwd ? fwd : bwd;
+        if (big <= (size_t)6 * 1024 * 1024) up(z.ksplit_max, 8 * big);
+        // need: per-tile column partials -- forward (conv output) and backward (the data gradient's
+        // output = this conv's input) reductions ride on the GEMM epilogues (+ kConvMultiMax: a
+        // position-class launch rounds every class up to whole tiles) -- or the BatchNorm kernels' own
+        up(z.need, (size_t)(cdiv(g.M, 64) + kConvMultiMax) * 2 * c.cout);
+        if (ci > 0) up(z.need, (size_t)(cdiv(B * g.H * g.W, 64) + kConvMultiMax) * 2 * c.cin);
+        up(z.need, bn_partial_floats(c.cout));
+    }
+    // the heads' wide linears also use the wgrad slabs
+    up(z.slabs_max, wgrad_scratch_floats(wgrad_args(B, 1, 1, A.feat + 128, 256, 1, 1, 1, 0, A.feat + 128)));
+    return z;
+}
+
+// Placement: the order and sizes of these takes ARE the workspace layout (tests/golden/plan_layout.json).
+// input image, padded stem weights, then y (pre-BN output, kept for backward) / z / stats of every
+// convolution in block order, the max-pool output and its argmax behind the stem's
+static void place_trunk(cilrs_net* n, Bump& bump) {
+    const Arch& A = *n->A;
+    auto place = [&](int ci) {
+        ConvG& g = n->cg[ci];
+        const int cout = A.convs[ci].cout;
+        g.y = bump.take((size_t)g.M * cout);
+        g.z = bump.take((size_t)g.M * cout);
+        g.stats = bump.take(4 * cout);
+    };
+    n->x4 = bump.take((size_t)n->B * n->H * n->W * 4);
+    n->w4 = bump.take((size_t)64 * 49 * 4);
+    place(0);
+    const size_t pooled = (size_t)n->B * n->H1 * n->W1 * 64;
+    n->pool = bump.take(pooled);
+    n->argmax_b = bump.take((pooled + 3) / 4) * sizeof(float);
+    for (const BlockT& blk : A.blocks)
+        for (int ci : {blk.conv1, blk.conv2, blk.conv3, blk.down})
+            if (ci >= 0) place(ci);
+}
+
+static void place_heads(cilrs_net* n, Bump& bump) {
+    const size_t B = n->B, comb = n->A->feat + 128;
+    const int NC = n->A->ncmd;
+    n->combined = bump.take(B * comb);
+    n->s1 = bump.take(B * 128);
+    n->p1 = bump.take(B * 256);
+    n->p2 = bump.take(B * 256);
+    for (int k = 0; k < NC; ++k) {
+        n->h1[k] = bump.take(B * 256);
+        n->h2[k] = bump.take(B * 256);
+    }
+    n->all_out = bump.take(NC * B * 4);
+    n->dcombined = bump.take(B * comb);
+    n->ds1 = bump.take(B * 128);
+    n->dp1 = bump.take(B * 256);
+    n->dp2 = bump.take(B * 256);
+    for (int k = 0; k < NC; ++k) {
+        n->dh1[k] = bump.take(B * 256);
+        n->dh2[k] = bump.take(B * 256);
+    }
+    for (int k = 0; k <= NC; ++k) n->dcomb_part[k] = bump.take(B * comb);
+    n->d_all = bump.take(NC * B * 4);
+    n->speed_in = bump.take(B);
+    n->cmd_b = bump.take(B * 2) * sizeof(float);
+}
+
+static void place_gradients(cilrs_net* n, Bump& bump, const PlanSizes& z) {
+    n->gmax = z.gmax;
+    for (int i = 0; i < kNumG; ++i) n->G[i] = bump.take(z.gmax);
+}
+static void place_scratch(cilrs_net* n, Bump& bump, const PlanSizes& z) {
+    n->bn_partial = bump.take(z.need);
+    n->bn_partial2 = bump.take(z.need);      // (the down-sample branch of a block, built beside conv1)
+    // [0, 3 x 2048) the BatchNorm-backward coefficients; [3 x 2048, 5 x 2048) where the data-gradient-
+    // only backward of a train-mode graph leaves the dgamma / dbeta by-products of its reductions
+    n->bn_coef = bump.take(5 * 2048);
+    n->slabs_floats = z.slabs_max;
+    n->slabs = bump.take(z.slabs_max > 0 ? z.slabs_max : 4);
+    n->ksplit_floats = z.ksplit_max;
+    n->ksplit = bump.take(z.ksplit_max > 0 ? z.ksplit_max : 4);
+    n->status_b = bump.take(64) * sizeof(float);
+}
+
+// (nothing placed: the tables point at the parameter arena and at the stats placed above)
+static void fill_bn_tables(cilrs_net* n) {
+    const Arch& A = *n->A;
+    bn_stats_layout(A, n->bn_stats);
+    n->bn_table.n = (int)A.convs.size();
+    for (size_t ci = 0; ci < A.convs.size(); ++ci) {
+        const BnT& b = A.bns[A.convs[ci].bn];
+        n->bn_table.C[ci] = b.C;
+        n->bn_table.gamma[ci] = (unsigned)b.gamma; n->bn_table.beta[ci] = (unsigned)b.beta;
+        n->bn_table.rm[ci] = (unsigned)b.rm; n->bn_table.rv[ci] = (unsigned)b.rv;
+        n->bn_table.stats[ci] = (unsigned)n->cg[ci].stats;
+    }
+}
+
+// 16-bit inference arenas (every conv but the stem): folded weights, biases, activations
+static void place_infer16(cilrs_net* n, Bump& bump, const PlanSizes& z) {
+    const Arch& A = *n->A;
+    size_t halfs = 0, floats = 0;
+    n->f16_table.n = (int)A.convs.size() - 1;
+    for (size_t ci = 1; ci < A.convs.size(); ++ci) {
+        const ConvT& c = A.convs[ci];
+        const int e = (int)ci - 1;
+        n->f16_table.cout[e] = c.cout;
+        n->f16_table.krow[e] = (unsigned)(c.k * c.k * c.cin);
+        n->f16_table.w[e] = (unsigned)c.w;
+        n->f16_table.stats[e] = (unsigned)n->cg[ci].stats;
+        n->f16_table.w16[e] = (unsigned)halfs;
+        n->f16_table.bias[e] = (unsigned)floats;
+        halfs += (size_t)c.cout * c.k * c.k * c.cin;
+        floats += (size_t)c.cout;
+    }
+    n->f16_w = bump.take((halfs + 1) / 2);
+    n->f16_bias = bump.take(floats);
+    n->stem16_w = bump.take(64 * 224 / 2);
+    n->stem16_b = bump.take(64);
+    n->f16_act_floats = (z.actmax + 1) / 2;                              // largest trunk tensor
+    for (int k = 0; k < 5; ++k) n->f16_act[k] = bump.take(n->f16_act_floats);
+}
+
+// CILRS_PLAN_BF16_TRAIN: 16-bit shadows of the training tensors
+static void place_bf16_shadows(cilrs_net* n, Bump& bump, const PlanSizes& z) {
+    const Arch& A = *n->A;
+    n->w16_all = bump.take((A.arena_floats + 1) / 2);
+    size_t halfs = 0, sl = 0;
+    for (size_t ci = 1; ci < A.convs.size(); ++ci) {
+        const ConvT& c = A.convs[ci];
+        const int e = n->tr_table.n++;
+        n->tr_table.cout[e] = c.cout; n->tr_table.k[e] = c.k; n->tr_table.cin[e] = c.cin;
+        n->tr_table.w[e] = (unsigned)c.w;
+        n->tr_table.wT[e] = (unsigned)halfs;
+        n->tr_table.tile_begin[e + 1] =
+            n->tr_table.tile_begin[e] + c.k * c.k * (c.cout / 32) * (c.cin / 32);
+        n->wT16_off[ci] = halfs;
+        halfs += ((size_t)c.cout * c.k * c.k * c.cin + 7) / 8 * 8;
+        n->z16[ci] = bump.take(((size_t)n->cg[ci].M * c.cout + 1) / 2);
+        const size_t f = wgrad_f16_scratch_floats(wgrad16_args(n, c, n->cg[ci]));
+        if (f > sl) sl = f;
+    }
+    n->wT16 = bump.take((halfs + 1) / 2);
+    n->pool16 = bump.take(((size_t)n->B * n->H1 * n->W1 * 64 + 1) / 2);
+    for (int i = 0; i < kNumG; ++i) n->G16[i] = bump.take((z.gmax + 1) / 2);
+    n->slabs16_floats = sl;
+    n->slabs16 = bump.take(sl > 0 ? sl : 4);
+}
+
+// Winograd filter images of the fp32 train plan's layers (cilrs_net::wino_slot).  wino_prepare sets
+// the kernels' attributes here, at plan build: outside any capture.
+static int place_wino(cilrs_net* n, Bump& bump) {
+    const Arch& A = *n->A;
+    WinoWeightTable& t = n->wino_table;
+    static const int wino_env = env_int("CILRS_WINO", 1);
+    if (n->bf16_train || !wino_env) return 0;
+    size_t floats = 0;
+    for (size_t ci = 1; ci < A.convs.size(); ++ci) {
+        const ConvT& c = A.convs[ci];
+        const ConvG& g = n->cg[ci];
+        if (!wino_supported(c.cin, c.cout, c.k, c.stride, c.pad) ||
+            !wino_supported(c.cout, c.cin, c.k, c.stride, c.pad) || c.cin % 32 != 0 ||
+            c.cin > 256 || c.cout > 256)
+            continue;
+        // one 64-tile x 64-channel block per CU: below ~half a chip of blocks the
+        // implicit GEMM (split-K, smaller tiles) wins (tools/wino_bench.py)
+        const int blocks = wino_groups(n->B, g.H, g.W) * (std::min(c.cin, c.cout) / 64);
+        if (wino_env == 1 && blocks < 128) continue;
+        const int e = t.n++;
+        t.K[e] = c.cout; t.C[e] = c.cin; t.w[e] = (unsigned)c.w;
+        t.u[e] = (unsigned)floats; floats += wino_weight_floats(c.cout, c.cin);
+        t.ud[e] = (unsigned)floats; floats += wino_weight_floats(c.cout, c.cin);
+        t.blk_begin[e + 1] = t.blk_begin[e] + (c.cout / 8) * (c.cin / 32);
+        n->wino_slot[ci] = e;
+    }
+    CILRS_CHECK(floats < (1ull << 32), "Winograd filter images exceed 32-bit offsets");
+    if (t.n == 0) return 0;
+    n->wino_base = bump.take(floats);
+    return wino_prepare();
+}
+
+// the persistent single-frame launch (infer_b1.hip): stage table, barrier counters, stamps, slabs
+static void place_b1(cilrs_net* n, Bump& bump) {
+    const Arch& A = *n->A;
+    n->b1_table = bump.take(kB1MaxStages * sizeof(B1Stage) / sizeof(float));
+    n->b1_sync = bump.take(kB1SyncInts);
+    n->b1_cmd = bump.take(16);
+    n->b1_stamps = bump.take(2 * (10 * (kB1MaxStages + 1) + kB1MaxStages * 512));
+    // split-K partial tiles: up to 4 slices of the largest [16-row tiles][Cout] output, twice
+    // (a stage may hold two convolutions)
+    size_t big = 0;
+    for (size_t ci = 1; ci < A.convs.size(); ++ci) {
+        const size_t o = (size_t)cdiv(n->cg[ci].M, 16) * 16 * A.convs[ci].cout;
+        if (o > big) big = o;
+    }
+    n->b1_slab_floats = 2 * 4 * big;
+    n->b1_slabs = bump.take(n->b1_slab_floats);
+}
+
 int cilrs_net_create_ex(int variant, int batch, int height, int width, unsigned flags,
                         cilrs_net** out) {
     CILRS_CHECK(out != nullptr, "cilrs_net_create: out is NULL");
@@ -938,277 +1213,30 @@ int cilrs_net_create_ex(int variant, int batch, int height, int width, unsigned 
     CILRS_CHECK(batch >= 1 && height >= 17 && width >= 17, "cilrs_net_create: bad geometry %d %d %d",
                 batch, height, width);
     const Arch& A = arch(variant);
-    const bool trainable = true;
-    cilrs_net* n = new cilrs_net();
+    CILRS_CHECK((int)A.convs.size() <= kMaxConvs, "too many convolutions for the BN tables");
+    std::unique_ptr<cilrs_net> n(new cilrs_net());      // (every failure below frees it)
     n->A = &A;
     n->B = batch; n->H = height; n->W = width;
-    n->cg.resize(A.convs.size());
+    n->bf16_train = (flags & 1u) != 0;
+    if (plan_geometry(n.get())) return 1;
+    const PlanSizes z = plan_sizes(n.get());
     Bump bump;
-    const int B = batch;
-    n->x4 = bump.take((size_t)B * height * width * 4);
-    n->w4 = bump.take((size_t)64 * 49 * 4);
-
-    auto out_dim = [](int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; };
-    // stem
-    {
-        ConvG& g = n->cg[0];
-        g.H = height; g.W = width;
-        g.Ho = out_dim(height, 7, 2, 3); g.Wo = out_dim(width, 7, 2, 3);
-        g.M = B * g.Ho * g.Wo;
-        g.y = bump.take(trainable ? (size_t)g.M * 64 : 4);
-        g.z = bump.take((size_t)g.M * 64);
-        g.stats = bump.take(4 * 64);
-        n->H0 = g.Ho; n->W0 = g.Wo;
-        n->H1 = out_dim(g.Ho, 3, 2, 1); n->W1 = out_dim(g.Wo, 3, 2, 1);
-    }
-    size_t gmax = (size_t)n->cg[0].M * 64;
-    size_t actmax = (size_t)B * n->H1 * n->W1 * 64;       // largest trunk tensor (elements)
-    n->pool = bump.take((size_t)B * n->H1 * n->W1 * 64);
-    const size_t argmax_floats = ((size_t)B * n->H1 * n->W1 * 64 + 3) / 4;
-    n->argmax_b = bump.take(argmax_floats) * sizeof(float);
-    int h = n->H1, w = n->W1;
-    size_t slabs_max = 0, ksplit_max = 0;
-    auto track = [&](const ConvT& c, const ConvG& g, int x_cin) {
-        if (trainable) {
-            WgradArgs wa;
-            memset(&wa, 0, sizeof(wa));
-            wa.N = B; wa.H = g.H; wa.W = g.W; wa.Cin = x_cin; wa.Ho = g.Ho; wa.Wo = g.Wo;
-            wa.Cout = c.cout; wa.KH = wa.KW = c.k; wa.stride = c.stride; wa.pad = c.pad;
-            const size_t sf = wgrad_scratch_floats(wa);
-            if (sf > slabs_max) slabs_max = sf;
-            if (x_cin == c.cin && wino_wgrad_on(c)) {
-                const size_t sw = wino_wgrad_scratch_floats(B, g.H, g.W, c.cin, c.cout);
-                if (sw > slabs_max) slabs_max = sw;
-            }
-        }
-        // split-K scratch: only worthwhile for the small-M layers
-        const size_t fwd = (size_t)g.M * c.cout, bwd = (size_t)B * g.H * g.W * c.cin;
-        const size_t big = fwd > bwd ? fwd : bwd;
-        if (big <= (size_t)6 * 1024 * 1024 && 8 * big > ksplit_max) ksplit_max = 8 * big;
-        if (fwd > actmax) actmax = fwd;
-    };
-    // geometry + activation buffers of one convolution (y: pre-BN output, kept for backward only)
-    auto place = [&](int ci, int in_h, int in_w) {
-        const ConvT& c = A.convs[ci];
-        ConvG& g = n->cg[ci];
-        g.H = in_h; g.W = in_w;
-        g.Ho = out_dim(in_h, c.k, c.stride, c.pad); g.Wo = out_dim(in_w, c.k, c.stride, c.pad);
-        g.M = B * g.Ho * g.Wo;
-        g.y = bump.take(trainable ? (size_t)g.M * c.cout : 4);
-        g.z = bump.take((size_t)g.M * c.cout);
-        g.stats = bump.take(4 * c.cout);
-        track(c, g, c.cin);
-    };
-    track(A.convs[0], n->cg[0], 4);
-    for (const BlockT& blk : A.blocks) {
-        place(blk.conv1, h, w);
-        const ConvG& g1 = n->cg[blk.conv1];
-        place(blk.conv2, g1.Ho, g1.Wo);
-        const ConvG& g2 = n->cg[blk.conv2];
-        int oh = g2.Ho, ow = g2.Wo;
-        if (blk.conv3 >= 0) place(blk.conv3, g2.Ho, g2.Wo);
-        if (blk.down >= 0) {
-            place(blk.down, h, w);
-            CILRS_CHECK(n->cg[blk.down].Ho == oh && n->cg[blk.down].Wo == ow,
-                        "downsample geometry mismatch");
-        }
-        const ConvT& c1 = A.convs[blk.conv1];
-        const size_t act = (size_t)B * h * w * c1.cin;
-        if (act > gmax) gmax = act;
-        // gradient buffers hold d(block input), d(block output) and every conv output's gradient
-        for (int ci : {blk.conv1, blk.conv2, blk.conv3, blk.down}) {
-            if (ci < 0) continue;
-            const size_t o = (size_t)n->cg[ci].M * A.convs[ci].cout;
-            if (o > gmax) gmax = o;
-        }
-        h = oh; w = ow;
-    }
-    n->featHW = h * w;
-    const int feat = A.feat, comb = A.feat + 128;
-    // heads
-    n->combined = bump.take((size_t)B * comb);
-    n->s1 = bump.take((size_t)B * 128);
-    n->p1 = bump.take((size_t)B * 256);
-    n->p2 = bump.take((size_t)B * 256);
-    const int NC = A.ncmd;
-    for (int k = 0; k < NC; ++k) {
-        n->h1[k] = bump.take((size_t)B * 256);
-        n->h2[k] = bump.take((size_t)B * 256);
-    }
-    n->all_out = bump.take((size_t)NC * B * 4);
-    n->dcombined = bump.take(trainable ? (size_t)B * comb : 4);
-    n->ds1 = bump.take(trainable ? (size_t)B * 128 : 4);
-    n->dp1 = bump.take(trainable ? (size_t)B * 256 : 4);
-    n->dp2 = bump.take(trainable ? (size_t)B * 256 : 4);
-    for (int k = 0; k < NC; ++k) {
-        n->dh1[k] = bump.take(trainable ? (size_t)B * 256 : 4);
-        n->dh2[k] = bump.take(trainable ? (size_t)B * 256 : 4);
-    }
-    for (int k = 0; k <= NC; ++k) n->dcomb_part[k] = bump.take(trainable ? (size_t)B * comb : 4);
-    n->d_all = bump.take((size_t)NC * B * 4);
-    n->speed_in = bump.take((size_t)B);
-    n->cmd_b = bump.take((size_t)B * 2) * sizeof(float);
-    // the heads' wide linears also use the wgrad slabs
-    if (trainable) {
-        WgradArgs wa;
-        memset(&wa, 0, sizeof(wa));
-        wa.N = B; wa.H = wa.W = wa.Ho = wa.Wo = 1; wa.Cin = comb; wa.Cout = 256;
-        wa.KH = wa.KW = 1; wa.stride = 1;
-        const size_t sf = wgrad_scratch_floats(wa);
-        if (sf > slabs_max) slabs_max = sf;
-    }
-    (void)feat;
-    if (!trainable) gmax = 4;
-    n->gmax = gmax;
-    for (int i = 0; i < kNumG; ++i) n->G[i] = bump.take(gmax);
-    {
-        size_t need = bn_partial_floats(512);
-        if (trainable)
-            for (size_t ci = 0; ci < A.convs.size(); ++ci) {
-                // per-tile column partials: forward (conv output) and backward (the data
-                // gradient's output = this conv's input) reductions ride on the GEMM epilogues
-                // (+ kConvMultiMax: a position-class launch rounds every class up to whole tiles)
-                const size_t t = (size_t)(cdiv(n->cg[ci].M, 64) + kConvMultiMax) * 2 * A.convs[ci].cout;
-                if (t > need) need = t;
-                const size_t tb = (size_t)(cdiv(B * n->cg[ci].H * n->cg[ci].W, 64) + kConvMultiMax) * 2 *
-                                  A.convs[ci].cin;
-                if (ci > 0 && tb > need) need = tb;
-                if (bn_partial_floats(A.convs[ci].cout) > need)
-                    need = bn_partial_floats(A.convs[ci].cout);
-            }
-        n->bn_partial = bump.take(need);
-        n->bn_partial2 = bump.take(need);      // (the down-sample branch of a block, built beside conv1)
-    }
-    // [0, 3 x 2048) the BatchNorm-backward coefficients; [3 x 2048, 5 x 2048) where the data-gradient-
-    // only backward of a train-mode graph leaves the dgamma / dbeta by-products of its reductions
-    n->bn_coef = bump.take(5 * 2048);
-    n->slabs_floats = slabs_max;
-    n->slabs = bump.take(slabs_max > 0 ? slabs_max : 4);
-    n->ksplit_floats = ksplit_max;
-    n->ksplit = bump.take(ksplit_max > 0 ? ksplit_max : 4);
-    n->status_b = bump.take(64) * sizeof(float);
-    CILRS_CHECK((int)A.convs.size() <= kMaxConvs, "too many convolutions for the BN tables");
-    bn_stats_layout(A, n->bn_stats);
-    n->bn_table.n = (int)A.convs.size();
-    for (size_t ci = 0; ci < A.convs.size(); ++ci) {
-        const BnT& b = A.bns[A.convs[ci].bn];
-        n->bn_table.C[ci] = b.C;
-        n->bn_table.gamma[ci] = (unsigned)b.gamma; n->bn_table.beta[ci] = (unsigned)b.beta;
-        n->bn_table.rm[ci] = (unsigned)b.rm; n->bn_table.rv[ci] = (unsigned)b.rv;
-        n->bn_table.stats[ci] = (unsigned)n->cg[ci].stats;
-    }
-    {   // 16-bit inference arenas (every conv but the stem): folded weights, biases, activations
-        size_t halfs = 0, floats = 0;
-        n->f16_table.n = (int)A.convs.size() - 1;
-        for (size_t ci = 1; ci < A.convs.size(); ++ci) {
-            const ConvT& c = A.convs[ci];
-            const int e = (int)ci - 1;
-            n->f16_table.cout[e] = c.cout;
-            n->f16_table.krow[e] = (unsigned)(c.k * c.k * c.cin);
-            n->f16_table.w[e] = (unsigned)c.w;
-            n->f16_table.stats[e] = (unsigned)n->cg[ci].stats;
-            n->f16_table.w16[e] = (unsigned)halfs;
-            n->f16_table.bias[e] = (unsigned)floats;
-            halfs += (size_t)c.cout * c.k * c.k * c.cin;
-            floats += (size_t)c.cout;
-        }
-        n->f16_w = bump.take((halfs + 1) / 2);
-        n->f16_bias = bump.take(floats);
-        n->stem16_w = bump.take(64 * 224 / 2);
-        n->stem16_b = bump.take(64);
-        n->f16_act_floats = (actmax + 1) / 2;                              // largest trunk tensor
-        for (int k = 0; k < 5; ++k) n->f16_act[k] = bump.take(n->f16_act_floats);
-    }
-    if (flags & 1u) {        // CILRS_PLAN_BF16_TRAIN: 16-bit shadows of the training tensors
-        n->bf16_train = true;
-        n->w16_all = bump.take((A.arena_floats + 1) / 2);
-        size_t halfs = 0, sl = 0;
-        n->tr_table.n = 0;
-        for (size_t ci = 1; ci < A.convs.size(); ++ci) {
-            const ConvT& c = A.convs[ci];
-            const int e = n->tr_table.n++;
-            n->tr_table.cout[e] = c.cout; n->tr_table.k[e] = c.k; n->tr_table.cin[e] = c.cin;
-            n->tr_table.w[e] = (unsigned)c.w;
-            n->tr_table.wT[e] = (unsigned)halfs;
-            n->tr_table.tile_begin[e] = e == 0 ? 0 : n->tr_table.tile_begin[e];
-            n->tr_table.tile_begin[e + 1] =
-                n->tr_table.tile_begin[e] + c.k * c.k * (c.cout / 32) * (c.cin / 32);
-            n->wT16_off[ci] = halfs;
-            halfs += ((size_t)c.cout * c.k * c.k * c.cin + 7) / 8 * 8;
-            n->z16[ci] = bump.take(((size_t)n->cg[ci].M * c.cout + 1) / 2);
-            const size_t f = wgrad_f16_scratch_floats(wgrad16_args(n, c, n->cg[ci]));
-            if (f > sl) sl = f;
-        }
-        n->wT16 = bump.take((halfs + 1) / 2);
-        n->pool16 = bump.take(((size_t)B * n->H1 * n->W1 * 64 + 1) / 2);
-        for (int i = 0; i < kNumG; ++i) n->G16[i] = bump.take((gmax + 1) / 2);
-        n->slabs16_floats = sl;
-        n->slabs16 = bump.take(sl > 0 ? sl : 4);
-    }
-    n->wino_table.n = 0;
-    n->wino_table.blk_begin[0] = 0;
-    {
-        static const int wino_env = getenv("CILRS_WINO") ? atoi(getenv("CILRS_WINO")) : 1;
-        if (trainable && !(flags & 1u) && wino_env) {
-            size_t floats = 0;
-            for (size_t ci = 1; ci < A.convs.size(); ++ci) {
-                const ConvT& c = A.convs[ci];
-                const ConvG& g = n->cg[ci];
-                if (!wino_supported(c.cin, c.cout, c.k, c.stride, c.pad) ||
-                    !wino_supported(c.cout, c.cin, c.k, c.stride, c.pad) || c.cin % 32 != 0 ||
-                    c.cin > 256 || c.cout > 256)
-                    continue;
-                // one 64-tile x 64-channel block per CU: below ~half a chip of blocks the
-                // implicit GEMM (split-K, smaller tiles) wins (tools/wino_bench.py)
-                const int blocks = wino_groups(B, g.H, g.W) * (std::min(c.cin, c.cout) / 64);
-                if (wino_env == 1 && blocks < 128) continue;
-                WinoWeightTable& t = n->wino_table;
-                const int e = t.n++;
-                t.K[e] = c.cout; t.C[e] = c.cin; t.w[e] = (unsigned)c.w;
-                t.u[e] = (unsigned)floats; floats += wino_weight_floats(c.cout, c.cin);
-                t.ud[e] = (unsigned)floats; floats += wino_weight_floats(c.cout, c.cin);
-                t.blk_begin[e + 1] = t.blk_begin[e] + (c.cout / 8) * (c.cin / 32);
-                n->wino_on[ci] = true;
-            }
-            CILRS_CHECK(floats < (1ull << 32), "Winograd filter images exceed 32-bit offsets");
-            if (n->wino_table.n) {
-                n->wino_base = bump.take(floats);
-                if (wino_prepare()) return 1;
-            }
-        }
-    }
-    if (batch == 1 && code_trunk(variant) == 0 && A.ncmd == 4) {     // (the persistent kernel is built for the reference's 4 commands)
-        n->b1_table = bump.take(kB1MaxStages * sizeof(B1Stage) / sizeof(float));
-        n->b1_sync = bump.take(kB1SyncInts);
-        n->b1_cmd = bump.take(16);
-        n->b1_stamps = bump.take(2 * (10 * (kB1MaxStages + 1) + kB1MaxStages * 512));
-        // split-K partial tiles: up to 4 slices of the largest [16-row tiles][Cout] output, twice
-        // (a stage may hold two convolutions)
-        size_t big = 0;
-        for (size_t ci = 1; ci < A.convs.size(); ++ci) {
-            const size_t o = (size_t)cdiv(n->cg[ci].M, 16) * 16 * A.convs[ci].cout;
-            if (o > big) big = o;
-        }
-        n->b1_slab_floats = 2 * 4 * big;
-        n->b1_slabs = bump.take(n->b1_slab_floats);
-    }
+    place_trunk(n.get(), bump);
+    place_heads(n.get(), bump);
+    place_gradients(n.get(), bump, z);
+    place_scratch(n.get(), bump, z);
+    fill_bn_tables(n.get());
+    place_infer16(n.get(), bump, z);
+    if (n->bf16_train) place_bf16_shadows(n.get(), bump, z);
+    if (place_wino(n.get(), bump)) return 1;
+    // (the persistent kernel is built for the reference's trunk and 4 commands)
+    if (batch == 1 && A.variant == 0 && A.ncmd == 4) place_b1(n.get(), bump);
     n->ws_bytes = bump.off * sizeof(float);
-    *out = n;
+    *out = n.release();
     return 0;
 }
 
-void cilrs_net_destroy(cilrs_net* net) {
-    if (net && net->streams_ready) {
-        (void)hipStreamDestroy(net->side[0]);
-        for (int i = 0; i < kNumG; ++i) (void)hipEventDestroy(net->gbuf_ev[i]);
-        (void)hipEventDestroy(net->fork_ev);
-        (void)hipEventDestroy(net->wprep_ev);
-        (void)hipEventDestroy(net->branch_ev);
-        (void)hipEventDestroy(net->heads_ev);
-    }
-    if (net && net->graph_exec) (void)hipGraphExecDestroy(net->graph_exec);
-    delete net;
-}
+void cilrs_net_destroy(cilrs_net* net) { delete net; }
 size_t cilrs_net_workspace_bytes(const cilrs_net* net) { return net ? net->ws_bytes : 0; }
 size_t cilrs_net_status_offset(const cilrs_net* net) { return net ? net->status_b : 0; }
 
@@ -1373,11 +1401,9 @@ static WinoWeightTable wino_subtable(const cilrs_net* net, int g0, int g1) {
     const WinoWeightTable& t = net->wino_table;
     WinoWeightTable o;
     memset(&o, 0, sizeof(o));
-    for (int e = 0; e < t.n; ++e) {
-        int grp = -1;
-        for (const ConvT& c : A.convs)
-            if ((unsigned)c.w == t.w[e]) grp = c.group;
-        if (grp < g0 || grp >= g1) continue;
+    for (size_t ci = 0; ci < A.convs.size(); ++ci) {
+        const int e = net->wino_slot[ci];
+        if (e < 0 || A.convs[ci].group < g0 || A.convs[ci].group >= g1) continue;
         const int k = o.n++;
         o.K[k] = t.K[e]; o.C[k] = t.C[e]; o.w[k] = t.w[e]; o.u[k] = t.u[e]; o.ud[k] = t.ud[e];
         o.blk_begin[k + 1] = o.blk_begin[k] + (t.blk_begin[e + 1] - t.blk_begin[e]);
@@ -1537,7 +1563,7 @@ static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train,
             //  cases without split-K, so that the plan, hence the summation order, of this
             //  convolution does not depend on whether the streams overlap)
             net->side_branch = aside ? 1 : 2;
-            int rc = bf16t ? conv_fwd16(net, cd, gd, blk.down, cur16, ws, st, &nbd)
+            int rc = bf16t ? conv_fwd16(net, cd, gd, cur16, ws, st, &nbd)
                            : conv_fwd(net, cd, gd, cur, cd.cin, P + cd.w, ws + gd.y, ws, st, &nbd);
             net->side_branch = 0;
             if (rc) return 1;
@@ -1556,7 +1582,7 @@ static int trunk_fwd_graph(cilrs_net* net, const cilrs_buffers* bufs, int train,
             const ConvG& g = net->cg[chain[i]];
             nb = 0;
             if (bf16t) {
-                if (conv_fwd16(net, c, g, chain[i], x16, ws, s, &nb)) return 1;
+                if (conv_fwd16(net, c, g, x16, ws, s, &nb)) return 1;
             } else {
                 if (conv_fwd(net, c, g, x, c.cin, P + c.w, ws + g.y, ws, s, &nb)) return 1;
             }
@@ -1623,8 +1649,8 @@ static int trunk_fwd_eval32(cilrs_net* net, const cilrs_buffers* bufs, hipStream
         a.addend = addend; a.relu = relu; a.relu_post = relu_post;
         a.N = B; a.H = g.H; a.W = g.W; a.Cin = c.cin; a.Ho = g.Ho; a.Wo = g.Wo;
         a.Cout = c.cout; a.K = c.k; a.stride = c.stride; a.pad = c.pad;
-        RUN(net, std::string("conv_fwd.") + kGroupName[c.group],
-            2.0 * g.M * c.cout * c.k * c.k * c.cin, 0.0, s, launch_conv_small(a, s));
+        RUN(net, std::string("conv_fwd.") + kGroupName[c.group], conv_flops(c, g), 0.0, s,
+            launch_conv_small(a, s));
         return 0;
     };
     const float* cur = ws + net->pool;
@@ -1694,10 +1720,8 @@ static int trunk_fwd_eval16(cilrs_net* net, const cilrs_buffers* bufs, int half,
         a.residual = residual; a.y = y; a.bf16 = bf16;
         a.N = B; a.H = g.H; a.W = g.W; a.Cin = c.cin; a.Ho = g.Ho; a.Wo = g.Wo;
         a.Cout = c.cout; a.K = c.k; a.stride = c.stride; a.pad = c.pad; a.relu = relu;
-        const double bytes = 2.0 * ((double)B * g.H * g.W * c.cin + (double)g.M * c.cout *
-                                    (residual ? 2.0 : 1.0) + (double)c.cout * c.k * c.k * c.cin);
-        RUN(net, std::string("conv_fwd.") + kGroupName[c.group],
-            2.0 * g.M * c.cout * c.k * c.k * c.cin, bytes, s, launch_conv_f16(a, s));
+        RUN(net, std::string("conv_fwd.") + kGroupName[c.group], conv_flops(c, g),
+            conv_bytes(net, c, g, 2, 2, 2, false, residual ? 2.0 : 1.0), s, launch_conv_f16(a, s));
         return 0;
     };
     for (const BlockT& blk : A.blocks) {
@@ -2389,7 +2413,7 @@ static int b1_launch(cilrs_net* net, const cilrs_buffers* bufs, const uint8_t* f
     a.sync = reinterpret_cast<int*>(ws + net->b1_sync);
     a.status = status_words(net, bufs);
     // CILRS_B1_STAMPS=1: block 0 records its clock at every stage (cilrs_net_b1_stage_us)
-    static const int stamps_on = getenv("CILRS_B1_STAMPS") ? atoi(getenv("CILRS_B1_STAMPS")) : 0;
+    static const int stamps_on = env_int("CILRS_B1_STAMPS", 0);
     a.stamps = stamps_on ? reinterpret_cast<long long*>(ws + net->b1_stamps) : nullptr;
     for (int i = 0; i < 3; ++i) { a.mean[i] = kImageMean[i]; a.stdv[i] = kImageStd[i]; }
     RUN(net, "infer_b1", 2.0 * 2.798e9 / 2.0, 0.0, s, launch_infer_b1(a, net->b1_blocks, s));
@@ -2535,7 +2559,7 @@ static int forward_u8_graph(cilrs_net* net, const cilrs_buffers* bufs, const uin
     if (fwd_begin(net, bufs, s)) return 1;
     const void* key[8] = {bufs->params, bufs->bn_running, bufs->workspace, frames, speed, command,
                           controls, pred_speed};
-    bool same = net->graph_exec != nullptr && net->graph_half == half &&
+    bool same = net->graph_exec.h != nullptr && net->graph_half == half &&
                 net->graph_wkey == net->weights_key;
     for (int i = 0; i < 8 && same; ++i) same = key[i] == net->graph_key[i];
     if (!same) {
@@ -2560,8 +2584,8 @@ static int forward_u8_graph(cilrs_net* net, const cilrs_buffers* bufs, const uin
         CILRS_CHECK(rc == 0, "forward_u8_graph: capture failed: %s", last_error());
         CILRS_CHECK(e == hipSuccess && graph != nullptr, "hipStreamEndCapture failed: %s",
                     hipGetErrorString(e));
-        if (net->graph_exec) { (void)hipGraphExecDestroy(net->graph_exec); net->graph_exec = nullptr; }
-        const hipError_t e2 = hipGraphInstantiate(&net->graph_exec, graph, nullptr, nullptr, 0);
+        if (net->graph_exec) { (void)hipGraphExecDestroy(net->graph_exec); net->graph_exec.h = nullptr; }
+        const hipError_t e2 = hipGraphInstantiate(&net->graph_exec.h, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
         CILRS_CHECK(e2 == hipSuccess, "hipGraphInstantiate failed: %s", hipGetErrorString(e2));
         for (int i = 0; i < 8; ++i) net->graph_key[i] = key[i];
@@ -3032,7 +3056,7 @@ struct BwdPass {
         const ConvG& g = net->cg[ci];
         if (lean_bn) { bn_of = nullptr; nbp = nullptr; }
         if (bf16t)
-            return conv_dgrad16(net, c, g, ci, Gh(gi), out32 ? nullptr : Gh(go),
+            return conv_dgrad16(net, c, g, Gh(gi), out32 ? nullptr : Gh(go),
                                 out32 ? Gf(go) : nullptr, gadd >= 0 ? Gh(gadd) : nullptr, ws, s,
                                 bn_of, nbp);
         return conv_dgrad(net, c, g, Gf(gi), P + c.w, Gf(go), gadd >= 0 ? Gf(gadd) : nullptr, ws, s,
@@ -3763,13 +3787,8 @@ int cilrs_net_profile_reset(cilrs_net* net) {
 static ConvArgs make_conv_fwd(const float* x, const float* w, float* y, int N, int H, int W, int Cin,
                               int Cout, int KH, int KW, int stride, int pad, int force_cfg,
                               int force_splitk, float* scratch, size_t scratch_floats) {
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
+    ConvArgs a = conv_args(N, H, W, Cin, Cout, KH, KW, stride, pad);
     a.x = x; a.w = w; a.y = y;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin;
-    a.Ho = (H + 2 * pad - KH) / stride + 1; a.Wo = (W + 2 * pad - KW) / stride + 1; a.Cout = Cout;
-    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
-    a.x_ld = Cin; a.y_ld = Cout; a.w_mode = 0; a.w_cin = Cin;
     a.scratch = scratch; a.scratch_floats = scratch_floats;
     a.force_cfg = force_cfg; a.force_splitk = force_splitk;
     return a;
@@ -3779,13 +3798,8 @@ static DgradArgs make_conv_dgrad(const float* dy, const float* w, float* dx, con
                                  int N, int H, int W, int Cin, int Cout, int K, int stride, int pad,
                                  int force_cfg, int force_splitk, float* scratch,
                                  size_t scratch_floats) {
-    DgradArgs a;
-    memset(&a, 0, sizeof(a));
+    DgradArgs a = dgrad_args(N, H, W, Cin, Cout, K, stride, pad);
     a.dy = dy; a.w = w; a.dx = dx; a.addend = addend;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin;
-    a.Ho = (H + 2 * pad - K) / stride + 1; a.Wo = (W + 2 * pad - K) / stride + 1;
-    a.Cout = Cout; a.K = K; a.stride = stride; a.pad = pad;
-    a.dy_ld = Cout; a.dx_ld = Cin;
     a.scratch = scratch; a.scratch_floats = scratch_floats;
     a.force_cfg = force_cfg; a.force_splitk = force_splitk;
     return a;
@@ -3883,7 +3897,7 @@ int cilrs_net_conv_classes(const cilrs_net* net, int conv, int* fwd, int* dgrad)
     const ConvG& g = net->cg[conv];
     // the stem has kernels of its own; a Winograd layer never reaches the implicit GEMM; the
     // 16-bit train mode runs other kernels
-    const bool igemm = conv > 0 && !net->wino_on[conv] && !net->bf16_train;
+    const bool igemm = conv > 0 && net->wino_slot[conv] < 0 && !net->bf16_train;
     const bool yes_f = igemm && conv_igemm_takes_classes(net->B, g.H, g.W, c.cin, c.cout, c.k, c.stride,
                                                          c.pad, false, net->ksplit_floats);
     const bool yes_d = igemm && conv_igemm_takes_classes(net->B, g.H, g.W, c.cin, c.cout, c.k, c.stride,
@@ -3893,31 +3907,17 @@ int cilrs_net_conv_classes(const cilrs_net* net, int conv, int* fwd, int* dgrad)
     return 0;
 }
 
-static WgradArgs make_wgrad(const float* x, const float* dy, float* dw, float* scratch, int N,
-                            int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
-                            int Cin_dst) {
-    WgradArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.dy = dy; a.dw = dw; a.slabs = scratch;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin;
-    a.Ho = (H + 2 * pad - KH) / stride + 1; a.Wo = (W + 2 * pad - KW) / stride + 1; a.Cout = Cout;
-    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
-    a.x_ld = Cin; a.dy_ld = Cout; a.Cin_dst = Cin_dst; a.accumulate = 0;
-    return a;
-}
-
 size_t cilrs_conv2d_wgrad_scratch_floats(int N, int H, int W, int Cin, int Cout, int KH, int KW,
                                          int stride, int pad) {
-    return wgrad_scratch_floats(
-        make_wgrad(nullptr, nullptr, nullptr, nullptr, N, H, W, Cin, Cout, KH, KW, stride, pad, Cin));
+    return wgrad_scratch_floats(wgrad_args(N, H, W, Cin, Cout, KH, KW, stride, pad, Cin));
 }
 
 int cilrs_conv2d_wgrad(const float* x, const float* dy, float* dw, float* scratch, int N, int H,
                        int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                        int Cin_dst, void* stream) {
-    return launch_conv_wgrad(
-        make_wgrad(x, dy, dw, scratch, N, H, W, Cin, Cout, KH, KW, stride, pad, Cin_dst),
-        reinterpret_cast<hipStream_t>(stream));
+    WgradArgs a = wgrad_args(N, H, W, Cin, Cout, KH, KW, stride, pad, Cin_dst);
+    a.x = x; a.dy = dy; a.dw = dw; a.slabs = scratch;
+    return launch_conv_wgrad(a, reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- the same three convolution operators on the 16-bit matrix pipe (operands rounded to bf16 /
