@@ -178,6 +178,10 @@ SIGNATURES = {
     "cilrs_optim_scratch_bytes": (sz, [vp]),
     "cilrs_optim_step": (i32, [i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, f64, f64, f64,
                                f64, f64, vp, f32, vp, vp, vp]),
+    "cilrs_sam_chunk_floats": (i32, []),
+    "cilrs_sam_scratch_bytes": (sz, [sz]),
+    "cilrs_sam_perturb": (i32, [vp, vp, vp, sz, f64, i32, vp, vp, vp]),
+    "cilrs_sam_restore": (i32, [vp, vp, sz, vp]),
     "cilrs_augment_u8": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
     "cilrs_batch_assemble": (i32, [vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,
                                    vp]),

@@ -392,6 +392,21 @@ class Engine:
         if keep:
             self._ft_expect = self.weights_epoch
 
+    def snapshot_bn(self, bn, nbt):
+        """Copy the running statistics and num_batches_tracked into `bn` / `nbt` (same shapes)."""
+        with torch.no_grad():
+            bn.copy_(self.bn)
+            nbt.copy_(self.nbt)
+
+    def put_back_bn(self, bn, nbt):
+        """Inverse of snapshot_bn, bit for bit.  The statistics go back through the library's copy
+        kernel, not torch's copy_: that would bump the version counters poll_versions watches, and
+        with them the key of a frozen prefix's cached state, on every step."""
+        L.check(L.lib().cilrs_sam_restore(L.ptr(self.bn), L.ptr(bn), self.bn.numel(),
+                                          self._stream()))
+        with torch.no_grad():
+            self.nbt.copy_(nbt)                   # (not among the polled tensors)
+
     def run_forward_ft(self, image, speed, command, e, g, dropout_p, seed):
         """Train-mode forward with the first `g` trunk groups taking no gradient and the first
         `e` (0 or g) of them in eval mode (cilrs_net_forward_ft); (0, 0) is run_forward."""

@@ -60,6 +60,14 @@ class TrainConfig:
     lr_schedule: str = "step"                          # "step" (StepLR) | "cosine"
     lr_epochs: int = 20                                # cosine: epochs down to lr_min
     lr_min: float = 0.0
+    # sharpness-aware minimisation (include/cilrs_hip.h "sharpness-aware minimisation"): the step's
+    # gradient is taken at w + e(w), |e| = sam_rho along the gradient at w (sam_adaptive: ASAM, the
+    # scale-invariant form), and applied at w -- two forward / backward passes per step.  0 = off,
+    # and then no launch, buffer or checkpoint differs.  sam_every: SAM runs on the optimizer steps
+    # t (1-based) with (t - 1) % sam_every == 0, the plain step on the others.
+    sam_rho: float = 0.0
+    sam_adaptive: bool = False
+    sam_every: int = 1
 
 
 GROUP_NAMES = ("stem", "layer1", "layer2", "layer3", "layer4", "heads")
@@ -118,6 +126,18 @@ def check_optim_config(cfg: TrainConfig):
             raise ValueError(f"lr_epochs must be an integer >= 1, got {cfg.lr_epochs!r}")
         if not (math.isfinite(cfg.lr_min) and 0.0 <= cfg.lr_min <= cfg.lr):
             raise ValueError(f"lr_min must lie in [0, lr], got {cfg.lr_min!r}")
+    check_sam_rho(cfg.sam_rho)
+    if not (isinstance(cfg.sam_every, int) and not isinstance(cfg.sam_every, bool)
+            and cfg.sam_every >= 1):
+        raise ValueError(f"sam_every must be an integer >= 1, got {cfg.sam_every!r}")
+
+
+def check_sam_rho(rho):
+    """float(rho) if it is a usable SAM radius (finite, >= 0; 0 = off), else ValueError."""
+    if isinstance(rho, bool) or not isinstance(rho, (int, float)) or not math.isfinite(rho) \
+            or rho < 0:
+        raise ValueError(f"sam_rho must be finite and >= 0 (0 = off), got {rho!r}")
+    return float(rho)
 
 
 def segment_table(params_layout, n_arena, decay_exempt_1d=False, lamb=False):
@@ -131,6 +151,11 @@ def segment_table(params_layout, n_arena, decay_exempt_1d=False, lamb=False):
     exempt = SEG_NO_DECAY | (SEG_NO_ADAPT if lamb else 0)
     flags = [exempt if decay_exempt_1d and len(p[3]) <= 1 else 0 for p in params_layout]
     return ends, flags
+
+
+def sam_step_due(sam_every: int, t: int) -> bool:
+    """Is optimizer step t (1-based) a SAM step?  Steps 1, 1 + sam_every, 1 + 2 sam_every, ..."""
+    return (int(t) - 1) % int(sam_every) == 0
 
 
 def ema_decay_at(decay: float, t: int, warmup: bool = True) -> float:
@@ -237,6 +262,17 @@ class Trainer:
         self._optim_table = None
         if cfg.optimizer != "adam":
             self._build_optim_table()
+        # SAM: the arena-sized copy of the weights a step starts from, the chunk sums and
+        # {S, norm, scale} of the last perturbation, the loss at w + e.  With sam_rho == 0 only
+        # the 32-byte loss buffer exists (Trainer.sharpness creates the others on first use).
+        self.sam_backup = None
+        self._sam_scratch = None
+        self._sam_out3 = None
+        self.sam_loss_buf = torch.zeros(8, dtype=torch.float32, device=dev)
+        self.sam_steps = 0
+        self._bn_snapshot = None
+        if cfg.sam_rho > 0:
+            self._sam_buffers()
         self.reducer = None
         self.rank = 0
         if process_group is not None:
@@ -297,6 +333,11 @@ class Trainer:
         return self.lr_at(max(self.step_count, 1))
 
     def _refuse_unserved_optimizer(self):
+        if self.cfg.sam_rho > 0 and self.fuse_optimizer:
+            raise RuntimeError("Trainer.fuse_optimizer cannot serve sam_rho: cilrs_net_backward_"
+                               "step updates a segment's weights under the remaining data "
+                               "gradients, before the perturbation can be taken back (leave "
+                               "fuse_optimizer off, the default)")
         if self.cfg.optimizer == "adam":
             return
         if self.fuse_optimizer:
@@ -318,9 +359,11 @@ class Trainer:
             raise RuntimeError("the model was moved/re-created after the Trainer was built")
         return eng
 
-    def loss(self, controls, targets, pred_speed, target_speed, want_grads=True):
+    def loss(self, controls, targets, pred_speed, target_speed, want_grads=True, out=None):
         """CILRSLoss (nb:514-527) / the documented MSE loss; returns device buffer [6] in
-        LOSS_KEYS order, plus (dcontrols, dpred_speed) when want_grads."""
+        LOSS_KEYS order, plus (dcontrols, dpred_speed) when want_grads.  out: the fp32 device
+        buffer (>= 6) the terms are written to instead of `loss_buf`."""
+        out = self.loss_buf if out is None else out
         b = controls.size(0)
         dc = dp = None
         if want_grads:
@@ -331,8 +374,8 @@ class Trainer:
         L.check(L.lib().cilrs_loss_fwd_bwd(
             L.ptr(controls), L.ptr(targets.contiguous()), L.ptr(pred_speed),
             L.ptr(target_speed.contiguous()), b, self._kind, self._w, 1.0, L.ptr(dc), L.ptr(dp),
-            L.ptr(self.loss_buf), self._stream()))
-        return self.loss_buf, dc, dp
+            L.ptr(out), self._stream()))
+        return out, dc, dp
 
     @property
     def group_steps(self):
@@ -421,6 +464,9 @@ class Trainer:
                                                       seed)
         # `speeds` is both an input and the speed head's regression target (nb:550)
         _, dc, dp = self.loss(controls, tgts, pred_speed, speeds)
+        sam = self.cfg.sam_rho > 0 and sam_step_due(self.cfg.sam_every, self.step_count + 1)
+        if sam:
+            pl, dc, dp = self._sam_second_pass(pl, dc, dp, imgs, speeds, cmds, tgts, e, g, seed)
         if self.reducer is None and self.cfg.grad_clip <= 0 and self.fuse_optimizer:
             # backward + Adam in one call: a segment's update runs as soon as its gradients are
             # complete (clipping needs the global norm first and keeps the two-call path below)
@@ -434,6 +480,8 @@ class Trainer:
                                   self.cfg.weight_decay, self.group_steps[0])
         elif self.reducer is None:
             eng.run_backward(pl, dc, dp)
+            if sam:
+                self._sam_restore(e, g)
             self.optimizer_step(1.0)
         elif self.cfg.grad_clip <= 0 and self.bucket_optimizer:
             # data parallel without clipping: Adam per all-reduce bucket, as soon as the bucket's
@@ -443,13 +491,119 @@ class Trainer:
             eng.wrote_trainable(e)
             scale = 1.0 / self.reducer.world_size
             self.arena_grad_scale = scale
-            self.reducer.backward_and_reduce(
-                eng, pl, dc, dp, frozen_groups=g,
-                after_bucket=lambda _i, b, e_: self._adam_range(b, e_, scale, None, g))
+            pending = [sam]       # SAM: w comes back before the first bucket's update (every
+                                  # backward segment is enqueued by then: they read w + e)
+
+            def after_bucket(_i, b, e_):
+                if pending[0]:
+                    pending[0] = False
+                    self._sam_restore(e, g)
+                self._adam_range(b, e_, scale, None, g)
+            self.reducer.backward_and_reduce(eng, pl, dc, dp, frozen_groups=g,
+                                             after_bucket=after_bucket)
         else:
             self.reducer.backward_and_reduce(eng, pl, dc, dp, frozen_groups=g)
+            if sam:
+                self._sam_restore(e, g)
             self.optimizer_step(1.0 / self.reducer.world_size)
         return self.loss_buf
+
+    # -- sharpness-aware minimisation --------------------------------------------------------------
+    def _sam_buffers(self):
+        """The backup arena, the chunk-sum scratch and out3 (its last three doubles), once."""
+        if self.sam_backup is None:
+            eng = self.eng
+            nbytes = L.lib().cilrs_sam_scratch_bytes(eng.n_arena)
+            if nbytes == 0:
+                raise RuntimeError("cilrs_sam_scratch_bytes refused the arena size")
+            self.sam_backup = torch.empty(eng.n_arena, dtype=torch.float32, device=eng.device)
+            self._sam_scratch = torch.zeros(nbytes // 8, dtype=torch.float64, device=eng.device)
+            self._sam_out3 = self._sam_scratch[nbytes // 8 - 3:]
+        return self.sam_backup
+
+    def _sam_perturb(self, e, g, rho, adaptive):
+        """w -> w + e(w) over the trainable range from the gradient arena as it stands; the write
+        is announced like Adam's (Winograd transforms, bf16 copies and a frozen prefix's cached
+        state behave as after an optimizer step)."""
+        eng = self.eng
+        backup = self._sam_buffers()
+        begin = eng.trainable_begin(g)
+        L.check(L.lib().cilrs_sam_perturb(
+            L.ptr(eng.params[begin:]), L.ptr(eng.grads[begin:]), L.ptr(backup[begin:]),
+            eng.n_arena - begin, float(rho), 1 if adaptive else 0, L.ptr(self._sam_scratch),
+            L.ptr(self._sam_out3), self._stream()))
+        eng.wrote_trainable(e)
+
+    def _sam_restore(self, e, g):
+        """w + e -> w, bit for bit (cilrs_sam_restore), announced like the perturbation."""
+        eng = self.eng
+        begin = eng.trainable_begin(g)
+        L.check(L.lib().cilrs_sam_restore(L.ptr(eng.params[begin:]), L.ptr(self.sam_backup[begin:]),
+                                          eng.n_arena - begin, self._stream()))
+        eng.wrote_trainable(e)
+
+    def _sam_second_pass(self, pl, dc, dp, imgs, speeds, cmds, tgts, e, g, seed):
+        """Behind the forward and loss at w: this rank's own gradient (no collective: under a
+        process group the perturbation is per rank, m-sharpness), the perturbation, and the forward
+        and loss at w + e with the same dropout masks.  The running BatchNorm statistics and
+        num_batches_tracked end as the forward at w left them: snapshot before the second forward,
+        put back behind it.  Returns what the step's backward consumes."""
+        eng, cfg = self.eng, self.cfg
+        eng.run_backward(pl, dc, dp)
+        self._sam_perturb(e, g, cfg.sam_rho, cfg.sam_adaptive)
+        self.sam_steps += 1
+        if self._bn_snapshot is None:
+            self._bn_snapshot = (torch.empty_like(eng.bn), torch.empty_like(eng.nbt))
+        eng.snapshot_bn(*self._bn_snapshot)
+        controls, pred_speed, pl = eng.run_forward_ft(imgs, speeds, cmds, e, g, cfg.dropout, seed)
+        eng.put_back_bn(*self._bn_snapshot)
+        _, dc, dp = self.loss(controls, tgts, pred_speed, speeds, out=self.sam_loss_buf)
+        return pl, dc, dp
+
+    def sam_norm(self):
+        """{S, norm, scale} of the last perturbation (a SAM step's or sharpness()'s) as a CPU
+        float64 tensor [3]: the sum of squares, its root -- the gradient norm (ASAM: of |w| g) --
+        and rho / (norm + 1e-12).  Like trust_ratios() the read is the only synchronisation."""
+        if self._sam_out3 is None:
+            raise RuntimeError("no SAM perturbation yet (TrainConfig.sam_rho, Trainer.sharpness)")
+        return self._sam_out3.detach().cpu().clone()
+
+    @torch.no_grad()
+    def sharpness(self, batches, rho=None, adaptive=None):
+        """Mean over `batches` of L(w + e(w)) - L(w), the first-order worst-case loss increase
+        within rho (the quantity SAM minimises), on the kernels of the SAM step.  Per batch:
+        run_forward_frozen (eval-mode BatchNorm, no dropout, buffers untouched), loss, backward,
+        perturb, run_forward_frozen, loss, restore; the sums are kept on the device in float64 and
+        read once at the end.  rho / adaptive: default to the config's.  OVERWRITES the gradient
+        arena; parameters, moments, EMA, step counts and BatchNorm buffers are bit for bit what
+        they were.  Over the trainable range when a prefix is frozen.  Allowed inside
+        ``with trainer.ema_weights():`` (the averaged weights' sharpness).  Returns loss,
+        loss_perturbed, sharpness, grad_norm (mean norm of sam_norm()) and batches."""
+        eng = self._ensure_engine()
+        rho = check_sam_rho(self.cfg.sam_rho if rho is None else rho)
+        adaptive = bool(self.cfg.sam_adaptive if adaptive is None else adaptive)
+        e, g = self._freeze_state()
+        self._sam_buffers()
+        acc = torch.zeros(3, dtype=torch.float64, device=eng.device)
+        n = 0
+        for imgs, speeds, cmds, tgts in batches:
+            controls, pred_speed, pl = eng.run_forward_frozen(imgs, speeds, cmds)
+            buf, dc, dp = self.loss(controls, tgts, pred_speed, speeds, out=self.sam_loss_buf)
+            acc[0:1] += buf[0:1].double()
+            eng.run_backward(pl, dc, dp)
+            self._sam_perturb(e, g, rho, adaptive)
+            controls, pred_speed, pl = eng.run_forward_frozen(imgs, speeds, cmds)
+            buf, _, _ = self.loss(controls, tgts, pred_speed, speeds, want_grads=False,
+                                  out=self.sam_loss_buf)
+            acc[1:2] += buf[0:1].double()
+            acc[2:3] += self._sam_out3[1:2]
+            self._sam_restore(e, g)
+            n += 1
+        if n == 0:
+            raise ValueError("Trainer.sharpness: no batches")
+        a, b, c = (acc / n).tolist()
+        eng.check_status()
+        return {"loss": a, "loss_perturbed": b, "sharpness": b - a, "grad_norm": c, "batches": n}
 
     def _adam_range(self, begin, end, grad_scale, clip_ptr=None, frozen_groups=0):
         """cilrs_adam_step over the trainable part of the arena range [begin, end) (step counts

@@ -998,6 +998,52 @@ int cilrs_optim_step(int kind, const cilrs_optim_table* table, int first_seg, in
                      const float* clip_out2, float grad_scale, void* scratch, float* ratio_out,
                      void* stream);
 
+/* ---- sharpness-aware minimisation (SAM / ASAM; csrc/sam.hip) ------------------------------------------
+ * Foret et al. 2021 and its scale-invariant form (Kwon et al. 2021): the gradient is taken at
+ * w + e(w), the worst nearby point to first order, and applied at w.  The reference trains without
+ * it and torch ships none, so this text is the definition -- the form of the widely used
+ * `adaptive=` implementations, e = rho * w^2 g / || |w| g ||: no eta term, ONE norm over the whole
+ * range.  The gradient's own scale cancels in e, so there is no grad_scale or clip argument.
+ *
+ * Over a flat range of n floats (n a multiple of 4, at most 2^30; all arrays 16-byte aligned: the
+ * trainable range of the arena).  fp32 unless a line says double:
+ *     t_i   = g_i                          [adaptive = 0]
+ *     t_i   = |p_i| * g_i                  [adaptive = 1; one fp32 rounding]
+ *     S     = sum_i (double)t_i * (double)t_i      [accumulated in double]
+ *     norm  = sqrt(S)                              [double]
+ *     scale = rho / (norm + 1e-12)                 [double];  s32 = (float)scale
+ *     backup_i = p_i
+ *     p_i   = p_i + s32 * g_i              [adaptive = 0; two roundings, no FMA]
+ *     p_i   = p_i + s32 * (|p_i| * t_i)    [adaptive = 1; three roundings, no FMA]
+ * rho = 0 and g = 0 leave p as it was (S = 0 gives scale = rho * 1e12, times zero); under
+ * adaptive = 1 a zero weight stays zero.
+ *
+ * Summation order: the range is cut, from its own start, into chunks of cilrs_sam_chunk_floats
+ * floats.  One workgroup reduces a chunk (thread t of 256 adds the squares of the chunk's quads
+ * t, t + 256, ... in element order; a butterfly adds the 64 lanes of a wave, (w0 + w1) + (w2 + w3)
+ * the four waves) and writes one double.  One workgroup then adds the chunk sums -- thread l takes
+ * sums l, l + 256, ... in index order, the same tree adds the threads -- and writes
+ * out3 = {S, norm, scale} (device, double).  No floating-point atomics: results are bit-identical
+ * from run to run and a function of the range's own data only -- a sub-range perturbed through
+ * offset pointers equals the same data perturbed stand-alone.  No sequential run of additions is
+ * longer than 1,024 terms (16 in a chunk), so S is within 2^-40 relative of the exactly rounded sum.
+ *
+ * scratch: cilrs_sam_scratch_bytes(n) bytes of device memory, 16-byte aligned (0: n unusable): one
+ * double per chunk, then room for three more, where out3 may point (out3: any 8-byte aligned device
+ * address).  backup: n floats that overlap neither params nor grads.
+ *
+ * cilrs_sam_perturb is three launches on `stream` (chunk sums, finalise, apply) with no host
+ * synchronisation, allocation or upload.  cilrs_sam_restore copies backup over params bit for bit
+ * (-0.0, denormals and NaN payloads included): (p + e) - e is not p in fp32, and the weights a step
+ * starts from must be the ones the optimizer updates.  Refused, before any launch: NULL pointers;
+ * n zero, not a multiple of 4 or above 2^30; misaligned pointers; backup overlapping params or
+ * grads; rho negative or not finite; adaptive not 0 or 1. */
+int cilrs_sam_chunk_floats(void);
+size_t cilrs_sam_scratch_bytes(size_t n);
+int cilrs_sam_perturb(float* params, const float* grads, float* backup, size_t n, double rho,
+                      int adaptive, void* scratch, double* out3, void* stream);
+int cilrs_sam_restore(float* params, const float* backup, size_t n, void* stream);
+
 /* In-place exchange of two arrays of n floats that do not overlap, in one pass.  The plans cache the
  * parameter arena's address: averaged weights are evaluated by swapping them into the arena and
  * out again, never by re-binding pointers. */
