@@ -7,5 +7,6 @@ from .data import (WEATHER_CONDITIONS, BatchLoader, CachedBatchLoader, CameraMod
                    weather_u8)
 from .model import CILRS, CILRSResNet50  # noqa: F401
 from .neighbours import NeighbourIndex  # noqa: F401
+from .priority import PrioritizedBatchLoader, PrioritySampler  # noqa: F401
 from .select import FramePool, Selection  # noqa: F401
 from .train import CONFIG_A, CONFIG_B, LOSS_KEYS, TrainConfig, Trainer  # noqa: F401

@@ -182,6 +182,13 @@ SIGNATURES = {
     "cilrs_sam_scratch_bytes": (sz, [sz]),
     "cilrs_sam_perturb": (i32, [vp, vp, vp, sz, f64, i32, vp, vp, vp]),
     "cilrs_sam_restore": (i32, [vp, vp, sz, vp]),
+    "cilrs_loss_fwd_bwd_rows": (i32, [vp, vp, vp, vp, i32, i32, c_float_p, f32, vp, vp, vp, vp, vp,
+                                      vp]),
+    "cilrs_priority_max_batch": (i32, []),
+    "cilrs_priority_fill": (i32, [vp, i64, vp, vp, vp]),
+    "cilrs_priority_update": (i32, [vp, i64, vp, vp, vp, f64, f64, vp, i32, vp]),
+    "cilrs_priority_scratch_bytes": (sz, [i64]),
+    "cilrs_priority_draw": (i32, [vp, i64, vp, i64, u64, u64, i32, i32, f64, vp, vp, vp, vp, vp]),
     "cilrs_augment_u8": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
     "cilrs_batch_assemble": (i32, [vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,
                                    vp]),

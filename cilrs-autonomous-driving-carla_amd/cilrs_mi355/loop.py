@@ -26,8 +26,17 @@ def train_one_epoch(trainer, batches):
     trainer.model.train()
     acc = None
     n = 0
+    # a loader that draws by priority (PrioritizedBatchLoader): its importance weights go into the
+    # step and the step's per-sample losses back into its table, all on the device
+    prioritised = hasattr(batches, "feedback")
     for imgs, speeds, cmds, tgts in batches:
-        buf = trainer.train_step(imgs, speeds, cmds, tgts)
+        if prioritised:
+            rows = torch.empty(imgs.size(0), dtype=torch.float32, device=imgs.device)
+            buf = trainer.train_step(imgs, speeds, cmds, tgts, sample_weight=batches.last_weight,
+                                     row_loss=rows)
+            batches.feedback(rows)
+        else:
+            buf = trainer.train_step(imgs, speeds, cmds, tgts)
         acc = buf[:6].double().clone() if acc is None else acc + buf[:6].double()
         n += 1
     if trainer.reducer is not None:
@@ -59,7 +68,7 @@ def train_one_epoch(trainer, batches):
 
 
 def fit(trainer, train_batches, val_batches, epochs=20, patience=6, out_dir=".", resume=None,
-        log=print, validate_ema=None, ema_bn_batches=None):
+        log=print, validate_ema=None, ema_bn_batches=None, sampler=None):
     """``train_batches`` / ``val_batches``: callables returning an iterable of
     (imgs, speeds, cmds, tgts) device batches for one epoch.
 
@@ -73,7 +82,12 @@ def fit(trainer, train_batches, val_batches, epochs=20, patience=6, out_dir=".",
     weights (``trainer.update_bn(ema_bn_batches(), ema=True)``) before each EMA validation, and
     the checkpoints carry the result: ``checkpoint_best.pth`` in its ``model_state_dict``'s buffer
     entries, ``checkpoint_latest.pth`` under ``ema_bn_state_dict``.  Without it every file has
-    the keys it always had."""
+    the keys it always had.
+
+    sampler: the `PrioritizedBatchLoader` (or `PrioritySampler`) behind ``train_batches``.  Its
+    ``state_dict()`` -- priority table, running maximum, draw counter -- is saved in
+    ``checkpoint_latest.pth`` under ``loop_state["sampler_state"]`` and restored on resume, so the
+    resumed run draws the batches the interrupted one would have."""
     has_ema = getattr(trainer, "ema", None) is not None
     use_ema = has_ema if validate_ema is None else bool(validate_ema)
     if use_ema and not has_ema:
@@ -100,6 +114,8 @@ def fit(trainer, train_batches, val_batches, epochs=20, patience=6, out_dir=".",
         if st is not None:      # keep the best checkpoint / patience / history across the restart
             best_val, best_epoch, bad = float(st["best_val"]), int(st["best_epoch"]), int(st["bad"])
             history = [dict(r) for r in st["history"]]
+            if sampler is not None and st.get("sampler_state") is not None:
+                sampler.load_state_dict(st["sampler_state"])
         log(f"resumed from {resume} at epoch {start_epoch}")
     for epoch in range(start_epoch, epochs + 1):
         t0 = time.time()
@@ -127,10 +143,12 @@ def fit(trainer, train_batches, val_batches, epochs=20, patience=6, out_dir=".",
         else:
             bad += 1
         if writer:
+            loop_state = {"best_val": float(best_val), "best_epoch": best_epoch, "bad": bad,
+                          "history": history}
+            if sampler is not None:
+                loop_state["sampler_state"] = sampler.state_dict()
             checkpoint.save_latest(latest_path, trainer.model, trainer, epoch,    # nb:642-646
-                                   loop_state={"best_val": float(best_val),
-                                               "best_epoch": best_epoch, "bad": bad,
-                                               "history": history})
+                                   loop_state=loop_state)
         barrier()
         if bad >= patience:                                        # nb:650-652
             log(f"early stopping at epoch {epoch}")

@@ -223,6 +223,7 @@ class Trainer:
         self._w = (C.c_float * 4)(*cfg.loss_weights)
         self._kind = 1 if cfg.loss == "l1" else 0
         self._seed_calls = 0
+        self.rows_calls = 0                    # launches of cilrs_loss_fwd_bwd_rows (Trainer.loss)
         self.arena_grad_scale = 1.0
         # True: single-GPU steps without clipping take cilrs_net_backward_step (a segment's Adam
         # update enqueued behind its gradients, on the weight-gradient stream) instead of backward +
@@ -359,10 +360,16 @@ class Trainer:
             raise RuntimeError("the model was moved/re-created after the Trainer was built")
         return eng
 
-    def loss(self, controls, targets, pred_speed, target_speed, want_grads=True, out=None):
+    def loss(self, controls, targets, pred_speed, target_speed, want_grads=True, out=None,
+             sample_weight=None, row_loss=None):
         """CILRSLoss (nb:514-527) / the documented MSE loss; returns device buffer [6] in
         LOSS_KEYS order, plus (dcontrols, dpred_speed) when want_grads.  out: the fp32 device
-        buffer (>= 6) the terms are written to instead of `loss_buf`."""
+        buffer (>= 6) the terms are written to instead of `loss_buf`.
+
+        sample_weight (device fp32 [B]): every sample's gradient is multiplied by its weight and
+        the terms are the weighted means; row_loss (device fp32 [B]): receives the unweighted
+        per-sample losses.  With either one the launch is cilrs_loss_fwd_bwd_rows (`rows_calls`
+        counts them), with neither it is cilrs_loss_fwd_bwd as ever."""
         out = self.loss_buf if out is None else out
         b = controls.size(0)
         dc = dp = None
@@ -371,6 +378,18 @@ class Trainer:
                 self._dgrads[b] = (torch.empty(b, 3, device=controls.device),
                                    torch.empty(b, device=controls.device))
             dc, dp = self._dgrads[b]
+        if sample_weight is not None or row_loss is not None:
+            for name, t in (("sample_weight", sample_weight), ("row_loss", row_loss)):
+                if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (b,)
+                                      or t.device != controls.device or not t.is_contiguous()):
+                    raise ValueError(f"{name} must be a contiguous fp32 [{b}] tensor on the "
+                                     "model's device")
+            self.rows_calls += 1
+            L.check(L.lib().cilrs_loss_fwd_bwd_rows(
+                L.ptr(controls), L.ptr(targets.contiguous()), L.ptr(pred_speed),
+                L.ptr(target_speed.contiguous()), b, self._kind, self._w, 1.0, L.ptr(dc), L.ptr(dp),
+                L.ptr(out), L.ptr(sample_weight), L.ptr(row_loss), self._stream()))
+            return out, dc, dp
         L.check(L.lib().cilrs_loss_fwd_bwd(
             L.ptr(controls), L.ptr(targets.contiguous()), L.ptr(pred_speed),
             L.ptr(target_speed.contiguous()), b, self._kind, self._w, 1.0, L.ptr(dc), L.ptr(dp),
@@ -442,8 +461,14 @@ class Trainer:
         self._adam_range(begin, eng.n_arena, grad_scale, clip_ptr, g)
 
     # -- one iteration of train_one_epoch's loop (nb:549-555) ------------------------------------
-    def train_step(self, imgs, speeds, cmds, tgts):
-        """Returns the device loss buffer [>=6] (LOSS_KEYS order); reading it is the only sync."""
+    def train_step(self, imgs, speeds, cmds, tgts, sample_weight=None, row_loss=None):
+        """Returns the device loss buffer [>=6] (LOSS_KEYS order); reading it is the only sync.
+
+        sample_weight / row_loss (device fp32 [B], `Trainer.loss`): importance weights on the
+        samples' gradients, and where the step's unweighted per-sample losses go -- what a
+        `PrioritizedBatchLoader` gives and takes.  Under SAM the weights apply to both passes and
+        row_loss is the first pass's (the loss at w).  With both None the step is launch for
+        launch what it always was."""
         self._refuse_inside_ema_weights("train_step")
         self._refuse_unserved_optimizer()
         if self.ema is not None and self.fuse_optimizer:
@@ -463,10 +488,12 @@ class Trainer:
         controls, pred_speed, pl = eng.run_forward_ft(imgs, speeds, cmds, e, g, self.cfg.dropout,
                                                       seed)
         # `speeds` is both an input and the speed head's regression target (nb:550)
-        _, dc, dp = self.loss(controls, tgts, pred_speed, speeds)
+        _, dc, dp = self.loss(controls, tgts, pred_speed, speeds, sample_weight=sample_weight,
+                              row_loss=row_loss)
         sam = self.cfg.sam_rho > 0 and sam_step_due(self.cfg.sam_every, self.step_count + 1)
         if sam:
-            pl, dc, dp = self._sam_second_pass(pl, dc, dp, imgs, speeds, cmds, tgts, e, g, seed)
+            pl, dc, dp = self._sam_second_pass(pl, dc, dp, imgs, speeds, cmds, tgts, e, g, seed,
+                                               sample_weight)
         if self.reducer is None and self.cfg.grad_clip <= 0 and self.fuse_optimizer:
             # backward + Adam in one call: a segment's update runs as soon as its gradients are
             # complete (clipping needs the global norm first and keeps the two-call path below)
@@ -542,7 +569,8 @@ class Trainer:
                                           eng.n_arena - begin, self._stream()))
         eng.wrote_trainable(e)
 
-    def _sam_second_pass(self, pl, dc, dp, imgs, speeds, cmds, tgts, e, g, seed):
+    def _sam_second_pass(self, pl, dc, dp, imgs, speeds, cmds, tgts, e, g, seed,
+                         sample_weight=None):
         """Behind the forward and loss at w: this rank's own gradient (no collective: under a
         process group the perturbation is per rank, m-sharpness), the perturbation, and the forward
         and loss at w + e with the same dropout masks.  The running BatchNorm statistics and
@@ -557,7 +585,8 @@ class Trainer:
         eng.snapshot_bn(*self._bn_snapshot)
         controls, pred_speed, pl = eng.run_forward_ft(imgs, speeds, cmds, e, g, cfg.dropout, seed)
         eng.put_back_bn(*self._bn_snapshot)
-        _, dc, dp = self.loss(controls, tgts, pred_speed, speeds, out=self.sam_loss_buf)
+        _, dc, dp = self.loss(controls, tgts, pred_speed, speeds, out=self.sam_loss_buf,
+                              sample_weight=sample_weight)
         return pl, dc, dp
 
     def sam_norm(self):
@@ -915,6 +944,24 @@ class Trainer:
         cmd_avg = {names[i]: (float(cs[i] / cc[i]) if cc[i] > 0 else float("nan"))
                    for i in range(nc)}
         return out, cmd_avg
+
+    @torch.no_grad()
+    def row_losses(self, batches):
+        """Eval-mode per-sample losses (include/cilrs_hip.h "prioritised sampling", l_b) of every
+        sample of `batches`, in order, as one device fp32 tensor: what warm-starts a
+        `PrioritySampler` (`sampler.update(pos, losses)`) and the per-frame error list a
+        `FramePool` takes.  No gradients, no optimizer state touched."""
+        self.model.eval()
+        out = []
+        for imgs, speeds, cmds, tgts in batches:
+            pc, ps = self.model(imgs, speeds, cmds)
+            rl = torch.empty(pc.size(0), dtype=torch.float32, device=pc.device)
+            self.loss(pc, tgts, ps, speeds, want_grads=False, out=self.sam_loss_buf, row_loss=rl)
+            out.append(rl)
+        if not out:
+            raise ValueError("Trainer.row_losses: no batches")
+        self.eng.check_status()
+        return torch.cat(out)
 
     def all_reduce_sum(self, t):
         """Sum of a (device) tensor over the data-parallel ranks; the tensor itself without them."""

@@ -36,13 +36,6 @@ struct AttrNorm {
 constexpr AttrNorm kAttrNorm = {{kImageMean[0], kImageMean[1], kImageMean[2]},
                                 {kImageStd[0], kImageStd[1], kImageStd[2]}};
 
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
 // the Box-Muller normal of augment.hip's GaussNoise for element `counter` of stream `seed`
 __device__ __forceinline__ float hash_normal(const unsigned long long seed,
                                              const unsigned long long counter) {

@@ -115,13 +115,6 @@ __device__ __forceinline__ int reflect101(int i, const int n) {
     return i;
 }
 
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
 // Weather for source pixel (y, x), in place on the uint8-valued floats c[3]: tone, fog, rain.
 __device__ __forceinline__ void weather_stages(const cilrs_weather_params& w, const int y,
                                                const int x, float c[3]) {

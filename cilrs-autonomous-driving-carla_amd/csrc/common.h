@@ -737,6 +737,95 @@ int launch_adam_groups_ema(float* p, const float* g, float* m, float* v, size_t 
 int launch_keep_head_inputs(const float* speed, const long long* cmd, float* speed_dst,
                             long long* cmd_dst, int B, hipStream_t s);
 
+#if defined(__HIPCC__)
+// splitmix64's finaliser: the counter hash of augment.hip (GaussNoise, rain), attribution.hip
+// (SmoothGrad noise) and priority.hip (the draw)
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+// ---- loss forward + gradient, one block of 256 threads ----------------------------------------------
+// kind 0: MSE (Config A)  total = mean_{b,c}(d^2) + w3 * mean_b(ds^2); per-channel = mean_b(d_c^2)
+// kind 1: L1  (Config B)  total = sum_c w_c * mean_b|d_c| + w3 * mean_b(ds^2)
+// out[6] = total, control, steer, throttle, brake, speed
+// The body of loss_kernel (heads_optim.hip; ROWS = false: row_weight and row_loss are not looked at)
+// and of loss_rows_kernel (priority.hip; ROWS = true: either may be NULL).  A weight of one
+// multiplies exactly, in the double sums and in the fp32 gradients, and the fold is the same, so the
+// two kernels write the same bits where no weights are given.  include/cilrs_hip.h "prioritised
+// sampling" defines the row term.
+template <bool ROWS>
+__device__ __forceinline__ void loss_block(
+    const float* __restrict__ pc, const float* __restrict__ tc, const float* __restrict__ ps,
+    const float* __restrict__ ts, const int B, const int kind, const float w0, const float w1,
+    const float w2, const float w3, const float grad_scale, float* __restrict__ dpc,
+    float* __restrict__ dps, float* __restrict__ out, const float* __restrict__ row_weight,
+    float* __restrict__ row_loss) {
+    __shared__ double red[4][256];
+    double a[4] = {0.0, 0.0, 0.0, 0.0};
+    const float invB = 1.0f / (float)B;
+    const float wc[3] = {w0, w1, w2};
+    for (int b = threadIdx.x; b < B; b += 256) {
+        const bool weighted = ROWS && row_weight != nullptr;
+        const float rw = weighted ? row_weight[b] : 1.0f;
+        double row = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float d = pc[b * 3 + c] - tc[b * 3 + c];
+            float g;
+            if (kind == 0) {
+                const double t = (double)d * (double)d;
+                if (ROWS) { a[c] += (double)rw * t; row += t; }
+                else a[c] += t;
+                g = 2.0f * d / (3.0f * (float)B);
+            } else {
+                const double t = (double)fabsf(d);
+                if (ROWS) { a[c] += (double)rw * t; row += (double)wc[c] * t; }
+                else a[c] += t;
+                g = wc[c] * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * invB;
+            }
+            if (dpc) {
+                g = g * grad_scale;
+                dpc[b * 3 + c] = weighted ? g * rw : g;
+            }
+        }
+        const float d = ps[b] - ts[b];
+        const double t = (double)d * (double)d;
+        if (ROWS) a[3] += (double)rw * t;
+        else a[3] += t;
+        if (dps) {
+            const float g = w3 * 2.0f * d * invB * grad_scale;
+            dps[b] = weighted ? g * rw : g;
+        }
+        if (ROWS && row_loss != nullptr) {
+            if (kind == 0) row = row / 3.0;
+            row_loss[b] = (float)(row + (double)w3 * t);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) red[c][threadIdx.x] = a[c];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int t = 0; t < 256; ++t)
+            for (int c = 0; c < 4; ++c) s[c] += red[c][t];
+        const float steer = (float)(s[0] / B), thr = (float)(s[1] / B), brk = (float)(s[2] / B);
+        const float spd = (float)(s[3] / B);
+        float control;
+        if (kind == 0) control = (float)((s[0] + s[1] + s[2]) / (3.0 * B));
+        else control = w0 * steer + w1 * thr + w2 * brk;
+        out[0] = control + w3 * spd;
+        out[1] = control;
+        out[2] = steer;
+        out[3] = thr;
+        out[4] = brk;
+        out[5] = spd;
+    }
+}
+#endif
+
 // ---- Monte-Carlo dropout through the heads (mc_heads.hip; cilrs_heads_mc) -----------------------
 #if defined(__HIPCC__)
 // The dropout hash of the heads (dropout_kernel, hgemm_kernel): the fp32 in [0, 1) from the top 24

@@ -486,55 +486,14 @@ __global__ __launch_bounds__(256) void eval_accumulate_kernel(
 }
 
 // ---- loss forward + gradient, one block --------------------------------------------------------
-// kind 0: MSE (Config A)  total = mean_{b,c}(d^2) + w3 * mean_b(ds^2); per-channel = mean_b(d_c^2)
-// kind 1: L1  (Config B)  total = sum_c w_c * mean_b|d_c| + w3 * mean_b(ds^2)
-// out[6] = total, control, steer, throttle, brake, speed
+// the body is common.h's loss_block, shared with priority.hip's loss_rows_kernel
 __global__ __launch_bounds__(256) void loss_kernel(
     const float* __restrict__ pc, const float* __restrict__ tc, const float* __restrict__ ps,
     const float* __restrict__ ts, const int B, const int kind, const float w0, const float w1,
     const float w2, const float w3, const float grad_scale, float* __restrict__ dpc,
     float* __restrict__ dps, float* __restrict__ out) {
-    __shared__ double red[4][256];
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    const float invB = 1.0f / (float)B;
-    const float wc[3] = {w0, w1, w2};
-    for (int b = threadIdx.x; b < B; b += 256) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float d = pc[b * 3 + c] - tc[b * 3 + c];
-            float g;
-            if (kind == 0) {
-                a[c] += (double)d * (double)d;
-                g = 2.0f * d / (3.0f * (float)B);
-            } else {
-                a[c] += (double)fabsf(d);
-                g = wc[c] * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * invB;
-            }
-            if (dpc) dpc[b * 3 + c] = g * grad_scale;
-        }
-        const float d = ps[b] - ts[b];
-        a[3] += (double)d * (double)d;
-        if (dps) dps[b] = w3 * 2.0f * d * invB * grad_scale;
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) red[c][threadIdx.x] = a[c];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int t = 0; t < 256; ++t)
-            for (int c = 0; c < 4; ++c) s[c] += red[c][t];
-        const float steer = (float)(s[0] / B), thr = (float)(s[1] / B), brk = (float)(s[2] / B);
-        const float spd = (float)(s[3] / B);
-        float control;
-        if (kind == 0) control = (float)((s[0] + s[1] + s[2]) / (3.0 * B));
-        else control = w0 * steer + w1 * thr + w2 * brk;
-        out[0] = control + w3 * spd;
-        out[1] = control;
-        out[2] = steer;
-        out[3] = thr;
-        out[4] = brk;
-        out[5] = spd;
-    }
+    loss_block<false>(pc, tc, ps, ts, B, kind, w0, w1, w2, w3, grad_scale, dpc, dps, out, nullptr,
+                      nullptr);
 }
 
 // ---- gradient norm + Adam ------------------------------------------------------------------------

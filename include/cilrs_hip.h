@@ -1044,6 +1044,75 @@ int cilrs_sam_perturb(float* params, const float* grads, float* backup, size_t n
                       int adaptive, void* scratch, double* out3, void* stream);
 int cilrs_sam_restore(float* params, const float* backup, size_t n, void* stream);
 
+/* ---- prioritised sampling: per-sample loss, priority table and draw (csrc/priority.hip) -------------
+ * Prioritised replay (Schaul et al. 2016) over recorded frames: a step writes its per-sample losses,
+ * they become priorities of the frames it saw, and the next batch's index is drawn from the
+ * priorities on the device.  The reference samples by command alone (notebook:383-423) and has
+ * none of this, so this text is the definition.
+ *
+ * cilrs_loss_fwd_bwd_rows: cilrs_loss_fwd_bwd plus two device arrays, each of which may be NULL:
+ * row_weight [batch] (in) and row_loss [batch] (out).  With d_c = controls[b][c] -
+ * target_controls[b][c] and d_s = pred_speed[b] - target_speed[b] (fp32 differences, as in the
+ * loss itself; everything after them in double, cast to fp32 once):
+ *     kind 0:  l_b = ((d_0^2 + d_1^2) + d_2^2) / 3 + w3 * d_s^2
+ *     kind 1:  l_b = ((w0 |d_0| + w1 |d_1|) + w2 |d_2|) + w3 * d_s^2
+ *     row_loss[b] = l_b                                         [never weighted]
+ * so that mean_b l_b is loss_out[0] without weights.  With weights every gradient element of row b
+ * is the unweighted fp32 one times row_weight[b] (one more rounding), and loss_out[0..5] are the
+ * weighted means (1 / batch) sum_b row_weight[b] * term.  With row_weight == NULL loss_out,
+ * dcontrols and dpred_speed are bit for bit cilrs_loss_fwd_bwd's: one workgroup, the same
+ * per-thread sums and the same fold (the two kernels share their body), and all-ones weights give
+ * those bits too.
+ *
+ * The table: q, uint32 [n], every entry in [1, 2^32 - 1]; 2^20 is priority 1.  Sums of entries are
+ * uint64 and n is at most 2^31, so the total stays below 2^63 and, integer addition being
+ * associative, does not depend on how the device groups it.  fixed(p) = llrint(p * 2^20) clamped to
+ * [1, 2^32 - 1]; what is not below the upper end, NaN included, takes it.  pmax_state: one device
+ * uint32, the running maximum of every q an update has written (the caller sets it, to 2^20, before
+ * the first fill).
+ *
+ * cilrs_priority_fill: q[i] = fixed(base[i] * pmax_state / 2^20) for all i -- what a frame holds
+ * until its first visit, PER's "new samples get the maximum priority" (base NULL: 1).
+ *
+ * cilrs_priority_update, for b in [0, batch), batch <= cilrs_priority_max_batch() = 1024:
+ *     x = (double)row_loss[b] + eps;   x^alpha = 1, x, sqrt(x) for alpha = 0, 1, 0.5, pow otherwise
+ *     q[pos[b]] = fixed(base[pos[b]] * x^alpha)          [double]
+ *     q[pos[b]] = 2^32 - 1 where row_loss[b] is not finite
+ * Where a position repeats inside pos the highest b alone writes; a position outside [0, n) is
+ * never written; then pmax_state = max(pmax_state, every q written).  One launch of one workgroup.
+ *
+ * cilrs_priority_draw, with total = sum q and, for b in [0, batch), batch <= 1024,
+ *     r_b = splitmix64(seed + (counter * batch + b) * 0xD1B54A32D192ED03)     [mod 2^64]
+ *     stratified and total >= batch:  quo = total / batch, rem = total % batch,
+ *         lo_b = quo * b + min(b, rem),  len_b = quo + (b < rem),  t_b = lo_b + mulhi64(r_b, len_b)
+ *     otherwise:                      t_b = mulhi64(r_b, total)
+ *     out_pos[b]    = the smallest i with q[0] + ... + q[i] > t_b      [< n, all integer so far]
+ *     out_index[b]  = subset ? subset[out_pos[b]] : out_pos[b]
+ *     out_weight[b] = v_b / max_b' v_b',  v_b = pow(total / (n * q[out_pos[b]]), beta)   [double]
+ * beta = 0 gives exactly 1.0f.  subset (int64 [n], or NULL) maps table positions to frames of a
+ * dataset of n_frames frames; its values are the caller's to check against n_frames, once.  Three
+ * launches on `stream` (sums of chunks of 1,024 entries, their scan, the draw), no host
+ * synchronisation, allocation or upload, no floating-point atomics.  scratch:
+ * cilrs_priority_scratch_bytes(n) bytes of device memory, 8-byte aligned (0: n unusable); q must be
+ * 16-byte aligned.  Refused before any launch: NULL pointers, n outside [1, 2^31], batch outside
+ * [1, 1024], alpha negative, eps not positive, beta outside [0, 1], misaligned q or scratch. */
+int cilrs_loss_fwd_bwd_rows(const float* controls, const float* target_controls,
+                            const float* pred_speed, const float* target_speed, int batch, int kind,
+                            const float* weights4_host, float grad_scale, float* dcontrols,
+                            float* dpred_speed, float* loss_out, const float* row_weight,
+                            float* row_loss, void* stream);
+int cilrs_priority_max_batch(void);
+int cilrs_priority_fill(uint32_t* q, int64_t n, const float* base, const uint32_t* pmax_state,
+                        void* stream);
+int cilrs_priority_update(uint32_t* q, int64_t n, const int64_t* pos, const float* row_loss,
+                          const float* base, double alpha, double eps, uint32_t* pmax_state,
+                          int batch, void* stream);
+size_t cilrs_priority_scratch_bytes(int64_t n);
+int cilrs_priority_draw(const uint32_t* q, int64_t n, const int64_t* subset, int64_t n_frames,
+                        uint64_t seed, uint64_t counter, int batch, int stratified, double beta,
+                        int64_t* out_pos, int64_t* out_index, float* out_weight, void* scratch,
+                        void* stream);
+
 /* In-place exchange of two arrays of n floats that do not overlap, in one pass.  The plans cache the
  * parameter arena's address: averaged weights are evaluated by swapping them into the arena and
  * out again, never by re-binding pointers. */
