@@ -1,5 +1,7 @@
 """cilrs_mi355 -- MI355X-native engine behind the reference's CILRS nn.Module boundary
 (model/autonomous_drive.py:361-399, notebook/notebook.ipynb:440-555)."""
+from .adversarial import GOALS as ADVERSARIAL_GOALS  # noqa: F401
+from .adversarial import Attack as AdversarialAttack  # noqa: F401
 from .bn_estimate import BatchNormEstimator, update_bn  # noqa: F401
 from .cluster import Clustering  # noqa: F401
 from .data import (WEATHER_CONDITIONS, BatchLoader, CachedBatchLoader, CameraModel,  # noqa: F401

@@ -270,6 +270,17 @@ SIGNATURES = {
                                     i32, vp, vp]),
     "cilrs_attr_finalize": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, c_float_p, vp, vp, vp, vp]),
     "cilrs_attr_finalize_threads": (i32, []),
+    "cilrs_adv_start": (i32, [vp, C.c_long, C.c_long, C.c_long, C.c_long, i32, i32, i32, f32,
+                              c_float_p, u64, c_float_p, vp, C.c_long, C.c_long, C.c_long, C.c_long,
+                              vp]),
+    "cilrs_adv_step": (i32, [vp, vp, C.c_long, C.c_long, C.c_long, C.c_long, vp, C.c_long, C.c_long,
+                             C.c_long, C.c_long, i32, i32, i32, f32, f32, c_float_p, vp, vp, vp,
+                             C.c_long, C.c_long, C.c_long, C.c_long, c_float_p, vp]),
+    "cilrs_adv_direction": (i32, [vp, vp, vp, vp, c_float_p, i32, i32, vp, vp, vp, vp, vp]),
+    "cilrs_adv_quantize": (i32, [vp, C.c_long, C.c_long, C.c_long, C.c_long, vp, i32, i32, i32, vp,
+                                 vp, vp]),
+    "cilrs_adv_quantize_threads": (i32, []),
+    "cilrs_adv_max_elements": (C.c_longlong, []),
     "cilrs_linear_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "cilrs_linear_bwd": (i32, [vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32,
                                vp]),

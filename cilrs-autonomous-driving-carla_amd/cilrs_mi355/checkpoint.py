@@ -77,7 +77,8 @@ def load_optimizer_state_dict(trainer, sd):
 # TrainConfig fields of the optimizer / schedule options: recorded only where they differ from their
 # defaults, so that a file written with none of them set has the keys it always had
 _OPTIONAL_FIELDS = ("optimizer", "decay_exempt_1d", "trust_clip", "warmup_steps", "lr_schedule",
-                    "lr_epochs", "lr_min", "sam_rho", "sam_adaptive", "sam_every")
+                    "lr_epochs", "lr_min", "sam_rho", "sam_adaptive", "sam_every", "adv_eps",
+                    "adv_alpha", "adv_random_start", "adv_every", "adv_clamp")
 
 
 def _set_options(cfg):

@@ -586,6 +586,95 @@ class Engine:
             scale, L.ptr(attr), L.ptr(signed_map), L.ptr(total), self._stream()))
         return attr
 
+    # ---- FGSM / PGD (csrc/adversarial.hip) ------------------------------------------------------
+    def _check_adv_image(self, t, name, shape=None):
+        if t.dtype != torch.float32 or t.dim() != 4 or t.size(1) != 3 or t.device != self.device:
+            raise RuntimeError(f"{name} must be float32 [B,3,H,W] on {self.device}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise RuntimeError(f"{name} must be float32 {tuple(shape)}, got {tuple(t.shape)}")
+        return t.size(0), t.size(2), t.size(3)
+
+    def _check_adv_rows(self, t, name, dtype, shape):
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()
+                              or t.device != self.device):
+            raise RuntimeError(f"{name} must be contiguous {dtype} {shape} on {self.device}")
+
+    @staticmethod
+    def _adv_floats(values, n):
+        return None if values is None else (C.c_float * n)(*[float(v) for v in values])
+
+    def run_adv_start(self, x, eps255, chan_scale3, seed, x_adv, range6=None):
+        """cilrs_adv_start: x_adv = x + e_c * (2u - 1) clamped to the eps ball (and range6), the
+        draw keyed on `seed` and the logical element index; eps255 = 0 is a copy.  x and x_adv
+        float32 [B,3,H,W] with any strides; fills and returns x_adv."""
+        b, h, w = self._check_adv_image(x, "x")
+        self._check_adv_image(x_adv, "x_adv", x.shape)
+        L.check(L.lib().cilrs_adv_start(
+            L.ptr(x), *x.stride(), b, h, w, float(eps255), self._adv_floats(chan_scale3, 3),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, self._adv_floats(range6, 6), L.ptr(x_adv),
+            *x_adv.stride(), self._stream()))
+        return x_adv
+
+    def run_adv_step(self, x, x_adv, g, alpha255, eps255, chan_scale3, row_dir=None, improved=None,
+                     best=None, range6=None):
+        """cilrs_adv_step: where improved[b], best = x_adv; then x_adv = clamp(x_adv + a_c *
+        row_dir[b] * sign(g)) in place.  x and x_adv must share their strides; g and best have
+        their own.  alpha255 = 0 performs the copy alone (g may then be None)."""
+        b, h, w = self._check_adv_image(x, "x")
+        self._check_adv_image(x_adv, "x_adv", x.shape)
+        if x.stride() != x_adv.stride():
+            raise RuntimeError(f"x and x_adv must have the same strides, got {x.stride()} and "
+                               f"{x_adv.stride()}")
+        if g is not None:
+            self._check_adv_image(g, "g", x.shape)
+        if best is not None:
+            self._check_adv_image(best, "best", x.shape)
+        self._check_adv_rows(row_dir, "row_dir", torch.float32, (b,))
+        self._check_adv_rows(improved, "improved", torch.int32, (b,))
+        zero = (0, 0, 0, 0)
+        L.check(L.lib().cilrs_adv_step(
+            L.ptr(x), L.ptr(x_adv), *x.stride(), L.ptr(g), *(g.stride() if g is not None else zero),
+            b, h, w, float(alpha255), float(eps255), self._adv_floats(chan_scale3, 3),
+            L.ptr(row_dir), L.ptr(improved), L.ptr(best),
+            *(best.stride() if best is not None else zero), self._adv_floats(range6, 6),
+            self._stream()))
+        return x_adv
+
+    def run_adv_direction(self, controls, pred_speed, ref_controls, ref_speed, w4, first, dev,
+                          best_dev, row_dir, improved):
+        """cilrs_adv_direction: dev = w . (outputs - ref) per frame, row_dir = its sign (+1 at 0),
+        improved = first or |dev| > |best_dev| (best_dev updated there)."""
+        b = controls.size(0)
+        for t, name, shape in ((controls, "controls", (b, 3)), (ref_controls, "ref_controls", (b, 3)),
+                               (pred_speed, "pred_speed", (b,)), (ref_speed, "ref_speed", (b,)),
+                               (dev, "dev", (b,)), (best_dev, "best_dev", (b,)),
+                               (row_dir, "row_dir", (b,))):
+            if t is None:
+                raise RuntimeError(f"{name} must be a tensor")
+            self._check_adv_rows(t, name, torch.float32, shape)
+        if improved is None:
+            raise RuntimeError("improved must be a tensor")
+        self._check_adv_rows(improved, "improved", torch.int32, (b,))
+        L.check(L.lib().cilrs_adv_direction(
+            L.ptr(controls), L.ptr(pred_speed), L.ptr(ref_controls), L.ptr(ref_speed),
+            self._adv_floats(w4, 4), b, 1 if first else 0, L.ptr(dev), L.ptr(best_dev),
+            L.ptr(row_dir), L.ptr(improved), self._stream()))
+
+    def run_adv_quantize(self, x_adv, frames_u8=None, out_u8=None, linf=None):
+        """cilrs_adv_quantize: x_adv float32 [B,3,H,W] (any strides) -> uint8 [B,H,W,3] camera
+        frames; linf (int32 [B], with the clean frames_u8) = max |q - frame| per frame.  Fills and
+        returns out_u8."""
+        b, h, w = self._check_adv_image(x_adv, "x_adv")
+        if out_u8 is None:
+            out_u8 = torch.empty(b, h, w, 3, dtype=torch.uint8, device=self.device)
+        self._check_adv_rows(out_u8, "out_u8", torch.uint8, (b, h, w, 3))
+        self._check_adv_rows(frames_u8, "frames_u8", torch.uint8, (b, h, w, 3))
+        self._check_adv_rows(linf, "linf", torch.int32, (b,))
+        L.check(L.lib().cilrs_adv_quantize(
+            L.ptr(x_adv), *x_adv.stride(), L.ptr(frames_u8), b, h, w, L.ptr(out_u8), L.ptr(linf),
+            self._stream()))
+        return out_u8
+
     def check_status(self):
         """Raise if the last forward saw an out-of-range command (one device->host read)."""
         if self.last_plan is not None:

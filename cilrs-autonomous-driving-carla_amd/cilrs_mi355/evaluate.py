@@ -8,7 +8,8 @@ module emits the same JSON schema.  Every batch costs one eval forward (the HIP 
 copied to the host until `report()`.
 
 `weather_sweep` and `view_sweep` score a checkpoint frame by frame under synthetic weather and from
-displaced viewpoints; `replay` closes the loop: recorded drives driven by the network's own steer,
+displaced viewpoints, `adversarial_sweep` under the worst perturbation of a few 8-bit levels next to
+a random one of the same size (csrc/adversarial.hip); `replay` closes the loop: recorded drives driven by the network's own steer,
 with the state, the view records and the metrics on the device (csrc/replay.hip).
 """
 from __future__ import annotations
@@ -239,6 +240,107 @@ def view_sweep(model, dataset, indices, lateral_m=(-1.0, -0.5, 0.0, 0.5, 1.0),
         "steer_per_deg": _slope(yaws, [cells[0.0][v]["steer_shift"] for v in yaws])
         if 0.0 in lats else None}
     return out
+
+
+def adversarial_sweep(model, dataset, indices, eps=(0.5, 1, 2, 4, 8), steps: int = 10,
+                      output="steer", goal: str = "error", batch: int = 128, seed: int = 0,
+                      **report_kw):
+    """How far the metrics move under the WORST perturbation of at most eps 8-bit levels per byte
+    (`adversarial.Attack`: PGD with `steps` steps, FGSM for steps = 1), next to a random-sign
+    control of the same size -- without the control the figures cannot tell a worst-case
+    perturbation from noise.  dataset: a filled `DeviceDataset`; goal "error" attacks w . (outputs -
+    labels), "deviate" w . (outputs - clean prediction); `output` picks w as in
+    `Predictor.saliency`.  The frames are scored as bytes: rounded, clipped, and through the same
+    eval-mode forward as `evaluate`, so the eps = 0 row is the plain evaluation of those frames.
+
+    -> {"clean": report, "eps": {eps: {"attack": row, "control": row}}, "steps", "goal", "seed"};
+    a row holds "report" (the evaluation report on the perturbed bytes), "steer_mae",
+    "dev_mean" / "dev_max" (|w . (outputs - reference)| over the frames), "share_over_0.1" (frames
+    with |dev| > 0.1) and "linf_max" / "linf_mean" (levels actually moved)."""
+    from .adversarial import Attack, attack_args
+    from .predict import Predictor
+    wts = Predictor._saliency_weights(output)
+    if goal not in ("error", "deviate"):
+        raise ValueError(f"adversarial_sweep: goal must be 'error' or 'deviate', got {goal!r}")
+    cells = [attack_args(e, steps, None, None, goal, seed, "adversarial_sweep") for e in eps]
+    if not dataset.filled:
+        raise RuntimeError("adversarial_sweep: the dataset's cache is not filled (call fill())")
+    index = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+    dataset.check_index(index)
+    if index.size < 1 or batch < 1:
+        raise ValueError("adversarial_sweep: no frames")
+    eng = model.engine()
+    if eng.train_precision != "fp32":
+        raise RuntimeError("adversarial_sweep: fp32 plans only")
+    dev = eng.device
+    was_training = model.training
+    model.eval()
+    idx_dev = torch.from_numpy(index).to(dev)
+    w_dev = torch.tensor(wts, dtype=torch.float64, device=dev)
+    attacks = {}
+
+    def batches():
+        for b0 in range(0, index.size, batch):
+            ids = idx_dev[b0:b0 + batch]
+            yield (dataset.cache[ids], dataset.speed[ids], dataset.command_dev[ids],
+                   dataset.targets[ids])
+
+    def run(perturb):
+        """One pass: perturb(attack, frames, spd, cmd, tgt) leaves bytes in attack.adv_u8."""
+        ev = Evaluator(model)
+        devs, linfs = [], []
+        for frames, spd, cmd, tgt in batches():
+            b = frames.size(0)
+            if b not in attacks:
+                attacks[b] = (Attack(eng, b, dataset.h, dataset.w),
+                              torch.tensor(wts[:3], device=dev).expand(b, 3).contiguous(),
+                              torch.full((b,), float(wts[3]), device=dev))
+            at, dc, ds = attacks[b]
+            ref = perturb(at, frames, spd, cmd, tgt, dc, ds)
+            with torch.no_grad():
+                pc, ps = model(at.clean_input(at.adv_u8, out=at.g), spd, cmd)
+            ev.update_predictions(pc, ps, tgt, spd, cmd)
+            d = torch.cat([pc - ref[0], (ps - ref[1])[:, None]], 1).double() @ w_dev
+            devs.append(d.abs())
+            linfs.append(at.linf.clone())
+        d = torch.cat(devs).cpu().numpy()
+        li = torch.cat(linfs).cpu().numpy()
+        rep = ev.report(**report_kw)
+        return {"report": rep, "steer_mae": rep["overall_metrics"]["Steer"]["MAE"],
+                "dev_mean": float(d.mean()), "dev_max": float(d.max()),
+                "share_over_0.1": float((d > 0.1).mean()), "linf_max": int(li.max()),
+                "linf_mean": float(li.mean())}
+
+    def reference(at, tgt, spd):
+        if goal == "error":
+            return tgt, spd
+        return at.ctrl0.clone(), at.spd0.clone()
+
+    out = {"eps": {}, "steps": int(steps), "goal": goal, "seed": int(seed)}
+    try:
+        for e, n, alpha, rs, _, sd in cells:
+            def attack(at, frames, spd, cmd, tgt, dc, ds):
+                at.run(frames, spd, cmd, dc, ds, wts, e, n, alpha, rs, goal, sd,
+                       targets=(tgt, spd) if goal == "error" else None, score=False)
+                return reference(at, tgt, spd)
+
+            def control(at, frames, spd, cmd, tgt, dc, ds):
+                if goal != "error":
+                    eng.run_forward_frozen_u8(frames, spd, cmd, out=(at.ctrl0, at.spd0))
+                at.random_sign_control(frames, e, sd)
+                return reference(at, tgt, spd)
+            out["eps"][e] = {"attack": run(attack), "control": run(control)}
+        out["clean"] = evaluate(model, _clean_batches(eng, batches), **report_kw)
+    finally:
+        if was_training:
+            model.train()
+    return out
+
+
+def _clean_batches(eng, batches):
+    """The frames of a sweep as `evaluate` takes them: preprocessed, no perturbation."""
+    for frames, spd, cmd, tgt in batches():
+        yield eng.run_attr_samples(frames, None, 0, 1, 0, 1, 0.0, 0), spd, cmd, tgt
 
 
 # ---- closed-loop replay -------------------------------------------------------------------------
@@ -484,6 +586,14 @@ def write_view_sweep(path, model, dataset, indices, **kw):
 def write_weather_sweep(path, model, dataset, indices, **kw):
     """`weather_sweep` written as JSON (severities become string keys)."""
     rep = weather_sweep(model, dataset, indices, **kw)
+    with open(path, "w") as f:
+        json.dump(rep, f, indent=2)
+    return rep
+
+
+def write_adversarial_sweep(path, model, dataset, indices, **kw):
+    """`adversarial_sweep` written as JSON (the eps values become string keys)."""
+    rep = adversarial_sweep(model, dataset, indices, **kw)
     with open(path, "w") as f:
         json.dump(rep, f, indent=2)
     return rep

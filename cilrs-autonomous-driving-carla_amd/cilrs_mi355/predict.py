@@ -676,6 +676,121 @@ class Predictor:
                         baseline_out=f_0, delta=total - (f_x - f_0))
         return out, o[10 * b:10 * b + hw].reshape(b, h, w).copy(), o[8 * b:9 * b].copy(), info
 
+    # ---- FGSM / PGD ------------------------------------------------------------------------------
+    def _adversarial_buffers(self):
+        """Pinned + device staging and the attack's device tensors of one adversarial call (cached)."""
+        adv = getattr(self, "_adv", None)
+        if adv is not None and adv["eng"] is self.eng:
+            return adv
+        from .adversarial import Attack
+        dev = self.eng.device
+        b, h, w = self.batch, self.frames_host.size(1), self.frames_host.size(2)
+        nfr = b * h * w * 3
+        # [frames | speed | d controls | d pred_speed | target controls | target speed | command]
+        o_spd = (nfr + 15) // 16 * 16
+        o_dc = o_spd + 4 * b
+        o_ds = o_dc + 12 * b
+        o_tc = o_ds + 4 * b
+        o_ts = o_tc + 12 * b
+        o_cmd = (o_ts + 4 * b + 7) // 8 * 8
+        host = torch.zeros(o_cmd + 8 * b, dtype=torch.uint8).pin_memory()
+        dbuf = torch.zeros_like(host, device=dev)
+
+        def views(buf):
+            f32 = lambda a, e: buf[a:e].view(torch.float32)
+            return (buf[:nfr].view(b, h, w, 3), f32(o_spd, o_dc), f32(o_dc, o_ds).view(b, 3),
+                    f32(o_ds, o_tc), f32(o_tc, o_ts).view(b, 3), f32(o_ts, o_ts + 4 * b),
+                    buf[o_cmd:o_cmd + 8 * b].view(torch.int64))
+        adv = dict(eng=self.eng, host=host, dev=dbuf, host_np=[v.numpy() for v in views(host)],
+                   dev_views=views(dbuf), attack=Attack(self.eng, b, h, w),
+                   out_host=torch.zeros(11 * b, dtype=torch.float32).pin_memory(),
+                   u8_host=torch.zeros(b, h, w, 3, dtype=torch.uint8).pin_memory())
+        self._adv = adv
+        return adv
+
+    @torch.no_grad()
+    def adversarial(self, frames_u8, speeds_kmh, commands, output="steer", eps=2.0, steps=10,
+                    alpha=None, random_start=None, goal="deviate", targets=None, seed=0):
+        """How far can a perturbation of at most `eps` 8-bit levels per byte move an output:
+        (out_clean [B,4], out_adv [B,4], adv_frames_u8 [B,H,W,3], info) by FGSM (steps=1) or PGD.
+
+        `output` picks w as in `saliency`.  goal="deviate" drives w . outputs away from the clean
+        prediction (either side, per frame), "error" away from `targets` ([B,4] in the units of
+        `out`, or [B,3] controls when w gives the speed no weight), "increase" / "decrease" push it
+        one way.  alpha: the step in levels (None: eps for one step, else 2.5 * eps / steps);
+        random_start: begin at a uniform point of the eps ball drawn on the device from `seed`
+        (None: for "deviate" only, where the clean frame itself has no ascent direction).  For
+        "deviate" and "error" the iterate with the largest |deviation| is kept, not the last one.
+        out_adv is the network's output on the returned BYTES (rounded, clipped to 0..255): what a
+        camera frame would give.  info: `dev` [B] = w . (outputs - reference) of the kept float
+        iterate, `dev_u8` [B] the same of out_adv, `linf` [B] = max |adv - frame| in levels, and
+        `steps`, `alpha`, `eps` (raw network outputs: pred_speed not multiplied by 90).
+        frames: uint8 [B,88,200,3] at the network resolution only; fp32 plans only.  Everything
+        runs on this predictor's stream, nothing per iteration touches the host, and the
+        persistent single-frame state is not disturbed."""
+        from .adversarial import attack_args
+        wts = self._saliency_weights(output)                       # ValueError before any launch
+        eps, steps, alpha, random_start, goal, seed = attack_args(eps, steps, alpha, random_start,
+                                                                  goal, seed)
+        frames = np.asarray(frames_u8)
+        b, h, w = self.batch, self.frames_host.size(1), self.frames_host.size(2)
+        if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[0] != b or \
+                frames.shape[3] not in (3, 4):
+            raise RuntimeError(f"adversarial: frames must be uint8 [{b},{h},{w},3]")
+        if frames.shape[1:] != (h, w, 3):
+            raise RuntimeError(f"adversarial: frames must be at the network resolution "
+                               f"[{b},{h},{w},3]; raw camera frames are not served (the "
+                               "perturbation lives in the network's input) -- resize them first")
+        cmds = self._check_commands(commands)
+        speeds = np.minimum(np.asarray(speeds_kmh, dtype=np.float64) / SPEED_NORM_FACTOR, 1.0)
+        if cmds.shape != (b,) or speeds.shape != (b,):
+            raise RuntimeError(f"adversarial: {b} speeds and commands expected")
+        tgt = None
+        if goal == "error":
+            if targets is None:
+                raise ValueError("adversarial: goal='error' needs targets")
+            tgt = np.asarray(targets, dtype=np.float32)
+            if tgt.shape not in ((b, 3), (b, 4)) or not np.isfinite(tgt).all():
+                raise ValueError(f"adversarial: targets must be finite [{b},4] (steer, throttle, "
+                                 f"brake, speed in km/h) or [{b},3]")
+            if tgt.shape == (b, 3) and wts[3] != 0:
+                raise ValueError("adversarial: [B,3] targets carry no speed, but `output` weighs it")
+        elif targets is not None:
+            raise ValueError("adversarial: targets belong to goal='error'")
+        if self.model.engine().train_precision != "fp32":
+            raise RuntimeError("adversarial: fp32 plans only (the model's training plan is "
+                               f"{self.model.engine().train_precision}; the eval-mode graph it "
+                               "differentiates needs train_precision='fp32')")
+        if self.model.engine() is not self.eng:
+            self.__init__(self.model, b, h, w, self.use_graph, self.half, self.persistent)
+        if self.model.training:
+            self.model.eval()
+        adv = self._adversarial_buffers()
+        f_np, s_np, dc_np, ds_np, tc_np, ts_np, c_np = adv["host_np"]
+        np.copyto(f_np, frames)
+        s_np[...] = speeds
+        dc_np[...] = wts[:3]
+        ds_np[...] = wts[3]
+        tc_np[...] = 0.0 if tgt is None else tgt[:, :3]
+        ts_np[...] = 0.0 if tgt is None or tgt.shape[1] == 3 else \
+            tgt[:, 3] / np.float32(SPEED_NORM_FACTOR)
+        c_np[...] = cmds
+        f_dev, s_dev, dc_dev, ds_dev, tc_dev, ts_dev, c_dev = adv["dev_views"]
+        at = adv["attack"]
+        self._order_after_weight_updates()
+        with torch.cuda.stream(self.stream):
+            adv["dev"].copy_(adv["host"], non_blocking=True)
+            at.run(f_dev, s_dev, c_dev, dc_dev, ds_dev, wts, eps, steps, alpha, random_start, goal,
+                   seed, targets=(tc_dev, ts_dev) if tgt is not None else None)
+            adv["out_host"].copy_(at.out, non_blocking=True)
+            adv["u8_host"].copy_(at.adv_u8, non_blocking=True)
+            self.stream.synchronize()
+        o = adv["out_host"].numpy()
+        info = dict(dev=o[8 * b:9 * b].copy(), dev_u8=o[9 * b:10 * b].copy(),
+                    linf=o[10 * b:].view(np.int32).copy(), steps=steps, alpha=alpha, eps=eps)
+        return (self._result4(o[:3 * b], o[3 * b:4 * b]), self._result4(o[4 * b:7 * b], o[7 * b:8 * b]),
+                adv["u8_host"].numpy().copy(), info)
+
     def predict_controls(self, image_rgb_u8, speed_kmh, command_idx):
         """Same return tuple as the reference's predict_controls (:918-920).  Frames that are not
         already 88x200x3 go through the fused resize (predict_camera)."""

@@ -68,6 +68,18 @@ class TrainConfig:
     sam_rho: float = 0.0
     sam_adaptive: bool = False
     sam_every: int = 1
+    # adversarial training (include/cilrs_hip.h "adversarial robustness"): the step is taken on
+    # x_adv = the batch moved by one signed-gradient step of adv_alpha 8-bit levels (FGSM), from a
+    # uniform random start in the eps ball when adv_random_start, kept within adv_eps levels of the
+    # clean batch -- one extra forward / data-gradient pass per due step.  adv_eps = 0: off, and then
+    # the step is launch for launch what it was.  adv_alpha None: 1.25 * adv_eps with a random
+    # start, else adv_eps.  adv_every: the optimizer steps t (1-based) with (t - 1) % adv_every == 0
+    # are adversarial.  adv_clamp: x_adv also stays inside the images of the bytes 0..255.
+    adv_eps: float = 0.0
+    adv_alpha: float = None
+    adv_random_start: bool = True
+    adv_every: int = 1
+    adv_clamp: bool = False
 
 
 GROUP_NAMES = ("stem", "layer1", "layer2", "layer3", "layer4", "heads")
@@ -130,6 +142,45 @@ def check_optim_config(cfg: TrainConfig):
     if not (isinstance(cfg.sam_every, int) and not isinstance(cfg.sam_every, bool)
             and cfg.sam_every >= 1):
         raise ValueError(f"sam_every must be an integer >= 1, got {cfg.sam_every!r}")
+    check_adv_config(cfg)
+
+
+def check_adv_config(cfg: TrainConfig):
+    """ValueError for an adversarial-training configuration no Trainer can serve."""
+    for name in ("adv_eps", "adv_alpha"):
+        v = getattr(cfg, name)
+        if name == "adv_alpha" and v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"{name} must be finite and >= 0 (8-bit levels), got {v!r}")
+    for name in ("adv_random_start", "adv_clamp"):
+        if not isinstance(getattr(cfg, name), bool):
+            raise ValueError(f"{name} must be True or False, got {getattr(cfg, name)!r}")
+    if not (isinstance(cfg.adv_every, int) and not isinstance(cfg.adv_every, bool)
+            and cfg.adv_every >= 1):
+        raise ValueError(f"adv_every must be an integer >= 1, got {cfg.adv_every!r}")
+    if cfg.adv_eps > 0 and cfg.sam_rho > 0:
+        raise ValueError("adv_eps > 0 together with sam_rho > 0: both take the step's extra pass "
+                         "(perturb the input or the weights, not both)")
+
+
+def adv_alpha(cfg: TrainConfig) -> float:
+    """The adversarial step in 8-bit levels: adv_alpha, or 1.25 * adv_eps with a random start and
+    adv_eps without."""
+    if cfg.adv_alpha is not None:
+        return float(cfg.adv_alpha)
+    return 1.25 * float(cfg.adv_eps) if cfg.adv_random_start else float(cfg.adv_eps)
+
+
+def adv_step_due(adv_every: int, t: int) -> bool:
+    """Is optimizer step t (1-based) adversarial?  Steps 1, 1 + adv_every, 1 + 2 adv_every, ..."""
+    return (int(t) - 1) % int(adv_every) == 0
+
+
+def adv_seed(torch_seed: int, call: int, rank: int = 0) -> int:
+    """64-bit key of the random start of the `call`-th adversarial step (cilrs_adv_start `seed`)."""
+    return ((torch_seed * 1000033 + call) ^ (rank * 0x9E3779B97F4A7C15) ^ 0xAD5EED) \
+        & 0xFFFFFFFFFFFFFFFF
 
 
 def check_sam_rho(rho):
@@ -274,6 +325,10 @@ class Trainer:
         self._bn_snapshot = None
         if cfg.sam_rho > 0:
             self._sam_buffers()
+        # adversarial training: batch-sized x_adv / image-gradient buffers (made on first use, in the
+        # images' strides) and the count of adversarial steps taken
+        self._adv_bufs = {}
+        self.adv_steps = 0
         self.reducer = None
         self.rank = 0
         if process_group is not None:
@@ -484,7 +539,14 @@ class Trainer:
         if g and self.reducer is None and self.cfg.grad_clip <= 0 and self.fuse_optimizer:
             raise RuntimeError("Trainer.fuse_optimizer cannot serve a frozen trunk prefix (one "
                                "fused update per backward segment, one step count)")
+        adv = self.cfg.adv_eps > 0 and adv_step_due(self.cfg.adv_every, self.step_count + 1)
+        if adv:
+            self._refuse_unserved_adversarial(e, g)
         seed = self.next_dropout_seed() if self.cfg.dropout > 0 else 0
+        if adv:
+            # (row_loss is the first pass's, like SAM's: the loss of the batch as it was drawn)
+            imgs = self._adversarial_batch(imgs, speeds, cmds, tgts, seed, sample_weight, row_loss)
+            row_loss = None
         controls, pred_speed, pl = eng.run_forward_ft(imgs, speeds, cmds, e, g, self.cfg.dropout,
                                                       seed)
         # `speeds` is both an input and the speed head's regression target (nb:550)
@@ -534,6 +596,49 @@ class Trainer:
                 self._sam_restore(e, g)
             self.optimizer_step(1.0 / self.reducer.world_size)
         return self.loss_buf
+
+    # -- adversarial training ----------------------------------------------------------------------
+    def _refuse_unserved_adversarial(self, e, g):
+        if g:
+            from .engine import SEG_NAMES
+            raise RuntimeError("CILRS adversarial training: the trunk is frozen up to "
+                               f"{SEG_NAMES[6 - g]} and the image gradient stops at the cut "
+                               "(unfreeze the trunk, or set adv_eps = 0)")
+        if self.eng.train_precision != "fp32":
+            raise RuntimeError("CILRS adversarial training: fp32 plans only (the image gradient of "
+                               f"the {self.eng.train_precision} training plan is not served)")
+
+    def _adversarial_batch(self, imgs, speeds, cmds, tgts, seed, sample_weight, row_loss):
+        """x_adv of a due step: random start, a train-mode forward with the
+        step's dropout masks, the loss, the data-gradient-only backward, the image gradient, one
+        signed step.  No collective: like SAM's first pass the perturbation is per rank.  The
+        running BatchNorm statistics and num_batches_tracked are put back, so the step ends as ONE
+        forward on x_adv leaves them."""
+        from .adversarial import CHAN_SCALE, RANGE6
+        eng, cfg = self.eng, self.cfg
+        key = (tuple(imgs.shape), tuple(imgs.stride()))
+        if key not in self._adv_bufs:
+            self._adv_bufs = {key: (torch.empty_strided(imgs.shape, imgs.stride(),
+                                                        dtype=torch.float32, device=imgs.device),
+                                    torch.empty_strided(imgs.shape, imgs.stride(),
+                                                        dtype=torch.float32, device=imgs.device))}
+        x_adv, grad = self._adv_bufs[key]
+        range6 = RANGE6 if cfg.adv_clamp else None
+        if self._bn_snapshot is None:
+            self._bn_snapshot = (torch.empty_like(eng.bn), torch.empty_like(eng.nbt))
+        self.adv_steps += 1
+        eng.snapshot_bn(*self._bn_snapshot)
+        eng.run_adv_start(imgs, cfg.adv_eps if cfg.adv_random_start else 0.0, CHAN_SCALE,
+                          adv_seed(torch.initial_seed(), self.adv_steps, self.rank), x_adv, range6)
+        controls, pred_speed, pl = eng.run_forward_ft(x_adv, speeds, cmds, 0, 0, cfg.dropout, seed)
+        _, dc, dp = self.loss(controls, tgts, pred_speed, speeds, out=self.sam_loss_buf,
+                              sample_weight=sample_weight, row_loss=row_loss)
+        eng.run_backward(pl, dc, dp, data_only=True)
+        eng.run_input_grads(pl, grad, None)      # (a plan that cannot give it refuses here)
+        eng.run_adv_step(imgs, x_adv, grad, adv_alpha(cfg), cfg.adv_eps, CHAN_SCALE, None, None,
+                         None, range6)
+        eng.put_back_bn(*self._bn_snapshot)
+        return x_adv
 
     # -- sharpness-aware minimisation --------------------------------------------------------------
     def _sam_buffers(self):

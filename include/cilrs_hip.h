@@ -1555,6 +1555,73 @@ int cilrs_attr_finalize(const float* acc, const uint8_t* frames_u8, const uint8_
                         float* signed_map, float* total, void* stream);
 int cilrs_attr_finalize_threads(void);
 
+/* Adversarial robustness (csrc/adversarial.hip; Predictor.adversarial, evaluate.adversarial_sweep
+ * and the adversarial train step of Trainer drive them): FGSM / PGD on the network's input.  The
+ * gradient of an iteration is a forward + cilrs_net_backward_data + cilrs_net_input_grads; these
+ * four launches are everything in between.  Streaming kernels, no atomics, every float operation
+ * rounded once (no FMA contraction): each result is the fp32 numpy expression bit for bit, and
+ * bit-identical from run to run.
+ *
+ * x = the clean normalised image, x_adv = the iterate, g = the image gradient, best = the kept
+ * iterate: logical NCHW f32 [B,3,H,W] with non-negative element strides (sn,sc,sh,sw).  Contiguous
+ * NCHW and the channels-last view with strides (3HW, 1, 3W, 3) move 16 bytes per access when every
+ * tensor of the call has that layout, H*W % 4 == 0 and the pointers are 16-byte aligned; anything
+ * else goes element by element through the strides, with the same results.
+ * Sizes are in 8-bit levels: chan_scale3 = three HOST floats, 1 / (255 * std_c) as for
+ * cilrs_attr_finalize; e_c = eps255 * chan_scale3[c] and a_c = alpha255 * chan_scale3[c], one fp32
+ * product each, formed on the host.  range6 (HOST floats lo_0, hi_0, lo_1, hi_1, lo_2, hi_2; may be
+ * NULL) = the images of the bytes 0 and 255 under the preprocessing.
+ *   clamp(t) = fminf(fmaxf(t, x - e_c), x + e_c), then, with range6,
+ *              fminf(fmaxf(t, lo_c), hi_c)                 (fminf / fmaxf drop a NaN operand)
+ *
+ * cilrs_adv_start: x_adv = clamp(x + e_c * r), r = (u + u) - 1, u = ((float)(h >> 40) + 1) * 2^-24
+ *   with h = splitmix64(seed + counter * 0xD1B54A32D192ED03) -- the first 24-bit field exactly as
+ *   cilrs_attr_samples takes u1 -- and counter = the element's LOGICAL index ((b*3 + c)*H + y)*W + x:
+ *   the draw does not depend on the strides.  x and x_adv have strides of their own.  eps255 = 0 is a
+ *   copy, bit for bit (no draw, no clamp).
+ * cilrs_adv_step (x and x_adv share one set of strides; g and best have their own), per element, in
+ *   this order:
+ *     1. improved != NULL, best != NULL and improved[b] != 0:  best = x_adv  (the iterate the last
+ *        forward saw: the value BEFORE this step)
+ *     2. s = g > 0 ? 1 : (g < 0 ? -1 : 0)                      (NaN: 0)
+ *     3. t = x_adv + (a_c * d_b) * s,  d_b = row_dir ? row_dir[b] : 1
+ *     4. x_adv = clamp(t)
+ *   alpha255 = 0: only step 1 runs and x_adv is not written -- every bit of it stays; g may be NULL
+ *   then, and only then.  With nothing to copy either, nothing is launched.
+ * cilrs_adv_direction: one thread per frame.  w4_host = four HOST floats over (steer, throttle,
+ *   brake, pred_speed); controls / ref_controls f32 [B,3], pred_speed / ref_speed f32 [B];
+ *     dev[b] = (w0*(c0-r0) + w1*(c1-r1)) + (w2*(c2-r2) + w3*(s-rs))       in that association
+ *     row_dir[b]  (f32) = dev >= 0 ? +1 : -1           -- ascends |dev|
+ *     improved[b] (i32) = first || |dev| > |best_dev[b]|;  where improved, best_dev[b] = dev
+ *   A non-finite dev never improves (not even with `first`; best_dev[b] is then set to 0) and gives
+ *   row_dir = +1.  ref = the clean prediction ("deviate") or the labels ("error").
+ * cilrs_adv_quantize: the iterate as a camera frame.  v = (x_adv * std_c + mean_c) * 255,
+ *   q = (uint8) rintf(fminf(fmaxf(v, 0), 255))  (NaN: 0) -> out_u8 uint8 [B,H,W,3];  linf (i32 [B],
+ *   may be NULL; needs frames_u8 uint8 [B,H,W,3]) = max |q - frame| over the frame: one workgroup of
+ *   cilrs_adv_quantize_threads() threads per frame, per-thread maximum, wave shuffles, LDS --
+ *   integers, so the result is exact.
+ *
+ * Refused (non-zero, text in cilrs_last_error, nothing launched): NULL tensors (the optional ones
+ * are exempt); a negative or non-finite eps255 / alpha255; a negative stride; B, H or W < 1 or
+ * B*3*H*W > cilrs_adv_max_elements() = 2^30 (element indices are ints in the kernels);
+ * g == NULL with alpha255 > 0; linf without frames_u8. */
+int cilrs_adv_start(const float* x, long xn, long xc, long xh, long xw, int B, int H, int W,
+                    float eps255, const float* chan_scale3, uint64_t seed, const float* range6,
+                    float* x_adv, long an, long ac, long ah, long aw, void* stream);
+int cilrs_adv_step(const float* x, float* x_adv, long sn, long sc, long sh, long sw, const float* g,
+                   long gn, long gc, long gh, long gw, int B, int H, int W, float alpha255,
+                   float eps255, const float* chan_scale3, const float* row_dir,
+                   const int32_t* improved, float* best, long bn, long bc, long bh, long bw,
+                   const float* range6, void* stream);
+int cilrs_adv_direction(const float* controls, const float* pred_speed, const float* ref_controls,
+                        const float* ref_speed, const float* w4_host, int B, int first, float* dev,
+                        float* best_dev, float* row_dir, int32_t* improved, void* stream);
+int cilrs_adv_quantize(const float* x_adv, long sn, long sc, long sh, long sw,
+                       const uint8_t* frames_u8, int B, int H, int W, uint8_t* out_u8, int32_t* linf,
+                       void* stream);
+int cilrs_adv_quantize_threads(void);
+long long cilrs_adv_max_elements(void);
+
 /* The bf16 training mode's operators on 16-bit tensors (round 4: every trunk tensor after the stem
  * -- activations, raw convolution outputs, gradients -- is stored in bf16; fp32 accumulation,
  * statistics and coefficients).  No reference counterpart (the reference trains in fp32,
